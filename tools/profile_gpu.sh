@@ -9,7 +9,7 @@ mkdir -p "$OUT"
 export TMPDIR=/tmp
 run() { # name, rocprof args...
   local name=$1; shift
-  timeout -k 10 300 rocprofv3 "$@" -d "$OUT/$name" -o "$name" -- python3 bench.py $ARGS > "$OUT/$name.log" 2>&1
+  timeout -k 10 300 rocprofv3 "$@" -d "$OUT/$name" -o "$name" -- python3 bench.py --full $ARGS > "$OUT/$name.log" 2>&1
   local rc=$?; echo "$name rc=$rc"
   # keep only text summaries (the sqlite files of long runs exceed what gpurun copies back)
   for db in $(find "$OUT/$name" -name "*.db"); do

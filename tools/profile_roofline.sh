@@ -11,7 +11,7 @@ mkdir -p "$OUT"
 export TMPDIR=/tmp
 run() { # name, rocprof args...
   local name=$1; shift
-  timeout -k 10 300 rocprofv3 "$@" -d "$OUT/$name" -o "$name" -- python3 bench.py --roofline-only --no-cpu-baseline $ARGS > "$OUT/$name.log" 2>&1
+  timeout -k 10 300 rocprofv3 "$@" -d "$OUT/$name" -o "$name" -- python3 bench.py --full --roofline-only --no-cpu-baseline $ARGS > "$OUT/$name.log" 2>&1
   local rc=$?; echo "$name rc=$rc"
   for db in $(find "$OUT/$name" -name "*.db"); do
     if [ "$name" = trace ]; then python3 tools/rocpd_summary.py trace "$db" > "$OUT/$name.summary.txt" 2>&1

@@ -1,7 +1,7 @@
 """Writes profiles/traffic.json's `<config>_1lane` entry from a tools/profile_roofline.sh
 run: FETCH_SIZE / WRITE_SIZE of the non-stats (<false>) dispatches, which are the two
-1-lane renders of `bench.py --roofline-only`, per dispatch. FETCH KB x 1024 x 2 (the
-gfx950 FETCH_SIZE correction of /opt/skills/guides/MI355X_MICROARCH.md), WRITE KB x 1024.
+1-lane renders of `bench.py --full --roofline-only`, per dispatch. FETCH KB x 1024 x 2 (the
+gfx950 FETCH_SIZE correction), WRITE KB x 1024.
 
   python tools/update_traffic.py ROOF_DIR [--config cfg2] [--build COMMIT] [--commit-dir profiles/NAME]
 
@@ -53,7 +53,7 @@ def main():
         "per_class_bytes_per_launch": fetch,
         "per_class_write_bytes_per_launch": write,
         "source": f"{rel}/pmc_fetch.json (FETCH_SIZE) and pmc_write.json (WRITE_SIZE): rocprofv3 --pmc over "
-                  f"`bench.py --roofline-only --no-cpu-baseline --config {args.config}` (tools/profile_roofline.sh; "
+                  f"`bench.py --full --roofline-only --no-cpu-baseline --config {args.config}` (tools/profile_roofline.sh; "
                   "the <false> dispatches are the two 1-lane renders); FETCH KB x1024 x2 (gfx950 correction, "
                   "MI355X_MICROARCH.md), WRITE KB x1024, / dispatches" + (f"; build of commit {args.build}" if args.build else ""),
         "profile": f"{rel}/pmc_fetch.json",
