@@ -41,7 +41,13 @@ $(OBJ)/rt_render.o: $(SRC)/rt_render.hip $(HDRS) $(ALL_SRC)
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -DRT_BUILD_SRC='"$(SRC_HASH)"' -c $< -o $@
 
-$(LIB)/librt_hip.so: $(OBJ)/rt_render.o $(OBJ)/rt_scene.host.o $(OBJ)/rt_imageio.host.o $(OBJ)/rt_capi_host.host.o
+# the post stage (feature pass + filter) in a translation unit of its own: the render
+# kernels' code generation does not depend on it
+$(OBJ)/rt_denoise.o: $(SRC)/rt_denoise.hip $(HDRS)
+	@mkdir -p $(OBJ)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+$(LIB)/librt_hip.so: $(OBJ)/rt_render.o $(OBJ)/rt_denoise.o $(OBJ)/rt_scene.host.o $(OBJ)/rt_imageio.host.o $(OBJ)/rt_capi_host.host.o
 	@mkdir -p $(LIB)
 	$(HIPCC) -shared --offload-arch=$(ARCH) -fPIC $^ -o $@
 
@@ -90,7 +96,8 @@ clean:
 variant: $(OBJ)/rt_scene.host.o $(OBJ)/rt_imageio.host.o $(OBJ)/rt_capi_host.host.o
 	@mkdir -p $(LIB)
 	$(HIPCC) $(HIPFLAGS) $(DEFS) -DRT_BUILD_SRC='"$(SRC_HASH)"' -DRT_BUILD_DEFS='"$(DEFS)"' -c $(SRC)/rt_render.hip -o $(OBJ)/rt_render_$(V).o
-	$(HIPCC) -shared --offload-arch=$(ARCH) -fPIC $(OBJ)/rt_render_$(V).o $^ -o $(LIB)/librt_hip_$(V).so
+	$(HIPCC) $(HIPFLAGS) $(DEFS) -c $(SRC)/rt_denoise.hip -o $(OBJ)/rt_denoise_$(V).o
+	$(HIPCC) -shared --offload-arch=$(ARCH) -fPIC $(OBJ)/rt_render_$(V).o $(OBJ)/rt_denoise_$(V).o $^ -o $(LIB)/librt_hip_$(V).so
 
 # the same for the hostsim build: make hostsim-variant V=name DEFS="-DRT_SLABS=0" ->
 # lib/librt_hostsim_name.so (RT_HOSTSIM_LIB=...; study probes such as tools/far_probe.py)
@@ -107,6 +114,14 @@ hostsim-variant: $(OBJ)/rt_imageio.host.o
 REFDIR ?= /root/reference
 REFOBJ := oracle/_ref/objO2
 build/shim_test: tests/native/shim_test.cpp include/render_kernel_hip.h include/rt_hip.h $(LIB)/librt_hostsim.so
+	@mkdir -p build
+	$(CXX) -std=gnu++20 -O2 -fopenmp -Iinclude -I$(REFDIR)/include -I$(REFDIR)/rapidobj -I$(REFDIR) $< \
+	  $(REFOBJ)/bvh.o $(REFOBJ)/flattened_bvh.o $(REFOBJ)/triangle.o $(REFOBJ)/vec.o $(REFOBJ)/color.o \
+	  $(REFOBJ)/mat.o $(REFOBJ)/camera.o $(REFOBJ)/ray.o $(REFOBJ)/utils.o -Wl,--gc-sections \
+	  -L$(LIB) -lrt_hostsim -Wl,-rpath,'$$ORIGIN/../$(LIB)' -o $@
+
+# the drop-in's denoise() against the C ABI's rt_render_features + rt_denoise (tests/test_denoise_shim.py)
+build/denoise_shim_test: tests/native/denoise_shim_test.cpp include/render_kernel_hip.h include/rt_hip.h $(LIB)/librt_hostsim.so
 	@mkdir -p build
 	$(CXX) -std=gnu++20 -O2 -fopenmp -Iinclude -I$(REFDIR)/include -I$(REFDIR)/rapidobj -I$(REFDIR) $< \
 	  $(REFOBJ)/bvh.o $(REFOBJ)/flattened_bvh.o $(REFOBJ)/triangle.o $(REFOBJ)/vec.o $(REFOBJ)/color.o \

@@ -107,6 +107,23 @@ public:
                                reinterpret_cast<float*>(&px)));
     }
 
+    // The call shape of Utils::OIDN_denoise(image, blend_factor) (utils.cpp:144-196): a new
+    // Image, blend_factor * filtered + (1 - blend_factor) * image, alpha 1. The filter is the
+    // edge-avoiding a-trous of rt_denoise with its default parameters, guided by the first-hit
+    // buffers rendered for the bound camera (image has the kernel's size).
+    Image denoise(const Image& image, float blend_factor) const
+    {
+        std::lock_guard<std::mutex> lk(m_mu);
+        const_cast<RenderKernel*>(this)->sync_materials();
+        const int w = image.width(), h = image.height();
+        std::vector<float> albedo((size_t)w * h * 4), normal_depth((size_t)w * h * 4);
+        check(rt_render_features(m_ctx, w, h, albedo.data(), normal_depth.data()));
+        Image out(w, h);
+        check(rt_denoise(m_ctx, w, h, image.data(), albedo.data(), normal_depth.data(), nullptr, blend_factor,
+                         out.data()));
+        return out;
+    }
+
     int device_count() const { return rt_device_count(m_ctx); }
 
 private:

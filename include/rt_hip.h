@@ -45,6 +45,14 @@ extern "C" {
 
 typedef struct rt_context rt_context;
 typedef struct rt_mesh rt_mesh;
+/* Parameters of rt_denoise (rt_denoise_default_params fills the defaults). */
+typedef struct rt_denoise_params {
+    int passes;          /* a-trous iterations, 1..10; pass i has step 1 << i */
+    float sigma_color;   /* colour edge-stopping width; pass i uses sigma_color * 2^-i */
+    float sigma_normal;  /* the same for the first-hit normals, */
+    float sigma_albedo;  /* ... albedo */
+    float sigma_depth;   /* ... and relative depth (t_p - t_q) / max(t_p, t_q) */
+} rt_denoise_params;
 
 /* ---------------------------------------------------------------- context */
 int rt_create(int device, rt_context** out);
@@ -79,7 +87,9 @@ int rt_test_fail_device(rt_context* ctx, int device);
  * "tail_spec_cam", "step_budget", "fast_k" (fast lane: that many of the slowest
  * paths go to a tail kernel early; 0: off), "fast_spp" (... from iteration
  * fast_spp x spp on), "near_scale" (the near box, scene box widened by this x its
- * largest extent: queries from outside it take the exact octree walk), the
+ * largest extent: queries from outside it take the exact octree walk), "dn_variant"
+ * (rt_denoise's filter kernel: 0 the product's choice per step, 1 direct loads, 2 the
+ * LDS-halo tile at every step that has one), the
  * stressor "force_fallback" (every k-th query by a ray hash skips to the exact
  * octree walk), "reset"). No parameter changes a result; the product never calls
  * it and reads no schedule from the environment. RT_ERR_ARG for an unknown key or
@@ -183,6 +193,52 @@ int rt_intersect(rt_context* ctx, const float* rays, int n, void* out);
  * (intersect_scene :453-483: closest by strict `<` in buffer order, so the
  * lowest triangle index wins a tie). */
 int rt_set_intersect_mode(rt_context* ctx, int use_bvh);
+
+/* ------------------------------------------------------------ post stage
+ * What replaces Utils::OIDN_denoise (utils.cpp:144-196; main.cpp:116-124 calls it at
+ * blend 1.0 / 0.75 / 0.5): first-hit feature buffers and an edge-avoiding a-trous
+ * filter (Dammertz et al. 2010) guided by them. A different algorithm from OIDN's
+ * network, so there is no parity with the reference's denoised images; the blend and
+ * alpha arithmetic are the reference's (utils.cpp:184-186).
+ *
+ * rt_render_features: for every pixel (x, y) of a w x h frame the camera ray through the
+ * centre of the pixel's jitter window (x_j = (float)x, y_j = (float)y in
+ * get_camera_ray, render_kernel.cpp:56-73, :88-89) and its first hit, bitwise what
+ * rt_intersect answers for that ray (rt_set_intersect_mode honoured). Two float[h][w][4]
+ * buffers: normal_depth = {n.xyz, t} (miss: {0, 0, 0, -1}) and albedo = {diffuse rgb of
+ * materials[material_indices[prim]], 0} (miss: zeros). RT_ERR_STATE without scene, BVH or
+ * camera. rt_camera_rays (host only) writes those rays, rays[h*w][6] = origin, direction.
+ *
+ * rt_denoise: `passes` a-trous iterations over rgba_in (float[h][w][4]), ping-pong; pass i
+ * has step s = 1 << i and, for pixel p, visits the taps q = p + s (dx, dy), (dy, dx) in
+ * {-2..2}^2 in that order (dy outer), skipping taps outside the image:
+ *   k = h[dy+2] h[dx+2], h = {1/16, 1/4, 3/8, 1/4, 1/16}
+ *   e = |c_p - c_q|^2 / (sigma_color 2^-i)^2 + |n_p - n_q|^2 / sigma_normal^2
+ *     + |a_p - a_q|^2 / sigma_albedo^2 + ((t_p - t_q) / max(t_p, t_q))^2 / sigma_depth^2
+ *   out_p = sum k expf(-e) c_q / sum k expf(-e)
+ * The depth term is 0 between two misses (t <= 0) and a tap is skipped between a hit and
+ * a miss; a tap whose colour is not finite is skipped and a centre that is not finite
+ * passes through. albedo and normal_depth both NULL: the guide terms drop out (the
+ * colour-only call the reference makes). Then rgb = blend * filtered + (1.0f - blend) *
+ * input, alpha 1.0f. Alpha plays no part in the filter. RT_ERR_ARG for passes outside
+ * 1..10, a sigma that is not finite and > 0, a non-finite blend, exactly one guide NULL,
+ * rgba_in == rgba_out, or a frame of more than 262140 rows or 2^27 - 1 pixels. params
+ * NULL: the defaults. Guides that hold a NaN give the taps they touch no weight; a pixel
+ * whose own guide is NaN passes through.
+ *
+ * The *_device forms take device pointers and a stream (NULL: default) and return
+ * without waiting. A multi-device context runs the post stage on its root device; the
+ * caller's current device is restored. rt_last_kernel_ms reports the stage's time (the
+ * device forms: -1, read rt_device_last_kernel_ms after synchronizing). */
+int rt_camera_rays(rt_context* ctx, int w, int h, float* rays); /* host only */
+int rt_render_features(rt_context* ctx, int w, int h, float* albedo, float* normal_depth);
+int rt_render_features_device(rt_context* ctx, int w, int h, void* d_albedo, void* d_normal_depth, void* stream);
+void rt_denoise_default_params(rt_denoise_params* params);
+int rt_denoise(rt_context* ctx, int w, int h, const float* rgba_in, const float* albedo, const float* normal_depth,
+               const rt_denoise_params* params, float blend, float* rgba_out);
+int rt_denoise_device(rt_context* ctx, int w, int h, const void* d_rgba_in, const void* d_albedo,
+                      const void* d_normal_depth, const rt_denoise_params* params, float blend, void* d_rgba_out,
+                      void* stream);
 
 /* Counters of the last render when enabled (RT_STAT_* order, rt_device.h);
  * with n up to 2 * RT_STAT_COUNT the second block is the share of the

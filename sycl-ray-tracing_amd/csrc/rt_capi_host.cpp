@@ -8,6 +8,7 @@
 #include <mutex>
 
 #include "rt_context.h"
+#include "rt_denoise.h"
 
 namespace {
 std::mutex g_err_mu;
@@ -235,6 +236,7 @@ int rt_test_schedule(rt_context* c, const char* key, double value)
     else if (k == "fast_k") s.fast_k = v;
     else if (k == "fast_spp") s.fast_spp = value;
     else if (k == "near_scale") s.near_scale = value;
+    else if (k == "dn_variant") s.dn_variant = std::max(0, std::min(2, v));
     else if (k == "reset") s = RtSchedule{};
     else return rt_fail(c, RT_ERR_ARG, "rt_test_schedule: unknown key " + k);
     return RT_OK;
@@ -507,6 +509,103 @@ int rt_intersect(rt_context* c, const float* rays, int n, void* out)
         c->mats_dirty_only = false;
     }
     return rt_backend_intersect(c, rays, n, out);
+}
+
+// ------------------------------------------------------------- post stage
+int rt_camera_rays(rt_context* c, int w, int h, float* rays)
+{
+    if (!c) return rt_fail(nullptr, RT_ERR_ARG, "rt_camera_rays: ctx is NULL");
+    if (!c->have_cam) return rt_fail(c, RT_ERR_STATE, "rt_camera_rays: camera not set");
+    if (w <= 0 || h <= 0 || !rays) return rt_fail(c, RT_ERR_ARG, "rt_camera_rays: bad arguments");
+    const rtk::CamView V = rtk::cam_view(c->cam, w, h);
+    for (int y = 0; y < h; y++)
+        for (int x = 0; x < w; x++) {
+            rtk::V3 o, d;
+            rtk::feature_ray(V, x, y, o, d);
+            float* r = rays + 6 * ((size_t)y * w + x);
+            r[0] = o.x, r[1] = o.y, r[2] = o.z, r[3] = d.x, r[4] = d.y, r[5] = d.z;
+        }
+    return RT_OK;
+}
+
+static int features_ready(rt_context* c, int w, int h, const void* alb, const void* nd)
+{
+    if (!c) return rt_fail(nullptr, RT_ERR_ARG, "rt_render_features: ctx is NULL");
+    if (!c->have_scene || !c->have_bvh) return rt_fail(c, RT_ERR_STATE, "rt_render_features: scene/BVH not set");
+    if (!c->have_cam) return rt_fail(c, RT_ERR_STATE, "rt_render_features: camera not set");
+    if (w <= 0 || h <= 0 || !alb || !nd || alb == nd) return rt_fail(c, RT_ERR_ARG, "rt_render_features: bad buffers");
+    if ((double)w * (double)h > 268435455.0) return rt_fail(c, RT_ERR_ARG, "rt_render_features: too many pixels");
+    if (c->dirty || c->mats_dirty_only) {
+        if (!c->have_env) {
+            // a 1x1 black env keeps the device view valid for ray queries (as rt_intersect)
+            const float z[3] = {0, 0, 0};
+            rt_set_env(c, z, 1, 1, 3, nullptr);
+        }
+        if (int r = rt_backend_upload(c)) return r;
+        c->dirty = false;
+        c->mats_dirty_only = false;
+    }
+    return RT_OK;
+}
+
+int rt_render_features(rt_context* c, int w, int h, float* albedo, float* normal_depth)
+{
+    if (int r = features_ready(c, w, h, albedo, normal_depth)) return r;
+    return rt_backend_features(c, w, h, albedo, normal_depth, false, nullptr);
+}
+
+int rt_render_features_device(rt_context* c, int w, int h, void* d_albedo, void* d_normal_depth, void* stream)
+{
+    if (int r = features_ready(c, w, h, d_albedo, d_normal_depth)) return r;
+    return rt_backend_features(c, w, h, d_albedo, d_normal_depth, true, stream);
+}
+
+// Defaults from the quality sweep on Cornell 64x64, 16 spp against 512 spp.
+void rt_denoise_default_params(rt_denoise_params* p)
+{
+    if (!p) return;
+    p->passes = 5;
+    p->sigma_color = 1.0f;
+    p->sigma_normal = 0.3f;
+    p->sigma_albedo = 0.1f;
+    p->sigma_depth = 0.1f;
+}
+
+static int denoise_ready(rt_context* c, int w, int h, const void* in, const void* alb, const void* nd,
+                         const rt_denoise_params* params, float blend, const void* out, rt_denoise_params& p)
+{
+    if (!c) return rt_fail(nullptr, RT_ERR_ARG, "rt_denoise: ctx is NULL");
+    if (w <= 0 || h <= 0 || !in || !out) return rt_fail(c, RT_ERR_ARG, "rt_denoise: bad buffers");
+    if ((double)w * (double)h > 134217727.0) return rt_fail(c, RT_ERR_ARG, "rt_denoise: too many pixels");
+    // (the filter kernels tile the frame 4 rows per block: 65535 blocks in y at most)
+    if (h > 4 * 65535) return rt_fail(c, RT_ERR_ARG, "rt_denoise: height above 262140 rows");
+    if (in == out) return rt_fail(c, RT_ERR_ARG, "rt_denoise: rgba_in and rgba_out are the same buffer");
+    if ((alb == nullptr) != (nd == nullptr))
+        return rt_fail(c, RT_ERR_ARG, "rt_denoise: albedo and normal_depth must both be given or both be NULL");
+    if (params) p = *params;
+    else rt_denoise_default_params(&p);
+    if (p.passes < 1 || p.passes > 10) return rt_fail(c, RT_ERR_ARG, "rt_denoise: passes must be 1..10");
+    const float sig[4] = {p.sigma_color, p.sigma_normal, p.sigma_albedo, p.sigma_depth};
+    for (float s : sig)
+        if (!std::isfinite(s) || !(s > 0.0f)) return rt_fail(c, RT_ERR_ARG, "rt_denoise: a sigma is not finite and > 0");
+    if (!std::isfinite(blend)) return rt_fail(c, RT_ERR_ARG, "rt_denoise: blend is not finite");
+    return RT_OK;
+}
+
+int rt_denoise(rt_context* c, int w, int h, const float* in, const float* alb, const float* nd,
+               const rt_denoise_params* params, float blend, float* out)
+{
+    rt_denoise_params p;
+    if (int r = denoise_ready(c, w, h, in, alb, nd, params, blend, out, p)) return r;
+    return rt_backend_denoise(c, w, h, in, alb, nd, p, blend, out, false, nullptr);
+}
+
+int rt_denoise_device(rt_context* c, int w, int h, const void* in, const void* alb, const void* nd,
+                      const rt_denoise_params* params, float blend, void* out, void* stream)
+{
+    rt_denoise_params p;
+    if (int r = denoise_ready(c, w, h, in, alb, nd, params, blend, out, p)) return r;
+    return rt_backend_denoise(c, w, h, in, alb, nd, p, blend, out, true, stream);
 }
 
 int rt_set_intersect_mode(rt_context* c, int use_bvh)

@@ -34,6 +34,7 @@ struct RtSchedule {
     double fast_spp = -1.0;    // ... at the lanes' first readback from iteration fast_spp x spp on
     double near_scale = -1.0;  // near box: the scene's box widened by this x its largest extent (rt_view_near;
                                // study probes only: answers never depend on it, only which walk gives them)
+    int dn_variant = 0;        // rt_denoise's filter kernel: 0 per step as measured, 1 direct, 2 LDS tile where built
 };
 
 // Diagnostics, read from the environment once when the context is created (rt_create*):
@@ -110,6 +111,12 @@ int rt_backend_render_variants(rt_context* ctx, int w, int h, int spp, int bounc
 bool rt_table_has_emissive_prim(const rt_context* ctx, const RtMat* table);
 int rt_backend_render_pixels(rt_context* ctx, int w, int h, int spp, int bounces, const int* xy, int n, float* rgba);
 int rt_backend_intersect(rt_context* ctx, const float* rays, int n, void* out);
+// The post stage (rt_denoise.h), on the context's root device. device = false: host buffers,
+// synchronous; true: device buffers on `stream`, no wait (hostsim: host pointers, stream unused).
+int rt_backend_features(rt_context* ctx, int w, int h, void* albedo, void* normal_depth, bool device, void* stream);
+// alb and nd both null: colour only. p is validated (rt_capi_host.cpp).
+int rt_backend_denoise(rt_context* ctx, int w, int h, const void* in, const void* alb, const void* nd,
+                       const rt_denoise_params& p, float blend, void* out, bool device, void* stream);
 
 int rt_fail(rt_context* ctx, int code, const std::string& msg);
 // RtDiag from the environment (rt_create*)

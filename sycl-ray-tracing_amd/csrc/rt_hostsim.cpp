@@ -9,11 +9,13 @@
 #include <omp.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
 
 #include "rt_context.h"
+#include "rt_denoise.h"
 #include "rt_wave.h"
 
 // Stack window and step budget of the host build: smaller than the
@@ -392,6 +394,63 @@ int rt_backend_intersect(rt_context* c, const float* rays, int n, void* out)
     }
     std::fill(c->stats, c->stats + RT_STAT_COUNT, 0ull);
     merge_stats(c->stats, st);
+    return RT_OK;
+}
+
+// The post stage on the host: the loops around rt_denoise.h's per-pixel functions that the
+// gfx950 kernels (rt_denoise.hip) run one thread per pixel. "Device" pointers are host
+// pointers in this build.
+int rt_backend_features(rt_context* c, int w, int h, void* albedo, void* normal_depth, bool, void*)
+{
+    const RtSceneView S = rt_host_view(c);
+    const rtk::CamView V = rtk::cam_view(c->cam, w, h);
+    float4_* alb = (float4_*)albedo;
+    float4_* nd = (float4_*)normal_depth;
+    const double t0 = omp_get_wtime();
+#pragma omp parallel
+    {
+        std::vector<rtk::StackEnt> stack(RT_STACK_CAP);
+#pragma omp for schedule(dynamic, 64)
+        for (long i = 0; i < (long)w * h; i++) {
+            const int y = (int)(i / w), x = (int)(i - (long)y * w);
+            rtk::feature_pixel(S, V, x, y, stack.data(), nd[i], alb[i]);
+        }
+    }
+    c->last_kernel_ms = (omp_get_wtime() - t0) * 1e3;
+    return RT_OK;
+}
+
+int rt_backend_denoise(rt_context* c, int w, int h, const void* in, const void* alb, const void* nd,
+                       const rt_denoise_params& p, float blend, void* out, bool, void*)
+{
+    const size_t n = (size_t)w * h;
+    std::vector<float4_> ping(p.passes > 1 ? n : 0), pong(p.passes > 2 ? n : 0);
+    const float4_* src = (const float4_*)in;
+    const double t0 = omp_get_wtime();
+    for (int i = 0; i < p.passes; i++) {
+        const bool last = i + 1 == p.passes;
+        rtk::DnPass P{w,
+                      h,
+                      1 << i,
+                      rtk::dn_inv_sigma2(std::ldexp((double)p.sigma_color, -i)),
+                      rtk::dn_inv_sigma2(p.sigma_normal),
+                      rtk::dn_inv_sigma2(p.sigma_albedo),
+                      rtk::dn_inv_sigma2(p.sigma_depth),
+                      src,
+                      (const float4_*)nd,
+                      (const float4_*)alb};
+        float4_* dst = last ? (float4_*)out : (i & 1) ? pong.data() : ping.data();
+        const rtk::DnDirect F{P};
+#pragma omp parallel for schedule(static)
+        for (int y = 0; y < h; y++)
+            for (int x = 0; x < w; x++) {
+                const size_t q = (size_t)y * w + x;
+                const float4_ f = rtk::dn_filter_pixel(P, x, y, F);
+                dst[q] = last ? rtk::dn_blend(f, ((const float4_*)in)[q], blend) : f;
+            }
+        src = dst;
+    }
+    c->last_kernel_ms = (omp_get_wtime() - t0) * 1e3;
     return RT_OK;
 }
 

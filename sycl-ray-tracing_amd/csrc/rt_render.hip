@@ -34,6 +34,7 @@
 #include <rccl/rccl.h>
 
 #include "rt_context.h"
+#include "rt_backend_hip.h"
 #include "rt_wave.h"
 #include "rt_quad.h"
 #include "rt_row.h"
@@ -206,6 +207,7 @@ struct Backend {
     hipEvent_t tev[RT_MAX_LANES][3][RT_MAX_TIMED_ITERS] = {};
     double kms[3] = {0, 0, 0};      // k_trace, k_step, k_tail
     long klaunch[3] = {0, 0, 0};
+    void* post = nullptr;           // the post stage's buffers (rt_denoise.hip owns them: rt_post_free)
 };
 
 int ensure(rt_context* c, DevBuf& b, size_t bytes)
@@ -1823,6 +1825,7 @@ void destroy_one(Backend* b)
         if (b->fev[l]) (void)hipEventDestroy(b->fev[l]);
         if (b->hev[l]) (void)hipEventDestroy(b->hev[l]);
     }
+    if (b->post) rt_post_free(b->post);
     if (b->h_fviews) (void)hipHostFree(b->h_fviews);
     if (b->fev_done) (void)hipEventDestroy(b->fev_done);
     if (b->fs) (void)hipStreamDestroy(b->fs);
@@ -2863,6 +2866,18 @@ int rt_backend_intersect(rt_context* c, const float* rays, int n, void* out)
     HIPCHK(c, hipEventElapsedTime(&ms, b->ev0, b->ev1));
     c->last_kernel_ms = ms;
     HIPCHK(c, hipMemcpy(out, dout, bo, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+// The root device's state for the post stage (rt_denoise.hip).
+int rt_backend_root(rt_context* c, RtRootDev* out)
+{
+    Backend* b = be(c);
+    out->device = b->device;
+    out->view = &b->view;
+    out->ev0 = b->ev0;
+    out->ev1 = b->ev1;
+    out->post = &b->post;
     return RT_OK;
 }
 

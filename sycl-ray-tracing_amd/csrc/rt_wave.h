@@ -332,18 +332,27 @@ RT_HD void store_path(const WaveView& W, int p, const PathReg& P, bool fin_chang
     if (fin_changed) W.p_fin[p] = f4(P.fin, 0.0f);
 }
 
+// get_camera_ray (render_kernel.cpp:56-73) for the jittered pixel position (xj, yj) of a
+// w x h frame; cam_o and aspect are the frame's constants (set_view_consts). Shared by the
+// render's samples (camera_ray) and the first-hit feature pass (rt_denoise.h).
+RT_HD void camera_ray_at(const RtCamera& cam, const float* cam_o, float aspect, int w, int h, float xj, float yj,
+                         V3& o, V3& d)
+{
+    float xn = xj / (float)w * 2.0f - 1.0f;
+    xn *= aspect;
+    float yn = yj / (float)h * 2.0f - 1.0f;
+    o = v3(cam_o[0], cam_o[1], cam_o[2]);
+    const V3 pd = xform_point(cam, v3(xn, yn, cam.fov_dist));
+    d = normalize(sub(pd, o));
+}
+
 // Camera ray of a sample (render_kernel.cpp:88-92, get_camera_ray :56-73): the two
 // jitter draws from rng, then the ray.
 RT_HD void camera_ray(const WaveView& W, int x, int y, Rng& rng, V3& o, V3& d)
 {
     float xj = ((float)x + 0.5f) + rng.next() - 1.0f;
     float yj = ((float)y + 0.5f) + rng.next() - 1.0f;
-    float xn = xj / (float)W.W * 2.0f - 1.0f;
-    xn *= W.aspect;
-    float yn = yj / (float)W.H * 2.0f - 1.0f;
-    o = v3(W.cam_o[0], W.cam_o[1], W.cam_o[2]);
-    const V3 pd = xform_point(W.cam, v3(xn, yn, W.cam.fov_dist));
-    d = normalize(sub(pd, o));
+    camera_ray_at(W.cam, W.cam_o, W.aspect, W.W, W.H, xj, yj, o, d);
 }
 
 // The next sample's camera ray, traced ahead. A sample's draws all happen at its

@@ -24,12 +24,13 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
+from ._capi import DenoiseParams  # noqa: F401
 from ._capi import (RT_ERR_ARG, RT_ERR_HIP, RT_ERR_IO, RT_ERR_NODEV, RT_ERR_STATE, RT_OK,  # noqa: F401
                     RtError, check, lib, ptr)
 
 __all__ = ["Camera", "Image", "ParsedOBJ", "parse_obj", "compute_env_map_cdf", "luminance_of_pixels", "BVH",
            "RenderKernel", "RtError", "octree_dump", "make_materials", "read_image_float", "write_image_png",
-           "image_to_rgba8"]
+           "image_to_rgba8", "DenoiseParams", "denoise_default_params"]
 
 
 # ------------------------------------------------------------------ camera
@@ -122,6 +123,26 @@ def write_image_png(image: Image, filename: str, flipY: bool = True) -> bool:
     check(lib(), lib().rt_write_png(filename.encode(), ptr(image.pixels), image.width, image.height, int(flipY)), None,
           f"write_image_png({filename})")
     return True
+
+
+def denoise_default_params(hostsim: bool = False) -> DenoiseParams:
+    """rt_denoise_default_params: the à-trous filter's defaults (passes and the four sigmas)."""
+    p = DenoiseParams()
+    lib(hostsim).rt_denoise_default_params(ctypes.byref(p))
+    return p
+
+
+def _denoise_params(L_, params) -> DenoiseParams:
+    """params: None (defaults), a DenoiseParams, or a dict of its fields over the defaults."""
+    if isinstance(params, DenoiseParams):
+        return params
+    p = DenoiseParams()
+    L_.rt_denoise_default_params(ctypes.byref(p))
+    for k, v in (params or {}).items():
+        if k not in dict(DenoiseParams._fields_):
+            raise TypeError(f"unknown denoise parameter {k}")
+        setattr(p, k, v)
+    return p
 
 
 # --------------------------------------------------------------------- OBJ
@@ -273,6 +294,61 @@ class RenderKernel:
                                               self.max_bounces, ctypes.c_void_p(d_fb), row_offset, row_stride,
                                               ctypes.c_void_p(stream) if stream else None), self.ctx,
               "rt_render_device")
+
+    # ---- post stage (what replaces Utils::OIDN_denoise, utils.cpp:144-196)
+    def camera_rays(self) -> np.ndarray:
+        """rt_camera_rays: the feature pass's rays, [h, w, 6] = origin, direction (host only)."""
+        rays = np.empty((self.height, self.width, 6), np.float32)
+        check(self.L, self.L.rt_camera_rays(self.ctx, self.width, self.height, ptr(rays)), self.ctx, "rt_camera_rays")
+        return rays
+
+    def features(self):
+        """rt_render_features: (albedo, normal_depth), each [h, w, 4] float32: the first hit of
+        every pixel's centre ray, {diffuse rgb, 0} and {n.xyz, t} (miss: zeros and t = -1)."""
+        self._sync_materials()
+        alb = np.empty((self.height, self.width, 4), np.float32)
+        nd = np.empty_like(alb)
+        check(self.L, self.L.rt_render_features(self.ctx, self.width, self.height, ptr(alb), ptr(nd)), self.ctx,
+              "rt_render_features")
+        return alb, nd
+
+    def features_device(self, d_albedo: int, d_normal_depth: int, stream: int | None = None):
+        """rt_render_features_device: the same into device buffers (w*h*4 floats each); no wait."""
+        self._sync_materials()
+        check(self.L, self.L.rt_render_features_device(self.ctx, self.width, self.height, ctypes.c_void_p(d_albedo),
+                                                       ctypes.c_void_p(d_normal_depth),
+                                                       ctypes.c_void_p(stream) if stream else None), self.ctx,
+              "rt_render_features_device")
+
+    def denoise(self, image: Image | None = None, blend_factor: float = 1.0, guides=True, params=None) -> Image:
+        """The call shape of Utils::OIDN_denoise(image, blend_factor): a new Image,
+        blend_factor * filtered + (1 - blend_factor) * image, alpha 1. image: default the frame
+        buffer. guides: True renders the feature buffers for the bound camera, False filters
+        on colour alone, or an (albedo, normal_depth) pair from features(). params: None, a
+        DenoiseParams or a dict of its fields."""
+        image = self.frame_buffer if image is None else image
+        src = np.ascontiguousarray(image.pixels, dtype=np.float32)
+        h, w = src.shape[:2]
+        alb = nd = None
+        if guides is True:
+            assert (w, h) == (self.width, self.height), "guides are rendered at the kernel's own size"
+            alb, nd = self.features()
+        elif guides:
+            alb, nd = (np.ascontiguousarray(g, dtype=np.float32).reshape(h, w, 4) for g in guides)
+        out = Image(w, h)
+        p = _denoise_params(self.L, params)
+        check(self.L, self.L.rt_denoise(self.ctx, w, h, ptr(src), ptr(alb), ptr(nd), ctypes.byref(p),
+                                        float(blend_factor), ptr(out.pixels)), self.ctx, "rt_denoise")
+        return out
+
+    def denoise_device(self, d_in: int, d_out: int, d_albedo: int | None = None, d_normal_depth: int | None = None,
+                       blend_factor: float = 1.0, params=None, stream: int | None = None, width=None, height=None):
+        """rt_denoise_device: device buffers (w*h*4 floats each), no wait."""
+        p = _denoise_params(self.L, params)
+        vp = lambda a: ctypes.c_void_p(a) if a else None  # noqa: E731
+        check(self.L, self.L.rt_denoise_device(self.ctx, int(width or self.width), int(height or self.height), vp(d_in),
+                                               vp(d_albedo), vp(d_normal_depth), ctypes.byref(p), float(blend_factor),
+                                               vp(d_out), vp(stream)), self.ctx, "rt_denoise_device")
 
     def render_variants(self, materials, frames=None, device_ptrs=None, row_offset: int = 0, row_stride: int = 1):
         """rt_render_variants: the material sweep as replicas. `materials` is

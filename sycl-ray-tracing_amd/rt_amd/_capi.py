@@ -26,6 +26,8 @@ EXPORTS = [
     "rt_set_intersect_mode", "rt_create_multi", "rt_device_count", "rt_set_materials", "rt_render_variants",
     "rt_create_multi_loopback", "rt_test_create_multi_rccl", "rt_test_fail_device", "rt_test_schedule", "rt_test_walk_log",
     "rt_test_walk_log_read", "rt_test_obj_parallel_min",
+    "rt_camera_rays", "rt_render_features", "rt_render_features_device", "rt_denoise_default_params", "rt_denoise",
+    "rt_denoise_device",
 ]
 
 # return codes (include/rt_hip.h)
@@ -35,6 +37,13 @@ P = ctypes.c_void_p
 I = ctypes.c_int
 L = ctypes.c_long
 F = ctypes.c_float
+
+
+class DenoiseParams(ctypes.Structure):
+    """struct rt_denoise_params (include/rt_hip.h)."""
+    _fields_ = [("passes", ctypes.c_int), ("sigma_color", F), ("sigma_normal", F), ("sigma_albedo", F),
+                ("sigma_depth", F)]
+
 
 _SIGS = {
     "rt_create": (I, [I, ctypes.POINTER(P)]),
@@ -78,6 +87,12 @@ _SIGS = {
     "rt_read_hdr": (I, [ctypes.c_char_p, I, P, P, P]),
     "rt_write_png": (I, [ctypes.c_char_p, P, I, I, I]),
     "rt_image_to_rgba8": (I, [P, L, P]),
+    "rt_camera_rays": (I, [P, I, I, P]),
+    "rt_render_features": (I, [P, I, I, P, P]),
+    "rt_render_features_device": (I, [P, I, I, P, P, P]),
+    "rt_denoise_default_params": (None, [ctypes.POINTER(DenoiseParams)]),
+    "rt_denoise": (I, [P, I, I, P, P, P, ctypes.POINTER(DenoiseParams), F, P]),
+    "rt_denoise_device": (I, [P, I, I, P, P, P, ctypes.POINTER(DenoiseParams), F, P, P]),
     # product-only extras
     "rt_device_libm": (I, [I, I, P, P, P, I]),
     "rt_device_last_kernel_ms": (ctypes.c_double, [P]),
@@ -86,6 +101,7 @@ _SIGS = {
     "rt_device_last_iterations": (I, [P]),
     "rt_device_exact_handovers": (I, [P, P, I]),
     "rt_device_queries": (I, [P, I, P, I, I, P, P, P]),
+    "rt_device_denoise_pass_ms": (I, [P, I, P, I]),
     # hostsim-only extra
     "rt_hostsim_heap_order": (I, [P, I, P, P]),
     "rt_hostsim_fast_queries": (I, [P, P, I, P, P]),

@@ -1,0 +1,72 @@
+"""python -m rt_amd.cli [obj] --sky= --w= --h= --samples= --bounces=
+
+The reference's command line (source/main.cpp:32-61, same flags and defaults) over the
+product library: ingest, RenderKernel.render(), the denoise stage at blend 1.0 / 0.75 / 0.5
+(main.cpp:118-120) and the four PNGs (main.cpp:122-125). Also --camera=<preset> (default
+the dragon camera, main.cpp:110), --out=<directory> (default .) and --hostsim (the CPU
+build of the device code, for machines without a GPU). The filter runs once; the three
+images are blends of its output with the render (utils.cpp:184-186).
+"""
+from __future__ import annotations
+
+import os
+import sys
+import time
+
+import numpy as np
+
+import rt_amd
+
+
+def parse(argv):
+    a = dict(obj="data/OBJs/cornell_pbr.obj", sky="data/Skyspheres/evening_road_01_puresky_2k.hdr", w=512, h=512,
+             samples=64, bounces=8, camera="dragon", out=".", hostsim=False)
+    for s in argv:
+        if s == "--hostsim":
+            a["hostsim"] = True
+        elif s.startswith(("--sky=", "--camera=", "--out=")):
+            k, v = s[2:].split("=", 1)
+            a[k] = v
+        elif s.startswith(("--w=", "--h=", "--samples=", "--bounces=")):
+            k, v = s[2:].split("=", 1)
+            a[k] = int(v)
+        else:
+            a["obj"] = s  # (assuming the OBJ file path, as main.cpp:57-59)
+    return a
+
+
+def blend(filtered: rt_amd.Image, image: rt_amd.Image, factor: float) -> rt_amd.Image:
+    """utils.cpp:184-186 in float32: factor * filtered + (1 - factor) * image, alpha 1."""
+    f = np.float32(factor)
+    out = rt_amd.Image(image.width, image.height)
+    out.pixels[..., :3] = f * filtered.pixels[..., :3] + (np.float32(1.0) - f) * image.pixels[..., :3]
+    out.pixels[..., 3] = 1.0
+    return out
+
+
+def main(argv=None) -> int:
+    a = parse(sys.argv[1:] if argv is None else argv)
+    print(f"Reading OBJ {a['obj']} ...")
+    P = rt_amd.parse_obj(a["obj"])
+    print(f"Reading Environment Map {a['sky']} ...")
+    sky = rt_amd.read_image_float(a["sky"])
+    print(f"[{a['w']}x{a['h']}]: {a['samples']} samples\n")
+    t0 = time.perf_counter()
+    fb = rt_amd.Image(a["w"], a["h"])
+    rk = rt_amd.RenderKernel(a["w"], a["h"], a["samples"], a["bounces"], fb, P.triangles, P.materials,
+                             P.emissive_triangle_indices, P.material_indices, None, rt_amd.BVH(P.triangles), sky,
+                             rt_amd.compute_env_map_cdf(sky), hostsim=a["hostsim"])
+    rk.set_camera(rt_amd.Camera.preset(a["camera"]))
+    rk.render()
+    print(f"{int((time.perf_counter() - t0) * 1e3)}ms")
+    with np.errstate(all="ignore"):
+        filtered = rk.denoise(fb, 1.0)
+        os.makedirs(a["out"], exist_ok=True)
+        rt_amd.write_image_png(fb, os.path.join(a["out"], "RT_output.png"))
+        for factor, name in ((1.0, "1"), (0.75, "0.75"), (0.5, "0.5")):
+            rt_amd.write_image_png(blend(filtered, fb, factor), os.path.join(a["out"], f"RT_output_denoised_{name}.png"))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
