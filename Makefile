@@ -47,7 +47,12 @@ $(OBJ)/rt_denoise.o: $(SRC)/rt_denoise.hip $(HDRS)
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(LIB)/librt_hip.so: $(OBJ)/rt_render.o $(OBJ)/rt_denoise.o $(OBJ)/rt_scene.host.o $(OBJ)/rt_imageio.host.o $(OBJ)/rt_capi_host.host.o
+# the ray queries (rt_query / rt_query_device) likewise
+$(OBJ)/rt_query.o: $(SRC)/rt_query.hip $(HDRS)
+	@mkdir -p $(OBJ)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+$(LIB)/librt_hip.so: $(OBJ)/rt_render.o $(OBJ)/rt_denoise.o $(OBJ)/rt_query.o $(OBJ)/rt_scene.host.o $(OBJ)/rt_imageio.host.o $(OBJ)/rt_capi_host.host.o
 	@mkdir -p $(LIB)
 	$(HIPCC) -shared --offload-arch=$(ARCH) -fPIC $^ -o $@
 
@@ -97,7 +102,8 @@ variant: $(OBJ)/rt_scene.host.o $(OBJ)/rt_imageio.host.o $(OBJ)/rt_capi_host.hos
 	@mkdir -p $(LIB)
 	$(HIPCC) $(HIPFLAGS) $(DEFS) -DRT_BUILD_SRC='"$(SRC_HASH)"' -DRT_BUILD_DEFS='"$(DEFS)"' -c $(SRC)/rt_render.hip -o $(OBJ)/rt_render_$(V).o
 	$(HIPCC) $(HIPFLAGS) $(DEFS) -c $(SRC)/rt_denoise.hip -o $(OBJ)/rt_denoise_$(V).o
-	$(HIPCC) -shared --offload-arch=$(ARCH) -fPIC $(OBJ)/rt_render_$(V).o $(OBJ)/rt_denoise_$(V).o $^ -o $(LIB)/librt_hip_$(V).so
+	$(HIPCC) $(HIPFLAGS) $(DEFS) -c $(SRC)/rt_query.hip -o $(OBJ)/rt_query_$(V).o
+	$(HIPCC) -shared --offload-arch=$(ARCH) -fPIC $(OBJ)/rt_render_$(V).o $(OBJ)/rt_denoise_$(V).o $(OBJ)/rt_query_$(V).o $^ -o $(LIB)/librt_hip_$(V).so
 
 # the same for the hostsim build: make hostsim-variant V=name DEFS="-DRT_SLABS=0" ->
 # lib/librt_hostsim_name.so (RT_HOSTSIM_LIB=...; study probes such as tools/far_probe.py)
@@ -131,6 +137,22 @@ build/denoise_shim_test: tests/native/denoise_shim_test.cpp include/render_kerne
 # the same drop-in linked to the product library (gfx950): built here, run on the GPU box by
 # tests/test_shim.py's gpu test (the box has no /root/reference; the binary carries what it needs)
 build/shim_test_hip: tests/native/shim_test.cpp include/render_kernel_hip.h include/rt_hip.h $(LIB)/librt_hip.so
+	@mkdir -p build
+	$(CXX) -std=gnu++20 -O2 -fopenmp -Iinclude -I$(REFDIR)/include -I$(REFDIR)/rapidobj -I$(REFDIR) $< \
+	  $(REFOBJ)/bvh.o $(REFOBJ)/flattened_bvh.o $(REFOBJ)/triangle.o $(REFOBJ)/vec.o $(REFOBJ)/color.o \
+	  $(REFOBJ)/mat.o $(REFOBJ)/camera.o $(REFOBJ)/ray.o $(REFOBJ)/utils.o -Wl,--gc-sections \
+	  -L$(LIB) -lrt_hip -Wl,-rpath,'$$ORIGIN/../$(LIB)' -o $@
+
+# the drop-in's query_closest / query_any against rt_intersect (tests/test_query_shim.py): linked to the
+# hostsim build, and (run on the GPU box) to the product library
+build/query_shim_test: tests/native/query_shim_test.cpp include/render_kernel_hip.h include/rt_hip.h $(LIB)/librt_hostsim.so
+	@mkdir -p build
+	$(CXX) -std=gnu++20 -O2 -fopenmp -Iinclude -I$(REFDIR)/include -I$(REFDIR)/rapidobj -I$(REFDIR) $< \
+	  $(REFOBJ)/bvh.o $(REFOBJ)/flattened_bvh.o $(REFOBJ)/triangle.o $(REFOBJ)/vec.o $(REFOBJ)/color.o \
+	  $(REFOBJ)/mat.o $(REFOBJ)/camera.o $(REFOBJ)/ray.o $(REFOBJ)/utils.o -Wl,--gc-sections \
+	  -L$(LIB) -lrt_hostsim -Wl,-rpath,'$$ORIGIN/../$(LIB)' -o $@
+
+build/query_shim_test_hip: tests/native/query_shim_test.cpp include/render_kernel_hip.h include/rt_hip.h $(LIB)/librt_hip.so
 	@mkdir -p build
 	$(CXX) -std=gnu++20 -O2 -fopenmp -Iinclude -I$(REFDIR)/include -I$(REFDIR)/rapidobj -I$(REFDIR) $< \
 	  $(REFOBJ)/bvh.o $(REFOBJ)/flattened_bvh.o $(REFOBJ)/triangle.o $(REFOBJ)/vec.o $(REFOBJ)/color.o \

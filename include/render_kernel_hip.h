@@ -124,12 +124,53 @@ public:
         return out;
     }
 
+    // INTERSECT_SCENE for a batch of rays through rt_query (the render's search-BVH walks, the
+    // exact walk behind them): hits[i] as BVH::intersect + the sphere loop fill it (t = -1 and
+    // primitive_index = -1 without a hit).
+    void query_closest(const std::vector<Ray>& rays, std::vector<HitInfo>& hits) const
+    {
+        std::lock_guard<std::mutex> lk(m_mu);
+        const std::vector<float> r = ray_floats(rays);
+        std::vector<int> rec(rays.size() * 11);
+        check(rt_query(m_ctx, RT_QUERY_CLOSEST, r.data(), (long)rays.size(), rec.data()));
+        hits.assign(rays.size(), HitInfo());
+        for (size_t i = 0; i < rays.size(); i++) {
+            const int* w = &rec[11 * i];
+            if (!w[0]) continue;
+            float f[7];
+            std::memcpy(f, w + 2, sizeof f);
+            hits[i].t = f[0];
+            hits[i].inter_point = Point(f[1], f[2], f[3]);
+            hits[i].normal_at_intersection = Vector(f[4], f[5], f[6]);
+            hits[i].primitive_index = w[1];
+        }
+    }
+
+    // The same as an occlusion test: hit[i] = 1 where INTERSECT_SCENE finds a hit.
+    void query_any(const std::vector<Ray>& rays, std::vector<char>& hit) const
+    {
+        std::lock_guard<std::mutex> lk(m_mu);
+        const std::vector<float> r = ray_floats(rays);
+        std::vector<int> found(rays.size());
+        check(rt_query(m_ctx, RT_QUERY_ANY, r.data(), (long)rays.size(), found.data()));
+        hit.assign(found.begin(), found.end());
+    }
+
     int device_count() const { return rt_device_count(m_ctx); }
 
 private:
     static void check(int rc)
     {
         if (rc != RT_OK) throw std::runtime_error(std::string("librt_hip: ") + rt_last_error(nullptr));
+    }
+
+    static std::vector<float> ray_floats(const std::vector<Ray>& rays)  // rays[n][6] = origin, direction
+    {
+        std::vector<float> r;
+        r.reserve(rays.size() * 6);
+        for (const Ray& q : rays)
+            r.insert(r.end(), {q.origin.x, q.origin.y, q.origin.z, q.direction.x, q.direction.y, q.direction.z});
+        return r;
     }
 
     std::vector<char> materials_bytes() const

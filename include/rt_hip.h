@@ -89,7 +89,8 @@ int rt_test_fail_device(rt_context* ctx, int device);
  * fast_spp x spp on), "near_scale" (the near box, scene box widened by this x its
  * largest extent: queries from outside it take the exact octree walk), "dn_variant"
  * (rt_denoise's filter kernel: 0 the product's choice per step, 1 direct loads, 2 the
- * LDS-halo tile at every step that has one), the
+ * LDS-halo tile at every step that has one), "rq_variant" (rt_query's search-BVH kernel:
+ * 0 the product's choice, 1 plain rounds of one query per quad, 2 per-quad refill), the
  * stressor "force_fallback" (every k-th query by a ray hash skips to the exact
  * octree walk), "reset"). No parameter changes a result; the product never calls
  * it and reads no schedule from the environment. RT_ERR_ARG for an unknown key or
@@ -186,6 +187,46 @@ int rt_render_pixels(rt_context* ctx, int width, int height, int samples, int ma
  * (origin, direction); out[n][11] = {found, primitive, t, point[3],
  * normal[3], u, v} with u = v = -1 (unused downstream). */
 int rt_intersect(rt_context* ctx, const float* rays, int n, void* out);
+
+/* ------------------------------------------------------------ ray queries
+ * INTERSECT_SCENE for a batch of n rays rays[n][6] (origin, direction) through the walks
+ * the render uses: visibility, ambient-occlusion, depth or picking rays from the caller's
+ * own buffers. Answers are rt_intersect's, bit for bit; the rays keep the caller's order.
+ *
+ * Routing (the render's policy): a query whose origin lies inside the near box (the
+ * scene's box widened on every side by half its largest extent) takes the search-BVH
+ * walk, four lanes per query; a walk that does not settle (a tie between octree leaves,
+ * a failed octree chain check, an overflow of the bounded stack) hands its query to the
+ * exact octree walk, as do all queries from outside the near box. A context with
+ * spheres, or in rt_set_intersect_mode(0), sends every query to the exact walk, and so
+ * does the flag RT_QUERY_EXACT. The shell limit of DESIGN.md §4 applies as it does to
+ * the render: from origins inside the near box but far outside the scene's box, the
+ * search-BVH walk can miss a grazing hit that the exact walk finds. A caller that needs
+ * the exact walk's answer for every origin passes RT_QUERY_EXACT.
+ *
+ * There is no t_max: the reference's shadow test is the closest hit followed by
+ * `t + 1e-4 < t_max` (render_kernel.cpp:744-759), and the render's occlusion walk has
+ * no distance either. A distance-limited test is RT_QUERY_CLOSEST plus that comparison
+ * on word 2 of the record.
+ *
+ * rt_query: host buffers; uploads, runs, waits, downloads; rt_last_kernel_ms is the
+ * kernels' time. rt_query_device: device buffers on `stream` (NULL: default), returns
+ * without waiting; rt_last_kernel_ms is -1 and rt_device_last_kernel_ms reads the
+ * events once the stream is synchronized. The workspace (the fallback list) belongs to
+ * the context and grows when n does; calls on one context must not overlap in time on
+ * different streams. A multi-device context runs queries on its root device (where
+ * d_rays, d_out and stream live) and restores the caller's current device.
+ * rt_query_last_exact: how many queries of the last call took the exact walk; waits for
+ * that call. RT_ERR_STATE without scene and BVH; RT_ERR_ARG for an unknown mode, n < 0,
+ * n >= 2^27 or a NULL buffer with n > 0; n == 0 is RT_OK and launches nothing. NaN and
+ * zero-direction rays answer as rt_intersect answers them (no hit). */
+#define RT_QUERY_CLOSEST 0   /* out[n][11], rt_intersect's record, bit for bit */
+#define RT_QUERY_ANY     1   /* out[n] int32: 1 if INTERSECT_SCENE finds a hit, else 0
+                                (the `found` word of rt_intersect) */
+#define RT_QUERY_EXACT   0x100 /* flag: every query takes the exact walk */
+int rt_query(rt_context* ctx, int mode, const float* rays /*[n][6]*/, long n, void* out);
+int rt_query_device(rt_context* ctx, int mode, const void* d_rays, long n, void* d_out, void* stream);
+long rt_query_last_exact(rt_context* ctx); /* queries of the last call that took the exact walk; waits */
 
 /* USE_BVH (render_kernel.h:13, render_kernel.cpp:504-511): 1 (the reference's
  * build, the default) answers INTERSECT_SCENE with the octree walk

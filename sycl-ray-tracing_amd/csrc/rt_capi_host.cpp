@@ -237,6 +237,7 @@ int rt_test_schedule(rt_context* c, const char* key, double value)
     else if (k == "fast_spp") s.fast_spp = value;
     else if (k == "near_scale") s.near_scale = value;
     else if (k == "dn_variant") s.dn_variant = std::max(0, std::min(2, v));
+    else if (k == "rq_variant") s.rq_variant = std::max(0, std::min(2, v));
     else if (k == "reset") s = RtSchedule{};
     else return rt_fail(c, RT_ERR_ARG, "rt_test_schedule: unknown key " + k);
     return RT_OK;
@@ -509,6 +510,63 @@ int rt_intersect(rt_context* c, const float* rays, int n, void* out)
         c->mats_dirty_only = false;
     }
     return rt_backend_intersect(c, rays, n, out);
+}
+
+// ------------------------------------------------------------ ray queries
+static int query_ready(rt_context* c, const char* fn, int mode, const void* rays, long n, const void* out)
+{
+    const std::string f = fn;
+    if (!c) return rt_fail(nullptr, RT_ERR_ARG, f + ": ctx is NULL");
+    if (!c->have_scene || !c->have_bvh) return rt_fail(c, RT_ERR_STATE, f + ": scene/BVH not set");
+    const int m = mode & ~RT_QUERY_EXACT;
+    if (m != RT_QUERY_CLOSEST && m != RT_QUERY_ANY) return rt_fail(c, RT_ERR_ARG, f + ": unknown mode");
+    if (n < 0) return rt_fail(c, RT_ERR_ARG, f + ": n is negative");
+    if (n >= (1L << 27)) return rt_fail(c, RT_ERR_ARG, f + ": n must be below 2^27");
+    if (n > 0 && (!rays || !out)) return rt_fail(c, RT_ERR_ARG, f + ": a buffer is NULL");
+    if (n == 0) {
+        c->query_exact = 0;
+        c->query_on_device = false;
+        return RT_OK;
+    }
+    if (c->dirty) {
+        if (!c->have_env) {
+            // a 1x1 black env keeps the device view valid for ray queries (as rt_intersect)
+            const float z[3] = {0, 0, 0};
+            rt_set_env(c, z, 1, 1, 3, nullptr);
+        }
+        if (int r = rt_backend_upload(c)) return r;
+        c->dirty = false;
+        c->mats_dirty_only = false;
+    }
+    return RT_OK;
+}
+
+// Spheres and the brute-force mode take k_intersect's path for every query (rt_query.h).
+static bool query_all_exact(const rt_context* c, int mode)
+{
+    return (mode & RT_QUERY_EXACT) != 0 || !c->spheres.empty() || c->brute;
+}
+
+int rt_query(rt_context* c, int mode, const float* rays, long n, void* out)
+{
+    if (int r = query_ready(c, "rt_query", mode, rays, n, out)) return r;
+    if (n == 0) return RT_OK;
+    return rt_backend_query(c, (mode & ~RT_QUERY_EXACT) == RT_QUERY_ANY, query_all_exact(c, mode), rays, n, out, false,
+                            nullptr);
+}
+
+int rt_query_device(rt_context* c, int mode, const void* d_rays, long n, void* d_out, void* stream)
+{
+    if (int r = query_ready(c, "rt_query_device", mode, d_rays, n, d_out)) return r;
+    if (n == 0) return RT_OK;
+    return rt_backend_query(c, (mode & ~RT_QUERY_EXACT) == RT_QUERY_ANY, query_all_exact(c, mode), d_rays, n, d_out,
+                            true, stream);
+}
+
+long rt_query_last_exact(rt_context* c)
+{
+    if (!c) return rt_fail(nullptr, RT_ERR_ARG, "rt_query_last_exact: ctx is NULL");
+    return rt_backend_query_last_exact(c);
 }
 
 // ------------------------------------------------------------- post stage

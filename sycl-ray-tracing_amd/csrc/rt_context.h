@@ -35,6 +35,7 @@ struct RtSchedule {
     double near_scale = -1.0;  // near box: the scene's box widened by this x its largest extent (rt_view_near;
                                // study probes only: answers never depend on it, only which walk gives them)
     int dn_variant = 0;        // rt_denoise's filter kernel: 0 per step as measured, 1 direct, 2 LDS tile where built
+    int rq_variant = 0;        // rt_query's fast kernel: 0 as measured, 1 plain grid-stride rounds, 2 per-quad refill
 };
 
 // Diagnostics, read from the environment once when the context is created (rt_create*):
@@ -91,6 +92,8 @@ struct rt_context {
     bool stats_seq = false;       // rt_set_stats(ctx, 2): occlusion walks unpaired (gfx950), see rt_hip.h
     unsigned long long stats[2 * RT_STAT_COUNT] = {};  // all kernels, then the gfx950 tail kernel's share
     double last_kernel_ms = 0.0;
+    long query_exact = 0;         // rt_query_last_exact: the last call's exact-walk count where the host knows it,
+    bool query_on_device = false; // ... else (gfx950, a routed call) it is read from the device's fallback counter
 
     bool dirty = true;            // host state changed since the last upload
     bool mats_dirty_only = false; // only the material table changed (rt_set_materials)
@@ -117,6 +120,14 @@ int rt_backend_features(rt_context* ctx, int w, int h, void* albedo, void* norma
 // alb and nd both null: colour only. p is validated (rt_capi_host.cpp).
 int rt_backend_denoise(rt_context* ctx, int w, int h, const void* in, const void* alb, const void* nd,
                        const rt_denoise_params& p, float blend, void* out, bool device, void* stream);
+
+// The ray queries (rt_query.h): n > 0 rays[n][6] -> out (closest: int32[n][11], any: int32[n]);
+// all_exact: every query takes the exact walk. device = false: host buffers, synchronous;
+// true: device buffers on `stream`, no wait (hostsim: host pointers, stream unused).
+int rt_backend_query(rt_context* ctx, bool any, bool all_exact, const void* rays, long n, void* out, bool device,
+                     void* stream);
+// Queries of the last rt_backend_query that took the exact walk (waits for them); < 0: an error.
+long rt_backend_query_last_exact(rt_context* ctx);
 
 int rt_fail(rt_context* ctx, int code, const std::string& msg);
 // RtDiag from the environment (rt_create*)

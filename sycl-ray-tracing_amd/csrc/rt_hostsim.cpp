@@ -16,6 +16,7 @@
 
 #include "rt_context.h"
 #include "rt_denoise.h"
+#include "rt_query.h"
 #include "rt_wave.h"
 
 // Stack window and step budget of the host build: smaller than the
@@ -453,6 +454,51 @@ int rt_backend_denoise(rt_context* c, int w, int h, const void* in, const void* 
     c->last_kernel_ms = (omp_get_wtime() - t0) * 1e3;
     return RT_OK;
 }
+
+// The ray queries on the host (rt_query.h): the routing of the gfx950 kernels (rt_query.hip)
+// with the one-lane search-BVH walks of rt_fast.h in the quads' place; fast_query_closest /
+// fast_query_any test far_origin themselves and say when the exact walk must answer.
+int rt_backend_query(rt_context* c, bool any, bool all_exact, const void* rays_v, long n, void* out_v, bool, void*)
+{
+    const RtSceneView S = rt_host_view(c);
+    const float* rays = (const float*)rays_v;
+    int32_t* out = (int32_t*)out_v;
+    long exact = 0;
+    const double t0 = omp_get_wtime();
+#pragma omp parallel reduction(+ : exact)
+    {
+        std::vector<rtk::StackEnt> stack(RT_STACK_CAP);
+        rtk::IdxStack<RT_HOSTSIM_FAST_CAP> fst;
+#pragma omp for schedule(dynamic, 64)
+        for (long i = 0; i < n; i++) {
+            const float* r = rays + 6 * (size_t)i;
+            const rtk::V3 o = rtk::v3(r[0], r[1], r[2]), d = rtk::v3(r[3], r[4], r[5]);
+            bool settled = false;
+            if (!all_exact) {
+                if (any) {
+                    const int a = rtk::fast_query_any(S, o, d, fst, nullptr);
+                    settled = a >= 0;
+                    if (settled) out[i] = a;
+                } else {
+                    float t;
+                    int k;
+                    settled = rtk::fast_query_closest(S, o, d, fst, t, k, nullptr);
+                    if (settled) rtk::rq_closest_record(S, o, d, t, k, out + RQ_WORDS * (size_t)i);
+                }
+            }
+            if (!settled) {
+                rtk::rq_exact(S, rays, (size_t)i, any, stack.data(), out);
+                exact++;
+            }
+        }
+    }
+    c->last_kernel_ms = (omp_get_wtime() - t0) * 1e3;
+    c->query_exact = exact;
+    c->query_on_device = false;
+    return RT_OK;
+}
+
+long rt_backend_query_last_exact(rt_context* c) { return c->query_exact; }
 
 // The search-BVH closest-hit query the render's k_trace stage runs (rt_fast.h
 // fast_query_closest, with its verification), for tests/test_hostsim.py: out_t = the

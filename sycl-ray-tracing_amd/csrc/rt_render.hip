@@ -208,6 +208,7 @@ struct Backend {
     double kms[3] = {0, 0, 0};      // k_trace, k_step, k_tail
     long klaunch[3] = {0, 0, 0};
     void* post = nullptr;           // the post stage's buffers (rt_denoise.hip owns them: rt_post_free)
+    void* query = nullptr;          // the ray-query workspace (rt_query.hip owns it: rt_query_free)
 };
 
 int ensure(rt_context* c, DevBuf& b, size_t bytes)
@@ -1826,6 +1827,7 @@ void destroy_one(Backend* b)
         if (b->hev[l]) (void)hipEventDestroy(b->hev[l]);
     }
     if (b->post) rt_post_free(b->post);
+    if (b->query) rt_query_free(b->query);
     if (b->h_fviews) (void)hipHostFree(b->h_fviews);
     if (b->fev_done) (void)hipEventDestroy(b->fev_done);
     if (b->fs) (void)hipStreamDestroy(b->fs);
@@ -2878,6 +2880,7 @@ int rt_backend_root(rt_context* c, RtRootDev* out)
     out->ev0 = b->ev0;
     out->ev1 = b->ev1;
     out->post = &b->post;
+    out->query = &b->query;
     return RT_OK;
 }
 

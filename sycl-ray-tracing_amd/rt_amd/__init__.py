@@ -24,6 +24,7 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
+from . import _capi
 from ._capi import DenoiseParams  # noqa: F401
 from ._capi import (RT_ERR_ARG, RT_ERR_HIP, RT_ERR_IO, RT_ERR_NODEV, RT_ERR_STATE, RT_OK,  # noqa: F401
                     RtError, check, lib, ptr)
@@ -397,6 +398,39 @@ class RenderKernel:
         out = np.zeros((rays.shape[0], 11), dtype=np.int32)
         check(self.L, self.L.rt_intersect(self.ctx, ptr(rays), rays.shape[0], ptr(out)), self.ctx, "rt_intersect")
         return out
+
+    # ---- batched ray queries (rt_query: the render's search-BVH walks, the exact walk behind them)
+    def _query_mode(self, mode, exact) -> int:
+        modes = {"closest": _capi.QUERY_CLOSEST, "any": _capi.QUERY_ANY}
+        if mode not in modes:
+            raise ValueError(f"query mode {mode!r}: 'closest' or 'any'")
+        return modes[mode] | (_capi.QUERY_EXACT if exact else 0)
+
+    def query(self, rays, mode: str = "closest", exact: bool = False) -> np.ndarray:
+        """rt_query on rays [n, 6] = origin, direction, in the caller's order. mode "closest":
+        int32 [n, 11], intersect()'s record bit for bit ({found, primitive, t, point, normal,
+        u, v}; .view(np.float32) for the float words); "any": int32 [n], its `found` word.
+        exact=True sends every query down the exact walk (RT_QUERY_EXACT)."""
+        m = self._query_mode(mode, exact)
+        rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
+        n = rays.shape[0]
+        out = np.zeros((n, 11) if mode == "closest" else (n,), dtype=np.int32)
+        check(self.L, self.L.rt_query(self.ctx, m, ptr(rays), n, ptr(out)), self.ctx, "rt_query")
+        return out
+
+    def query_device(self, d_rays: int, n: int, d_out: int, mode: str = "closest", exact: bool = False,
+                     stream: int | None = None):
+        """rt_query_device: device buffers (n*6 floats in, n*11 or n int32 out) on `stream`; no wait."""
+        vp = lambda a: ctypes.c_void_p(a) if a else None  # noqa: E731
+        check(self.L, self.L.rt_query_device(self.ctx, self._query_mode(mode, exact), vp(d_rays), int(n), vp(d_out),
+                                             vp(stream)), self.ctx, "rt_query_device")
+
+    def query_last_exact(self) -> int:
+        """rt_query_last_exact: queries of the last query call that took the exact walk (waits)."""
+        r = int(self.L.rt_query_last_exact(self.ctx))
+        if r < 0:
+            check(self.L, r, self.ctx, "rt_query_last_exact")
+        return r
 
     def set_use_bvh(self, use_bvh: bool = True):
         """USE_BVH (render_kernel.h:13): False switches INTERSECT_SCENE to the

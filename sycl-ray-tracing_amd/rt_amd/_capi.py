@@ -28,6 +28,7 @@ EXPORTS = [
     "rt_test_walk_log_read", "rt_test_obj_parallel_min",
     "rt_camera_rays", "rt_render_features", "rt_render_features_device", "rt_denoise_default_params", "rt_denoise",
     "rt_denoise_device",
+    "rt_query", "rt_query_device", "rt_query_last_exact",
 ]
 
 # return codes (include/rt_hip.h)
@@ -73,6 +74,9 @@ _SIGS = {
     "rt_render_pixels": (I, [P, I, I, I, I, P, I, P]),
     "rt_render_variants": (I, [P, I, I, I, I, I, P, I, I, I, P, P]),
     "rt_intersect": (I, [P, P, I, P]),
+    "rt_query": (I, [P, I, P, L, P]),
+    "rt_query_device": (I, [P, I, P, L, P, P]),
+    "rt_query_last_exact": (L, [P]),
     "rt_set_stats": (I, [P, I]),
     "rt_set_intersect_mode": (I, [P, I]),
     "rt_get_stats": (I, [P, P, I]),
@@ -106,6 +110,9 @@ _SIGS = {
     "rt_hostsim_heap_order": (I, [P, I, P, P]),
     "rt_hostsim_fast_queries": (I, [P, P, I, P, P]),
 }
+
+# rt_query modes (include/rt_hip.h)
+QUERY_CLOSEST, QUERY_ANY, QUERY_EXACT = 0, 1, 0x100
 
 STAT_NAMES = ["rays", "vol", "tri", "leaf", "mat", "env", "cdf", "heap_slow", "any_rays", "any_vol", "any_tri",
               "any_leaf", "verify", "fallback", "quad_visits", "wave_slots", "refills", "drain_slots", "drain_visits",
