@@ -529,6 +529,69 @@ extern "C" int rt_hostsim_fast_queries(rt_context* c, const float* rays, int n, 
     return RT_OK;
 }
 
+// What the leaf visits of a ray's occlusion walk meet (tests/test_trace_fixed_cost.py selects its
+// rays by these): the whole search BVH under the ray's boxes is walked, no early exit, and every
+// leaf (a pack of up to four triangles, one per lane of a quad) is classified by the lanes whose
+// Moller-Trumbore test hits and by their octree leaves. out[n][4]:
+//   [0] the most hit lanes in one pack
+//   [1] packs with two or more hit lanes in one octree leaf
+//   [2] packs whose hit lanes lie in different octree leaves
+//   [3] of those, packs where the first hit lane's leaf fails its chain check (a second check runs)
+extern "C" int rt_hostsim_leaf_hits(rt_context* c, const float* rays, int n, int* out)
+{
+    if (!c || n < 0 || (n > 0 && (!rays || !out))) return RT_ERR_ARG;
+    if (!c->have_bvh) return RT_ERR_STATE;
+    const RtSceneView S = rt_host_view(c);
+#pragma omp parallel
+    {
+        std::vector<int> stack;
+#pragma omp for schedule(dynamic, 64)
+        for (int i = 0; i < n; i++) {
+            const float* r = rays + 6 * (size_t)i;
+            const rtk::V3 o = rtk::v3(r[0], r[1], r[2]), d = rtk::v3(r[3], r[4], r[5]);
+            int* w = out + 4 * (size_t)i;
+            w[0] = w[1] = w[2] = w[3] = 0;
+            if (rt_isnan(o.x) || rt_isnan(o.y) || rt_isnan(o.z) || rt_isnan(d.x) || rt_isnan(d.y) || rt_isnan(d.z)) continue;
+            const rtk::RayB rb = rtk::rayb_setup(o, d);
+            rtk::RayK K;
+            rtk::ray_setup(o, d, K);
+            stack.assign(1, 0);
+            while (!stack.empty()) {
+                const int cur = stack.back();
+                stack.pop_back();
+                rtk::ItemRecs R;
+                rtk::load_item(S, cur, R);
+                if (cur >= 0) {
+                    const rtk::Bvh4R nd = rtk::node_of(R);
+                    float tn[4];
+                    bool hit[4];
+                    rtk::box4(S, cur, nd, rb, o, d, __builtin_inff(), tn, hit);
+                    for (int ch = 0; ch < 4; ch++)
+                        if (hit[ch]) stack.push_back(nd.cnt[ch] > 0 ? rtk::leaf_item(nd.ref[ch], nd.cnt[ch]) : nd.ref[ch]);
+                    continue;
+                }
+                const int cnt = ((~cur) & 3) + 1;
+                int leaves[4], nh = 0;
+                for (int j = 0; j < cnt; j++) {
+                    float t;
+                    if (rtk::tri_test_v(rtk::ld3(R.q[3 * j]), rtk::ld3(R.q[3 * j + 1]), rtk::ld3(R.q[3 * j + 2]), o, d, t))
+                        leaves[nh++] = (int)rt_asuint(R.q[3 * j + 1].w);
+                }
+                if (nh > w[0]) w[0] = nh;
+                bool same = false, other = false;
+                for (int a = 0; a < nh; a++)
+                    for (int b = a + 1; b < nh; b++) (leaves[a] == leaves[b] ? same : other) = true;
+                if (same) w[1]++;
+                if (other) {
+                    w[2]++;
+                    if (!rtk::chain_ok(S, K, leaves[0], false, 0.0f, nullptr)) w[3]++;
+                }
+            }
+        }
+    }
+    return RT_OK;
+}
+
 // Heap-order emulation self-check against std::priority_queue (exported for
 // tests/test_hostsim.py): keys[m] in push order -> order[m] of pushed indices.
 #include <queue>

@@ -160,8 +160,14 @@ __device__ __forceinline__ float quad_tri(const RtSceneView& S, int item, int su
 // starts at -inf / +inf, so the combination order does not change the result
 // (a +-0 can differ in sign, and only ever meets comparisons). rec is
 // quad-uniform; the answer is returned to every lane.
-__device__ __forceinline__ bool quad_chain_ok(const RtSceneView& S, V3 o, V3 d, int rec, bool need_t2, float t2,
-                                              int sub, Stats* st)
+//
+// The lane's terms of the ray alone (ray_setup's: plane normal . origin, 1 / (normal . direction))
+// are a ChainRay, computed once for every record checked against the same ray.
+struct ChainRay {
+    float num0, num1;
+    double r0, r1;
+};
+__device__ __forceinline__ ChainRay quad_chain_ray(V3 o, V3 d, int sub)
 {
     const float s3 = rt_sqrtf(3.0f) / 3;
     // the 7 plane normals of bvh.cpp:8-16 (ray_setup), selected without a private array
@@ -171,8 +177,17 @@ __device__ __forceinline__ bool quad_chain_ok(const RtSceneView& S, V3 o, V3 d, 
     };
     const int p0 = sub, p1 = sub + 4;  // p1 == 7: none
     const V3 n0 = normal(p0), n1 = normal(p1 < 7 ? p1 : 0);
-    const float num0 = dot(n0, o), num1 = dot(n1, o);
-    const double r0 = 1.0 / (double)dot(n0, d), r1 = 1.0 / (double)dot(n1, d);
+    ChainRay c;
+    c.num0 = dot(n0, o), c.num1 = dot(n1, o);
+    c.r0 = 1.0 / (double)dot(n0, d), c.r1 = 1.0 / (double)dot(n1, d);
+    return c;
+}
+__device__ __forceinline__ bool quad_chain_ok(const RtSceneView& S, const ChainRay& cr, int rec, bool need_t2, float t2,
+                                              int sub, Stats* st)
+{
+    const int p0 = sub, p1 = sub + 4;  // p1 == 7: none
+    const float num0 = cr.num0, num1 = cr.num1;
+    const double r0 = cr.r0, r1 = cr.r1;
     for (;;) {
         if (st && sub == 0) st->c[RT_STAT_VERIFY]++;
         const float* nd = (const float*)(S.nodes + rec);  // RtNode: dn[7], df[7], ref, cnt
@@ -208,6 +223,11 @@ __device__ __forceinline__ bool quad_chain_ok(const RtSceneView& S, V3 o, V3 d, 
         if (S.chain_monotone) return true;
         rec = par;
     }
+}
+__device__ __forceinline__ bool quad_chain_ok(const RtSceneView& S, V3 o, V3 d, int rec, bool need_t2, float t2,
+                                              int sub, Stats* st)
+{
+    return quad_chain_ok(S, quad_chain_ray(o, d, sub), rec, need_t2, t2, sub, st);
 }
 
 // A quad's walk, one trip per quad_visit call and specialized by kind (ANY: an
@@ -264,10 +284,22 @@ __device__ __forceinline__ bool qstate_begin(QState& q, V3 o, V3 d, int sub, Sta
 #ifndef RT_POP_PAIRED
 #define RT_POP_PAIRED 1
 #endif
-template <bool ANY, int DESC = RT_VISIT_DESCEND, bool PAIR = true, class QSTK>
+// BRUTE (USE_BVH 0 scenes: a leaf's hits need no octree verification, ties go to the lowest
+// original index): RT_BRUTE_SCENE reads S.brute; RT_BRUTE_OFF / RT_BRUTE_ON compile one side only, and
+// with RT_BRUTE_OFF the walk neither loads nor reduces nor keeps the triangles' original indices (h.prim).
+#define RT_BRUTE_SCENE (-1)
+#define RT_BRUTE_OFF 0
+#define RT_BRUTE_ON 1
+template <int BRUTE>
+__device__ __forceinline__ bool scene_brute(const RtSceneView& S)
+{
+    return BRUTE == RT_BRUTE_SCENE ? S.brute != 0 : BRUTE == RT_BRUTE_ON;
+}
+template <bool ANY, int DESC = RT_VISIT_DESCEND, bool PAIR = true, int BRUTE = RT_BRUTE_SCENE, class QSTK>
 __device__ __forceinline__ int quad_visit(const RtSceneView& S, QState& q, QSTK& stk, int sub, Stats* st)
 {
     FastHit& h = q.h;
+    const bool brute = scene_brute<BRUTE>(S);
 #pragma unroll 1
     for (int dd = 0; dd < DESC && q.cur >= 0; dd++) {
         if (ANY) {
@@ -377,24 +409,30 @@ __device__ __forceinline__ int quad_visit(const RtSceneView& S, QState& q, QSTK&
         const float tv = quad_tri<!ANY>(S, q.cur, sub, q.o, q.d, k, leaf, prim);
         if (ANY) {
             const int hitb = tv < __builtin_inff() ? 1 : 0;
-            if (S.brute) {
+            if (brute) {
                 if (qor(hitb)) {
                     h.k = 1;
                     return 1;
                 }
-            } else {
-                const int h1 = qdpp<RT_QX1>(hitb), h2 = qdpp<RT_QX2>(hitb), h3 = qdpp<RT_QX3>(hitb);
+            } else if (int hm = qor(hitb << sub)) {  // the quad's hit lanes, bit j = lane j
                 const int l1 = qdpp<RT_QX1>(leaf), l2 = qdpp<RT_QX2>(leaf), l3 = qdpp<RT_QX3>(leaf);
-#pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    const int x = j ^ sub;
-                    const int hj = x == 0 ? hitb : x == 1 ? h1 : x == 2 ? h2 : h3;
-                    if (!hj) continue;
+                // The ray's terms once for the visit's hits, and one check per octree leaf: hit lanes
+                // that share the leaf checked last share its record and its answer. One loop, not
+                // one copy of the check per lane: a wave runs it as often as its quad with the
+                // most leaves to check needs (mostly once), whichever lanes the hits are in.
+                const ChainRay cr = quad_chain_ray(q.o, q.d, sub);
+                int checked = -1;  // (a hit's leaf is a record index, >= 0)
+#pragma unroll 1
+                while (hm) {
+                    const int x = (__ffs(hm) - 1) ^ sub;
+                    hm &= hm - 1;
                     const int lj = x == 0 ? leaf : x == 1 ? l1 : x == 2 ? l2 : l3;
-                    if (quad_chain_ok(S, q.o, q.d, lj, false, 0.0f, sub, st)) {
+                    if (lj == checked) continue;
+                    if (quad_chain_ok(S, cr, lj, false, 0.0f, sub, st)) {
                         h.k = 1;
                         return 1;
                     }
+                    checked = lj;
                 }
             }
         } else {
@@ -407,10 +445,10 @@ __device__ __forceinline__ int quad_visit(const RtSceneView& S, QState& q, QSTK&
             float m2 = tv > m1 ? tv : __builtin_inff();
             m2 = __builtin_fminf(m2, qdppf<RT_QX1>(m2));
             m2 = __builtin_fminf(m2, qdppf<RT_QX2>(m2));
-            int key = tv == m1 ? (S.brute ? prim : k) : 0x7fffffff;
+            int key = tv == m1 ? (brute ? prim : k) : 0x7fffffff;
             key = min(key, qdpp<RT_QX1>(key));
             key = min(key, qdpp<RT_QX2>(key));
-            const bool mine = tv == m1 && (S.brute ? prim : k) == key;
+            const bool mine = tv == m1 && (brute ? prim : k) == key;
             const int wk = qor(mine ? k : 0), wl = qor(mine ? leaf : 0), wp = qor(mine ? prim : 0);
             const bool mixed = qor(tv == m1 && m1 < __builtin_inff() && leaf != wl ? 1 : 0) != 0;
             if (m1 < h.t) {
@@ -422,7 +460,7 @@ __device__ __forceinline__ int quad_visit(const RtSceneView& S, QState& q, QSTK&
                 h.tie = mixed;
             } else if (m1 == h.t && m1 < __builtin_inff()) {
                 h.t2 = __builtin_fminf(h.t2, m2);
-                if (S.brute) {
+                if (brute) {
                     h.tie = true;
                     if (wp < h.prim) h.k = wk, h.leaf = wl, h.prim = wp;
                 } else if (!mixed && wl == h.leaf) {
@@ -484,6 +522,7 @@ __device__ __forceinline__ int quad_visit(const RtSceneView& S, QState& q, QSTK&
 
 // The closest-hit answer of a finished walk: true with (t, k), false when the exact
 // octree walk must answer (a tie, or the verification fails: rt_fast.h).
+template <int BRUTE = RT_BRUTE_SCENE>
 __device__ __forceinline__ bool quad_closest_answer(const RtSceneView& S, const QState& q, int sub, float& t_out,
                                                     int& k_out, Stats* st)
 {
@@ -495,7 +534,7 @@ __device__ __forceinline__ bool quad_closest_answer(const RtSceneView& S, const 
     }
     // the found hit fuzzier than its box pad (rt_fast.h fuzzy_tri, marked by quad_tri)
     if (RT_FUZZ_CHECK && (h.leaf & RT_FZ_BIT)) return false;
-    if (S.brute) {
+    if (scene_brute<BRUTE>(S)) {
         t_out = h.t;
         k_out = h.k;
         return true;

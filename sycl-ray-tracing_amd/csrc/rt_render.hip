@@ -977,7 +977,8 @@ struct RowInQuadStack {
 // BVH, rt_row.h). With quads, the drain (the wave's stream out, its last long walks running
 // while the other quads idle) continues those walks as rows: same items, same stack entries
 // (the 16-wide BVH is numbered like the 4-wide one), half the trips per remaining level.
-template <bool ANY, bool STATS, bool PAIR, int G, class QSTK>
+// BRUTE: rt_quad.h (RT_BRUTE_OFF: the product's walks carry no original indices, QState.h.prim is dead).
+template <bool ANY, bool STATS, bool PAIR, int G, int BRUTE, class QSTK>
 __device__ __forceinline__ void trace_stream(const rtk::WaveView& W, const RtSceneView& S, QSTK& stk, const int* s_pre,
                                              int first, int total, int wg, int wn, int32_t* fbn, rtk::RayRec* fbl,
                                              rtk::Stats* ps, const QPrefetch& pf)
@@ -1011,7 +1012,7 @@ __device__ __forceinline__ void trace_stream(const rtk::WaveView& W, const RtSce
         int k = 0;
         int why = res < 0 ? 3 : 0;  // (walk log: why the exact walk answers: 1 tie, 2 chain check, 3 stack overflow)
         // (rows: each quad of the row verifies alike; one counts)
-        if (res > 0 && !ANY && !rtk::quad_closest_answer(S, q, sub & 3, t, k, gs == 4 || sub == 0 ? ps : nullptr)) {
+        if (res > 0 && !ANY && !rtk::quad_closest_answer<BRUTE>(S, q, sub & 3, t, k, gs == 4 || sub == 0 ? ps : nullptr)) {
             res = -1;
             why = q.h.tie ? 1 : 2;
         }
@@ -1097,9 +1098,9 @@ __device__ __forceinline__ void trace_stream(const rtk::WaveView& W, const RtSce
         if (active) {
             int res;
             if constexpr (G == 4)
-                res = rtk::quad_visit<ANY, RT_VISIT_DESCEND, PAIR>(S, q, stk, sub, ps);
+                res = rtk::quad_visit<ANY, RT_VISIT_DESCEND, PAIR, BRUTE>(S, q, stk, sub, ps);
             else
-                res = rtk::row_visit<ANY, RT_VISIT_DESCEND>(S, q, stk, sub, ps);
+                res = rtk::row_visit<ANY, RT_VISIT_DESCEND, BRUTE>(S, q, stk, sub, ps);
             q.calls += G == 4 ? 1 : 2;
             if (res != 0) {
                 active = false;
@@ -1125,8 +1126,9 @@ __device__ __forceinline__ void trace_stream(const rtk::WaveView& W, const RtSce
         q.o = rtk::v3(pf(q.o.x), pf(q.o.y), pf(q.o.z));
         q.d = rtk::v3(pf(q.d.x), pf(q.d.y), pf(q.d.z));
         for (int i = 0; i < 3; i++) q.rb.inv[i] = pf(q.rb.inv[i]), q.rb.oi[i] = pf(q.rb.oi[i]);
-        q.h.t = pf(q.h.t), q.h.t2 = pf(q.h.t2), q.h.k = pi(q.h.k), q.h.leaf = pi(q.h.leaf), q.h.prim = pi(q.h.prim);
-        q.h.tie = pi(q.h.tie ? 1 : 0) != 0, q.h.ovf = pi(q.h.ovf ? 1 : 0) != 0;
+        q.h.t = pf(q.h.t), q.h.t2 = pf(q.h.t2), q.h.k = pi(q.h.k), q.h.leaf = pi(q.h.leaf);
+        if (BRUTE != RT_BRUTE_OFF) q.h.prim = pi(q.h.prim);  // (else no walk reads it)
+        q.h.tie = pi(q.h.tie ? 1 : 0) != 0;  // (q.h.ovf: the one-lane walks' flag; these walks return -1 instead)
         q.sp = pi(q.sp), q.cur = pi(q.cur), q.calls = pi(q.calls);
         target = (uint32_t)pi((int)target);
         // its stack (<= RT_QSTACK entries), through registers: read everything, then write
@@ -1164,7 +1166,7 @@ __device__ __forceinline__ void trace_stream(const rtk::WaveView& W, const RtSce
                 if (lane == 0) ps->c[RT_STAT_DRAIN_SLOTS] += 4;
             }
             if (active) {
-                const int res = rtk::row_visit<ANY, RT_VISIT_DESCEND>(S, q, rs, sub, ps);
+                const int res = rtk::row_visit<ANY, RT_VISIT_DESCEND, BRUTE>(S, q, rs, sub, ps);
                 q.calls += 2;
                 if (res != 0) {
                     active = false;
@@ -1175,7 +1177,10 @@ __device__ __forceinline__ void trace_stream(const rtk::WaveView& W, const RtSce
     }
 }
 
-template <bool STATS, bool PAIR = true, int G = 4>
+// BRUTE (rt_quad.h): RT_BRUTE_OFF and RT_BRUTE_ON are answers only for a scene of that kind; the
+// kernel does not check it. A launch site either dispatches on W.S.brute (run_wave) or uses
+// RT_BRUTE_SCENE, which reads it.
+template <bool STATS, bool PAIR = true, int G = 4, int BRUTE = RT_BRUTE_SCENE>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_TRACE_OCC, 8))) void k_trace(rtk::WaveView W, int par, unsigned long long* stats)
 {
     __shared__ uint32_t s_lds[RT_LDS_WORDS * 256];
@@ -1233,16 +1238,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_TRACE_OC
     if constexpr (G == 4) {
         rtk::QuadStack<RT_QSTACK, 64> stk{s_lds + (threadIdx.x >> 2), (float*)s_lds + RT_QSTACK * 64 + (threadIdx.x >> 2)};
         if (closest)
-            trace_stream<false, STATS, PAIR, 4>(W, S, stk, s_pre, c0, total, wg, wn, fbn, fbl, ps, pf);
+            trace_stream<false, STATS, PAIR, 4, BRUTE>(W, S, stk, s_pre, c0, total, wg, wn, fbn, fbl, ps, pf);
         else
-            trace_stream<true, STATS, PAIR, 4>(W, S, stk, s_pre, a0, total, wg, wn, fbn, fbl, ps, pf);
+            trace_stream<true, STATS, PAIR, 4, BRUTE>(W, S, stk, s_pre, a0, total, wg, wn, fbn, fbl, ps, pf);
     } else {
         static_assert(2 * RT_RSTACK * 16 <= RT_LDS_WORDS * 256, "row stacks fit k_trace's LDS");
         rtk::QuadStack<RT_RSTACK, 16> stk{s_lds + (threadIdx.x >> 4), (float*)s_lds + RT_RSTACK * 16 + (threadIdx.x >> 4)};
         if (closest)
-            trace_stream<false, STATS, PAIR, 16>(W, S, stk, s_pre, c0, total, wg, wn, fbn, fbl, ps, pf);
+            trace_stream<false, STATS, PAIR, 16, BRUTE>(W, S, stk, s_pre, c0, total, wg, wn, fbn, fbl, ps, pf);
         else
-            trace_stream<true, STATS, PAIR, 16>(W, S, stk, s_pre, a0, total, wg, wn, fbn, fbl, ps, pf);
+            trace_stream<true, STATS, PAIR, 16, BRUTE>(W, S, stk, s_pre, a0, total, wg, wn, fbn, fbl, ps, pf);
     }
     flush_stats<STATS>(st, stats);
 }
@@ -2238,8 +2243,10 @@ int run_wave(rt_context* c, Backend* b, int w, int h, int spp, int bounces, cons
             hipLaunchKernelGGL((k_trace<true, false>), g, dim3(threads), 0, La.s, W, par, stats);
         else if (S)
             hipLaunchKernelGGL((k_trace<true, true>), g, dim3(threads), 0, La.s, W, par, stats);
+        else if (W.S.brute)  // (USE_BVH 0 scenes: the walks that keep the triangles' original indices)
+            hipLaunchKernelGGL((k_trace<false, true, 4, RT_BRUTE_ON>), g, dim3(threads), 0, La.s, W, par, stats);
         else
-            hipLaunchKernelGGL((k_trace<false, true>), g, dim3(threads), 0, La.s, W, par, stats);
+            hipLaunchKernelGGL((k_trace<false, true, 4, RT_BRUTE_OFF>), g, dim3(threads), 0, La.s, W, par, stats);
         if (T) HIPCHK(c, hipEventRecord(La.tev[1][La.it], La.s));
         HIPCHK(c, hipGetLastError());
         return RT_OK;

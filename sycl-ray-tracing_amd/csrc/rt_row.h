@@ -93,10 +93,11 @@ __device__ __forceinline__ unsigned row_bits(unsigned long long b) { return (uns
 // quad_visit: 0 go on, 1 the walk is over (ANY: q.h.k = 1 occluded / 0 not; else the
 // closest-hit record in q.h, to quad_closest_answer), -1 the bounded stack overflowed.
 // sub = lane within the row (0..15); q.cur is a 16-wide node index or a leaf item.
-template <bool ANY, int DESC, class RSTK>
+template <bool ANY, int DESC, int BRUTE = RT_BRUTE_SCENE, class RSTK>
 __device__ __forceinline__ int row_visit(const RtSceneView& S, QState& q, RSTK& stk, int sub, Stats* st)
 {
     FastHit& h = q.h;
+    const bool brute = scene_brute<BRUTE>(S);
 #pragma unroll 1
     for (int dd = 0; dd < DESC && q.cur >= 0; dd++) {
         const float4_* p = (const float4_*)(S.bvh16 + (size_t)q.cur * RT_BVH16_W + sub);
@@ -180,28 +181,33 @@ __device__ __forceinline__ int row_visit(const RtSceneView& S, QState& q, RSTK& 
         if (g < nl) tv = quad_tri<!ANY>(S, mine_leaf, sub & 3, q.o, q.d, k, leaf, prim);
         if (ANY) {
             unsigned hm = row_bits(__ballot(tv < __builtin_inff()));
-            if (S.brute) {
+            if (brute) {
                 if (hm) {
                     h.k = 1;
                     return 1;
                 }
-            } else {
+            } else if (hm) {
+                // (rt_quad.h: the ray's terms once, and one check per run of hits in one octree leaf)
+                const ChainRay cr = quad_chain_ray(q.o, q.d, sub & 3);
+                int checked = -1;
                 while (hm) {  // row-uniform: each hit's octree chain, checked by every quad of the row
                     const int j = __ffs(hm) - 1;
                     hm &= hm - 1u;
                     const int lj = __shfl(leaf, (int)(__lane_id() & 48) + j);
-                    if (quad_chain_ok(S, q.o, q.d, lj, false, 0.0f, sub & 3, sub == 0 ? st : nullptr)) {
+                    if (lj == checked) continue;
+                    if (quad_chain_ok(S, cr, lj, false, 0.0f, sub & 3, sub == 0 ? st : nullptr)) {
                         h.k = 1;
                         return 1;
                     }
+                    checked = lj;
                 }
             }
         } else {
             // rt_quad.h's leaf reduction over the row's sixteen hits (rt_fast.h fast_take)
             const float m1 = row_minf(tv);
             const float m2 = row_minf(tv > m1 ? tv : __builtin_inff());
-            const int key = row_min(tv == m1 ? (S.brute ? prim : k) : 0x7fffffff);
-            const bool mine = tv == m1 && (S.brute ? prim : k) == key;
+            const int key = row_min(tv == m1 ? (brute ? prim : k) : 0x7fffffff);
+            const bool mine = tv == m1 && (brute ? prim : k) == key;
             const int wk = row_or(mine ? k : 0), wl = row_or(mine ? leaf : 0), wp = row_or(mine ? prim : 0);
             const bool mixed = row_or(tv == m1 && m1 < __builtin_inff() && leaf != wl ? 1 : 0) != 0;
             if (m1 < h.t) {
@@ -213,7 +219,7 @@ __device__ __forceinline__ int row_visit(const RtSceneView& S, QState& q, RSTK& 
                 h.tie = mixed;
             } else if (m1 == h.t && m1 < __builtin_inff()) {
                 h.t2 = __builtin_fminf(h.t2, m2);
-                if (S.brute) {
+                if (brute) {
                     h.tie = true;
                     if (wp < h.prim) h.k = wk, h.leaf = wl, h.prim = wp;
                 } else if (!mixed && wl == h.leaf) {

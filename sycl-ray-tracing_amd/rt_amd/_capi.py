@@ -109,6 +109,7 @@ _SIGS = {
     # hostsim-only extra
     "rt_hostsim_heap_order": (I, [P, I, P, P]),
     "rt_hostsim_fast_queries": (I, [P, P, I, P, P]),
+    "rt_hostsim_leaf_hits": (I, [P, P, I, P]),
 }
 
 # rt_query modes (include/rt_hip.h)

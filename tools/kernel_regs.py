@@ -6,14 +6,16 @@ import subprocess
 import sys
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# the Makefile's HIPFLAGS (also tools/trace_asm_split.py)
+HIPCC = "/opt/rocm/bin/hipcc"
+HIPCC_FLAGS = ["-std=c++17", "-O3", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=off", "-fno-fast-math",
+               "-fno-gpu-flush-denormals-to-zero", "-fhip-fp32-correctly-rounded-divide-sqrt", "-Wno-unused-function",
+               "-Wno-unknown-pragmas"]
 
 
 def usage(src=None, extra=()):
     src = src or os.path.join(REPO, "sycl-ray-tracing_amd", "csrc", "rt_render.hip")
-    cmd = ["/opt/rocm/bin/hipcc", "-std=c++17", "-O3", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=off",
-           "-fno-fast-math", "-fno-gpu-flush-denormals-to-zero", "-fhip-fp32-correctly-rounded-divide-sqrt",
-           "-Wno-unused-function", "-Wno-unknown-pragmas", "-Rpass-analysis=kernel-resource-usage", *extra,
-           "-c", src, "-o", "/tmp/kernel_regs.o"]
+    cmd = [HIPCC, *HIPCC_FLAGS, "-Rpass-analysis=kernel-resource-usage", *extra, "-c", src, "-o", "/tmp/kernel_regs.o"]
     out = subprocess.run(cmd, capture_output=True, text=True).stderr
     rows, cur = {}, None
     for line in out.splitlines():
