@@ -90,7 +90,9 @@ int rt_test_fail_device(rt_context* ctx, int device);
  * largest extent: queries from outside it take the exact octree walk), "dn_variant"
  * (rt_denoise's filter kernel: 0 the product's choice per step, 1 direct loads, 2 the
  * LDS-halo tile at every step that has one), "rq_variant" (rt_query's search-BVH kernel:
- * 0 the product's choice, 1 plain rounds of one query per quad, 2 per-quad refill), the
+ * 0 the product's choice, 1 plain rounds of one query per quad, 2 per-quad refill),
+ * "chain_full" (1: the scene view reports an unmonotone tree, so the leaf verification
+ * walks the whole ancestor chain instead of one slab test), the
  * stressor "force_fallback" (every k-th query by a ray hash skips to the exact
  * octree walk), "reset"). No parameter changes a result; the product never calls
  * it and reads no schedule from the environment. RT_ERR_ARG for an unknown key or

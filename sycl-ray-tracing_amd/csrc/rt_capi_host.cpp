@@ -69,7 +69,7 @@ RtSceneView rt_host_view(const rt_context* c)
     v.ew = c->ew;
     v.eh = c->eh;
     v.n_tris = (int)(c->tris.size() / 9);
-    v.chain_monotone = c->flat.chain_monotone ? 1 : 0;
+    v.chain_monotone = rt_view_chain_monotone(c);
     v.bvh4 = c->flat.bvh4.data();
     v.bvh16 = c->flat.bvh16.data();
     v.bvh4s = c->flat.bvh4s.data();
@@ -81,6 +81,8 @@ RtSceneView rt_host_view(const rt_context* c)
     rt_view_near(c, v);
     return v;
 }
+
+int rt_view_chain_monotone(const rt_context* c) { return c->flat.chain_monotone && !c->sched.chain_full ? 1 : 0; }
 
 void rt_view_near(const rt_context* c, RtSceneView& v)
 {
@@ -238,7 +240,14 @@ int rt_test_schedule(rt_context* c, const char* key, double value)
     else if (k == "near_scale") s.near_scale = value;
     else if (k == "dn_variant") s.dn_variant = std::max(0, std::min(2, v));
     else if (k == "rq_variant") s.rq_variant = std::max(0, std::min(2, v));
-    else if (k == "reset") s = RtSchedule{};
+    else if (k == "chain_full") {
+        // the devices' views carry the flag: the next call uploads them again
+        if (s.chain_full != (v != 0)) c->dirty = true;
+        s.chain_full = v != 0;
+    } else if (k == "reset") {
+        if (s.chain_full) c->dirty = true;
+        s = RtSchedule{};
+    }
     else return rt_fail(c, RT_ERR_ARG, "rt_test_schedule: unknown key " + k);
     return RT_OK;
 }

@@ -36,6 +36,8 @@ struct RtSchedule {
                                // study probes only: answers never depend on it, only which walk gives them)
     int dn_variant = 0;        // rt_denoise's filter kernel: 0 per step as measured, 1 direct, 2 LDS tile where built
     int rq_variant = 0;        // rt_query's fast kernel: 0 as measured, 1 plain grid-stride rounds, 2 per-quad refill
+    bool chain_full = false;   // the scene view reports chain_monotone = 0: chain_ok / quad_chain_ok run their full
+                               // ancestor-chain loop (rt_fast.h), which no tree the host builds reaches otherwise
 };
 
 // Diagnostics, read from the environment once when the context is created (rt_create*):
@@ -170,6 +172,8 @@ RtSceneView rt_host_view(const rt_context* ctx);  // host-memory view (hostsim)
 #define RT_NEAR_SCALE 0.5
 #endif
 void rt_view_near(const rt_context* ctx, RtSceneView& v);
+// The view's chain_monotone: the built tree's (rt_scene.h FlatBvh), 0 under sched.chain_full.
+int rt_view_chain_monotone(const rt_context* ctx);
 // Does any primitive (triangle or sphere) use a material with a positive
 // emission component (the test at render_kernel.cpp:696)? If not, the
 // BRDF->light query of sample_light_sources can never contribute.

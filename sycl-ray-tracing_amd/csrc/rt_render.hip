@@ -1912,7 +1912,7 @@ int upload_one(rt_context* c, Backend* b, const std::vector<int32_t>& matk, bool
     v.ew = c->ew;
     v.eh = c->eh;
     v.n_tris = (int)(c->tris.size() / 9);
-    v.chain_monotone = c->flat.chain_monotone ? 1 : 0;
+    v.chain_monotone = rt_view_chain_monotone(c);
     v.brute = c->brute ? 1 : 0;
     v.bvh4 = (const Bvh4Node*)b->bvh4.p;
     v.bvh16 = (const Bvh4Child*)b->bvh16.p;
