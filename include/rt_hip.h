@@ -113,6 +113,13 @@ int rt_test_schedule(rt_context* ctx, const char* key, double value);
 #define RT_WLOG_FLOATS 12
 int rt_test_walk_log(rt_context* ctx, int min_calls, int sample_every, int capacity);
 long rt_test_walk_log_read(const rt_context* ctx, float* out, long capacity);
+/* TEST ONLY. rt_device_env_search: the env-map CDF search (sample_environment_map's two
+ * searches, render_kernel.cpp:532-567) alone, for n caller values over ctx's env:
+ * xy_out[2 i] = x, xy_out[2 i + 1] = y. form 0: what the shading kernels run (on the GPU
+ * with their LDS staging of the row tables), form 1: the same tables read from global
+ * memory whatever the env's height. The hostsim build runs its one host form for both.
+ * Never called by the product paths. */
+int rt_device_env_search(rt_context* ctx, int form, const float* values, int n, int* xy_out);
 void rt_destroy(rt_context* ctx);
 const char* rt_last_error(const rt_context* ctx); /* ctx may be NULL: last global error */
 int rt_version(void);

@@ -592,6 +592,22 @@ extern "C" int rt_hostsim_leaf_hits(rt_context* c, const float* rays, int n, int
     return RT_OK;
 }
 
+// TEST ONLY (include/rt_hip.h): the env-CDF search alone, as the host build runs it (there is no
+// LDS copy here: forms 0 and 1 read the same tables through cdf_search and cdf_search_global).
+extern "C" int rt_device_env_search(rt_context* c, int form, const float* values, int n, int* xy_out)
+{
+    if (!c || n <= 0 || !values || !xy_out || form < 0 || form > 1) return RT_ERR_ARG;
+    if (!c->have_env) return RT_ERR_STATE;
+    const RtSceneView S = rt_host_view(c);
+    for (int i = 0; i < n; i++) {
+        if (form == 0)
+            rtk::cdf_search(S, values[i], xy_out[2 * i], xy_out[2 * i + 1], nullptr);
+        else
+            rtk::cdf_search_global(S, values[i], xy_out[2 * i], xy_out[2 * i + 1]);
+    }
+    return RT_OK;
+}
+
 // Heap-order emulation self-check against std::priority_queue (exported for
 // tests/test_hostsim.py): keys[m] in push order -> order[m] of pushed indices.
 #include <queue>

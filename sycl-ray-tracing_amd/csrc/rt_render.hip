@@ -1721,6 +1721,22 @@ __global__ void k_libm(int fn, const float* __restrict__ in, const float* __rest
     out[i] = r;
 }
 
+// TEST ONLY (rt_device_env_search): cdf_search alone over caller values. form 0: as the shading
+// kernels run it, after lds_shade_init's staging; form 1: every table from global memory.
+__global__ void k_env_search(RtSceneView S, int form, const float* __restrict__ values, int n, int* __restrict__ xy)
+{
+    if (form == 0) rtk::lds_shade_init(S);
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        int x, y;
+        if (form == 0)
+            rtk::cdf_search(S, values[i], x, y, nullptr);
+        else
+            rtk::cdf_search_global(S, values[i], x, y);
+        xy[2 * i] = x;
+        xy[2 * i + 1] = y;
+    }
+}
+
 // ------------------------------------------------------------- wave memory
 }  // namespace
 
@@ -2907,6 +2923,33 @@ extern "C" int rt_device_libm(int device, int fn, const float* in, const float* 
     (void)hipFree(d_in2);
     (void)hipFree(d_out);
     return e == hipSuccess ? RT_OK : RT_ERR_HIP;
+}
+
+// TEST ONLY (include/rt_hip.h): the env-CDF search alone on the context's env, several blocks
+// (each stages its own LDS copy in form 0).
+extern "C" int rt_device_env_search(rt_context* c, int form, const float* values, int n, int* xy_out)
+{
+    if (!c || !c->backend || n <= 0 || !values || !xy_out || form < 0 || form > 1) return RT_ERR_ARG;
+    if (!c->have_env) return RT_ERR_STATE;
+    Backend* b = be(c);
+    HIPCHK(c, hipSetDevice(b->device));
+    if (c->dirty) {
+        if (int r = rt_backend_upload(c)) return r;
+        c->dirty = false;
+    }
+    float* d_v = nullptr;
+    int* d_xy = nullptr;
+    HIPCHK(c, hipMalloc(&d_v, (size_t)n * 4));
+    HIPCHK(c, hipMalloc(&d_xy, (size_t)n * 8));
+    HIPCHK(c, hipMemcpy(d_v, values, (size_t)n * 4, hipMemcpyHostToDevice));
+    const int threads = 256, blocks = std::min((n + threads - 1) / threads, 64);
+    hipLaunchKernelGGL(k_env_search, dim3(blocks), dim3(threads), 0, 0, b->view, form, d_v, n, d_xy);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpy(xy_out, d_xy, (size_t)n * 8, hipMemcpyDeviceToHost);
+    (void)hipFree(d_v);
+    (void)hipFree(d_xy);
+    HIPCHK(c, e);
+    return RT_OK;
 }
 
 // Search-BVH query micro-benchmark: rays[n][8] (origin xyz _, direction xyz _),

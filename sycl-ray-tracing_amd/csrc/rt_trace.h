@@ -951,4 +951,16 @@ RT_HD void cdf_search(const RtSceneView& S, float value, int& x, int& y, Stats* 
     if (st) st->c[RT_STAT_CDF] += probes;
 }
 
+// TEST ONLY (rt_device_env_search, form 1): cdf_search with the fence search's row tables read
+// from global memory whatever eh, the form the shading kernels take above RT_CDF_LDS_ROWS rows.
+RT_HD void cdf_search_global(const RtSceneView& S, float value, int& x, int& y)
+{
+    if (!S.cdf_fence) {
+        cdf_search(S, value, x, y, nullptr);
+        return;
+    }
+    y = fence_count(S.cdf_row, S.cdf_fence, S.eh - 1, value);
+    x = fence_count(S.cdf + (size_t)y * S.ew, S.cdf_fence + (size_t)(1 + y) * 272, S.ew - 1, value);
+}
+
 }  // namespace rtk

@@ -25,7 +25,7 @@ EXPORTS = [
     "rt_octree_dump", "rt_read_hdr", "rt_write_png", "rt_image_to_rgba8",
     "rt_set_intersect_mode", "rt_create_multi", "rt_device_count", "rt_set_materials", "rt_render_variants",
     "rt_create_multi_loopback", "rt_test_create_multi_rccl", "rt_test_fail_device", "rt_test_schedule", "rt_test_walk_log",
-    "rt_test_walk_log_read", "rt_test_obj_parallel_min",
+    "rt_test_walk_log_read", "rt_test_obj_parallel_min", "rt_device_env_search",
     "rt_camera_rays", "rt_render_features", "rt_render_features_device", "rt_denoise_default_params", "rt_denoise",
     "rt_denoise_device",
     "rt_query", "rt_query_device", "rt_query_last_exact",
@@ -56,6 +56,7 @@ _SIGS = {
     "rt_test_walk_log": (I, [P, I, I, I]),
     "rt_test_walk_log_read": (L, [P, P, L]),
     "rt_test_obj_parallel_min": (I, [L]),
+    "rt_device_env_search": (I, [P, I, P, I, P]),
     "rt_device_count": (I, [P]),
     "rt_set_materials": (I, [P, P, I]),
     "rt_destroy": (None, [P]),

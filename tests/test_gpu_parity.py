@@ -234,6 +234,29 @@ def test_gpu_libm_binary_matches_glibc(fn):
     assert same.all()
 
 
+def test_gpu_libm_tonemap_domain_matches_glibc():
+    """The tone map's rt_powf(1 - rt_expf(-1.5 v), 1 / 2.2) on a framebuffer that is negative,
+    huge, infinite or NaN on entry, and the fresnel exponent: powf at negative, zero, denormal,
+    unit, infinite and NaN bases, expf at -1.5 v for the extreme v; bitwise, NaN matching NaN."""
+    m = _glibc()
+    with np.errstate(over="ignore"):
+        bases = np.array([-np.inf, -100.0, -1.0, -1e-40, -0.0, 0.0, 1e-45, 1e-40, 1.0 - 2.0 ** -24, 1.0, 1.0 + 2.0 ** -23,
+                          100.0, np.inf, np.nan], np.float32)
+        x = np.repeat(bases, 2)
+        y = np.tile(np.array([np.float32(1.0) / np.float32(2.2), np.float32(5.0)], np.float32), bases.shape[0])
+        out = np.zeros_like(x)
+        assert _capi.lib().rt_device_libm(0, 1, _capi.ptr(x), _capi.ptr(y), _capi.ptr(out), x.shape[0]) == 0
+        want = np.array([m.powf(float(a), float(b)) for a, b in zip(x, y)], np.float32)
+        same = (out.view(np.uint32) == want.view(np.uint32)) | (np.isnan(out) & np.isnan(want))
+        assert same.all(), (x[~same], y[~same], out[~same], want[~same])
+        v = np.float32(-1.5) * np.array([-100.0, 1e30, np.inf, -np.inf], np.float32)
+        out = np.zeros_like(v)
+        assert _capi.lib().rt_device_libm(0, 0, _capi.ptr(v), None, _capi.ptr(out), v.shape[0]) == 0
+        want = np.array([m.expf(float(a)) for a in v], np.float32)
+    same = (out.view(np.uint32) == want.view(np.uint32)) | (np.isnan(out) & np.isnan(want))
+    assert same.all(), (v[~same], out[~same], want[~same])
+
+
 def test_gpu_ieee_div_sqrt_f64():
     """IEEE f32 division / sqrt with denormals, and the f64 GGX path, on device."""
     rng = np.random.default_rng(5)

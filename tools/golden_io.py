@@ -124,7 +124,9 @@ def compare_rgb(a: np.ndarray, b: np.ndarray) -> dict:
     nan_mismatch = int(np.count_nonzero(na != nb))
     both = ~(na | nb)
     diff = np.zeros_like(a)
-    diff[both] = np.abs(a[both] - b[both])
+    with np.errstate(invalid="ignore"):
+        # (equal values differ by 0, two infinities of one sign included: inf - inf is NaN)
+        diff[both] = np.where(a[both] == b[both], np.float32(0.0), np.abs(a[both] - b[both]))
     linf = float(diff.max()) if diff.size else 0.0
     if nan_mismatch:
         linf = float("inf")
