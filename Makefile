@@ -23,13 +23,13 @@ HDRS := $(wildcard $(SRC)/*.h) include/rt_hip.h
 # the kernel sources' hash, compiled into each library (rt_build_id) so a run reports the build it loaded
 SRC_HASH := $(shell cat $(SRC)/* include/*.h 2>/dev/null | sha256sum | cut -c1-12)
 
-all: $(LIB)/librt_hip.so $(LIB)/librt_hostsim.so oracle/liboracle.so build/libm_check build/cdf_check stamp
+all: $(LIB)/librt_hip.so $(LIB)/librt_hostsim.so oracle/liboracle.so build/libm_check build/cdf_check build/plan_check stamp
 
 $(OBJ)/%.host.o: $(SRC)/%.cpp $(HDRS)
 	@mkdir -p $(OBJ)
 	$(CXX) $(CXXFLAGS) -c $< -o $@
 
-# (the two objects that compile SRC_HASH in as rt_build_id depend on every file it hashes,
+# (the two objects that compile SRC_HASH in as rt_build_id, rt_hostsim.o and rt_backend.o, depend on every file it hashes,
 # so a change to a host-only source cannot leave a stale build id in the library)
 ALL_SRC := $(wildcard $(SRC)/*) $(wildcard include/*.h)
 
@@ -37,9 +37,9 @@ $(OBJ)/rt_hostsim.o: $(SRC)/rt_hostsim.cpp $(HDRS) $(ALL_SRC)
 	@mkdir -p $(OBJ)
 	$(CXX) $(CXXFLAGS) -fopenmp -DRT_BUILD_SRC='"$(SRC_HASH)"' -c $< -o $@
 
-$(OBJ)/rt_render.o: $(SRC)/rt_render.hip $(HDRS) $(ALL_SRC)
+$(OBJ)/rt_render.o: $(SRC)/rt_render.hip $(HDRS)
 	@mkdir -p $(OBJ)
-	$(HIPCC) $(HIPFLAGS) -DRT_BUILD_SRC='"$(SRC_HASH)"' -c $< -o $@
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 # the post stage (feature pass + filter) in a translation unit of its own: the render
 # kernels' code generation does not depend on it
@@ -52,7 +52,12 @@ $(OBJ)/rt_query.o: $(SRC)/rt_query.hip $(HDRS)
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(LIB)/librt_hip.so: $(OBJ)/rt_render.o $(OBJ)/rt_denoise.o $(OBJ)/rt_query.o $(OBJ)/rt_scene.host.o $(OBJ)/rt_imageio.host.o $(OBJ)/rt_capi_host.host.o
+# the kernel-free half of the backend: contexts, uploads, the drivers over run_wave, rt_build_id
+$(OBJ)/rt_backend.o: $(SRC)/rt_backend.hip $(HDRS) $(ALL_SRC)
+	@mkdir -p $(OBJ)
+	$(HIPCC) $(HIPFLAGS) -DRT_BUILD_SRC='"$(SRC_HASH)"' -c $< -o $@
+
+$(LIB)/librt_hip.so: $(OBJ)/rt_render.o $(OBJ)/rt_backend.o $(OBJ)/rt_denoise.o $(OBJ)/rt_query.o $(OBJ)/rt_scene.host.o $(OBJ)/rt_imageio.host.o $(OBJ)/rt_capi_host.host.o
 	@mkdir -p $(LIB)
 	$(HIPCC) -shared --offload-arch=$(ARCH) -fPIC $^ -o $@
 
@@ -78,6 +83,11 @@ build/cdf_check: tests/native/cdf_check.cpp $(OBJ)/rt_scene.host.o $(HDRS)
 	@mkdir -p build
 	$(CXX) $(CXXFLAGS) -I$(SRC) $< $(OBJ)/rt_scene.host.o -o $@
 
+# the wavefront plan (rt_plan.h wave_plan) against a table worked out from the expressions it replaced
+build/plan_check: tests/native/plan_check.cpp $(HDRS)
+	@mkdir -p build
+	$(CXX) $(CXXFLAGS) -I$(SRC) $< -o $@
+
 # CPU replay of logged rays over search-BVH variants (tools/probe/walk_probe.cpp; study tool)
 build/walk_probe: tools/probe/walk_probe.cpp $(OBJ)/rt_scene.host.o $(HDRS)
 	@mkdir -p build
@@ -100,10 +110,11 @@ clean:
 # experiment builds: make variant V=name DEFS="-DRT_TAIL_OCC=2" -> lib/librt_hip_name.so (RT_HIP_LIB=...)
 variant: $(OBJ)/rt_scene.host.o $(OBJ)/rt_imageio.host.o $(OBJ)/rt_capi_host.host.o
 	@mkdir -p $(LIB)
-	$(HIPCC) $(HIPFLAGS) $(DEFS) -DRT_BUILD_SRC='"$(SRC_HASH)"' -DRT_BUILD_DEFS='"$(DEFS)"' -c $(SRC)/rt_render.hip -o $(OBJ)/rt_render_$(V).o
+	$(HIPCC) $(HIPFLAGS) $(DEFS) -c $(SRC)/rt_render.hip -o $(OBJ)/rt_render_$(V).o
+	$(HIPCC) $(HIPFLAGS) $(DEFS) -DRT_BUILD_SRC='"$(SRC_HASH)"' -DRT_BUILD_DEFS='"$(DEFS)"' -c $(SRC)/rt_backend.hip -o $(OBJ)/rt_backend_$(V).o
 	$(HIPCC) $(HIPFLAGS) $(DEFS) -c $(SRC)/rt_denoise.hip -o $(OBJ)/rt_denoise_$(V).o
 	$(HIPCC) $(HIPFLAGS) $(DEFS) -c $(SRC)/rt_query.hip -o $(OBJ)/rt_query_$(V).o
-	$(HIPCC) -shared --offload-arch=$(ARCH) -fPIC $(OBJ)/rt_render_$(V).o $(OBJ)/rt_denoise_$(V).o $(OBJ)/rt_query_$(V).o $^ -o $(LIB)/librt_hip_$(V).so
+	$(HIPCC) -shared --offload-arch=$(ARCH) -fPIC $(OBJ)/rt_render_$(V).o $(OBJ)/rt_backend_$(V).o $(OBJ)/rt_denoise_$(V).o $(OBJ)/rt_query_$(V).o $^ -o $(LIB)/librt_hip_$(V).so
 
 # the same for the hostsim build: make hostsim-variant V=name DEFS="-DRT_SLABS=0" ->
 # lib/librt_hostsim_name.so (RT_HOSTSIM_LIB=...; study probes such as tools/far_probe.py)

@@ -1,0 +1,618 @@
+// rt_backend.hip — the kernel-free half of the gfx950 backend: contexts and their devices
+// (create / destroy / upload, RCCL loading), the multi-device, variant and pixel-list
+// drivers over rt_render.hip's run_wave, and the rt_device_* accessors.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+#include <mutex>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include <dlfcn.h>
+
+#include <rccl/rccl.h>
+
+#include "rt_backend_hip.h"
+#include "rt_wave.h"
+
+namespace {
+// A context drives one Backend per device. rt_create: one device, renders on the
+// caller's stream. rt_create_multi: devices[0] is the root that holds the caller's
+// framebuffer; a render shards its rows over the devices (render_multi).
+struct Group {
+    std::vector<Backend*> dev;     // dev[0]: the root
+    bool multi = false;            // rt_create_multi over two or more devices
+    bool loopback = false;         // (RT_MULTI_LOOPBACK test contexts) shards exchanged by device copies
+    std::vector<ncclComm_t> comms; // ncclCommInitAll over the devices, in order (RCCL exchange)
+};
+
+Group* grp(rt_context* c) { return (Group*)c->backend; }
+Backend* be(rt_context* c) { return grp(c)->dev[0]; }
+
+// RCCL, loaded on the first multi-device context: the library need not be present
+// (or be the same build as a framework's own copy) for single-device use.
+struct Rccl {
+    void* h = nullptr;
+    decltype(&ncclCommInitAll) init = nullptr;
+    decltype(&ncclCommDestroy) destroy = nullptr;
+    decltype(&ncclScatter) scatter = nullptr;
+    decltype(&ncclGather) gather = nullptr;
+    decltype(&ncclGroupStart) group_start = nullptr;
+    decltype(&ncclGroupEnd) group_end = nullptr;
+    decltype(&ncclGetErrorString) errstr = nullptr;
+};
+std::mutex g_rccl_mu;
+Rccl g_rccl;
+
+const Rccl* rccl_load(std::string& err)
+{
+    std::lock_guard<std::mutex> lk(g_rccl_mu);
+    if (g_rccl.h) return &g_rccl;
+    void* h = dlopen("librccl.so.1", RTLD_NOW | RTLD_GLOBAL);
+    if (!h) h = dlopen("/opt/rocm/lib/librccl.so.1", RTLD_NOW | RTLD_GLOBAL);
+    if (!h) {
+        err = std::string("librt_hip: RCCL not found (librccl.so.1): ") + dlerror();
+        return nullptr;
+    }
+    Rccl r;
+    r.h = h;
+    r.init = (decltype(r.init))dlsym(h, "ncclCommInitAll");
+    r.destroy = (decltype(r.destroy))dlsym(h, "ncclCommDestroy");
+    r.scatter = (decltype(r.scatter))dlsym(h, "ncclScatter");
+    r.gather = (decltype(r.gather))dlsym(h, "ncclGather");
+    r.group_start = (decltype(r.group_start))dlsym(h, "ncclGroupStart");
+    r.group_end = (decltype(r.group_end))dlsym(h, "ncclGroupEnd");
+    r.errstr = (decltype(r.errstr))dlsym(h, "ncclGetErrorString");
+    if (!r.init || !r.destroy || !r.scatter || !r.gather || !r.group_start || !r.group_end || !r.errstr) {
+        err = "librt_hip: librccl.so.1 lacks ncclCommInitAll / ncclScatter / ncclGather";
+        return nullptr;
+    }
+    g_rccl = r;
+    return &g_rccl;
+}
+
+#define NCCLCHK(ctx, R, expr)                                                                    \
+    do {                                                                                         \
+        ncclResult_t e_ = (expr);                                                                \
+        if (e_ != ncclSuccess) return rt_fail(ctx, RT_ERR_HIP, std::string(#expr ": ") + (R)->errstr(e_)); \
+    } while (0)
+
+int create_one(rt_context* c, int device, Backend** out)
+{
+    int n = 0;
+    hipError_t e = hipGetDeviceCount(&n);
+    if (e != hipSuccess || n == 0)
+        return rt_fail(c, RT_ERR_NODEV, "librt_hip: no HIP device available (this library has no CPU path)");
+    if (device < 0 || device >= n) return rt_fail(c, RT_ERR_NODEV, "librt_hip: device index out of range");
+    HIPCHK(c, hipSetDevice(device));
+    Backend* b = new Backend();
+    *out = b;
+    b->device = device;
+    HIPCHK(c, hipEventCreate(&b->ev0.h));
+    HIPCHK(c, hipEventCreate(&b->ev1.h));
+    for (int l = 0; l < RT_MAX_LANES; l++) {
+        HIPCHK(c, hipHostMalloc((void**)&b->h_act[l].h, rt_wave_readback_bytes(), hipHostMallocDefault));
+        HIPCHK(c, hipEventCreateWithFlags(&b->ev_lane[l].h, hipEventDisableTiming));
+        HIPCHK(c, hipEventCreateWithFlags(&b->ev_join[l].h, hipEventDisableTiming));
+        if (l > 0) HIPCHK(c, hipStreamCreateWithFlags(&b->ls[l].h, hipStreamNonBlocking));
+    }
+    HIPCHK(c, hipStreamCreateWithFlags(&b->own.h, hipStreamNonBlocking));
+    HIPCHK(c, hipEventCreateWithFlags(&b->ev_fork.h, hipEventDisableTiming));
+    HIPCHK(c, hipEventCreateWithFlags(&b->ev_done.h, hipEventDisableTiming));
+    return RT_OK;
+}
+
+void destroy_one(Backend* b)
+{
+    (void)hipSetDevice(b->device);
+    (void)hipDeviceSynchronize();
+    delete b;
+}
+
+// Scene, BVH and env of the context into one device's memory (replicated per device).
+int upload_one(rt_context* c, Backend* b, const std::vector<int32_t>& matk, bool mats_only)
+{
+    HIPCHK(c, hipSetDevice(b->device));
+    // the previous render may still run (rt_render_device returns at once, its kernels on
+    // non-blocking streams that a null-stream copy does not wait for): it reads these tables
+    if (b->done_recorded) HIPCHK(c, hipEventSynchronize(b->ev_done));
+    int r = 0;
+    if (mats_only) {  // rt_set_materials: the material table (and what depends on it) alone
+        if ((r = upload(c, b->mats, c->mats))) return r;
+        b->view.mats = (const RtMat*)b->mats.p;
+        b->view.n_mats = (int)c->mats.size();
+        b->bl_rays = rt_scene_has_emissive_prim(c) ? 1 : 0;
+        return RT_OK;
+    }
+    // device triangle records carry the material index in e1.w (rt_wave.h hit_from)
+    std::vector<float4_> tri4 = c->flat.tri4;
+    for (size_t k = 0; k < matk.size(); k++) std::memcpy(&tri4[3 * k + 1].w, &matk[k], 4);
+    if ((r = upload(c, b->nodes, c->flat.nodes)) || (r = upload(c, b->tri4, tri4)) ||
+        (r = upload(c, b->prim2k, c->flat.prim2k)) || (r = upload(c, b->mat_idx, c->mat_idx)) ||
+        (r = upload(c, b->mats, c->mats)) || (r = upload(c, b->emissive, c->emissive)) ||
+        (r = upload(c, b->spheres, c->spheres)) || (r = upload(c, b->env, c->env)) ||
+        (r = upload(c, b->env_lum, c->env_lum)) || (r = upload(c, b->cdf, c->cdf)) ||
+        (r = upload(c, b->bvh4, c->flat.bvh4)) || (r = upload(c, b->bvh16, c->flat.bvh16)) ||
+        (r = upload(c, b->bvh4s, c->flat.bvh4s)) || (r = upload(c, b->bvh16s, c->flat.bvh16s)) ||
+        (r = upload(c, b->bvh_tri4, c->flat.bvh_tri4)) ||
+        (r = upload(c, b->parent, c->flat.parent)) || (r = upload(c, b->leaf_of, c->flat.leaf_of)) ||
+        (r = upload(c, b->cdf_row, c->cdf_row)) || (r = upload(c, b->cdf_coarse, c->cdf_coarse)) ||
+        (r = upload(c, b->cdf_fence, c->cdf_fence)) || (r = upload(c, b->matk, matk)) ||
+        (r = ensure(c, b->stats, 2 * RT_STAT_COUNT * sizeof(unsigned long long))))
+        return r;
+    for (int l = 0; l < RT_MAX_LANES; l++)
+        if ((r = ensure(c, b->counters[l], rt_wave_counter_bytes()))) return r;
+    RtSceneView v{};
+    v.nodes = (const RtNode*)b->nodes.p;
+    v.tri4 = (const float4_*)b->tri4.p;
+    v.prim2k = (const int32_t*)b->prim2k.p;
+    v.mat_idx = (const int32_t*)b->mat_idx.p;
+    v.matk = (const int32_t*)b->matk.p;
+    v.mats = (const RtMat*)b->mats.p;
+    v.n_mats = (int)c->mats.size();
+    v.emissive = (const int32_t*)b->emissive.p;
+    v.spheres = (const float4_*)b->spheres.p;
+    v.env = (const float4_*)b->env.p;
+    v.env_lum = (const float*)b->env_lum.p;
+    v.cdf = (const float*)b->cdf.p;
+    v.cdf_row = (const float*)b->cdf_row.p;
+    v.cdf_coarse = (const float*)b->cdf_coarse.p;
+    v.cdf_fence = c->cdf_fence.empty() ? nullptr : (const float*)b->cdf_fence.p;
+    v.cdf_cw = c->cdf_cw;
+    v.cdf_total = c->cdf.empty() ? 0.0f : c->cdf.back();
+    v.n_emissive = (int)c->emissive.size();
+    v.n_spheres = (int)(c->spheres.size() / 2);
+    v.ew = c->ew;
+    v.eh = c->eh;
+    v.n_tris = (int)(c->tris.size() / 9);
+    v.chain_monotone = rt_view_chain_monotone(c);
+    v.brute = c->brute ? 1 : 0;
+    v.bvh4 = (const Bvh4Node*)b->bvh4.p;
+    v.bvh16 = (const Bvh4Child*)b->bvh16.p;
+    v.bvh4s = (const float4_*)b->bvh4s.p;
+    v.bvh16s = (const float4_*)b->bvh16s.p;
+    v.bvh_tri4 = (const float4_*)b->bvh_tri4.p;
+    v.parent = (const int32_t*)b->parent.p;
+    v.leaf_of = (const int32_t*)b->leaf_of.p;
+    v.tri_mat = 1;
+    rt_view_near(c, v);
+    b->view = v;
+    b->bl_rays = rt_scene_has_emissive_prim(c) ? 1 : 0;
+    b->any_rays = v.n_spheres == 0 ? 1 : 0;
+    return RT_OK;
+}
+}  // namespace
+
+int rt_backend_create(rt_context* c)
+{
+    Group* g = new Group();
+    c->backend = g;
+    // (one listed device: a single-device context on it, unless a test asks for the driver
+    // and a one-rank RCCL clique: rt_test_create_multi_rccl)
+    g->multi = c->devices.size() > 1 || (c->force_multi && !c->devices.empty());
+    g->loopback = g->multi && c->loopback;
+    const std::vector<int> ids = g->multi ? c->devices : std::vector<int>{c->device};
+    for (int d : ids) {
+        Backend* b = nullptr;
+        const int r = create_one(c, d, &b);
+        if (b) {
+            b->index = (int)g->dev.size();
+            g->dev.push_back(b);
+        }
+        if (r) return r;
+    }
+    if (g->multi && !g->loopback) {
+        std::string err;
+        const Rccl* R = rccl_load(err);
+        if (!R) return rt_fail(c, RT_ERR_NODEV, err);
+        g->comms.resize(ids.size());
+        NCCLCHK(c, R, R->init(g->comms.data(), (int)ids.size(), ids.data()));
+    }
+    return RT_OK;
+}
+
+void rt_backend_destroy(rt_context* c)
+{
+    Group* g = grp(c);
+    if (!g) return;
+    for (Backend* b : g->dev) destroy_one(b);
+    if (!g->comms.empty()) {
+        std::string err;
+        if (const Rccl* R = rccl_load(err))
+            for (ncclComm_t cm : g->comms)
+                if (cm) (void)R->destroy(cm);
+    }
+    delete g;
+    c->backend = nullptr;
+}
+
+int rt_backend_upload(rt_context* c)
+{
+    Group* g = grp(c);
+    const bool mats_only = c->mats_dirty_only && !c->dirty;
+    // material index of each leaf-order triangle k: mat_idx[prim(k)] (rt_trace.h load_mat_hit)
+    std::vector<int32_t> matk;
+    if (!mats_only) {
+        matk.resize(c->flat.tri4.size() / 3);
+        for (size_t k = 0; k < matk.size(); k++) {
+            int32_t prim;
+            std::memcpy(&prim, &c->flat.tri4[3 * k].w, 4);
+            matk[k] = c->mat_idx[prim];
+        }
+    }
+    for (Backend* b : g->dev)
+        if (int r = upload_one(c, b, matk, mats_only)) return r;
+    return RT_OK;
+}
+
+
+namespace {
+int finish_stats(rt_context* c, Backend* b, hipStream_t s)
+{
+    if (!c->stats_enabled) return RT_OK;
+    HIPCHK(c, hipMemcpyAsync(c->stats, b->stats.p, sizeof(c->stats), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    return RT_OK;
+}
+
+// Rows of a multi-device render: request row j (image row off + j*stride) belongs to
+// device j mod N. Device d's rows go to block d of the root's staging buffer (rows_max
+// rows each; the tail of a short block is padding), ncclScatter sends block d to
+// device d, every device renders its block with its own wavefront loop (one host
+// thread per device: run_wave polls its lanes), and ncclGather brings the blocks back
+// for the un-permute. Pack and un-permute are strided 2-D copies on the root.
+int render_multi(rt_context* c, Group* g, int w, int h, int spp, int bounces, float4_* fb, int off, int stride,
+                 hipStream_t s)
+{
+    const int N = (int)g->dev.size();
+    std::string err;
+    const Rccl* R = nullptr;
+    if (!g->loopback && !(R = rccl_load(err))) return rt_fail(c, RT_ERR_NODEV, err);
+    const int rows = (h - off + stride - 1) / stride;
+    const int rows_max = (rows + N - 1) / N;
+    const size_t blk = (size_t)rows_max * w;  // float4 per block
+    auto rows_of = [&](int d) { return rows > d ? (rows - d + N - 1) / N : 0; };
+    Backend* root = g->dev[0];
+    for (int d = 1; d < N; d++) {
+        HIPCHK(c, hipSetDevice(g->dev[d]->device));
+        if (int r = ensure(c, g->dev[d]->shard, std::max<size_t>(blk, 1) * sizeof(float4_))) return r;
+    }
+    HIPCHK(c, hipSetDevice(root->device));
+    if (int r = ensure(c, root->shard, std::max<size_t>(blk, 1) * N * sizeof(float4_))) return r;
+    float4_* stage = (float4_*)root->shard.p;
+    HIPCHK(c, hipEventRecord(root->ev0, s));
+    const size_t pitch = (size_t)w * sizeof(float4_);
+    for (int d = 0; d < N; d++)
+        if (rows_of(d))
+            HIPCHK(c, hipMemcpy2DAsync(stage + d * blk, pitch, fb + (size_t)d * w, N * pitch, pitch, rows_of(d),
+                                       hipMemcpyDeviceToDevice, s));
+    std::vector<hipStream_t> st(N);
+    for (int d = 0; d < N; d++) st[d] = d == 0 ? s : g->dev[d]->own;
+    const size_t cnt = blk * 4;  // floats per block
+    if (g->loopback) {  // block d -> device d by a device copy on the root stream; the shard streams wait for it
+        for (int d = 1; d < N; d++)
+            HIPCHK(c, hipMemcpyAsync(g->dev[d]->shard.p, stage + d * blk, blk * sizeof(float4_), hipMemcpyDeviceToDevice, s));
+        HIPCHK(c, hipEventRecord(root->ev_fork, s));
+        for (int d = 1; d < N; d++) {
+            HIPCHK(c, hipSetDevice(g->dev[d]->device));
+            HIPCHK(c, hipStreamWaitEvent(st[d], root->ev_fork, 0));
+        }
+        HIPCHK(c, hipSetDevice(root->device));
+    } else {
+        NCCLCHK(c, R, R->group_start());
+        for (int d = 0; d < N; d++)
+            NCCLCHK(c, R, R->scatter(stage, d == 0 ? (void*)stage : g->dev[d]->shard.p, cnt, ncclFloat, 0, g->comms[d], st[d]));
+        NCCLCHK(c, R, R->group_end());
+    }
+    // the wavefront loops, one host thread per device; errors are collected per device
+    // and raised once after the join (rt_for_devices). run_wave resets the stats itself.
+    if (int r = rt_for_devices(c, N, [&](int d) -> int {
+            Backend* b = g->dev[d];
+            HIPCHK(c, hipSetDevice(b->device));
+            const rtk::PixSrc src{w, off + d * stride, N * stride, nullptr};
+            float4_* dst = d == 0 ? stage : (float4_*)g->dev[d]->shard.p;
+            return run_wave(c, b, w, h, spp, bounces, src, rows_of(d) * w, dst, st[d]);
+        }))
+        return r;
+    HIPCHK(c, hipSetDevice(root->device));
+    if (g->loopback) {  // each block back to the root after its device's loop; the root stream waits for all
+        for (int d = 1; d < N; d++) {
+            Backend* b = g->dev[d];
+            HIPCHK(c, hipSetDevice(b->device));
+            HIPCHK(c, hipMemcpyAsync(stage + d * blk, g->dev[d]->shard.p, blk * sizeof(float4_), hipMemcpyDeviceToDevice, st[d]));
+            HIPCHK(c, hipEventRecord(b->ev_join[0], st[d]));
+            HIPCHK(c, hipSetDevice(root->device));
+            HIPCHK(c, hipStreamWaitEvent(s, b->ev_join[0], 0));
+        }
+    } else {
+        NCCLCHK(c, R, R->group_start());
+        for (int d = 0; d < N; d++)
+            NCCLCHK(c, R, R->gather(d == 0 ? (const void*)stage : g->dev[d]->shard.p, stage, cnt, ncclFloat, 0, g->comms[d], st[d]));
+        NCCLCHK(c, R, R->group_end());
+    }
+    for (int d = 0; d < N; d++)
+        if (rows_of(d))
+            HIPCHK(c, hipMemcpy2DAsync(fb + (size_t)d * w, N * pitch, stage + d * blk, pitch, pitch, rows_of(d),
+                                       hipMemcpyDeviceToDevice, s));
+    HIPCHK(c, hipEventRecord(root->ev1, s));
+    if (c->stats_enabled) {  // counters summed over the devices
+        unsigned long long sum[2 * RT_STAT_COUNT] = {};
+        for (int d = 0; d < N; d++) {
+            HIPCHK(c, hipSetDevice(g->dev[d]->device));
+            HIPCHK(c, hipMemcpyAsync(c->stats, g->dev[d]->stats.p, sizeof(c->stats), hipMemcpyDeviceToHost, st[d]));
+            HIPCHK(c, hipStreamSynchronize(st[d]));
+            for (int i = 0; i < 2 * RT_STAT_COUNT; i++) sum[i] += c->stats[i];
+        }
+        std::memcpy(c->stats, sum, sizeof sum);
+        HIPCHK(c, hipSetDevice(root->device));
+    }
+    root->last_iters = 0;
+    for (Backend* b : g->dev) root->last_iters = std::max(root->last_iters, b->last_iters);
+    return RT_OK;
+}
+}  // namespace
+
+int rt_backend_render(rt_context* c, int w, int h, int spp, int bounces, float* host_fb, void* dev_fb, int row_offset,
+                      int row_stride, void* stream)
+{
+    Group* g = grp(c);
+    Backend* b = be(c);
+    HIPCHK(c, hipSetDevice(b->device));
+    hipStream_t s = (hipStream_t)stream;
+    const int rows_local = (h - row_offset + row_stride - 1) / row_stride;
+    const size_t npx = (size_t)rows_local * w;
+    if (npx > 0x7fffffff / 8) return rt_fail(c, RT_ERR_ARG, "render: too many pixels for one launch");
+    float4_* fb = (float4_*)dev_fb;
+    if (host_fb) {
+        if (int r = ensure(c, b->fb, npx * sizeof(float4_))) return r;
+        fb = (float4_*)b->fb.p;
+        HIPCHK(c, hipMemcpyAsync(fb, host_fb, npx * sizeof(float4_), hipMemcpyHostToDevice, s));
+    }
+    if (g->multi) {
+        if (int r = render_multi(c, g, w, h, spp, bounces, fb, row_offset, row_stride, s)) return r;
+    } else {
+        rtk::PixSrc src{w, row_offset, row_stride, nullptr};
+        HIPCHK(c, hipEventRecord(b->ev0, s));
+        if (int r = run_wave(c, b, w, h, spp, bounces, src, (int)npx, fb, s)) return r;
+        HIPCHK(c, hipEventRecord(b->ev1, s));
+    }
+    if (host_fb) {
+        HIPCHK(c, hipMemcpyAsync(host_fb, fb, npx * sizeof(float4_), hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipStreamSynchronize(s));
+        float ms = 0;
+        HIPCHK(c, hipEventElapsedTime(&ms, b->ev0, b->ev1));
+        c->last_kernel_ms = ms;
+    } else {
+        c->last_kernel_ms = -1.0;  // read with rt_device_last_kernel_ms after the caller synchronizes
+    }
+    return g->multi ? RT_OK : finish_stats(c, b, s);
+}
+
+// The material sweep as replicas (rt_render_variants): variant v on device v mod N, one
+// host thread per device (rt_for_devices), each device walking its variants in order on
+// its own stream: the variant's table goes into the device's material buffer with a copy
+// ordered after the previous variant's frame (same stream), then the wavefront loop.
+// No exchange between devices.
+int rt_backend_render_variants(rt_context* c, int w, int h, int spp, int bounces, int n_var,
+                               const std::vector<RtMat>& tabs, int n_mats, int off, int stride, float* host_fb,
+                               void* const* d_fbs)
+{
+    Group* g = grp(c);
+    const int N = (int)g->dev.size();
+    const int rows = (h - off + stride - 1) / stride;
+    const size_t npx = (size_t)rows * w;
+    if (npx > 0x7fffffff / 8) return rt_fail(c, RT_ERR_ARG, "render: too many pixels for one launch");
+    std::vector<float> ms(N, 0.0f);
+    // counters summed over every variant of every device (run_wave zeroes a device's per render)
+    std::vector<std::vector<unsigned long long>> vsum(N, std::vector<unsigned long long>(2 * RT_STAT_COUNT, 0));
+    const int r = rt_for_devices(c, N, [&](int d) -> int {
+        Backend* b = g->dev[d];
+        HIPCHK(c, hipSetDevice(b->device));
+        hipStream_t s = b->own;
+        if (b->done_recorded) HIPCHK(c, hipEventSynchronize(b->ev_done));  // (the table and buffers are reused)
+        if (int e = ensure(c, b->mats, (size_t)n_mats * sizeof(RtMat))) return e;
+        b->view.mats = (const RtMat*)b->mats.p;
+        b->view.n_mats = n_mats;
+        if (host_fb)
+            if (int e = ensure(c, b->fb, npx * sizeof(float4_))) return e;
+        HIPCHK(c, hipEventRecord(b->ev0, s));
+        for (int v = d; v < n_var; v += N) {
+            const RtMat* tab = tabs.data() + (size_t)v * n_mats;
+            b->bl_rays = rt_table_has_emissive_prim(c, tab) ? 1 : 0;
+            // (pageable source: the copy is staged before the call returns, and ordered on s
+            // after the previous variant's frame, whose lanes joined back into s)
+            HIPCHK(c, hipMemcpyAsync(b->mats.p, tab, (size_t)n_mats * sizeof(RtMat), hipMemcpyHostToDevice, s));
+            float4_* fb = host_fb ? (float4_*)b->fb.p : (float4_*)d_fbs[v];
+            if (host_fb)
+                HIPCHK(c, hipMemcpyAsync(fb, host_fb + 4 * npx * v, npx * sizeof(float4_), hipMemcpyHostToDevice, s));
+            const rtk::PixSrc src{w, off, stride, nullptr};
+            if (int e = run_wave(c, b, w, h, spp, bounces, src, (int)npx, fb, s)) return e;
+            if (host_fb)
+                HIPCHK(c, hipMemcpyAsync(host_fb + 4 * npx * v, fb, npx * sizeof(float4_), hipMemcpyDeviceToHost, s));
+            if (c->stats_enabled) {  // (diagnostic renders: this variant's counters, before the next zeroes them)
+                unsigned long long one[2 * RT_STAT_COUNT];
+                HIPCHK(c, hipMemcpyAsync(one, b->stats.p, sizeof one, hipMemcpyDeviceToHost, s));
+                HIPCHK(c, hipStreamSynchronize(s));
+                for (int i = 0; i < 2 * RT_STAT_COUNT; i++) vsum[d][i] += one[i];
+            }
+        }
+        HIPCHK(c, hipEventRecord(b->ev1, s));
+        HIPCHK(c, hipStreamSynchronize(s));
+        HIPCHK(c, hipEventElapsedTime(&ms[d], b->ev0, b->ev1));
+        return 0;
+    });
+    // the bound table comes back with the next render's upload (rt_render_variants marks it)
+    for (Backend* b : g->dev) b->bl_rays = rt_scene_has_emissive_prim(c) ? 1 : 0;
+    HIPCHK(c, hipSetDevice(be(c)->device));
+    if (r) return r;
+    c->last_kernel_ms = *std::max_element(ms.begin(), ms.end());
+    if (c->stats_enabled)  // every variant of every device, summed
+        for (int i = 0; i < 2 * RT_STAT_COUNT; i++) {
+            c->stats[i] = 0;
+            for (int d = 0; d < N; d++) c->stats[i] += vsum[d][i];
+        }
+    return RT_OK;
+}
+
+// One device's share of a pixel list (host buffers in and out).
+static int render_pixels_one(rt_context* c, Backend* b, int w, int h, int spp, int bounces, const int* xy, int n,
+                             float* rgba, float* ms_out)
+{
+    HIPCHK(c, hipSetDevice(b->device));
+    if (n == 0) return RT_OK;
+    const size_t bxy = (size_t)n * 8, brgba = (size_t)n * 16;
+    if (int r = ensure(c, b->xy, bxy)) return r;
+    if (int r = ensure(c, b->fb, brgba)) return r;
+    hipStream_t s = b->own;
+    HIPCHK(c, hipMemcpyAsync(b->xy.p, xy, bxy, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(b->fb.p, rgba, brgba, hipMemcpyHostToDevice, s));
+    if (c->stats_enabled) HIPCHK(c, hipMemsetAsync(b->stats.p, 0, b->stats.bytes, s));
+    rtk::PixSrc src{w, 0, 1, (const int32_t*)b->xy.p};
+    HIPCHK(c, hipEventRecord(b->ev0, s));
+    if (int r = run_wave(c, b, w, h, spp, bounces, src, n, (float4_*)b->fb.p, s)) return r;
+    HIPCHK(c, hipEventRecord(b->ev1, s));
+    HIPCHK(c, hipMemcpyAsync(rgba, b->fb.p, brgba, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    float ms = 0;
+    HIPCHK(c, hipEventElapsedTime(&ms, b->ev0, b->ev1));
+    *ms_out = ms;
+    return RT_OK;
+}
+
+int rt_backend_render_pixels(rt_context* c, int w, int h, int spp, int bounces, const int* xy, int n, float* rgba)
+{
+    Group* g = grp(c);
+    const int N = (int)g->dev.size();
+    if (N == 1) {
+        float ms = 0;
+        if (int r = render_pixels_one(c, g->dev[0], w, h, spp, bounces, xy, n, rgba, &ms)) return r;
+        c->last_kernel_ms = ms;
+        return finish_stats(c, g->dev[0], g->dev[0]->own);
+    }
+    // pixel i -> device i mod N (pixels are independent); host-side split and merge
+    std::vector<std::vector<int>> pxy(N);
+    std::vector<std::vector<float>> prgba(N);
+    for (int i = 0; i < n; i++) {
+        pxy[i % N].push_back(xy[2 * i]);
+        pxy[i % N].push_back(xy[2 * i + 1]);
+        prgba[i % N].insert(prgba[i % N].end(), rgba + 4 * (size_t)i, rgba + 4 * (size_t)i + 4);
+    }
+    std::vector<int> rc(N, RT_OK);
+    std::vector<float> ms(N, 0.0f);
+    {
+        std::vector<std::thread> th;
+        for (int d = 0; d < N; d++)
+            th.emplace_back([&, d] {
+                rc[d] = render_pixels_one(c, g->dev[d], w, h, spp, bounces, pxy[d].data(), (int)pxy[d].size() / 2,
+                                          prgba[d].data(), &ms[d]);
+            });
+        for (auto& t : th) t.join();
+    }
+    for (int d = 0; d < N; d++)
+        if (rc[d]) return rc[d];
+    for (int i = 0; i < n; i++) std::memcpy(rgba + 4 * (size_t)i, &prgba[i % N][4 * (size_t)(i / N)], 16);
+    c->last_kernel_ms = *std::max_element(ms.begin(), ms.end());
+    if (c->stats_enabled) {
+        unsigned long long sum[2 * RT_STAT_COUNT] = {};
+        for (int d = 0; d < N; d++) {
+            if (int r = finish_stats(c, g->dev[d], g->dev[d]->own)) return r;
+            for (int i = 0; i < 2 * RT_STAT_COUNT; i++) sum[i] += c->stats[i];
+        }
+        std::memcpy(c->stats, sum, sizeof sum);
+    }
+    return RT_OK;
+}
+
+Backend* rt_backend_dev0(rt_context* c) { return be(c); }
+
+// The root device's state for the post stage (rt_denoise.hip) and the ray queries (rt_query.hip).
+int rt_backend_root(rt_context* c, RtRootDev* out)
+{
+    Backend* b = be(c);
+    out->device = b->device;
+    out->view = &b->view;
+    out->ev0 = b->ev0;
+    out->ev1 = b->ev1;
+    out->post = &b->post;
+    out->query = &b->query;
+    return RT_OK;
+}
+
+// Time between the events around the last rt_render_device launch sequence
+// (recorded on its stream); call after synchronizing that stream.
+extern "C" double rt_device_last_kernel_ms(rt_context* c)
+{
+    if (!c || !c->backend) return -1.0;
+    Backend* b = be(c);
+    float ms = 0;
+    if (hipEventSynchronize(b->ev1) != hipSuccess) return -1.0;
+    if (hipEventElapsedTime(&ms, b->ev0, b->ev1) != hipSuccess) return -1.0;
+    c->last_kernel_ms = ms;
+    return ms;
+}
+
+// Iterations the last wavefront render took.
+extern "C" int rt_device_last_iterations(rt_context* c) { return c && c->backend ? be(c)->last_iters : -1; }
+
+// Queries k_trace handed to the exact octree walk (ties, failed verifications, stack
+// overflows, far origins, the force_fallback stressor) in every render on every device of
+// the context since the last reset: the walks' health figure (~2e-6 per sample on cfg2).
+// Waits for the devices.
+extern "C" int rt_device_exact_handovers(rt_context* c, unsigned long long* out, int reset)
+{
+    if (!c || !c->backend || !out) return rt_fail(c, RT_ERR_ARG, "rt_device_exact_handovers: no context or no output");
+    unsigned long long sum = 0;
+    DeviceScope sc;  // (the caller's device is current again on every return)
+    for (Backend* b : grp(c)->dev) {
+        if (int r = sc.enter(c, b->device)) return r;
+        HIPCHK(c, hipDeviceSynchronize());
+        if (!b->handovers.p) continue;
+        unsigned long long v = 0;
+        HIPCHK(c, hipMemcpy(&v, b->handovers.p, 8, hipMemcpyDeviceToHost));
+        sum += v;
+        if (reset) HIPCHK(c, hipMemset(b->handovers.p, 0, 8));
+    }
+    *out = sum;
+    return RT_OK;
+}
+
+// Per-kernel-class timing (k_trace, k_step, k_tail) over the renders since it
+// was enabled, summed over the context's devices: out_ms[3] total ms (HIP events
+// around every launch on its lane's stream), out_launches[3].
+extern "C" int rt_device_kernel_timing(rt_context* c, int enable, double* out_ms, long* out_launches)
+{
+    if (!c || !c->backend) return RT_ERR_ARG;
+    Group* g = grp(c);
+    for (int k = 0; k < 3; k++) {
+        double ms = 0;
+        long n = 0;
+        for (Backend* b : g->dev) ms += b->kms[k], n += b->klaunch[k];
+        if (out_ms) out_ms[k] = ms;
+        if (out_launches) out_launches[k] = n;
+    }
+    if (enable >= 0)
+        for (Backend* b : g->dev) {
+            b->timing = enable != 0;
+            for (int k = 0; k < 3; k++) b->kms[k] = 0, b->klaunch[k] = 0;
+        }
+    return RT_OK;
+}
+
+// Wavefront lanes (streams) per render on every device of the context (RT_LANES at
+// creation; 1 serializes a render's launches, for per-launch kernel timing; 0: auto).
+extern "C" int rt_device_set_lanes(rt_context* c, int lanes)
+{
+    if (!c || !c->backend || lanes < 0) return RT_ERR_ARG;
+    for (Backend* b : grp(c)->dev) b->lanes = std::min(RT_MAX_LANES, lanes);
+    return RT_OK;
+}
+
+#ifndef RT_BUILD_SRC
+#define RT_BUILD_SRC "unknown"
+#endif
+#ifndef RT_BUILD_DEFS
+#define RT_BUILD_DEFS ""
+#endif
+extern "C" const char* rt_build_id(void) { return "src=" RT_BUILD_SRC " defs=" RT_BUILD_DEFS " (gfx950)"; }

@@ -20,13 +20,6 @@
 #include "rt_backend_hip.h"
 #include "rt_denoise.h"
 
-#define HIPCHK(ctx, expr)                                                                         \
-    do {                                                                                          \
-        hipError_t e_ = (expr);                                                                   \
-        if (e_ != hipSuccess)                                                                     \
-            return rt_fail(ctx, RT_ERR_HIP, std::string(#expr ": ") + hipGetErrorString(e_));     \
-    } while (0)
-
 namespace {
 
 __global__ __launch_bounds__(256) void k_features(RtSceneView S, rtk::CamView V, float4_* __restrict__ alb,
@@ -119,50 +112,20 @@ bool dn_use_lds(int variant, int step)
     return step <= 2;
 }
 
-struct DevBuf {
-    void* p = nullptr;
-    size_t bytes = 0;
-};
-
 // The post stage's buffers on the root device, cached across calls like the render's.
 struct Post {
     DevBuf io;    // host-pointer calls: input, output, albedo, normal_depth
     DevBuf pp;    // ping-pong colour buffers between passes
     // optional per-pass timing (rt_device_denoise_pass_ms): an event before each pass and after the last
     bool timing = false;
-    hipEvent_t pev[11] = {};
+    Event pev[11];
     int timed_passes = 0;
-};
-
-int ensure(rt_context* c, DevBuf& b, size_t bytes)
-{
-    if (b.bytes >= bytes && b.p) return RT_OK;
-    if (b.p) HIPCHK(c, hipFree(b.p));
-    b.p = nullptr;
-    b.bytes = 0;
-    HIPCHK(c, hipMalloc(&b.p, bytes));
-    b.bytes = bytes;
-    return RT_OK;
-}
-
-// The root device made current for the call; the caller's device restored afterwards.
-struct DeviceScope {
-    int prev = -1;
-    ~DeviceScope()
-    {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
 };
 
 int enter(rt_context* c, RtRootDev& R, DeviceScope& sc, Post** post)
 {
     if (int r = rt_backend_root(c, &R)) return r;
-    int cur = -1;
-    HIPCHK(c, hipGetDevice(&cur));
-    if (cur != R.device) {
-        HIPCHK(c, hipSetDevice(R.device));
-        sc.prev = cur;
-    }
+    if (int r = sc.enter(c, R.device)) return r;
     if (!*R.post) *R.post = new Post();
     *post = (Post*)*R.post;
     return RT_OK;
@@ -188,16 +151,7 @@ int launch_pass(rt_context* c, const rtk::DnPass& P, float4_* out, const float4_
 
 }  // namespace
 
-void rt_post_free(void* post)
-{
-    Post* p = (Post*)post;
-    if (!p) return;
-    if (p->io.p) (void)hipFree(p->io.p);
-    if (p->pp.p) (void)hipFree(p->pp.p);
-    for (hipEvent_t e : p->pev)
-        if (e) (void)hipEventDestroy(e);
-    delete p;
-}
+void rt_post_free(void* post) { delete (Post*)post; }
 
 int rt_backend_features(rt_context* c, int w, int h, void* albedo, void* normal_depth, bool device, void* stream)
 {
@@ -307,7 +261,7 @@ extern "C" int rt_device_denoise_pass_ms(rt_context* c, int enable, double* out_
     Post* post = nullptr;
     if (int r = enter(c, R, sc, &post)) return r;
     if (enable == 1 && !post->pev[0])
-        for (hipEvent_t& e : post->pev) HIPCHK(c, hipEventCreate(&e));
+        for (Event& e : post->pev) HIPCHK(c, hipEventCreate(&e.h));
     if (enable >= 0) {
         post->timing = enable == 1;
         if (!post->timing) post->timed_passes = 0;

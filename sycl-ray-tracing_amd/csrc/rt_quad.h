@@ -548,3 +548,18 @@ __device__ __forceinline__ bool quad_closest_answer(const RtSceneView& S, const 
 }
 
 }  // namespace rtk
+
+// Wave-aggregated append (every lane of the wave calls it converged): this lane's slot in
+// the list whose size lives at *counter, -1 when it does not want one.
+__device__ __forceinline__ int wave_append(int32_t* counter, bool want)
+{
+    const unsigned long long b = __ballot(want);
+    if (b == 0) return -1;
+    const int lane = (int)__lane_id();
+    const int leader = __ffsll((long long)b) - 1;
+    int base = 0;
+    if (lane == leader) base = atomicAdd(counter, __popcll(b));
+    base = __shfl(base, leader);
+    const unsigned long long lt = lane == 0 ? 0ull : (b & (~0ull >> (64 - lane)));
+    return want ? base + __popcll(lt) : -1;
+}

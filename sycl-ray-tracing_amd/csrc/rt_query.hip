@@ -27,32 +27,10 @@
 #include "rt_query.h"
 #include "rt_quad.h"
 
-#define HIPCHK(ctx, expr)                                                                         \
-    do {                                                                                          \
-        hipError_t e_ = (expr);                                                                   \
-        if (e_ != hipSuccess)                                                                     \
-            return rt_fail(ctx, RT_ERR_HIP, std::string(#expr ": ") + hipGetErrorString(e_));     \
-    } while (0)
-
 #define RQ_QSTACK 32  // stack entries per quad (item + key), k_trace's RT_QSTACK
 #define RQ_REFILL 4   // idle quads of a wave that trigger a refill, k_trace's RT_TRACE_REFILL
 
 namespace {
-
-// Wave-aggregated append (every lane of the wave calls it converged): this lane's slot in
-// the list whose size lives at *counter, -1 when it does not want one.
-__device__ __forceinline__ int wave_append(int32_t* counter, bool want)
-{
-    const unsigned long long b = __ballot(want);
-    if (b == 0) return -1;
-    const int lane = (int)__lane_id();
-    const int leader = __ffsll((long long)b) - 1;
-    int base = 0;
-    if (lane == leader) base = atomicAdd(counter, __popcll(b));
-    base = __shfl(base, leader);
-    const unsigned long long lt = lane == 0 ? 0ull : (b & (~0ull >> (64 - lane)));
-    return want ? base + __popcll(lt) : -1;
-}
 
 struct RqRay {
     rtk::V3 o, d;
@@ -183,54 +161,24 @@ __global__ __launch_bounds__(256) void k_rq_exact(RtSceneView S, const float* __
     }
 }
 
-struct DevBuf {
-    void* p = nullptr;
-    size_t bytes = 0;
-};
-
 // The queries' workspace on the root device, cached across calls and grown on demand like
 // the post stage's buffers.
 struct Query {
     DevBuf list;     // 64 B (the fallback count in its first word), then n indices
     DevBuf io;       // host-pointer calls: the rays, then the answers
-    hipEvent_t done = nullptr;  // the end of the last call's kernels (rt_query_last_exact waits for it)
+    Event done;  // the end of the last call's kernels (rt_query_last_exact waits for it)
     int blocks[4] = {0, 0, 0, 0};  // resident blocks per CU of k_rq_fast<ANY, REFILL>, asked once
     int cus = 0;
-};
-
-int ensure(rt_context* c, DevBuf& b, size_t bytes)
-{
-    if (b.bytes >= bytes && b.p) return RT_OK;
-    if (b.p) HIPCHK(c, hipFree(b.p));
-    b.p = nullptr;
-    b.bytes = 0;
-    HIPCHK(c, hipMalloc(&b.p, bytes));
-    b.bytes = bytes;
-    return RT_OK;
-}
-
-// The root device made current for the call; the caller's device restored afterwards.
-struct DeviceScope {
-    int prev = -1;
-    ~DeviceScope()
-    {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
 };
 
 int enter(rt_context* c, RtRootDev& R, DeviceScope& sc, Query** query)
 {
     if (int r = rt_backend_root(c, &R)) return r;
-    int cur = -1;
-    HIPCHK(c, hipGetDevice(&cur));
-    if (cur != R.device) {
-        HIPCHK(c, hipSetDevice(R.device));
-        sc.prev = cur;
-    }
+    if (int r = sc.enter(c, R.device)) return r;
     if (!*R.query) {
         Query* q = new Query();
         *R.query = q;
-        HIPCHK(c, hipEventCreate(&q->done));
+        HIPCHK(c, hipEventCreate(&q->done.h));
         HIPCHK(c, hipDeviceGetAttribute(&q->cus, hipDeviceAttributeMultiprocessorCount, R.device));
         const void* fn[4] = {(const void*)k_rq_fast<false, false>, (const void*)k_rq_fast<false, true>,
                              (const void*)k_rq_fast<true, false>, (const void*)k_rq_fast<true, true>};
@@ -253,15 +201,7 @@ bool use_refill(int variant) { return variant != 1; }
 
 }  // namespace
 
-void rt_query_free(void* query)
-{
-    Query* q = (Query*)query;
-    if (!q) return;
-    if (q->list.p) (void)hipFree(q->list.p);
-    if (q->io.p) (void)hipFree(q->io.p);
-    if (q->done) (void)hipEventDestroy(q->done);
-    delete q;
-}
+void rt_query_free(void* query) { delete (Query*)query; }
 
 int rt_backend_query(rt_context* c, bool any, bool all_exact, const void* rays, long n, void* out, bool device,
                      void* stream)

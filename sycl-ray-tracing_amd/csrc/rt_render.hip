@@ -20,41 +20,21 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <string>
 #include <vector>
 #include <algorithm>
 
-#include <dlfcn.h>
 #include <chrono>
-#include <mutex>
 #include <thread>
 
-#include <rccl/rccl.h>
-
-#include "rt_context.h"
 #include "rt_backend_hip.h"
 #include "rt_wave.h"
 #include "rt_quad.h"
 #include "rt_row.h"
 #include "rt_octet.h"
 
-#define HIPCHK(ctx, expr)                                                                         \
-    do {                                                                                          \
-        hipError_t e_ = (expr);                                                                   \
-        if (e_ != hipSuccess)                                                                     \
-            return rt_fail(ctx, RT_ERR_HIP, std::string(#expr ": ") + hipGetErrorString(e_));     \
-    } while (0)
-
 namespace {
 
-#define RT_MAX_TIMED_ITERS 16384
-#define RT_MAX_LANES 4  // wavefront lanes (streams) per render (run_wave)
-#define RT_FAST_K 768         // fast lane: paths handed over (run_wave)
-#define RT_FAST_SPP 2.25      // ... from iteration RT_FAST_SPP x spp on
-#define RT_FAST_MAX_SPP 4096  // ... in renders of at most this many samples per pixel
-#define RT_LANES4_MAX 1572864  // auto lanes: 4 at most this many slots per launch, else 3
 #ifndef RT_STEP_OCC
 #define RT_STEP_OCC 3  // k_step waves per SIMD
 #endif
@@ -68,11 +48,6 @@ namespace {
 #ifndef RT_TAIL_ROWS
 #define RT_TAIL_ROWS 1  // k_tail walks with rows (rt_row.h)
 #endif
-
-struct DevBuf {
-    void* p = nullptr;
-    size_t bytes = 0;
-};
 
 // counters[] layout (int32). Iteration i (p = i & 1) runs k_trace(i) then
 // k_step(i); every set is zeroed by a launch between its last reader and its
@@ -163,75 +138,6 @@ __host__ __device__ __forceinline__ int seg_counter(int par, int j)
     return s.heavy ? hc_at(par, s.kind, s.shard) : qc_at(par, s.kind, s.shard);
 }
 
-struct Backend {
-    int device = 0;
-    int index = 0;    // position in the context's device list (0: the root)
-    hipStream_t own = nullptr;  // device-side work not on a caller's stream (multi-device shards, pixel lists)
-    DevBuf nodes, tri4, prim2k, mat_idx, mats, emissive, spheres, env, env_lum, cdf;
-    DevBuf bvh4, bvh16, bvh4s, bvh16s, bvh_tri4, parent, leaf_of, cdf_row, cdf_coarse, cdf_fence, matk;
-    DevBuf stats;     // 2 x RT_STAT_COUNT u64: all kernels, then the tail kernel's share
-    DevBuf handovers; // u64: queries k_trace handed to the exact walk, every render since the last reset
-    DevBuf iterq;     // stats renders: per-iteration {queries, live slots} (RT_ITER_LOG)
-    DevBuf wlog;      // stats renders with a walk log: count (256 B), then 3 float4 per record
-    DevBuf wave[RT_MAX_LANES];      // per lane: path state, pending records, results, queues, lists
-    DevBuf counters[RT_MAX_LANES];  // per lane: C_COUNT int32
-    // fast lane (rt_test_schedule fast_k): per lane its handed-over list + ticket, counters,
-    // samples-done histogram and spill area; the lanes' views for the one tail kernel over them
-    DevBuf fast[RT_MAX_LANES], fcnt[RT_MAX_LANES], fhist[RT_MAX_LANES], fspill[RT_MAX_LANES], fviews;
-    int32_t* h_hist[RT_MAX_LANES] = {};
-    rtk::WaveView* h_fviews = nullptr;  // pinned
-    hipEvent_t fev[RT_MAX_LANES] = {}, fev_done = nullptr;
-    hipEvent_t hev[RT_MAX_LANES] = {};  // fast lane: each lane's samples-done histogram readback
-    bool fev_done_recorded = false;
-    hipEvent_t ftev[2] = {};  // (timed renders: around the fast lane's kernel)
-    hipStream_t fs = nullptr;  // the fast lane's stream with 4 lanes (fewer: the first idle lane stream)
-    DevBuf xy;        // pixel list (rt_render_pixels)
-    DevBuf fb;        // host-fb staging
-    int32_t* h_act[RT_MAX_LANES] = {};     // per lane, pinned: live-slot counters (sharded) + 8 fallback counters
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    hipEvent_t ev_done = nullptr;  // end of the last run_wave (all lanes joined): the next render waits for it
-    bool done_recorded = false;
-    hipStream_t ls[RT_MAX_LANES] = {};      // lanes 1.. streams (lane 0 runs on the caller's)
-    hipEvent_t ev_fork = nullptr, ev_join[RT_MAX_LANES] = {}, ev_lane[RT_MAX_LANES] = {};
-    int lanes = 0;                          // RT_LANES; 0: auto, 4 lanes for launches of at most RT_LANES4_MAX
-                                            // slots, else 3 (cfg2 1-4 lanes: 452 / 499 / 519 / 509 Msamples/s, r01;
-                                            // r03: 3 / 4 lanes cfg2 147.5 / 148.6 ms, cfg4 8-way shard 398 / 386 ms,
-                                            // 6 / 8 lanes 230-710 ms: more streams than the 4 hardware queues)
-    RtSceneView view{};
-    int bl_rays = 1, any_rays = 1;
-    int last_iters = 0;
-    int tail_iter = -1;     // iteration whose step launch was the tail kernel (-1: none)
-    int budget = 1024;  // steps per query per launch before it parks (RT_STEP_BUDGET)
-    // optional per-kernel timing: events around each launch of each class
-    bool timing = false;
-    hipEvent_t tev[RT_MAX_LANES][3][RT_MAX_TIMED_ITERS] = {};
-    double kms[3] = {0, 0, 0};      // k_trace, k_step, k_tail
-    long klaunch[3] = {0, 0, 0};
-    void* post = nullptr;           // the post stage's buffers (rt_denoise.hip owns them: rt_post_free)
-    void* query = nullptr;          // the ray-query workspace (rt_query.hip owns it: rt_query_free)
-};
-
-int ensure(rt_context* c, DevBuf& b, size_t bytes)
-{
-    if (b.bytes >= bytes && b.p) return RT_OK;
-    if (b.p) HIPCHK(c, hipFree(b.p));
-    b.p = nullptr;
-    b.bytes = 0;
-    if (bytes == 0) return RT_OK;
-    HIPCHK(c, hipMalloc(&b.p, bytes));
-    b.bytes = bytes;
-    return RT_OK;
-}
-
-template <class T>
-int upload(rt_context* c, DevBuf& b, const std::vector<T>& v)
-{
-    const size_t bytes = v.size() * sizeof(T);
-    if (int r = ensure(c, b, bytes > 0 ? bytes : 16)) return r;
-    if (bytes) HIPCHK(c, hipMemcpy(b.p, v.data(), bytes, hipMemcpyHostToDevice));
-    return RT_OK;
-}
-
 
 // ------------------------------------------------------------ wave helpers
 #ifndef RT_DEBUG_FB
@@ -245,20 +151,6 @@ __device__ unsigned long long rt_dbg_fb[8];  // k_trace closest fallbacks, octet
 #define RT_DBG(i) ((void)0)
 #endif
 __device__ __forceinline__ int lane_id() { return __lane_id(); }
-
-// Wave-aggregated append: every lane of the wave must call this converged.
-// Returns this lane's slot in the queue whose size lives at *counter.
-__device__ __forceinline__ int wave_append(int32_t* counter, bool want)
-{
-    const unsigned long long b = __ballot(want);
-    if (b == 0) return -1;
-    const int leader = __ffsll((long long)b) - 1;
-    int base = 0;
-    if (lane_id() == leader) base = atomicAdd(counter, __popcll(b));
-    base = __shfl(base, leader);
-    const unsigned long long lt = (lane_id() == 0) ? 0ull : (b & (~0ull >> (64 - lane_id())));
-    return want ? base + __popcll(lt) : -1;
-}
 
 // Per-lane traversal stack in LDS: entry i of thread t at [i * 256 + t]
 // (a wave at equal depth touches 64 consecutive words: no bank conflicts).
@@ -598,10 +490,8 @@ __device__ __forceinline__ void walk_done(const rtk::WaveView& W, int par, uint3
     W.done[par][j] = (int32_t)(target >> 3);
 }
 
-#ifndef RT_EXACT_OCTET
-#define RT_EXACT_OCTET 1  // k_step's exact walks: 8 lanes per query (rt_octet.h); 0: one lane per query
-#endif
-#if RT_EXACT_OCTET
+// (k_step's exact walks take 8 lanes per query, rt_octet.h; the one-lane-per-query walks they
+// replaced were measured in profiles/r04m_exact_octets.json)
 // Exact octree walks of k_step(i) (par = i & 1), one octet of lanes per query (rt_octet.h):
 // the walks parked by k_step(i - 1) (PARK[par ^ 1], the first n_res tickets), then the
 // fallbacks of k_trace(i) (FB[par]). ANY selects the occlusion walk.
@@ -681,125 +571,6 @@ __device__ void exact_octets(const rtk::WaveView& W, int par, uint32_t* lds, int
         }
     }
 }
-#else
-// Exact octree walks of k_step(i) (par = i & 1): the walks parked by k_step(i - 1)
-// (PARK[par ^ 1], the first n_res tickets), then the fallbacks of k_trace(i) (FB[par]).
-__device__ void exact_closest(const rtk::WaveView& W, int par, uint32_t* lds, int lane, int n_res, int total,
-                              rtk::Stats* st)
-{
-    using FAST = LdsStack<RT_LDS_CAP_CLOSEST>;
-    rtk::SpillStack<FAST> stk{FAST{lds + threadIdx.x, (float*)lds + RT_LDS_CAP_CLOSEST * 256 + threadIdx.x},
-                              W.spill_r + (size_t)lane * RT_STACK_CAP, W.spill_k + (size_t)lane * RT_STACK_CAP};
-    const rtk::RayRec* fb = W.fb_c[par];
-    rtk::TravC T;
-    bool has = false, drained = false;
-    uint32_t target = 0;
-    for (;;) {
-        const bool need = !has;
-        const unsigned long long bneed = __ballot(need);
-        const int nneed = __popcll(bneed);
-        if (!drained && (nneed >= RT_REFILL || nneed == 64)) {
-            int base = 0;
-            if (lane_id() == 0) base = atomicAdd(W.counters + C_TK_EXACT_C, nneed);
-            base = __shfl(base, 0);
-            if (base + nneed >= total) drained = true;
-            if (need) {
-                const int idx = base + __popcll(bneed & ((1ull << lane_id()) - 1ull));
-                if (idx < n_res) {
-                    target = rtk::travc_resume(&W.park_c[par ^ 1][idx], T, stk);
-                    has = true;
-                } else if (idx < total) {
-                    const rtk::RayRec r = fb[idx - n_res];
-                    target = (rt_asuint(r.o.w) << 3) | rt_asuint(r.d.w);
-                    if (st) st->c[RT_STAT_FALLBACK]++;
-                    has = rtk::travc_begin(W.S, T, rtk::v3of(r.o), rtk::v3of(r.d), st);
-                    if (!has) {
-                        rtk::finish_closest(W, target, T.o, T.d, T.best_t, T.best_k);
-                        walk_done(W, par, target);
-                    }
-                }
-            }
-        }
-        if (!__any(has)) {
-            if (drained) break;
-            continue;
-        }
-        if (has) {
-            if (!rtk::travc_step(W.S, T, stk, st)) {
-                rtk::finish_closest(W, target, T.o, T.d, T.best_t, T.best_k);
-                walk_done(W, par, target);
-                has = false;
-            } else if (T.steps >= W.budget && rtk::travc_parkable(T)) {
-                const int ps = atomicAdd(W.counters + C_PARKC0 + par, 1);
-                if (ps < W.park_cap) {
-                    rtk::travc_park(T, stk, target, &W.park_c[par][ps]);
-                    has = false;
-                } else {
-                    T.steps = 0;  // park pool full: keep going
-                }
-            }
-        }
-    }
-}
-
-__device__ void exact_any(const rtk::WaveView& W, int par, uint32_t* lds, int lane, int n_res, int total,
-                          rtk::Stats* st)
-{
-    using FAST = LdsStack<RT_LDS_CAP_ANY>;
-    rtk::SpillStack<FAST> stk{FAST{lds + threadIdx.x, nullptr}, W.spill_r + (size_t)lane * RT_STACK_CAP, nullptr};
-    const rtk::RayRec* fb = W.fb_a[par];
-    rtk::TravA T;
-    bool has = false, drained = false;
-    uint32_t target = 0;
-    for (;;) {
-        const bool need = !has;
-        const unsigned long long bneed = __ballot(need);
-        const int nneed = __popcll(bneed);
-        if (!drained && (nneed >= RT_REFILL || nneed == 64)) {
-            int base = 0;
-            if (lane_id() == 0) base = atomicAdd(W.counters + C_TK_EXACT_A, nneed);
-            base = __shfl(base, 0);
-            if (base + nneed >= total) drained = true;
-            if (need) {
-                const int idx = base + __popcll(bneed & ((1ull << lane_id()) - 1ull));
-                if (idx < n_res) {
-                    target = rtk::trava_resume(&W.park_a[par ^ 1][idx], T, stk);
-                    has = true;
-                } else if (idx < total) {
-                    const rtk::RayRec r = fb[idx - n_res];
-                    target = (rt_asuint(r.o.w) << 3) | rt_asuint(r.d.w);
-                    if (st) st->c[RT_STAT_FALLBACK]++;
-                    has = rtk::trava_begin(W.S, T, rtk::v3of(r.o), rtk::v3of(r.d), st);
-                    if (!has) {
-                        rtk::finish_any(W, target, T.hit);  // (false, or the brute-force answer)
-                        walk_done(W, par, target);
-                    }
-                }
-            }
-        }
-        if (!__any(has)) {
-            if (drained) break;
-            continue;
-        }
-        if (has) {
-            if (!rtk::trava_step(W.S, T, stk, st)) {
-                rtk::finish_any(W, target, T.hit);
-                walk_done(W, par, target);
-                has = false;
-            } else if (T.steps >= W.budget && rtk::trava_parkable(T)) {
-                const int ps = atomicAdd(W.counters + C_PARKA0 + par, 1);
-                if (ps < W.park_cap) {
-                    rtk::trava_park(T, stk, target, &W.park_a[par][ps]);
-                    has = false;
-                } else {
-                    T.steps = 0;
-                }
-            }
-        }
-    }
-}
-
-#endif
 
 // Path step of iteration i (par = i & 1): resolve, shade, next sample, for
 // every live path not waiting on an exact walk; the first blocks instead run
@@ -835,24 +606,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_STEP_OCC
     // (the host launches >= 3 blocks, so both exact roles and the path step each get one:
     // with gridDim 3, half = 1; above, the exact roles take at most half of the grid)
     const int half = min(W.spill_lanes / 512, max(1, (int)gridDim.x / 4));
-    constexpr int WPB = RT_EXACT_OCTET ? 32 : 64;  // walks per block at once (octets / lanes)
+    constexpr int WPB = 32;  // walks per block at once (octets)
     const int nbe_c = min(half, (ec + WPB - 1) / WPB), nbe_a = min(half, (ea + WPB - 1) / WPB);
     const int b = (int)blockIdx.x;
     if (b < nbe_c) {
-#if RT_EXACT_OCTET
         exact_octets<false>(W, par, s_lds, b * 256 + (int)threadIdx.x, nrc, ec, ps);
-#else
-        exact_closest(W, par, s_lds, b * 256 + (int)threadIdx.x, nrc, ec, ps);
-#endif
         flush_stats<STATS>(st, stats);
         return;
     }
     if (b < nbe_c + nbe_a) {
-#if RT_EXACT_OCTET
         exact_octets<true>(W, par, s_lds, (W.spill_lanes / 512 + b - nbe_c) * 256 + (int)threadIdx.x, nra, ea, ps);
-#else
-        exact_any(W, par, s_lds, (W.spill_lanes / 512 + b - nbe_c) * 256 + (int)threadIdx.x, nra, ea, ps);
-#endif
         flush_stats<STATS>(st, stats);
         return;
     }
@@ -1740,285 +1503,56 @@ __global__ void k_env_search(RtSceneView S, int form, const float* __restrict__ 
 // ------------------------------------------------------------- wave memory
 }  // namespace
 
-// ------------------------------------------------------------------- hooks
-namespace {
-// A context drives one Backend per device. rt_create: one device, renders on the
-// caller's stream. rt_create_multi: devices[0] is the root that holds the caller's
-// framebuffer; a render shards its rows over the devices (render_multi).
-struct Group {
-    std::vector<Backend*> dev;     // dev[0]: the root
-    bool multi = false;            // rt_create_multi over two or more devices
-    bool loopback = false;         // (RT_MULTI_LOOPBACK test contexts) shards exchanged by device copies
-    std::vector<ncclComm_t> comms; // ncclCommInitAll over the devices, in order (RCCL exchange)
-    DevBuf stage;                  // root: N blocks of rows_max rows (scatter source / gather target)
-    std::vector<DevBuf> shard;     // device d >= 1: its block
-};
-
-Group* grp(rt_context* c) { return (Group*)c->backend; }
-Backend* be(rt_context* c) { return grp(c)->dev[0]; }
-
-// RCCL, loaded on the first multi-device context: the library need not be present
-// (or be the same build as a framework's own copy) for single-device use.
-struct Rccl {
-    void* h = nullptr;
-    decltype(&ncclCommInitAll) init = nullptr;
-    decltype(&ncclCommDestroy) destroy = nullptr;
-    decltype(&ncclScatter) scatter = nullptr;
-    decltype(&ncclGather) gather = nullptr;
-    decltype(&ncclGroupStart) group_start = nullptr;
-    decltype(&ncclGroupEnd) group_end = nullptr;
-    decltype(&ncclGetErrorString) errstr = nullptr;
-};
-std::mutex g_rccl_mu;
-Rccl g_rccl;
-
-const Rccl* rccl_load(std::string& err)
-{
-    std::lock_guard<std::mutex> lk(g_rccl_mu);
-    if (g_rccl.h) return &g_rccl;
-    void* h = dlopen("librccl.so.1", RTLD_NOW | RTLD_GLOBAL);
-    if (!h) h = dlopen("/opt/rocm/lib/librccl.so.1", RTLD_NOW | RTLD_GLOBAL);
-    if (!h) {
-        err = std::string("librt_hip: RCCL not found (librccl.so.1): ") + dlerror();
-        return nullptr;
-    }
-    Rccl r;
-    r.h = h;
-    r.init = (decltype(r.init))dlsym(h, "ncclCommInitAll");
-    r.destroy = (decltype(r.destroy))dlsym(h, "ncclCommDestroy");
-    r.scatter = (decltype(r.scatter))dlsym(h, "ncclScatter");
-    r.gather = (decltype(r.gather))dlsym(h, "ncclGather");
-    r.group_start = (decltype(r.group_start))dlsym(h, "ncclGroupStart");
-    r.group_end = (decltype(r.group_end))dlsym(h, "ncclGroupEnd");
-    r.errstr = (decltype(r.errstr))dlsym(h, "ncclGetErrorString");
-    if (!r.init || !r.destroy || !r.scatter || !r.gather || !r.group_start || !r.group_end || !r.errstr) {
-        err = "librt_hip: librccl.so.1 lacks ncclCommInitAll / ncclScatter / ncclGather";
-        return nullptr;
-    }
-    g_rccl = r;
-    return &g_rccl;
-}
-
-#define NCCLCHK(ctx, R, expr)                                                                    \
-    do {                                                                                         \
-        ncclResult_t e_ = (expr);                                                                \
-        if (e_ != ncclSuccess) return rt_fail(ctx, RT_ERR_HIP, std::string(#expr ": ") + (R)->errstr(e_)); \
-    } while (0)
-
-int create_one(rt_context* c, int device, Backend** out)
-{
-    int n = 0;
-    hipError_t e = hipGetDeviceCount(&n);
-    if (e != hipSuccess || n == 0)
-        return rt_fail(c, RT_ERR_NODEV, "librt_hip: no HIP device available (this library has no CPU path)");
-    if (device < 0 || device >= n) return rt_fail(c, RT_ERR_NODEV, "librt_hip: device index out of range");
-    HIPCHK(c, hipSetDevice(device));
-    Backend* b = new Backend();
-    *out = b;
-    b->device = device;
-    HIPCHK(c, hipEventCreate(&b->ev0));
-    HIPCHK(c, hipEventCreate(&b->ev1));
-    for (int l = 0; l < RT_MAX_LANES; l++) {
-        HIPCHK(c, hipHostMalloc((void**)&b->h_act[l], RT_QSHARDS * RT_CSTRIDE * 4 + 64, hipHostMallocDefault));
-        HIPCHK(c, hipEventCreateWithFlags(&b->ev_lane[l], hipEventDisableTiming));
-        HIPCHK(c, hipEventCreateWithFlags(&b->ev_join[l], hipEventDisableTiming));
-        if (l > 0) HIPCHK(c, hipStreamCreateWithFlags(&b->ls[l], hipStreamNonBlocking));
-    }
-    HIPCHK(c, hipStreamCreateWithFlags(&b->own, hipStreamNonBlocking));
-    HIPCHK(c, hipEventCreateWithFlags(&b->ev_fork, hipEventDisableTiming));
-    HIPCHK(c, hipEventCreateWithFlags(&b->ev_done, hipEventDisableTiming));
-    return RT_OK;
-}
-
-void destroy_one(Backend* b)
-{
-    (void)hipSetDevice(b->device);
-    (void)hipDeviceSynchronize();
-    DevBuf* all[] = {&b->nodes, &b->tri4, &b->prim2k, &b->mat_idx, &b->mats, &b->emissive, &b->spheres, &b->env,
-                     &b->env_lum, &b->cdf, &b->bvh4, &b->bvh16, &b->bvh4s, &b->bvh16s, &b->bvh_tri4, &b->parent, &b->leaf_of, &b->cdf_row, &b->cdf_coarse,
-                     &b->cdf_fence, &b->matk, &b->stats, &b->xy, &b->fb, &b->iterq, &b->wlog, &b->fviews};
-    for (DevBuf* d : all)
-        if (d->p) (void)hipFree(d->p);
-    for (int l = 0; l < RT_MAX_LANES; l++)
-        for (DevBuf* d : {&b->wave[l], &b->counters[l], &b->fast[l], &b->fcnt[l], &b->fhist[l], &b->fspill[l]})
-            if (d->p) (void)hipFree(d->p);
-    for (int l = 0; l < RT_MAX_LANES; l++) {
-        if (b->h_hist[l]) (void)hipHostFree(b->h_hist[l]);
-        if (b->fev[l]) (void)hipEventDestroy(b->fev[l]);
-        if (b->hev[l]) (void)hipEventDestroy(b->hev[l]);
-    }
-    if (b->post) rt_post_free(b->post);
-    if (b->query) rt_query_free(b->query);
-    if (b->h_fviews) (void)hipHostFree(b->h_fviews);
-    if (b->fev_done) (void)hipEventDestroy(b->fev_done);
-    if (b->fs) (void)hipStreamDestroy(b->fs);
-    for (hipEvent_t e : b->ftev)
-        if (e) (void)hipEventDestroy(e);
-    for (int l = 0; l < RT_MAX_LANES; l++) {
-        if (b->h_act[l]) (void)hipHostFree(b->h_act[l]);
-        if (b->ev_lane[l]) (void)hipEventDestroy(b->ev_lane[l]);
-        if (b->ev_join[l]) (void)hipEventDestroy(b->ev_join[l]);
-        if (b->ls[l]) (void)hipStreamDestroy(b->ls[l]);
-    }
-    if (b->own) (void)hipStreamDestroy(b->own);
-    if (b->ev_fork) (void)hipEventDestroy(b->ev_fork);
-    if (b->ev_done) (void)hipEventDestroy(b->ev_done);
-    for (auto& lane : b->tev)
-        for (auto& row : lane)
-            for (hipEvent_t ev : row)
-                if (ev) (void)hipEventDestroy(ev);
-    if (b->ev0) (void)hipEventDestroy(b->ev0);
-    if (b->ev1) (void)hipEventDestroy(b->ev1);
-    delete b;
-}
-
-// Scene, BVH and env of the context into one device's memory (replicated per device).
-int upload_one(rt_context* c, Backend* b, const std::vector<int32_t>& matk, bool mats_only)
-{
-    HIPCHK(c, hipSetDevice(b->device));
-    // the previous render may still run (rt_render_device returns at once, its kernels on
-    // non-blocking streams that a null-stream copy does not wait for): it reads these tables
-    if (b->done_recorded) HIPCHK(c, hipEventSynchronize(b->ev_done));
-    int r = 0;
-    if (mats_only) {  // rt_set_materials: the material table (and what depends on it) alone
-        if ((r = upload(c, b->mats, c->mats))) return r;
-        b->view.mats = (const RtMat*)b->mats.p;
-        b->view.n_mats = (int)c->mats.size();
-        b->bl_rays = rt_scene_has_emissive_prim(c) ? 1 : 0;
-        return RT_OK;
-    }
-    // device triangle records carry the material index in e1.w (rt_wave.h hit_from)
-    std::vector<float4_> tri4 = c->flat.tri4;
-    for (size_t k = 0; k < matk.size(); k++) std::memcpy(&tri4[3 * k + 1].w, &matk[k], 4);
-    if ((r = upload(c, b->nodes, c->flat.nodes)) || (r = upload(c, b->tri4, tri4)) ||
-        (r = upload(c, b->prim2k, c->flat.prim2k)) || (r = upload(c, b->mat_idx, c->mat_idx)) ||
-        (r = upload(c, b->mats, c->mats)) || (r = upload(c, b->emissive, c->emissive)) ||
-        (r = upload(c, b->spheres, c->spheres)) || (r = upload(c, b->env, c->env)) ||
-        (r = upload(c, b->env_lum, c->env_lum)) || (r = upload(c, b->cdf, c->cdf)) ||
-        (r = upload(c, b->bvh4, c->flat.bvh4)) || (r = upload(c, b->bvh16, c->flat.bvh16)) ||
-        (r = upload(c, b->bvh4s, c->flat.bvh4s)) || (r = upload(c, b->bvh16s, c->flat.bvh16s)) ||
-        (r = upload(c, b->bvh_tri4, c->flat.bvh_tri4)) ||
-        (r = upload(c, b->parent, c->flat.parent)) || (r = upload(c, b->leaf_of, c->flat.leaf_of)) ||
-        (r = upload(c, b->cdf_row, c->cdf_row)) || (r = upload(c, b->cdf_coarse, c->cdf_coarse)) ||
-        (r = upload(c, b->cdf_fence, c->cdf_fence)) || (r = upload(c, b->matk, matk)) ||
-        (r = ensure(c, b->stats, 2 * RT_STAT_COUNT * sizeof(unsigned long long))))
-        return r;
-    for (int l = 0; l < RT_MAX_LANES; l++)
-        if ((r = ensure(c, b->counters[l], C_COUNT * sizeof(int32_t)))) return r;
-    RtSceneView v{};
-    v.nodes = (const RtNode*)b->nodes.p;
-    v.tri4 = (const float4_*)b->tri4.p;
-    v.prim2k = (const int32_t*)b->prim2k.p;
-    v.mat_idx = (const int32_t*)b->mat_idx.p;
-    v.matk = (const int32_t*)b->matk.p;
-    v.mats = (const RtMat*)b->mats.p;
-    v.n_mats = (int)c->mats.size();
-    v.emissive = (const int32_t*)b->emissive.p;
-    v.spheres = (const float4_*)b->spheres.p;
-    v.env = (const float4_*)b->env.p;
-    v.env_lum = (const float*)b->env_lum.p;
-    v.cdf = (const float*)b->cdf.p;
-    v.cdf_row = (const float*)b->cdf_row.p;
-    v.cdf_coarse = (const float*)b->cdf_coarse.p;
-    v.cdf_fence = c->cdf_fence.empty() ? nullptr : (const float*)b->cdf_fence.p;
-    v.cdf_cw = c->cdf_cw;
-    v.cdf_total = c->cdf.empty() ? 0.0f : c->cdf.back();
-    v.n_emissive = (int)c->emissive.size();
-    v.n_spheres = (int)(c->spheres.size() / 2);
-    v.ew = c->ew;
-    v.eh = c->eh;
-    v.n_tris = (int)(c->tris.size() / 9);
-    v.chain_monotone = rt_view_chain_monotone(c);
-    v.brute = c->brute ? 1 : 0;
-    v.bvh4 = (const Bvh4Node*)b->bvh4.p;
-    v.bvh16 = (const Bvh4Child*)b->bvh16.p;
-    v.bvh4s = (const float4_*)b->bvh4s.p;
-    v.bvh16s = (const float4_*)b->bvh16s.p;
-    v.bvh_tri4 = (const float4_*)b->bvh_tri4.p;
-    v.parent = (const int32_t*)b->parent.p;
-    v.leaf_of = (const int32_t*)b->leaf_of.p;
-    v.tri_mat = 1;
-    rt_view_near(c, v);
-    b->view = v;
-    b->bl_rays = rt_scene_has_emissive_prim(c) ? 1 : 0;
-    b->any_rays = v.n_spheres == 0 ? 1 : 0;
-    return RT_OK;
-}
-}  // namespace
-
-int rt_backend_create(rt_context* c)
-{
-    Group* g = new Group();
-    c->backend = g;
-    // (one listed device: a single-device context on it, unless a test asks for the driver
-    // and a one-rank RCCL clique: rt_test_create_multi_rccl)
-    g->multi = c->devices.size() > 1 || (c->force_multi && !c->devices.empty());
-    g->loopback = g->multi && c->loopback;
-    const std::vector<int> ids = g->multi ? c->devices : std::vector<int>{c->device};
-    for (int d : ids) {
-        Backend* b = nullptr;
-        const int r = create_one(c, d, &b);
-        if (b) {
-            b->index = (int)g->dev.size();
-            g->dev.push_back(b);
-        }
-        if (r) return r;
-    }
-    if (g->multi) g->shard.resize(ids.size());
-    if (g->multi && !g->loopback) {
-        std::string err;
-        const Rccl* R = rccl_load(err);
-        if (!R) return rt_fail(c, RT_ERR_NODEV, err);
-        g->comms.resize(ids.size());
-        NCCLCHK(c, R, R->init(g->comms.data(), (int)ids.size(), ids.data()));
-    }
-    return RT_OK;
-}
-
-void rt_backend_destroy(rt_context* c)
-{
-    Group* g = grp(c);
-    if (!g) return;
-    for (Backend* b : g->dev) destroy_one(b);
-    if (!g->comms.empty()) {
-        std::string err;
-        if (const Rccl* R = rccl_load(err))
-            for (ncclComm_t cm : g->comms)
-                if (cm) (void)R->destroy(cm);
-    }
-    for (size_t d = 0; d < g->shard.size(); d++)
-        if (g->shard[d].p) {
-            (void)hipSetDevice(g->multi ? c->devices[d] : c->device);
-            (void)hipFree(g->shard[d].p);
-        }
-    if (g->stage.p) {
-        (void)hipSetDevice(g->multi ? c->devices[0] : c->device);
-        (void)hipFree(g->stage.p);
-    }
-    delete g;
-    c->backend = nullptr;
-}
-
-int rt_backend_upload(rt_context* c)
-{
-    Group* g = grp(c);
-    const bool mats_only = c->mats_dirty_only && !c->dirty;
-    // material index of each leaf-order triangle k: mat_idx[prim(k)] (rt_trace.h load_mat_hit)
-    std::vector<int32_t> matk;
-    if (!mats_only) {
-        matk.resize(c->flat.tri4.size() / 3);
-        for (size_t k = 0; k < matk.size(); k++) {
-            int32_t prim;
-            std::memcpy(&prim, &c->flat.tri4[3 * k].w, 4);
-            matk[k] = c->mat_idx[prim];
-        }
-    }
-    for (Backend* b : g->dev)
-        if (int r = upload_one(c, b, matk, mats_only)) return r;
-    return RT_OK;
-}
+size_t rt_wave_counter_bytes() { return C_COUNT * sizeof(int32_t); }
+size_t rt_wave_readback_bytes() { return RT_QSHARDS * RT_CSTRIDE * 4 + 64; }
 
 namespace {
+const int threads = 256;
+const WaveKnobs knobs{RT_TRACE_OCC, RT_TAIL_OCC, RT_HEAVY_CALLS, RT_TAIL_ROWS, RT_DRAIN_ROWS, RT_TAIL_MAXP, RT_QSHARDS};
+
+// One launch helper per kernel family: (SEQ, S, brute / rows) -> the instantiation.
+// SEQ: counter renders with unpaired occlusion walks; S: counter renders; brute: USE_BVH 0
+// scenes (the walks that keep the triangles' original indices); rows: k_tail walks by rows.
+#define RT_LAUNCH(K) hipLaunchKernelGGL(K, g, dim3(threads), 0, s, W, par, stats)
+void launch_k_trace(bool SEQ, bool S, bool brute, dim3 g, hipStream_t s, const rtk::WaveView& W, int par,
+                    unsigned long long* stats)
+{
+    if (SEQ) RT_LAUNCH((k_trace<true, false>));
+    else if (S) RT_LAUNCH((k_trace<true, true>));
+    else if (brute) RT_LAUNCH((k_trace<false, true, 4, RT_BRUTE_ON>));
+    else RT_LAUNCH((k_trace<false, true, 4, RT_BRUTE_OFF>));
+}
+void launch_k_tail_fast(bool SEQ, bool S, dim3 g, hipStream_t s, const rtk::WaveView* fv, int4 parts,
+                        unsigned long long* stats)
+{
+    if (SEQ) hipLaunchKernelGGL((k_tail_fast<true, false, 4>), g, dim3(threads), 0, s, fv, parts, stats);
+    else if (S) hipLaunchKernelGGL((k_tail_fast<true, true, 16>), g, dim3(threads), 0, s, fv, parts, stats);
+    else hipLaunchKernelGGL((k_tail_fast<false, true, 16>), g, dim3(threads), 0, s, fv, parts, stats);
+}
+void launch_k_step(bool S, dim3 g, hipStream_t s, const rtk::WaveView& W, int par, unsigned long long* stats)
+{
+    if (S) RT_LAUNCH(k_step<true>);
+    else RT_LAUNCH(k_step<false>);
+}
+void launch_k_tail(bool SEQ, bool S, bool rows, dim3 g, hipStream_t s, const rtk::WaveView& W, int par,
+                   unsigned long long* stats)
+{
+    if (SEQ) RT_LAUNCH((k_tail<true, false, 4>));
+    else if (S) RT_LAUNCH((rows ? k_tail<true, true, 16> : k_tail<true, true, 4>));
+    else RT_LAUNCH((rows ? k_tail<false, true, 16> : k_tail<false, true, 4>));
+}
+#undef RT_LAUNCH
+// The readback a lane waits for: none, the live count (read_live), or the fallback counts
+// (the tail entry check of issue).
+enum class Await { None, Live, Fallbacks };
+// A lane's share of the fast lane, in order of life:
+//   Waiting -> HistPending   process: the lane reached fast_iter; k_hist's histogram is on its way back
+//   HistPending -> HandNext  fast_threshold: the histogram has landed, the threshold is known
+//   HandNext -> Handed       launch_step: k_hand ran before this k_step
+//   Waiting / HistPending -> NoShare   process: the lane is done or enters its tail first
+// (NoShare from the start without a fast lane). fast_launch runs once no lane is before Handed.
+enum class Fast { Waiting, HistPending, HandNext, Handed, NoShare };
+
 // One wavefront run over a subset of the launch's pixels (a "lane"): its own
 // path slots, queues, counters and stream. run_wave drives RT_LANES lanes on
 // as many streams (row j of the launch -> lane j % lanes) so that one lane's
@@ -2033,38 +1567,76 @@ struct WaveLane {
     int n = 0, it = 0, tail_iter = -1;
     long live = 0;  // live paths at the last readback (an upper bound: paths only finish)
     bool done = false, tail_next = false;
-    int await = 0;  // 0 none, 1 live count, 2 fallback counts (tail entry check)
-    int fast_state = 0;  // fast lane: 0 waiting, 4 threshold read back (pending), 1 hand-over at the
-                         // next k_step, 2 handed over, 3 none
+    Await await = Await::None;
+    Fast fast = Fast::NoShare;
     int fast_thr = 0, fast_n = 0;  // ... samples-done threshold, paths at most
-    hipEvent_t (*tev)[RT_MAX_TIMED_ITERS] = nullptr;  // [3][RT_MAX_TIMED_ITERS]
+    Event (*tev)[RT_MAX_TIMED_ITERS] = nullptr;  // [3][RT_MAX_TIMED_ITERS]
 };
 
-// Runs the wavefront loop for n slots of `src` into fb (device, n float4).
-int run_wave(rt_context* c, Backend* b, int w, int h, int spp, int bounces, const rtk::PixSrc& src, int n,
-                    float4_* fb, hipStream_t s)
+// One call of run_wave: the plan, the lanes and the launches on their streams.
+struct WaveRun {
+    rt_context* c;
+    Backend* b;
+    int w, h, spp, bounces;
+    const rtk::PixSrc& src;
+    int n;
+    float4_* fb;
+    hipStream_t s;
+    int dev_cus = 256;
+    WavePlan P{};
+    WaveLane L[RT_MAX_LANES];
+    bool S = false, SEQ = false, wlog = false;
+    unsigned long long* stats = nullptr;
+    const char* iter_log = nullptr;  // per-iteration log of lane 0: counts (stats renders) / ms (timed)
+    hipStream_t fstream = nullptr;
+    bool fast_launched = false, fast_ran = false;
+    long max_iters = 0;
+    static constexpr size_t act_bytes = RT_QSHARDS * RT_CSTRIDE * 4;
+
+    int begin();
+    int init_lane(int l);
+    int launch_trace(WaveLane& La);
+    int fast_launch();
+    int fast_threshold(WaveLane& La);
+    int launch_step(WaveLane& La);
+    int launch_tail(WaveLane& La, int par);
+    int read_live(WaveLane& La);
+    int issue(WaveLane& La);
+    int process(WaveLane& La);
+    int start_hist(WaveLane& La);
+    int poll();
+    int finish();
+    int report();
+    int lane_of(const WaveLane& La) const { return (int)(&La - L); }
+    // grids sized by the last known live count: k_step one slot per thread; k_trace up to
+    // five queries per path, a quad each, over two grid-fills, never fewer blocks than the
+    // exact-walk roles can claim (dev_cus * 4) plus room for the fast roles
+    // (k_step: at least 3 blocks, one per exact-walk role and one for the path step, so a
+    // small live count with fallbacks or parked walks pending still steps its paths)
+    int step_blocks_of(const WaveLane& La) const
+    {
+        return (int)std::max(3l, std::min((La.live + threads - 1) / threads, (long)dev_cus * RT_STEP_FILL));
+    }
+    int trace_blocks_of(const WaveLane& La) const
+    {
+        const long want = (20 * La.live + 2 * threads - 1) / (2 * threads);
+        return (int)std::min((long)P.trace_blocks, std::max(want, (long)dev_cus * 4 + 64));
+    }
+};
+
+int WaveRun::begin()
 {
-    if (n <= 0) return RT_OK;
     // every render of a context reuses its lanes' slots and counters: the previous render
     // (whose tail kernel may still run, on another stream) must finish first
     if (b->done_recorded) HIPCHK(c, hipStreamWaitEvent(s, b->ev_done, 0));
-    int dev_cus = 256;
     (void)hipDeviceGetAttribute(&dev_cus, hipDeviceAttributeMultiprocessorCount, b->device);
-    const int threads = 256;
-    // k_trace: wave-strided over 2 grid-fills; RT_TRACE_OCC blocks resident per CU (quad
-    // walks: 6 waves/SIMD measured best, 423 vs 374 Msamples/s at 4 and 350 at 8)
-    // k_trace grid-fills (RT_TRACE_FILLS): with per-wave query streams one fill is best, a wave's
-    // stream is longer and its end (the last long walk) costs less; cfg2: 0.75 / 1 / 1.25 / 1.5 / 2 / 3
-    // -> 739 / 730-740 / 731 / 724 / 708-710 / 692 Msamples/s
-    const int trace_blocks = dev_cus * RT_TRACE_OCC;
-    const RtSchedule& sc = c->sched;
     const RtDiag& dg = c->diag;
-    const bool S = c->stats_enabled;
-    const bool SEQ = S && c->stats_seq;  // (counter renders with unpaired occlusion walks: rt_set_stats(ctx, 2))
-    unsigned long long* stats = (unsigned long long*)b->stats.p;
+    S = c->stats_enabled;
+    SEQ = S && c->stats_seq;  // (counter renders with unpaired occlusion walks: rt_set_stats(ctx, 2))
+    stats = (unsigned long long*)b->stats.p;
     if (S) HIPCHK(c, hipMemsetAsync(b->stats.p, 0, b->stats.bytes, s));
-    const char* iter_log = dg.iter_log.empty() ? nullptr : dg.iter_log.c_str();  // per-iteration log of lane 0: counts (stats renders) / ms (timed)
-    const bool wlog = S && dg.wlog_cap > 0 && b->index == 0;
+    iter_log = dg.iter_log.empty() ? nullptr : dg.iter_log.c_str();
+    wlog = S && dg.wlog_cap > 0 && b->index == 0;
     if (wlog) {
         if (int r = ensure(c, b->wlog, 256 + (size_t)dg.wlog_cap * 48)) return r;
         HIPCHK(c, hipMemsetAsync(b->wlog.p, 0, 256, s));
@@ -2077,393 +1649,333 @@ int run_wave(rt_context* c, Backend* b, int w, int h, int spp, int bounces, cons
         if (int r = ensure(c, b->iterq, RT_MAX_TIMED_ITERS * 24)) return r;
         HIPCHK(c, hipMemsetAsync(b->iterq.p, 0, RT_MAX_TIMED_ITERS * 24, s));
     }
-    // lanes: rows interleave (row j of the launch -> lane j % lanes); pixel lists split in runs
-    const int lanes_set = sc.lanes > 0 ? std::min(RT_MAX_LANES, sc.lanes) : b->lanes;
-    const int fast_k = spp <= RT_FAST_MAX_SPP ? std::max(0, std::min(1 << 16, sc.fast_k >= 0 ? sc.fast_k : RT_FAST_K)) : 0;
-    // (auto: 3 lanes with the fast lane, the fourth hardware queue its stream)
-    int nl = lanes_set > 0 ? lanes_set : n <= RT_LANES4_MAX && fast_k == 0 ? 4 : 3;
     const int rows = src.xy ? 0 : n / src.W;
-    while (nl > 1 && (n < nl * 65536 || (!src.xy && rows < nl))) nl--;
-    WaveLane L[RT_MAX_LANES];
-    const int force_fb = sc.force_fallback;  // (test stressor, rt_test_schedule)
-    const int heavy_calls = sc.heavy_calls >= 0 ? sc.heavy_calls : RT_HEAVY_CALLS;
-    // the next sample's camera ray traced ahead (rt_wave.h next_camera): 1; 0 off; 2 only where
-    // the pixel's previous sample ended (cfg2 -1.5 ms, the cfg4 8-way shard unchanged, r04)
-    const int spec_cam = sc.spec_cam >= 0 ? sc.spec_cam : 1;
-    // The camera ray traced ahead costs a walk whenever the sample goes on. In k_tail a round
-    // waits for its path's slowest query, often that camera walk: there it is off (cfg4 8-way
-    // shard 352.3-354.6 -> 343.5 ms, cfg2 142.5-143.6 -> 141.3-141.6, profiles/r04q_cam.json).
-    const int tail_spec_cam = sc.tail_spec_cam >= 0 ? sc.tail_spec_cam : 0;  // the tail kernel's mode (as spec_cam)
-    // k_tail paths per wave: a round waits for the slowest walk of the wave's ~3 P queries, so
-    // fewer paths per wave move each chain faster. With the entry held at the same live count
-    // (r03, P x RT_TAIL_ENTER = 3.5): P = 5 / 3 / 2 / 1 -> cfg2 886-893 / 892-896 / 897-901 /
-    // 887-890 Msamples/s, cfg4 8-way shard (slowest rank) 401 / - / 390 / 405 ms
-    // row walks (rt_row.h, 16 lanes per query over the 16-wide BVH) where walks are latency-bound:
-    // the tail kernel (tail_rows: its rounds wait for their slowest walk). cfg4 8-way shard, one
-    // MI355X (profiles/r04c_row_probe.json, r04d_tail_probe.json): quads 380-382 ms; tail rows
-    // 367-370; rows for whole k_trace launches below 32 K / 131 K paths 415 / 420-428 ms (removed).
-    // (counter renders with unpaired occlusion walks, SEQ: every walk a quad walk, so that the box
-    // tests counted are the ones a one-node-per-trip walk makes; a row trip tests 16)
-    const int tail_rows = SEQ ? 0 : sc.tail_rows >= 0 ? (sc.tail_rows != 0) : RT_TAIL_ROWS;
-    const int drain_rows = SEQ ? 0 : sc.drain_rows >= 0 ? sc.drain_rows : RT_DRAIN_ROWS;  // k_trace: a drain's walks continue as rows
-    // (rows: one path per wave, its ~4 queries on the wave's 4 rows: shard 367 ms vs 2 / 3 paths
-    // 373-378 / 373-375 at the same entry live count)
-    const int tail_p = sc.tail_paths >= 0 ? std::min(RT_TAIL_MAXP, sc.tail_paths) : tail_rows ? 1 : 2;
-    const int tail_blocks = dev_cus * RT_TAIL_OCC;  // one grid-fill of k_tail
-    // a lane enters the tail kernel at 2x one grid-fill's pool (the waves refill from the live
-    // list): with 2 paths per wave, RT_TAIL_ENTER = 1.4 / 1.75 / 2.2 / 2.8 -> cfg2 888-897 /
-    // 891-898 / 893-897 / 874-879 Msamples/s (5 paths at 0.7: 888-892), cfg4 8-way shard
-    // 393.5 / 389.6 / 393.1 / - ms (profiles/r03_tail_paths_ab.json)
-    // (4 lanes, the auto count of launches of <= 1.5 M slots: 1.4 — cfg4 8-way shard, 4 rounds on
-    // one MI355X: 2.0 / 1.5 / 1.25 / 1.0 -> 384-391 / 380-384 / 379-383 / 382-390 ms,
-    // profiles/r03_tail_enter4.json)
-    const double tail_enter = sc.tail_enter >= 0.0 ? sc.tail_enter : nl == 4 ? 1.4 : 2.0;
-    // Fast lane: from iteration fast_spp x spp on, each lane's share of the fast_k live paths
-    // with the fewest samples done (the pixels with the longest chains, tools/fastlane_model.py)
-    // leaves the wavefront at the lane's next k_step; when every lane has handed its share over,
-    // one tail kernel steps them all on a stream of their own (an idle lane's: 3 lanes + the fast
-    // lane are the 4 hardware queues), at a tail round's pace beside the wavefront. cfg4 8-way
-    // shard (rank 1) / cfg2, one MI355X, 3 rounds (profiles/r05_fast_lane.json): 4 lanes, none
-    // 319.7-323.9 / 134.9-135.4 ms; 3 lanes + fast lane 768 paths at 2.0 / 2.25 x spp
-    // 311.5-316.1 / 134.7-136.4 and 312.2-316.9 / 133.7-134.0; 1024 paths 308.1-317.6; 1536 and
-    // more slower (r04's fast lane beside 4 lanes, a fifth stream: slower, r04x).
-    const long fast_iter = (long)((sc.fast_spp >= 0.0 ? sc.fast_spp : RT_FAST_SPP) * spp);
-    bool fast_launched = false, fast_ran = false;
-    if (fast_k > 0 && nl == RT_MAX_LANES && !b->fs) HIPCHK(c, hipStreamCreateWithFlags(&b->fs, hipStreamNonBlocking));
-    const hipStream_t fstream = fast_k > 0 ? (nl < RT_MAX_LANES ? b->ls[nl] : b->fs) : nullptr;
-    const long tail_max = (long)(tail_enter * tail_blocks * 4 * tail_p / nl);
+    P = wave_plan(c->sched, knobs, WaveSource{src.xy != nullptr, src.W, src.off, src.stride}, n, rows, spp, dev_cus, SEQ,
+                  b->lanes, b->budget);
+    const int nl = P.lanes;
+    if (P.fast_k > 0 && nl == RT_MAX_LANES && !b->fs) HIPCHK(c, hipStreamCreateWithFlags(&b->fs.h, hipStreamNonBlocking));
+    fstream = P.fast_k > 0 ? (hipStream_t)(nl < RT_MAX_LANES ? b->ls[nl] : b->fs) : nullptr;
     if (nl > 1) {
         HIPCHK(c, hipEventRecord(b->ev_fork, s));
         for (int l = 1; l < nl; l++) HIPCHK(c, hipStreamWaitEvent(b->ls[l], b->ev_fork, 0));
     }
-    for (int l = 0; l < nl; l++) {
-        WaveLane& La = L[l];
-        rtk::PixSrc ls = src;
-        float4_* lfb = fb;
-        int fb_rs = 1;
-        if (nl == 1) {
-            La.n = n;
-        } else if (src.xy) {
-            const int b0 = (int)((long)n * l / nl), b1 = (int)((long)n * (l + 1) / nl);
-            La.n = b1 - b0;
-            ls.xy = src.xy + 2 * (size_t)b0;
-            lfb = fb + b0;
-        } else {
-            La.n = ((rows - l + nl - 1) / nl) * src.W;
-            ls.off = src.off + l * src.stride;
-            ls.stride = nl * src.stride;
-            lfb = fb + (size_t)l * src.W;
-            fb_rs = nl;
-        }
-        La.live = La.n;
-        La.s = l == 0 ? s : b->ls[l];
-        La.cnt = (int32_t*)b->counters[l].p;
-        La.h = b->h_act[l];
-        La.ev = b->ev_lane[l];
-        La.tev = b->tev[l];
-        rtk::WaveView& W = La.W;
-        W.park_cap = 1 << 16;
-        W.heavy_calls = heavy_calls;
-        W.spec_cam = spec_cam;
-        W.shards = RT_QSHARDS;
-        W.seg_cap = 64 * (((La.n + 63) / 64 + RT_QSHARDS - 1) / RT_QSHARDS);  // (append_emit: chunks per shard)
-        W.spill_lanes = dev_cus * 4 * threads;  // exact walks: up to dev_cus * 2 blocks per role
-        W.fspill_lanes = 0;
-        const size_t need = rtk::wave_carve(nullptr, (size_t)La.n, W);
-        if (int r = ensure(c, b->wave[l], need)) return r;
-        rtk::wave_carve((char*)b->wave[l].p, (size_t)La.n, W);
-        W.S = b->view;
-        rt_view_near(c, W.S);  // (rt_test_schedule may have changed it since the upload)
-        W.cam = c->cam;
-        W.src = ls;
-        W.W = w;
-        W.H = h;
-        W.spp = spp;
-        W.bounces = bounces;
-        rtk::set_view_consts(W);
-        W.n_slots = La.n;
-        W.bl_rays = b->bl_rays;
-        W.any_rays = b->any_rays;
-        W.fb = lfb;
-        W.fb_rs = fb_rs;
-        W.budget = sc.step_budget > 0 ? sc.step_budget : b->budget;
-        W.counters = La.cnt;
-        W.tail_paths = tail_p;
-        W.drain_rows = drain_rows;
-        W.force_fb = force_fb;
-        W.fast_cap = 0;
-        La.fast_state = fast_k > 0 ? 0 : 3;
-        La.fast_n = (int)((long)fast_k * (l + 1) / nl - (long)fast_k * l / nl);
-        if (fast_k > 0) {  // the fast lane's buffers and events (first use)
-            if (int r = ensure(c, b->fast[l], (size_t)(La.fast_n + 1) * 4)) return r;
-            if (int r = ensure(c, b->fcnt[l], C_COUNT * sizeof(int32_t))) return r;
-            if (int r = ensure(c, b->fhist[l], (RT_FAST_MAX_SPP + 1) * 4)) return r;
-            if (int r = ensure(c, b->fspill[l], (size_t)((La.fast_n + 3) / 4) * threads * RT_STACK_CAP * 8)) return r;
-            if (!b->h_hist[l]) HIPCHK(c, hipHostMalloc((void**)&b->h_hist[l], (RT_FAST_MAX_SPP + 1) * 4, hipHostMallocDefault));
-            if (!b->fev[l]) HIPCHK(c, hipEventCreateWithFlags(&b->fev[l], hipEventDisableTiming));
-            if (!b->hev[l]) HIPCHK(c, hipEventCreateWithFlags(&b->hev[l], hipEventDisableTiming));
-            HIPCHK(c, hipMemsetAsync(b->fcnt[l].p, 0, C_COUNT * sizeof(int32_t), La.s));
-        }
-        W.iterq = (S && iter_log && l == 0) ? (int32_t*)b->iterq.p : nullptr;
-        W.handovers = (unsigned long long*)b->handovers.p;
-        if (wlog) {
-            W.wlog_n = (int32_t*)b->wlog.p;
-            W.wlog = (float4_*)((char*)b->wlog.p + 256);
-            W.wlog_min = dg.wlog_min;
-            W.wlog_cap = dg.wlog_cap;
-            W.wlog_every = dg.wlog_every;
-        }
-        La.lists[0] = (int32_t*)W.act_in;
-        La.lists[1] = W.act_out;
-        HIPCHK(c, hipMemsetAsync(La.cnt, 0, C_COUNT * sizeof(int32_t), La.s));
-        HIPCHK(c, hipMemsetAsync(W.r_park, 0, (size_t)La.n * 4, La.s));
-        W.act_in = La.lists[1];
-        W.act_out = La.lists[0];
-        hipLaunchKernelGGL(k_init, dim3((La.n + threads - 1) / threads), dim3(threads), 0, La.s, W);
-        HIPCHK(c, hipGetLastError());
-    }
+    for (int l = 0; l < nl; l++)
+        if (int r = init_lane(l)) return r;
     if (dg.verbose)
-        fprintf(stderr, "[rt] run_wave n=%d lanes=%d cus=%d trace_blocks=%d budget=%d\n", n, nl, dev_cus, trace_blocks,
+        fprintf(stderr, "[rt] run_wave n=%d lanes=%d cus=%d trace_blocks=%d budget=%d\n", n, nl, dev_cus, P.trace_blocks,
                 L[0].W.budget);
-
     // A sample takes at most bounces + 1 iterations without fallbacks; an
     // exact walk delays its path by at least one iteration. The bound only
     // guards against a runaway loop.
-    const long max_iters = 64l * spp * ((long)bounces + 1) + 4096;
-    const size_t act_bytes = RT_QSHARDS * RT_CSTRIDE * 4;
-    // grids sized by the last known live count: k_step one slot per thread; k_trace up to
-    // five queries per path, a quad each, over two grid-fills, never fewer blocks than the
-    // exact-walk roles can claim (dev_cus * 4) plus room for the fast roles
-    // (k_step: at least 3 blocks, one per exact-walk role and one for the path step, so a
-    // small live count with fallbacks or parked walks pending still steps its paths)
-    auto step_blocks_of = [&](const WaveLane& La) {
-        return (int)std::max(3l, std::min((La.live + threads - 1) / threads, (long)dev_cus * RT_STEP_FILL));
-    };
-    auto trace_blocks_of = [&](const WaveLane& La) {
-        const long want = (20 * La.live + 2 * threads - 1) / (2 * threads);
-        return (int)std::min((long)trace_blocks, std::max(want, (long)dev_cus * 4 + 64));
-    };
-    auto launch_trace = [&](WaveLane& La) -> int {
-        rtk::WaveView& W = La.W;
-        const int par = La.it & 1;
-        W.iter = La.it;
-        W.act_in = La.lists[par];
-        W.act_out = La.lists[par ^ 1];
-        const bool T = b->timing && La.it < RT_MAX_TIMED_ITERS;
-        if (T)
-            for (int k = 0; k < 3; k++)
-                if (!La.tev[k][La.it]) HIPCHK(c, hipEventCreate(&La.tev[k][La.it]));
-        if (T) HIPCHK(c, hipEventRecord(La.tev[0][La.it], La.s));
-        const dim3 g(trace_blocks_of(La));
-        if (SEQ)
-            hipLaunchKernelGGL((k_trace<true, false>), g, dim3(threads), 0, La.s, W, par, stats);
-        else if (S)
-            hipLaunchKernelGGL((k_trace<true, true>), g, dim3(threads), 0, La.s, W, par, stats);
-        else if (W.S.brute)  // (USE_BVH 0 scenes: the walks that keep the triangles' original indices)
-            hipLaunchKernelGGL((k_trace<false, true, 4, RT_BRUTE_ON>), g, dim3(threads), 0, La.s, W, par, stats);
-        else
-            hipLaunchKernelGGL((k_trace<false, true, 4, RT_BRUTE_OFF>), g, dim3(threads), 0, La.s, W, par, stats);
-        if (T) HIPCHK(c, hipEventRecord(La.tev[1][La.it], La.s));
-        HIPCHK(c, hipGetLastError());
-        return RT_OK;
-    };
-    // the fast lane's tail kernel, once every lane has handed its share over (or has none)
-    auto fast_launch = [&]() -> int {
-        if (fast_k == 0 || fast_launched) return RT_OK;
-        bool any = false;
-        for (int l = 0; l < nl; l++) {
-            if (L[l].fast_state < 2 || L[l].fast_state == 4) return RT_OK;  // (a lane still to hand over)
-            any = any || L[l].fast_state == 2;
-        }
-        fast_launched = true;
-        if (!any) return RT_OK;
-        if (!b->h_fviews)
-            HIPCHK(c, hipHostMalloc((void**)&b->h_fviews, sizeof(rtk::WaveView) * RT_MAX_LANES, hipHostMallocDefault));
-        if (!b->fev_done) HIPCHK(c, hipEventCreateWithFlags(&b->fev_done, hipEventDisableTiming));
-        if (b->fev_done_recorded) HIPCHK(c, hipEventSynchronize(b->fev_done));  // (the last render's copy of the views)
-        if (int r = ensure(c, b->fviews, sizeof(rtk::WaveView) * RT_MAX_LANES)) return r;
-        int start[RT_MAX_LANES + 1] = {}, tot = 0;
-        for (int l = 0; l < RT_MAX_LANES; l++) {
-            start[l] = tot;
-            if (l >= nl || L[l].fast_state != 2) continue;
-            rtk::WaveView FW = L[l].W;
-            FW.act_in = (int32_t*)b->fast[l].p;
-            FW.counters = (int32_t*)b->fcnt[l].p;
-            FW.fast_cap = L[l].fast_n;
-            FW.tail_paths = 1;  // (one path per wave, its queries on the wave's rows)
-            const int blocks = (L[l].fast_n + 3) / 4;
-            FW.spill_r = (uint32_t*)b->fspill[l].p;
-            FW.spill_k = (float*)((uint32_t*)b->fspill[l].p + (size_t)blocks * threads * RT_STACK_CAP);
-            FW.iterq = nullptr;
-            FW.spec_cam = spec_cam ? tail_spec_cam : 0;
-            b->h_fviews[l] = FW;
-            tot += blocks;
-            HIPCHK(c, hipStreamWaitEvent(fstream, b->fev[l], 0));
-        }
-        HIPCHK(c, hipMemcpyAsync(b->fviews.p, b->h_fviews, sizeof(rtk::WaveView) * RT_MAX_LANES, hipMemcpyHostToDevice,
-                                 fstream));
-        const rtk::WaveView* fv = (const rtk::WaveView*)b->fviews.p;
-        if (b->timing) {
-            for (hipEvent_t& e : b->ftev)
-                if (!e) HIPCHK(c, hipEventCreate(&e));
-            HIPCHK(c, hipEventRecord(b->ftev[0], fstream));
-        }
-        const int4 parts = make_int4(start[0], start[1], start[2], start[3]);
-        if (SEQ)
-            hipLaunchKernelGGL((k_tail_fast<true, false, 4>), dim3(tot), dim3(threads), 0, fstream, fv, parts, stats);
-        else if (S)
-            hipLaunchKernelGGL((k_tail_fast<true, true, 16>), dim3(tot), dim3(threads), 0, fstream, fv, parts, stats);
-        else
-            hipLaunchKernelGGL((k_tail_fast<false, true, 16>), dim3(tot), dim3(threads), 0, fstream, fv, parts, stats);
-        HIPCHK(c, hipGetLastError());
-        if (b->timing) HIPCHK(c, hipEventRecord(b->ftev[1], fstream));
-        HIPCHK(c, hipEventRecord(b->fev_done, fstream));
-        b->fev_done_recorded = fast_ran = true;
-        return RT_OK;
-    };
-    // the fast lane's threshold: the samples-done count of the lane's fast_n-th slowest live
-    // path, from the histogram k_hist read back (polled: the host thread serving every lane
-    // never blocks on it; the hand-over happens at the first k_step after it has landed)
-    auto fast_threshold = [&](WaveLane& La) -> int {
-        const int l = (int)(&La - L);
-        const hipError_t q = hipEventQuery(b->hev[l]);
-        if (q == hipErrorNotReady) return RT_OK;
-        HIPCHK(c, q);
-        long acc = 0;
-        int thr = spp;
-        for (int k = 0; k <= spp; k++)
-            if ((acc += b->h_hist[l][k]) >= La.fast_n) {
-                thr = k;
-                break;
-            }
-        La.fast_thr = thr;
-        La.fast_state = 1;
-        return RT_OK;
-    };
-    auto launch_step = [&](WaveLane& La) -> int {
-        const int par = La.it & 1;
-        const int l = (int)(&La - L);
-        if (La.fast_state == 4)
-            if (int r = fast_threshold(La)) return r;
-        const bool hand = La.fast_state == 1;
-        int32_t* fl = (int32_t*)b->fast[l].p;
-        if (hand) {  // this step hands the lane's slowest paths to the fast lane
-            HIPCHK(c, hipMemsetAsync(fl + La.fast_n, 0, 4, La.s));
-            rtk::WaveView HW = La.W;
-            HW.fast_list = fl;
-            HW.fast_ticket = fl + La.fast_n;
-            HW.fast_cap = La.fast_n;
-            HW.fast_thr = La.fast_thr;
-            hipLaunchKernelGGL(k_hand, dim3((unsigned)std::min(1024l, (La.live + threads - 1) / threads)), dim3(threads), 0,
-                               La.s, HW, par);
-            HIPCHK(c, hipGetLastError());
-        }
-        if (S)
-            hipLaunchKernelGGL(k_step<true>, dim3(step_blocks_of(La)), dim3(threads), 0, La.s, La.W, par, stats);
-        else
-            hipLaunchKernelGGL(k_step<false>, dim3(step_blocks_of(La)), dim3(threads), 0, La.s, La.W, par, stats);
-        if (hand) {  // (its list's length as shard 0 of the fast lane's counters)
-            La.fast_state = 2;
-            HIPCHK(c, hipMemcpyAsync((int32_t*)b->fcnt[l].p + ac_at(0, 0), fl + La.fast_n, 4, hipMemcpyDeviceToDevice, La.s));
-            HIPCHK(c, hipEventRecord(b->fev[l], La.s));
-            if (int r = fast_launch()) return r;
-        }
-        if (b->timing && La.it < RT_MAX_TIMED_ITERS) HIPCHK(c, hipEventRecord(La.tev[2][La.it], La.s));
-        HIPCHK(c, hipGetLastError());
-        La.it++;
-        return RT_OK;
-    };
-    auto read_live = [&](WaveLane& La) -> int {  // ACT counts of the next iteration
-        HIPCHK(c, hipMemcpyAsync(La.h, La.cnt + ac_at(La.it & 1, 0), act_bytes, hipMemcpyDeviceToHost, La.s));
-        HIPCHK(c, hipEventRecord(La.ev, La.s));
-        La.await = 1;
-        return RT_OK;
-    };
-    // enqueue up to 8 iterations, then a readback
-    auto issue = [&](WaveLane& La) -> int {
-        for (int k = 0; k < 8 && La.it < max_iters; k++) {
-            if (int r = launch_trace(La)) return r;
-            if (La.tail_next) {  // does any query wait for the exact walk?
-                HIPCHK(c, hipMemcpyAsync(La.h + act_bytes / 4, La.cnt, 8 * 4, hipMemcpyDeviceToHost, La.s));
-                HIPCHK(c, hipEventRecord(La.ev, La.s));
-                La.await = 2;
-                return RT_OK;
-            }
-            if (int r = launch_step(La)) return r;
-            if ((La.it & 7) == 0) break;
-        }
-        return read_live(La);
-    };
-    auto process = [&](WaveLane& La) -> int {
-        HIPCHK(c, hipEventSynchronize(La.ev));
-        const int kind = La.await;
-        La.await = 0;
-        if (kind == 2) {  // (a fallback pending: step, then the live count, checked again next iteration)
-            const int par = La.it & 1;
-            const int32_t* f = La.h + act_bytes / 4;
-            if (f[C_FBC0 + par] == 0 && f[C_FBA0 + par] == 0 && f[C_PARKC0 + (par ^ 1)] == 0 &&
-                f[C_PARKA0 + (par ^ 1)] == 0) {  // (k_trace(i) released DONE[par ^ 1])
-                // few paths left and none waits: the tail kernel finishes them all
-                HIPCHK(c, hipMemsetAsync(La.cnt + C_TK_TAIL, 0, 4, La.s));
-                const dim3 g(tail_blocks);
-                La.W.spec_cam = spec_cam ? tail_spec_cam : 0;  // (the lane's last launch)
-                if (SEQ)
-                    hipLaunchKernelGGL((k_tail<true, false, 4>), g, dim3(threads), 0, La.s, La.W, par, stats);
-                else if (S)
-                    hipLaunchKernelGGL((tail_rows ? k_tail<true, true, 16> : k_tail<true, true, 4>), g, dim3(threads), 0, La.s, La.W, par, stats);
-                else
-                    hipLaunchKernelGGL((tail_rows ? k_tail<false, true, 16> : k_tail<false, true, 4>), g, dim3(threads), 0, La.s, La.W, par, stats);
-                if (b->timing && La.it < RT_MAX_TIMED_ITERS) HIPCHK(c, hipEventRecord(La.tev[2][La.it], La.s));
-                HIPCHK(c, hipGetLastError());
-                La.tail_iter = La.it;
-                La.it++;
-                La.done = true;
-                return RT_OK;
-            }
-            if (int r = launch_step(La)) return r;
-            return read_live(La);
-        }
-        long live = 0;
-        for (int j = 0; j < RT_QSHARDS; j++) live += La.h[j * RT_CSTRIDE];
-        La.live = live;
-        La.done = live == 0;
-        La.tail_next = !La.done && live <= tail_max;
-        if ((La.fast_state == 0 || La.fast_state == 4) && (La.done || La.tail_next)) {  // (no hand-over from this lane)
-            if (La.fast_state == 4) HIPCHK(c, hipEventSynchronize(b->hev[(int)(&La - L)]));  // (its readback is done with h_hist)
-            La.fast_state = 3;
-            if (int r = fast_launch()) return r;
-        } else if (La.fast_state == 0 && La.it >= fast_iter) {
-            // the samples-done histogram of the lane's live paths, read back asynchronously
-            // (fast_threshold picks it up from a later k_step launch)
-            const int l = (int)(&La - L);
-            int32_t* hh = (int32_t*)b->fhist[l].p;
-            HIPCHK(c, hipMemsetAsync(hh, 0, (size_t)(spp + 1) * 4, La.s));
-            rtk::WaveView HW = La.W;
-            HW.act_in = La.lists[La.it & 1];
-            hipLaunchKernelGGL(k_hist, dim3((unsigned)std::min(1024l, (live + threads - 1) / threads)), dim3(threads), 0,
-                               La.s, HW, La.it & 1, hh);
-            HIPCHK(c, hipGetLastError());
-            HIPCHK(c, hipMemcpyAsync(b->h_hist[l], hh, (size_t)(spp + 1) * 4, hipMemcpyDeviceToHost, La.s));
-            HIPCHK(c, hipEventRecord(b->hev[l], La.s));
-            La.fast_state = 4;
-        }
-        return RT_OK;
-    };
+    max_iters = 64l * spp * ((long)bounces + 1) + 4096;
     for (int l = 0; l < nl; l++)
         if (int r = issue(L[l])) return r;
-    // The host serves whichever lane's readback has completed (hipEventQuery), so a lane whose
-    // batch is done is refilled at once instead of idling while the host blocks on another
-    // lane's event (blocking in lane order left lanes idle 17-34 ms of a 367-ms cfg4 8-way
-    // shard: profiles/r04e_tl.json; 379.5-380.2 -> 370.5-373.2 ms, cfg2 148.5-149.7 -> 148.0,
-    // profiles/r04i_drain_probe.json).
-    // (a thread that finds no lane done for a while sleeps between polls: in a multi-device
-    // render every device thread polls like this, and the caller's host work shares the cores)
+    return RT_OK;
+}
+
+// The lane's buffers carved, its view filled, its counters zeroed and k_init on its stream.
+int WaveRun::init_lane(int l)
+{
+    WaveLane& La = L[l];
+    const LanePlan& lp = P.lane[l];
+    const RtDiag& dg = c->diag;
+    rtk::PixSrc ls = src;
+    if (src.xy) ls.xy = src.xy + 2 * (size_t)lp.first;
+    ls.off = lp.off;
+    ls.stride = lp.stride;
+    La.n = lp.n;
+    La.live = La.n;
+    La.s = l == 0 ? s : (hipStream_t)b->ls[l];
+    La.cnt = (int32_t*)b->counters[l].p;
+    La.h = b->h_act[l];
+    La.ev = b->ev_lane[l];
+    La.tev = b->tev[l];
+    rtk::WaveView& W = La.W;
+    W.park_cap = 1 << 16;
+    W.heavy_calls = P.heavy_calls;
+    W.spec_cam = P.spec_cam;
+    W.shards = RT_QSHARDS;
+    W.seg_cap = lp.seg_cap;
+    W.spill_lanes = dev_cus * 4 * threads;  // exact walks: up to dev_cus * 2 blocks per role
+    W.fspill_lanes = 0;
+    const size_t need = rtk::wave_carve(nullptr, (size_t)La.n, W);
+    if (int r = ensure(c, b->wave[l], need)) return r;
+    rtk::wave_carve((char*)b->wave[l].p, (size_t)La.n, W);
+    W.S = b->view;
+    rt_view_near(c, W.S);  // (rt_test_schedule may have changed it since the upload)
+    W.cam = c->cam;
+    W.src = ls;
+    W.W = w;
+    W.H = h;
+    W.spp = spp;
+    W.bounces = bounces;
+    rtk::set_view_consts(W);
+    W.n_slots = La.n;
+    W.bl_rays = b->bl_rays;
+    W.any_rays = b->any_rays;
+    W.fb = fb + lp.first;
+    W.fb_rs = lp.fb_rs;
+    W.budget = P.budget;
+    W.counters = La.cnt;
+    W.tail_paths = P.tail_p;
+    W.drain_rows = P.drain_rows;
+    W.force_fb = c->sched.force_fallback;  // (test stressor, rt_test_schedule)
+    W.fast_cap = 0;
+    La.fast = P.fast_k > 0 ? Fast::Waiting : Fast::NoShare;
+    La.fast_n = lp.fast_n;
+    if (P.fast_k > 0) {  // the fast lane's buffers and events (first use)
+        if (int r = ensure(c, b->fast[l], (size_t)(La.fast_n + 1) * 4)) return r;
+        if (int r = ensure(c, b->fcnt[l], C_COUNT * sizeof(int32_t))) return r;
+        if (int r = ensure(c, b->fhist[l], (RT_FAST_MAX_SPP + 1) * 4)) return r;
+        if (int r = ensure(c, b->fspill[l], (size_t)((La.fast_n + 3) / 4) * threads * RT_STACK_CAP * 8)) return r;
+        if (!b->h_hist[l]) HIPCHK(c, hipHostMalloc((void**)&b->h_hist[l].h, (RT_FAST_MAX_SPP + 1) * 4, hipHostMallocDefault));
+        if (!b->fev[l]) HIPCHK(c, hipEventCreateWithFlags(&b->fev[l].h, hipEventDisableTiming));
+        if (!b->hev[l]) HIPCHK(c, hipEventCreateWithFlags(&b->hev[l].h, hipEventDisableTiming));
+        HIPCHK(c, hipMemsetAsync(b->fcnt[l].p, 0, C_COUNT * sizeof(int32_t), La.s));
+    }
+    W.iterq = (S && iter_log && l == 0) ? (int32_t*)b->iterq.p : nullptr;
+    W.handovers = (unsigned long long*)b->handovers.p;
+    if (wlog) {
+        W.wlog_n = (int32_t*)b->wlog.p;
+        W.wlog = (float4_*)((char*)b->wlog.p + 256);
+        W.wlog_min = dg.wlog_min;
+        W.wlog_cap = dg.wlog_cap;
+        W.wlog_every = dg.wlog_every;
+    }
+    La.lists[0] = (int32_t*)W.act_in;
+    La.lists[1] = W.act_out;
+    HIPCHK(c, hipMemsetAsync(La.cnt, 0, C_COUNT * sizeof(int32_t), La.s));
+    HIPCHK(c, hipMemsetAsync(W.r_park, 0, (size_t)La.n * 4, La.s));
+    W.act_in = La.lists[1];
+    W.act_out = La.lists[0];
+    hipLaunchKernelGGL(k_init, dim3((La.n + threads - 1) / threads), dim3(threads), 0, La.s, W);
+    HIPCHK(c, hipGetLastError());
+    return RT_OK;
+}
+
+int WaveRun::launch_trace(WaveLane& La)
+{
+    rtk::WaveView& W = La.W;
+    const int par = La.it & 1;
+    W.iter = La.it;
+    W.act_in = La.lists[par];
+    W.act_out = La.lists[par ^ 1];
+    const bool T = b->timing && La.it < RT_MAX_TIMED_ITERS;
+    if (T)
+        for (int k = 0; k < 3; k++)
+            if (!La.tev[k][La.it]) HIPCHK(c, hipEventCreate(&La.tev[k][La.it].h));
+    if (T) HIPCHK(c, hipEventRecord(La.tev[0][La.it], La.s));
+    launch_k_trace(SEQ, S, W.S.brute, dim3(trace_blocks_of(La)), La.s, W, par, stats);
+    if (T) HIPCHK(c, hipEventRecord(La.tev[1][La.it], La.s));
+    HIPCHK(c, hipGetLastError());
+    return RT_OK;
+}
+
+// the fast lane's tail kernel, once every lane has handed its share over (or has none)
+int WaveRun::fast_launch()
+{
+    const int nl = P.lanes;
+    if (P.fast_k == 0 || fast_launched) return RT_OK;
+    bool any = false;
+    for (int l = 0; l < nl; l++) {
+        if (L[l].fast != Fast::Handed && L[l].fast != Fast::NoShare) return RT_OK;  // (a lane still to hand over)
+        any = any || L[l].fast == Fast::Handed;
+    }
+    fast_launched = true;
+    if (!any) return RT_OK;
+    if (!b->h_fviews)
+        HIPCHK(c, hipHostMalloc((void**)&b->h_fviews.h, sizeof(rtk::WaveView) * RT_MAX_LANES, hipHostMallocDefault));
+    if (!b->fev_done) HIPCHK(c, hipEventCreateWithFlags(&b->fev_done.h, hipEventDisableTiming));
+    if (b->fev_done_recorded) HIPCHK(c, hipEventSynchronize(b->fev_done));  // (the last render's copy of the views)
+    if (int r = ensure(c, b->fviews, sizeof(rtk::WaveView) * RT_MAX_LANES)) return r;
+    int start[RT_MAX_LANES + 1] = {}, tot = 0;
+    for (int l = 0; l < RT_MAX_LANES; l++) {
+        start[l] = tot;
+        if (l >= nl || L[l].fast != Fast::Handed) continue;
+        rtk::WaveView FW = L[l].W;
+        FW.act_in = (int32_t*)b->fast[l].p;
+        FW.counters = (int32_t*)b->fcnt[l].p;
+        FW.fast_cap = L[l].fast_n;
+        FW.tail_paths = 1;  // (one path per wave, its queries on the wave's rows)
+        const int blocks = (L[l].fast_n + 3) / 4;
+        FW.spill_r = (uint32_t*)b->fspill[l].p;
+        FW.spill_k = (float*)((uint32_t*)b->fspill[l].p + (size_t)blocks * threads * RT_STACK_CAP);
+        FW.iterq = nullptr;
+        FW.spec_cam = P.spec_cam ? P.tail_spec_cam : 0;
+        b->h_fviews.h[l] = FW;
+        tot += blocks;
+        HIPCHK(c, hipStreamWaitEvent(fstream, b->fev[l], 0));
+    }
+    HIPCHK(c, hipMemcpyAsync(b->fviews.p, b->h_fviews, sizeof(rtk::WaveView) * RT_MAX_LANES, hipMemcpyHostToDevice,
+                             fstream));
+    if (b->timing) {
+        for (Event& e : b->ftev)
+            if (!e) HIPCHK(c, hipEventCreate(&e.h));
+        HIPCHK(c, hipEventRecord(b->ftev[0], fstream));
+    }
+    launch_k_tail_fast(SEQ, S, dim3(tot), fstream, (const rtk::WaveView*)b->fviews.p,
+                       make_int4(start[0], start[1], start[2], start[3]), stats);
+    HIPCHK(c, hipGetLastError());
+    if (b->timing) HIPCHK(c, hipEventRecord(b->ftev[1], fstream));
+    HIPCHK(c, hipEventRecord(b->fev_done, fstream));
+    b->fev_done_recorded = fast_ran = true;
+    return RT_OK;
+}
+
+// the fast lane's threshold: the samples-done count of the lane's fast_n-th slowest live
+// path, from the histogram k_hist read back (polled: the host thread serving every lane
+// never blocks on it; the hand-over happens at the first k_step after it has landed)
+int WaveRun::fast_threshold(WaveLane& La)
+{
+    const int l = lane_of(La);
+    const hipError_t q = hipEventQuery(b->hev[l]);
+    if (q == hipErrorNotReady) return RT_OK;
+    HIPCHK(c, q);
+    long acc = 0;
+    int thr = spp;
+    for (int k = 0; k <= spp; k++)
+        if ((acc += b->h_hist[l].h[k]) >= La.fast_n) {
+            thr = k;
+            break;
+        }
+    La.fast_thr = thr;
+    La.fast = Fast::HandNext;
+    return RT_OK;
+}
+
+int WaveRun::launch_step(WaveLane& La)
+{
+    const int par = La.it & 1;
+    const int l = lane_of(La);
+    if (La.fast == Fast::HistPending)
+        if (int r = fast_threshold(La)) return r;
+    const bool hand = La.fast == Fast::HandNext;
+    int32_t* fl = (int32_t*)b->fast[l].p;
+    if (hand) {  // this step hands the lane's slowest paths to the fast lane
+        HIPCHK(c, hipMemsetAsync(fl + La.fast_n, 0, 4, La.s));
+        rtk::WaveView HW = La.W;
+        HW.fast_list = fl;
+        HW.fast_ticket = fl + La.fast_n;
+        HW.fast_cap = La.fast_n;
+        HW.fast_thr = La.fast_thr;
+        hipLaunchKernelGGL(k_hand, dim3((unsigned)std::min(1024l, (La.live + threads - 1) / threads)), dim3(threads), 0,
+                           La.s, HW, par);
+        HIPCHK(c, hipGetLastError());
+    }
+    launch_k_step(S, dim3(step_blocks_of(La)), La.s, La.W, par, stats);
+    if (hand) {  // (its list's length as shard 0 of the fast lane's counters)
+        La.fast = Fast::Handed;
+        HIPCHK(c, hipMemcpyAsync((int32_t*)b->fcnt[l].p + ac_at(0, 0), fl + La.fast_n, 4, hipMemcpyDeviceToDevice, La.s));
+        HIPCHK(c, hipEventRecord(b->fev[l], La.s));
+        if (int r = fast_launch()) return r;
+    }
+    if (b->timing && La.it < RT_MAX_TIMED_ITERS) HIPCHK(c, hipEventRecord(La.tev[2][La.it], La.s));
+    HIPCHK(c, hipGetLastError());
+    La.it++;
+    return RT_OK;
+}
+
+// few paths left and none waits: the tail kernel finishes them all
+int WaveRun::launch_tail(WaveLane& La, int par)
+{
+    HIPCHK(c, hipMemsetAsync(La.cnt + C_TK_TAIL, 0, 4, La.s));
+    La.W.spec_cam = P.spec_cam ? P.tail_spec_cam : 0;  // (the lane's last launch)
+    launch_k_tail(SEQ, S, P.tail_rows, dim3(P.tail_blocks), La.s, La.W, par, stats);
+    if (b->timing && La.it < RT_MAX_TIMED_ITERS) HIPCHK(c, hipEventRecord(La.tev[2][La.it], La.s));
+    HIPCHK(c, hipGetLastError());
+    La.tail_iter = La.it;
+    La.it++;
+    La.done = true;
+    return RT_OK;
+}
+
+int WaveRun::read_live(WaveLane& La)  // ACT counts of the next iteration
+{
+    HIPCHK(c, hipMemcpyAsync(La.h, La.cnt + ac_at(La.it & 1, 0), act_bytes, hipMemcpyDeviceToHost, La.s));
+    HIPCHK(c, hipEventRecord(La.ev, La.s));
+    La.await = Await::Live;
+    return RT_OK;
+}
+
+// enqueue up to 8 iterations, then a readback
+int WaveRun::issue(WaveLane& La)
+{
+    for (int k = 0; k < 8 && La.it < max_iters; k++) {
+        if (int r = launch_trace(La)) return r;
+        if (La.tail_next) {  // does any query wait for the exact walk?
+            HIPCHK(c, hipMemcpyAsync(La.h + act_bytes / 4, La.cnt, 8 * 4, hipMemcpyDeviceToHost, La.s));
+            HIPCHK(c, hipEventRecord(La.ev, La.s));
+            La.await = Await::Fallbacks;
+            return RT_OK;
+        }
+        if (int r = launch_step(La)) return r;
+        if ((La.it & 7) == 0) break;
+    }
+    return read_live(La);
+}
+
+int WaveRun::process(WaveLane& La)
+{
+    HIPCHK(c, hipEventSynchronize(La.ev));
+    const Await kind = La.await;
+    La.await = Await::None;
+    if (kind == Await::Fallbacks) {  // (a fallback pending: step, then the live count, checked again next iteration)
+        const int par = La.it & 1;
+        const int32_t* f = La.h + act_bytes / 4;
+        if (f[C_FBC0 + par] == 0 && f[C_FBA0 + par] == 0 && f[C_PARKC0 + (par ^ 1)] == 0 &&
+            f[C_PARKA0 + (par ^ 1)] == 0)  // (k_trace(i) released DONE[par ^ 1])
+            return launch_tail(La, par);
+        if (int r = launch_step(La)) return r;
+        return read_live(La);
+    }
+    long live = 0;
+    for (int j = 0; j < RT_QSHARDS; j++) live += La.h[j * RT_CSTRIDE];
+    La.live = live;
+    La.done = live == 0;
+    La.tail_next = !La.done && live <= P.tail_max;
+    const bool before_hand = La.fast == Fast::Waiting || La.fast == Fast::HistPending;
+    if (before_hand && (La.done || La.tail_next)) {  // (no hand-over from this lane)
+        if (La.fast == Fast::HistPending) HIPCHK(c, hipEventSynchronize(b->hev[lane_of(La)]));  // (its readback is done with h_hist)
+        La.fast = Fast::NoShare;
+        return fast_launch();
+    }
+    if (La.fast == Fast::Waiting && La.it >= P.fast_iter) return start_hist(La);
+    return RT_OK;
+}
+
+// the samples-done histogram of the lane's live paths, read back asynchronously
+// (fast_threshold picks it up from a later k_step launch)
+int WaveRun::start_hist(WaveLane& La)
+{
+    const int l = lane_of(La);
+    int32_t* hh = (int32_t*)b->fhist[l].p;
+    HIPCHK(c, hipMemsetAsync(hh, 0, (size_t)(spp + 1) * 4, La.s));
+    rtk::WaveView HW = La.W;
+    HW.act_in = La.lists[La.it & 1];
+    hipLaunchKernelGGL(k_hist, dim3((unsigned)std::min(1024l, (La.live + threads - 1) / threads)), dim3(threads), 0, La.s,
+                       HW, La.it & 1, hh);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(b->h_hist[l], hh, (size_t)(spp + 1) * 4, hipMemcpyDeviceToHost, La.s));
+    HIPCHK(c, hipEventRecord(b->hev[l], La.s));
+    La.fast = Fast::HistPending;
+    return RT_OK;
+}
+
+// The host serves whichever lane's readback has completed (hipEventQuery), so a lane whose
+// batch is done is refilled at once instead of idling while the host blocks on another
+// lane's event (blocking in lane order left lanes idle 17-34 ms of a 367-ms cfg4 8-way
+// shard: profiles/r04e_tl.json; 379.5-380.2 -> 370.5-373.2 ms, cfg2 148.5-149.7 -> 148.0,
+// profiles/r04i_drain_probe.json).
+// (a thread that finds no lane done for a while sleeps between polls: in a multi-device
+// render every device thread polls like this, and the caller's host work shares the cores)
+int WaveRun::poll()
+{
     auto idle_since = std::chrono::steady_clock::now();
     for (;;) {
         bool any = false, moved = false;
-        for (int l = 0; l < nl; l++) {
+        for (int l = 0; l < P.lanes; l++) {
             WaveLane& La = L[l];
-            if (La.await) {
+            if (La.await != Await::None) {
                 any = true;
                 const hipError_t q = hipEventQuery(La.ev);
                 if (q == hipErrorNotReady) continue;
@@ -2471,7 +1983,7 @@ int run_wave(rt_context* c, Backend* b, int w, int h, int spp, int bounces, cons
                 if (int r = process(La)) return r;
                 moved = true;
             }
-            if (!La.done && !La.await) {
+            if (!La.done && La.await == Await::None) {
                 if (La.it >= max_iters) {
                     HIPCHK(c, hipStreamSynchronize(La.s));
                     return rt_fail(c, RT_ERR_STATE, "render: wavefront loop did not drain in " +
@@ -2491,7 +2003,14 @@ int run_wave(rt_context* c, Backend* b, int w, int h, int spp, int bounces, cons
             std::this_thread::yield();
         }
     }
-    for (int l = 0; l < nl; l++) {  // each lane's pixels tone-mapped after its last step
+    return RT_OK;
+}
+
+// each lane's pixels tone-mapped after its last step; the lanes joined back into s
+int WaveRun::finish()
+{
+    const int nl = P.lanes;
+    for (int l = 0; l < nl; l++) {
         if (fast_ran)
             HIPCHK(c, hipStreamWaitEvent(L[l].s, b->fev_done, 0));  // (and the fast lane's)
         hipLaunchKernelGGL(k_tonemap, dim3((L[l].n + threads - 1) / threads), dim3(threads), 0, L[l].s, L[l].W);
@@ -2508,6 +2027,14 @@ int run_wave(rt_context* c, Backend* b, int w, int h, int spp, int bounces, cons
     b->tail_iter = L[0].tail_iter;
     HIPCHK(c, hipEventRecord(b->ev_done, s));
     b->done_recorded = true;
+    return RT_OK;
+}
+
+// The run's diagnostics: walk log, iteration counts, per-kernel ms, timeline, RT_DEBUG_FB.
+int WaveRun::report()
+{
+    const int nl = P.lanes;
+    const RtDiag& dg = c->diag;
     if (wlog) {  // (diagnostics: device 0's records of this render replace the last render's)
         int32_t nw = 0;
         HIPCHK(c, hipMemcpyAsync(&nw, b->wlog.p, 4, hipMemcpyDeviceToHost, s));
@@ -2595,286 +2122,22 @@ int run_wave(rt_context* c, Backend* b, int w, int h, int spp, int bounces, cons
 #endif
     return RT_OK;
 }
-
-int finish_stats(rt_context* c, Backend* b, hipStream_t s)
-{
-    if (!c->stats_enabled) return RT_OK;
-    HIPCHK(c, hipMemcpyAsync(c->stats, b->stats.p, sizeof(c->stats), hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    return RT_OK;
-}
-
-// Rows of a multi-device render: request row j (image row off + j*stride) belongs to
-// device j mod N. Device d's rows go to block d of the root's staging buffer (rows_max
-// rows each; the tail of a short block is padding), ncclScatter sends block d to
-// device d, every device renders its block with its own wavefront loop (one host
-// thread per device: run_wave polls its lanes), and ncclGather brings the blocks back
-// for the un-permute. Pack and un-permute are strided 2-D copies on the root.
-int render_multi(rt_context* c, Group* g, int w, int h, int spp, int bounces, float4_* fb, int off, int stride,
-                 hipStream_t s)
-{
-    const int N = (int)g->dev.size();
-    std::string err;
-    const Rccl* R = nullptr;
-    if (!g->loopback && !(R = rccl_load(err))) return rt_fail(c, RT_ERR_NODEV, err);
-    const int rows = (h - off + stride - 1) / stride;
-    const int rows_max = (rows + N - 1) / N;
-    const size_t blk = (size_t)rows_max * w;  // float4 per block
-    auto rows_of = [&](int d) { return rows > d ? (rows - d + N - 1) / N : 0; };
-    Backend* root = g->dev[0];
-    for (int d = 1; d < N; d++) {
-        HIPCHK(c, hipSetDevice(g->dev[d]->device));
-        if (int r = ensure(c, g->shard[d], std::max<size_t>(blk, 1) * sizeof(float4_))) return r;
-    }
-    HIPCHK(c, hipSetDevice(root->device));
-    if (int r = ensure(c, g->stage, std::max<size_t>(blk, 1) * N * sizeof(float4_))) return r;
-    float4_* stage = (float4_*)g->stage.p;
-    HIPCHK(c, hipEventRecord(root->ev0, s));
-    const size_t pitch = (size_t)w * sizeof(float4_);
-    for (int d = 0; d < N; d++)
-        if (rows_of(d))
-            HIPCHK(c, hipMemcpy2DAsync(stage + d * blk, pitch, fb + (size_t)d * w, N * pitch, pitch, rows_of(d),
-                                       hipMemcpyDeviceToDevice, s));
-    std::vector<hipStream_t> st(N);
-    for (int d = 0; d < N; d++) st[d] = d == 0 ? s : g->dev[d]->own;
-    const size_t cnt = blk * 4;  // floats per block
-    if (g->loopback) {  // block d -> device d by a device copy on the root stream; the shard streams wait for it
-        for (int d = 1; d < N; d++)
-            HIPCHK(c, hipMemcpyAsync(g->shard[d].p, stage + d * blk, blk * sizeof(float4_), hipMemcpyDeviceToDevice, s));
-        HIPCHK(c, hipEventRecord(root->ev_fork, s));
-        for (int d = 1; d < N; d++) {
-            HIPCHK(c, hipSetDevice(g->dev[d]->device));
-            HIPCHK(c, hipStreamWaitEvent(st[d], root->ev_fork, 0));
-        }
-        HIPCHK(c, hipSetDevice(root->device));
-    } else {
-        NCCLCHK(c, R, R->group_start());
-        for (int d = 0; d < N; d++)
-            NCCLCHK(c, R, R->scatter(stage, d == 0 ? (void*)stage : g->shard[d].p, cnt, ncclFloat, 0, g->comms[d], st[d]));
-        NCCLCHK(c, R, R->group_end());
-    }
-    // the wavefront loops, one host thread per device; errors are collected per device
-    // and raised once after the join (rt_for_devices). run_wave resets the stats itself.
-    if (int r = rt_for_devices(c, N, [&](int d) -> int {
-            Backend* b = g->dev[d];
-            HIPCHK(c, hipSetDevice(b->device));
-            const rtk::PixSrc src{w, off + d * stride, N * stride, nullptr};
-            float4_* dst = d == 0 ? stage : (float4_*)g->shard[d].p;
-            return run_wave(c, b, w, h, spp, bounces, src, rows_of(d) * w, dst, st[d]);
-        }))
-        return r;
-    HIPCHK(c, hipSetDevice(root->device));
-    if (g->loopback) {  // each block back to the root after its device's loop; the root stream waits for all
-        for (int d = 1; d < N; d++) {
-            Backend* b = g->dev[d];
-            HIPCHK(c, hipSetDevice(b->device));
-            HIPCHK(c, hipMemcpyAsync(stage + d * blk, g->shard[d].p, blk * sizeof(float4_), hipMemcpyDeviceToDevice, st[d]));
-            HIPCHK(c, hipEventRecord(b->ev_join[0], st[d]));
-            HIPCHK(c, hipSetDevice(root->device));
-            HIPCHK(c, hipStreamWaitEvent(s, b->ev_join[0], 0));
-        }
-    } else {
-        NCCLCHK(c, R, R->group_start());
-        for (int d = 0; d < N; d++)
-            NCCLCHK(c, R, R->gather(d == 0 ? (const void*)stage : g->shard[d].p, stage, cnt, ncclFloat, 0, g->comms[d], st[d]));
-        NCCLCHK(c, R, R->group_end());
-    }
-    for (int d = 0; d < N; d++)
-        if (rows_of(d))
-            HIPCHK(c, hipMemcpy2DAsync(fb + (size_t)d * w, N * pitch, stage + d * blk, pitch, pitch, rows_of(d),
-                                       hipMemcpyDeviceToDevice, s));
-    HIPCHK(c, hipEventRecord(root->ev1, s));
-    if (c->stats_enabled) {  // counters summed over the devices
-        unsigned long long sum[2 * RT_STAT_COUNT] = {};
-        for (int d = 0; d < N; d++) {
-            HIPCHK(c, hipSetDevice(g->dev[d]->device));
-            HIPCHK(c, hipMemcpyAsync(c->stats, g->dev[d]->stats.p, sizeof(c->stats), hipMemcpyDeviceToHost, st[d]));
-            HIPCHK(c, hipStreamSynchronize(st[d]));
-            for (int i = 0; i < 2 * RT_STAT_COUNT; i++) sum[i] += c->stats[i];
-        }
-        std::memcpy(c->stats, sum, sizeof sum);
-        HIPCHK(c, hipSetDevice(root->device));
-    }
-    root->last_iters = 0;
-    for (Backend* b : g->dev) root->last_iters = std::max(root->last_iters, b->last_iters);
-    return RT_OK;
-}
 }  // namespace
 
-int rt_backend_render(rt_context* c, int w, int h, int spp, int bounces, float* host_fb, void* dev_fb, int row_offset,
-                      int row_stride, void* stream)
+int run_wave(rt_context* c, Backend* b, int w, int h, int spp, int bounces, const rtk::PixSrc& src, int n, float4_* fb,
+             hipStream_t s)
 {
-    Group* g = grp(c);
-    Backend* b = be(c);
-    HIPCHK(c, hipSetDevice(b->device));
-    hipStream_t s = (hipStream_t)stream;
-    const int rows_local = (h - row_offset + row_stride - 1) / row_stride;
-    const size_t npx = (size_t)rows_local * w;
-    if (npx > 0x7fffffff / 8) return rt_fail(c, RT_ERR_ARG, "render: too many pixels for one launch");
-    float4_* fb = (float4_*)dev_fb;
-    if (host_fb) {
-        if (int r = ensure(c, b->fb, npx * sizeof(float4_))) return r;
-        fb = (float4_*)b->fb.p;
-        HIPCHK(c, hipMemcpyAsync(fb, host_fb, npx * sizeof(float4_), hipMemcpyHostToDevice, s));
-    }
-    if (g->multi) {
-        if (int r = render_multi(c, g, w, h, spp, bounces, fb, row_offset, row_stride, s)) return r;
-    } else {
-        rtk::PixSrc src{w, row_offset, row_stride, nullptr};
-        HIPCHK(c, hipEventRecord(b->ev0, s));
-        if (int r = run_wave(c, b, w, h, spp, bounces, src, (int)npx, fb, s)) return r;
-        HIPCHK(c, hipEventRecord(b->ev1, s));
-    }
-    if (host_fb) {
-        HIPCHK(c, hipMemcpyAsync(host_fb, fb, npx * sizeof(float4_), hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipStreamSynchronize(s));
-        float ms = 0;
-        HIPCHK(c, hipEventElapsedTime(&ms, b->ev0, b->ev1));
-        c->last_kernel_ms = ms;
-    } else {
-        c->last_kernel_ms = -1.0;  // read with rt_device_last_kernel_ms after the caller synchronizes
-    }
-    return g->multi ? RT_OK : finish_stats(c, b, s);
-}
-
-// The material sweep as replicas (rt_render_variants): variant v on device v mod N, one
-// host thread per device (rt_for_devices), each device walking its variants in order on
-// its own stream: the variant's table goes into the device's material buffer with a copy
-// ordered after the previous variant's frame (same stream), then the wavefront loop.
-// No exchange between devices.
-int rt_backend_render_variants(rt_context* c, int w, int h, int spp, int bounces, int n_var,
-                               const std::vector<RtMat>& tabs, int n_mats, int off, int stride, float* host_fb,
-                               void* const* d_fbs)
-{
-    Group* g = grp(c);
-    const int N = (int)g->dev.size();
-    const int rows = (h - off + stride - 1) / stride;
-    const size_t npx = (size_t)rows * w;
-    if (npx > 0x7fffffff / 8) return rt_fail(c, RT_ERR_ARG, "render: too many pixels for one launch");
-    std::vector<float> ms(N, 0.0f);
-    // counters summed over every variant of every device (run_wave zeroes a device's per render)
-    std::vector<std::vector<unsigned long long>> vsum(N, std::vector<unsigned long long>(2 * RT_STAT_COUNT, 0));
-    const int r = rt_for_devices(c, N, [&](int d) -> int {
-        Backend* b = g->dev[d];
-        HIPCHK(c, hipSetDevice(b->device));
-        hipStream_t s = b->own;
-        if (b->done_recorded) HIPCHK(c, hipEventSynchronize(b->ev_done));  // (the table and buffers are reused)
-        if (int e = ensure(c, b->mats, (size_t)n_mats * sizeof(RtMat))) return e;
-        b->view.mats = (const RtMat*)b->mats.p;
-        b->view.n_mats = n_mats;
-        if (host_fb)
-            if (int e = ensure(c, b->fb, npx * sizeof(float4_))) return e;
-        HIPCHK(c, hipEventRecord(b->ev0, s));
-        for (int v = d; v < n_var; v += N) {
-            const RtMat* tab = tabs.data() + (size_t)v * n_mats;
-            b->bl_rays = rt_table_has_emissive_prim(c, tab) ? 1 : 0;
-            // (pageable source: the copy is staged before the call returns, and ordered on s
-            // after the previous variant's frame, whose lanes joined back into s)
-            HIPCHK(c, hipMemcpyAsync(b->mats.p, tab, (size_t)n_mats * sizeof(RtMat), hipMemcpyHostToDevice, s));
-            float4_* fb = host_fb ? (float4_*)b->fb.p : (float4_*)d_fbs[v];
-            if (host_fb)
-                HIPCHK(c, hipMemcpyAsync(fb, host_fb + 4 * npx * v, npx * sizeof(float4_), hipMemcpyHostToDevice, s));
-            const rtk::PixSrc src{w, off, stride, nullptr};
-            if (int e = run_wave(c, b, w, h, spp, bounces, src, (int)npx, fb, s)) return e;
-            if (host_fb)
-                HIPCHK(c, hipMemcpyAsync(host_fb + 4 * npx * v, fb, npx * sizeof(float4_), hipMemcpyDeviceToHost, s));
-            if (c->stats_enabled) {  // (diagnostic renders: this variant's counters, before the next zeroes them)
-                unsigned long long one[2 * RT_STAT_COUNT];
-                HIPCHK(c, hipMemcpyAsync(one, b->stats.p, sizeof one, hipMemcpyDeviceToHost, s));
-                HIPCHK(c, hipStreamSynchronize(s));
-                for (int i = 0; i < 2 * RT_STAT_COUNT; i++) vsum[d][i] += one[i];
-            }
-        }
-        HIPCHK(c, hipEventRecord(b->ev1, s));
-        HIPCHK(c, hipStreamSynchronize(s));
-        HIPCHK(c, hipEventElapsedTime(&ms[d], b->ev0, b->ev1));
-        return 0;
-    });
-    // the bound table comes back with the next render's upload (rt_render_variants marks it)
-    for (Backend* b : g->dev) b->bl_rays = rt_scene_has_emissive_prim(c) ? 1 : 0;
-    HIPCHK(c, hipSetDevice(be(c)->device));
-    if (r) return r;
-    c->last_kernel_ms = *std::max_element(ms.begin(), ms.end());
-    if (c->stats_enabled)  // every variant of every device, summed
-        for (int i = 0; i < 2 * RT_STAT_COUNT; i++) {
-            c->stats[i] = 0;
-            for (int d = 0; d < N; d++) c->stats[i] += vsum[d][i];
-        }
-    return RT_OK;
-}
-
-// One device's share of a pixel list (host buffers in and out).
-static int render_pixels_one(rt_context* c, Backend* b, int w, int h, int spp, int bounces, const int* xy, int n,
-                             float* rgba, float* ms_out)
-{
-    HIPCHK(c, hipSetDevice(b->device));
-    if (n == 0) return RT_OK;
-    const size_t bxy = (size_t)n * 8, brgba = (size_t)n * 16;
-    if (int r = ensure(c, b->xy, bxy)) return r;
-    if (int r = ensure(c, b->fb, brgba)) return r;
-    hipStream_t s = b->own;
-    HIPCHK(c, hipMemcpyAsync(b->xy.p, xy, bxy, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(b->fb.p, rgba, brgba, hipMemcpyHostToDevice, s));
-    if (c->stats_enabled) HIPCHK(c, hipMemsetAsync(b->stats.p, 0, b->stats.bytes, s));
-    rtk::PixSrc src{w, 0, 1, (const int32_t*)b->xy.p};
-    HIPCHK(c, hipEventRecord(b->ev0, s));
-    if (int r = run_wave(c, b, w, h, spp, bounces, src, n, (float4_*)b->fb.p, s)) return r;
-    HIPCHK(c, hipEventRecord(b->ev1, s));
-    HIPCHK(c, hipMemcpyAsync(rgba, b->fb.p, brgba, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    float ms = 0;
-    HIPCHK(c, hipEventElapsedTime(&ms, b->ev0, b->ev1));
-    *ms_out = ms;
-    return RT_OK;
-}
-
-int rt_backend_render_pixels(rt_context* c, int w, int h, int spp, int bounces, const int* xy, int n, float* rgba)
-{
-    Group* g = grp(c);
-    const int N = (int)g->dev.size();
-    if (N == 1) {
-        float ms = 0;
-        if (int r = render_pixels_one(c, g->dev[0], w, h, spp, bounces, xy, n, rgba, &ms)) return r;
-        c->last_kernel_ms = ms;
-        return finish_stats(c, g->dev[0], g->dev[0]->own);
-    }
-    // pixel i -> device i mod N (pixels are independent); host-side split and merge
-    std::vector<std::vector<int>> pxy(N);
-    std::vector<std::vector<float>> prgba(N);
-    for (int i = 0; i < n; i++) {
-        pxy[i % N].push_back(xy[2 * i]);
-        pxy[i % N].push_back(xy[2 * i + 1]);
-        prgba[i % N].insert(prgba[i % N].end(), rgba + 4 * (size_t)i, rgba + 4 * (size_t)i + 4);
-    }
-    std::vector<int> rc(N, RT_OK);
-    std::vector<float> ms(N, 0.0f);
-    {
-        std::vector<std::thread> th;
-        for (int d = 0; d < N; d++)
-            th.emplace_back([&, d] {
-                rc[d] = render_pixels_one(c, g->dev[d], w, h, spp, bounces, pxy[d].data(), (int)pxy[d].size() / 2,
-                                          prgba[d].data(), &ms[d]);
-            });
-        for (auto& t : th) t.join();
-    }
-    for (int d = 0; d < N; d++)
-        if (rc[d]) return rc[d];
-    for (int i = 0; i < n; i++) std::memcpy(rgba + 4 * (size_t)i, &prgba[i % N][4 * (size_t)(i / N)], 16);
-    c->last_kernel_ms = *std::max_element(ms.begin(), ms.end());
-    if (c->stats_enabled) {
-        unsigned long long sum[2 * RT_STAT_COUNT] = {};
-        for (int d = 0; d < N; d++) {
-            if (int r = finish_stats(c, g->dev[d], g->dev[d]->own)) return r;
-            for (int i = 0; i < 2 * RT_STAT_COUNT; i++) sum[i] += c->stats[i];
-        }
-        std::memcpy(c->stats, sum, sizeof sum);
-    }
-    return RT_OK;
+    if (n <= 0) return RT_OK;
+    WaveRun R{c, b, w, h, spp, bounces, src, n, fb, s};
+    if (int r = R.begin()) return r;
+    if (int r = R.poll()) return r;
+    if (int r = R.finish()) return r;
+    return R.report();
 }
 
 int rt_backend_intersect(rt_context* c, const float* rays, int n, void* out)
 {
-    Backend* b = be(c);
+    Backend* b = rt_backend_dev0(c);
     HIPCHK(c, hipSetDevice(b->device));
     const size_t br = (size_t)n * 24, bo = (size_t)n * 44;
     if (int r = ensure(c, b->xy, br + bo)) return r;
@@ -2894,35 +2157,18 @@ int rt_backend_intersect(rt_context* c, const float* rays, int n, void* out)
     return RT_OK;
 }
 
-// The root device's state for the post stage (rt_denoise.hip).
-int rt_backend_root(rt_context* c, RtRootDev* out)
-{
-    Backend* b = be(c);
-    out->device = b->device;
-    out->view = &b->view;
-    out->ev0 = b->ev0;
-    out->ev1 = b->ev1;
-    out->post = &b->post;
-    out->query = &b->query;
-    return RT_OK;
-}
-
 // Device self-tests of the numerics (libm restatement, IEEE div/sqrt/f64).
 extern "C" int rt_device_libm(int device, int fn, const float* in, const float* in2, float* out, int n)
 {
     if (hipSetDevice(device) != hipSuccess) return RT_ERR_NODEV;
-    float *d_in = nullptr, *d_in2 = nullptr, *d_out = nullptr;
     const size_t b = (size_t)n * 4;
-    if (hipMalloc(&d_in, b) != hipSuccess || hipMalloc(&d_in2, b) != hipSuccess || hipMalloc(&d_out, b) != hipSuccess)
-        return RT_ERR_HIP;
-    (void)hipMemcpy(d_in, in, b, hipMemcpyHostToDevice);
-    if (in2) (void)hipMemcpy(d_in2, in2, b, hipMemcpyHostToDevice);
-    hipLaunchKernelGGL(k_libm, dim3((n + 255) / 256), dim3(256), 0, 0, fn, d_in, d_in2, d_out, n);
-    hipError_t e = hipMemcpy(out, d_out, b, hipMemcpyDeviceToHost);
-    (void)hipFree(d_in);
-    (void)hipFree(d_in2);
-    (void)hipFree(d_out);
-    return e == hipSuccess ? RT_OK : RT_ERR_HIP;
+    DevBuf d_in, d_in2, d_out;
+    if (ensure(nullptr, d_in, b) || ensure(nullptr, d_in2, b) || ensure(nullptr, d_out, b)) return RT_ERR_HIP;
+    (void)hipMemcpy(d_in.p, in, b, hipMemcpyHostToDevice);
+    if (in2) (void)hipMemcpy(d_in2.p, in2, b, hipMemcpyHostToDevice);
+    hipLaunchKernelGGL(k_libm, dim3((n + 255) / 256), dim3(256), 0, 0, fn, (const float*)d_in.p, (const float*)d_in2.p,
+                       (float*)d_out.p, n);
+    return hipMemcpy(out, d_out.p, b, hipMemcpyDeviceToHost) == hipSuccess ? RT_OK : RT_ERR_HIP;
 }
 
 // TEST ONLY (include/rt_hip.h): the env-CDF search alone on the context's env, several blocks
@@ -2931,24 +2177,20 @@ extern "C" int rt_device_env_search(rt_context* c, int form, const float* values
 {
     if (!c || !c->backend || n <= 0 || !values || !xy_out || form < 0 || form > 1) return RT_ERR_ARG;
     if (!c->have_env) return RT_ERR_STATE;
-    Backend* b = be(c);
+    Backend* b = rt_backend_dev0(c);
     HIPCHK(c, hipSetDevice(b->device));
     if (c->dirty) {
         if (int r = rt_backend_upload(c)) return r;
         c->dirty = false;
     }
-    float* d_v = nullptr;
-    int* d_xy = nullptr;
-    HIPCHK(c, hipMalloc(&d_v, (size_t)n * 4));
-    HIPCHK(c, hipMalloc(&d_xy, (size_t)n * 8));
-    HIPCHK(c, hipMemcpy(d_v, values, (size_t)n * 4, hipMemcpyHostToDevice));
+    DevBuf v, xy;
+    if (int r = ensure(c, v, (size_t)n * 4)) return r;
+    if (int r = ensure(c, xy, (size_t)n * 8)) return r;
+    HIPCHK(c, hipMemcpy(v.p, values, (size_t)n * 4, hipMemcpyHostToDevice));
     const int threads = 256, blocks = std::min((n + threads - 1) / threads, 64);
-    hipLaunchKernelGGL(k_env_search, dim3(blocks), dim3(threads), 0, 0, b->view, form, d_v, n, d_xy);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpy(xy_out, d_xy, (size_t)n * 8, hipMemcpyDeviceToHost);
-    (void)hipFree(d_v);
-    (void)hipFree(d_xy);
-    HIPCHK(c, e);
+    hipLaunchKernelGGL(k_env_search, dim3(blocks), dim3(threads), 0, 0, b->view, form, (const float*)v.p, n, (int*)xy.p);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpy(xy_out, xy.p, (size_t)n * 8, hipMemcpyDeviceToHost));
     return RT_OK;
 }
 
@@ -2960,7 +2202,7 @@ extern "C" int rt_device_queries(rt_context* c, int mode, const float* rays, int
                                  int* out_k, double* ms)
 {
     if (!c || !c->backend || n <= 0 || reps < 1 || mode < 0 || mode > 9) return RT_ERR_ARG;
-    Backend* b = be(c);
+    Backend* b = rt_backend_dev0(c);
     HIPCHK(c, hipSetDevice(b->device));
     if (c->dirty) {
         if (int r = rt_backend_upload(c)) return r;
@@ -2971,17 +2213,18 @@ extern "C" int rt_device_queries(rt_context* c, int mode, const float* rays, int
     const int threads = 256, blocks = std::min((n + threads - 1) / threads, cus * 8);
     const int qblocks = std::min((4 * n + threads - 1) / threads, cus * 16);
     const int rblocks = std::min((16 * n + threads - 1) / threads, cus * 16);
-    float4_* d_rays = nullptr;
-    float* d_t = nullptr;
-    int* d_k = nullptr;
-    uint32_t* sr = nullptr;
-    float* sk = nullptr;
     const size_t lanes = (size_t)blocks * threads;
-    HIPCHK(c, hipMalloc(&d_rays, (size_t)n * 32));
-    HIPCHK(c, hipMalloc(&d_t, (size_t)n * 4));
-    HIPCHK(c, hipMalloc(&d_k, (size_t)n * 4));
-    HIPCHK(c, hipMalloc(&sr, lanes * RT_SPILL_FAST * 4));
-    HIPCHK(c, hipMalloc(&sk, lanes * RT_SPILL_FAST * 4));
+    DevBuf b_rays, b_t, b_k, b_sr, b_sk;
+    if (int r = ensure(c, b_rays, (size_t)n * 32)) return r;
+    if (int r = ensure(c, b_t, (size_t)n * 4)) return r;
+    if (int r = ensure(c, b_k, (size_t)n * 4)) return r;
+    if (int r = ensure(c, b_sr, lanes * RT_SPILL_FAST * 4)) return r;
+    if (int r = ensure(c, b_sk, lanes * RT_SPILL_FAST * 4)) return r;
+    float4_* d_rays = (float4_*)b_rays.p;
+    float* d_t = (float*)b_t.p;
+    int* d_k = (int*)b_k.p;
+    uint32_t* sr = (uint32_t*)b_sr.p;
+    float* sk = (float*)b_sk.p;
     HIPCHK(c, hipMemcpy(d_rays, rays, (size_t)n * 32, hipMemcpyHostToDevice));
     auto launch = [&]() {
         switch (mode) {
@@ -3008,86 +2251,5 @@ extern "C" int rt_device_queries(rt_context* c, int mode, const float* rays, int
     if (ms) *ms = t / reps;
     HIPCHK(c, hipMemcpy(out_t, d_t, (size_t)n * 4, hipMemcpyDeviceToHost));
     HIPCHK(c, hipMemcpy(out_k, d_k, (size_t)n * 4, hipMemcpyDeviceToHost));
-    (void)hipFree(d_rays);
-    (void)hipFree(d_t);
-    (void)hipFree(d_k);
-    (void)hipFree(sr);
-    (void)hipFree(sk);
     return RT_OK;
 }
-
-// Time between the events around the last rt_render_device launch sequence
-// (recorded on its stream); call after synchronizing that stream.
-extern "C" double rt_device_last_kernel_ms(rt_context* c)
-{
-    if (!c || !c->backend) return -1.0;
-    Backend* b = be(c);
-    float ms = 0;
-    if (hipEventSynchronize(b->ev1) != hipSuccess) return -1.0;
-    if (hipEventElapsedTime(&ms, b->ev0, b->ev1) != hipSuccess) return -1.0;
-    c->last_kernel_ms = ms;
-    return ms;
-}
-
-// Iterations the last wavefront render took.
-extern "C" int rt_device_last_iterations(rt_context* c) { return c && c->backend ? be(c)->last_iters : -1; }
-
-// Queries k_trace handed to the exact octree walk (ties, failed verifications, stack
-// overflows, far origins, the force_fallback stressor) in every render on every device of
-// the context since the last reset: the walks' health figure (~2e-6 per sample on cfg2).
-// Waits for the devices.
-extern "C" int rt_device_exact_handovers(rt_context* c, unsigned long long* out, int reset)
-{
-    if (!c || !c->backend || !out) return RT_ERR_ARG;
-    unsigned long long sum = 0;
-    for (Backend* b : grp(c)->dev) {
-        HIPCHK(c, hipSetDevice(b->device));
-        HIPCHK(c, hipDeviceSynchronize());
-        if (!b->handovers.p) continue;
-        unsigned long long v = 0;
-        HIPCHK(c, hipMemcpy(&v, b->handovers.p, 8, hipMemcpyDeviceToHost));
-        sum += v;
-        if (reset) HIPCHK(c, hipMemset(b->handovers.p, 0, 8));
-    }
-    *out = sum;
-    return RT_OK;
-}
-
-// Per-kernel-class timing (k_trace, k_step, k_tail) over the renders since it
-// was enabled, summed over the context's devices: out_ms[3] total ms (HIP events
-// around every launch on its lane's stream), out_launches[3].
-extern "C" int rt_device_kernel_timing(rt_context* c, int enable, double* out_ms, long* out_launches)
-{
-    if (!c || !c->backend) return RT_ERR_ARG;
-    Group* g = grp(c);
-    for (int k = 0; k < 3; k++) {
-        double ms = 0;
-        long n = 0;
-        for (Backend* b : g->dev) ms += b->kms[k], n += b->klaunch[k];
-        if (out_ms) out_ms[k] = ms;
-        if (out_launches) out_launches[k] = n;
-    }
-    if (enable >= 0)
-        for (Backend* b : g->dev) {
-            b->timing = enable != 0;
-            for (int k = 0; k < 3; k++) b->kms[k] = 0, b->klaunch[k] = 0;
-        }
-    return RT_OK;
-}
-
-// Wavefront lanes (streams) per render on every device of the context (RT_LANES at
-// creation; 1 serializes a render's launches, for per-launch kernel timing; 0: auto).
-extern "C" int rt_device_set_lanes(rt_context* c, int lanes)
-{
-    if (!c || !c->backend || lanes < 0) return RT_ERR_ARG;
-    for (Backend* b : grp(c)->dev) b->lanes = std::min(RT_MAX_LANES, lanes);
-    return RT_OK;
-}
-
-#ifndef RT_BUILD_SRC
-#define RT_BUILD_SRC "unknown"
-#endif
-#ifndef RT_BUILD_DEFS
-#define RT_BUILD_DEFS ""
-#endif
-extern "C" const char* rt_build_id(void) { return "src=" RT_BUILD_SRC " defs=" RT_BUILD_DEFS " (gfx950)"; }
