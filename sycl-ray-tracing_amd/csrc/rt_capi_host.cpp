@@ -424,6 +424,21 @@ int rt_set_env(rt_context* c, const float* px, int w, int h, int ch, const float
     return RT_OK;
 }
 
+}  // extern "C"
+
+// rt_intersect, rt_query and rt_render_features need no env, but the device view must be valid:
+// a 1x1 black texel stands in. It is not the caller's env: have_env stays false, so a render
+// still asks for one (check_ready), and a later rt_set_env replaces it.
+static void placeholder_env(rt_context* c)
+{
+    if (c->have_env) return;
+    const float z[3] = {0, 0, 0};
+    rt_set_env(c, z, 1, 1, 3, nullptr);
+    c->have_env = false;
+}
+
+extern "C" {
+
 int rt_set_camera(rt_context* c, const float view[16], float fov_dist)
 {
     if (!c || !view) return rt_fail(c, RT_ERR_ARG, "rt_set_camera: bad arguments");
@@ -508,11 +523,7 @@ int rt_intersect(rt_context* c, const float* rays, int n, void* out)
     if (n < 0 || (n > 0 && (!rays || !out))) return rt_fail(c, RT_ERR_ARG, "rt_intersect: bad buffers");
     if (n == 0) return RT_OK;
     if (c->dirty) {
-        if (!c->have_env) {
-            // a 1x1 black env keeps the device view valid for ray queries
-            const float z[3] = {0, 0, 0};
-            rt_set_env(c, z, 1, 1, 3, nullptr);
-        }
+        placeholder_env(c);
         int r = rt_backend_upload(c);
         if (r) return r;
         c->dirty = false;
@@ -538,11 +549,7 @@ static int query_ready(rt_context* c, const char* fn, int mode, const void* rays
         return RT_OK;
     }
     if (c->dirty) {
-        if (!c->have_env) {
-            // a 1x1 black env keeps the device view valid for ray queries (as rt_intersect)
-            const float z[3] = {0, 0, 0};
-            rt_set_env(c, z, 1, 1, 3, nullptr);
-        }
+        placeholder_env(c);
         if (int r = rt_backend_upload(c)) return r;
         c->dirty = false;
         c->mats_dirty_only = false;
@@ -603,11 +610,7 @@ static int features_ready(rt_context* c, int w, int h, const void* alb, const vo
     if (w <= 0 || h <= 0 || !alb || !nd || alb == nd) return rt_fail(c, RT_ERR_ARG, "rt_render_features: bad buffers");
     if ((double)w * (double)h > 268435455.0) return rt_fail(c, RT_ERR_ARG, "rt_render_features: too many pixels");
     if (c->dirty || c->mats_dirty_only) {
-        if (!c->have_env) {
-            // a 1x1 black env keeps the device view valid for ray queries (as rt_intersect)
-            const float z[3] = {0, 0, 0};
-            rt_set_env(c, z, 1, 1, 3, nullptr);
-        }
+        placeholder_env(c);
         if (int r = rt_backend_upload(c)) return r;
         c->dirty = false;
         c->mats_dirty_only = false;

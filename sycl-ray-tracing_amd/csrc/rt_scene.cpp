@@ -1526,6 +1526,7 @@ void build_search_bvh(FlatBvh& out)
     lap("chain check + prims");
     SahBuilder B(P, out.bvh);
     B.workers = worker_count();
+    out.bvh.clear();  // (a context rebound to an empty scene: not the previous scene's tree)
     if (n > 0) B.run();
     lap("SAH build");
     out.bvh_tri4.resize(3 * (size_t)n);
