@@ -93,6 +93,32 @@ public:
         check(rt_render(m_ctx, m_width, m_height, m_render_samples, m_max_bounces, m_frame_buffer.data()));
     }
 
+    // render() in passes of pass_samples samples (rt_progress_*): the Image& is the base the
+    // frame adds to, and after each pass it holds the image so far and on_pass(image, done,
+    // total) is called; returning false stops the progression there. After the last pass the
+    // Image& holds what render() would have left, bit for bit. Before that it is a preview: the
+    // mean of the first `done` samples of the render_samples chain (the reference seeds a pixel
+    // with its sample count), not the frame a render of `done` samples gives. Single device only.
+    template <class F>
+    void render_progressive(int pass_samples, F&& on_pass)
+    {
+        std::lock_guard<std::mutex> lk(m_mu);
+        sync_materials();
+        check(rt_progress_begin(m_ctx, m_width, m_height, m_render_samples, m_max_bounces, m_frame_buffer.data(), 0, 1));
+        for (int done = 0; done < m_render_samples;) {
+            int info[8];
+            if (rt_progress_advance(m_ctx, pass_samples, nullptr) != RT_OK ||
+                rt_progress_resolve(m_ctx, m_frame_buffer.data()) != RT_OK || rt_progress_info(m_ctx, info) != RT_OK) {
+                const std::string err = std::string("librt_hip: ") + rt_last_error(nullptr);
+                rt_progress_end(m_ctx);
+                throw std::runtime_error(err);
+            }
+            done = info[3];
+            if (!on_pass(static_cast<const Image&>(m_frame_buffer), done, m_render_samples)) break;
+        }
+        rt_progress_end(m_ctx);
+    }
+
     // Thread-safe like the reference's (whose render() calls it from an OpenMP parallel-for,
     // render_kernel.cpp:189-211): calls on one kernel are serialized, since they share the
     // context's device buffers and the material-sync state. For throughput, hand pixel

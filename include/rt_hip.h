@@ -290,6 +290,54 @@ int rt_denoise_device(rt_context* ctx, int w, int h, const void* d_rgba_in, cons
                       const void* d_normal_depth, const rt_denoise_params* params, float blend, void* d_rgba_out,
                       void* stream);
 
+/* ---------------------------------------------------- progressive rendering
+ * A frame of samples_total samples rendered in passes: previews after the first few
+ * samples, slices that fit a time budget, checkpoints that another process resumes.
+ *
+ * The reference seeds a pixel's chain with 31 + x*y*samples (render_kernel.cpp:77), so
+ * samples 0..s-1 of an N-sample frame are not the s-sample frame: the total is declared at
+ * rt_progress_begin and fixed. Between passes the context keeps, per pixel of the row shard
+ * (rows y = row_offset + j*row_stride, as rt_render_device), the base value the frame adds
+ * to and one float4 of state {final_color rgb, RNG bits}, in buffers of its own: other
+ * renders, queries and post-stage calls on the context between passes leave them alone.
+ * Every pixel pauses at its pass's last sample, so `done` is one number.
+ *
+ * rt_progress_begin: fb_rgba_base is host memory, rows_local*w*4 floats, row j of the
+ *   shard at offset j*w*4 (NULL: (0, 0, 0, 1) per pixel). Replaces a running progression.
+ * rt_progress_advance: the next min(samples, remaining) samples of every pixel on `stream`
+ *   (NULL: default), returning without waiting for the device. Nothing left: RT_OK, no launch.
+ * rt_progress_resolve / _device: writes tonemap(base + final_color / (float)done) for every
+ *   pixel of the shard (rows_local*w*4 floats; host: waits; device: on `stream`), with the
+ *   render's own division and tone-map operations, so after passes that sum to the total the
+ *   words are rt_render's / rt_render_device's into a framebuffer holding the base, however
+ *   the total was split. It changes no state. Before that point it is a preview: the mean of
+ *   the first `done` samples of the N-sample chain, which is not the reference's
+ *   `done`-sample frame (except where x*y == 0: there the seed is 31 for every count).
+ *   done == 0: RT_ERR_STATE.
+ * rt_progress_info: info = {w, h, total, done, bounces, row_offset, row_stride, rows_local}.
+ * rt_progress_save: header (magic, format version, the eight info words; 10 int32), then
+ *   the base, then the state; returns the size (buf NULL or capacity too small: only the
+ *   size). Waits for the passes. rt_progress_load installs a saved progression at its `done`
+ *   (scene, BVH, env and camera bound, as for begin). RT_ERR_ARG for a bad magic or version,
+ *   a size that does not match the header, or done > total. The header does not fingerprint
+ *   the scene: the caller must bind the scene, env, camera and intersect mode it saved under.
+ * rt_progress_end: drops the progression and its buffers; harmless without one.
+ *
+ * rt_set_scene, rt_build_bvh, rt_set_bvh_preorder, rt_set_env, rt_set_camera,
+ * rt_set_materials and rt_set_intersect_mode end a progression. RT_ERR_STATE: no scene,
+ * BVH, env or camera bound; no progression. RT_ERR_ARG: non-positive sizes, total or
+ * `samples`, negative bounces, a row shard outside the frame, a NULL output, a multi-device
+ * context (not supported: run one process per GPU with its own row shard). */
+int rt_progress_begin(rt_context* ctx, int width, int height, int samples_total, int max_bounces,
+                      const float* fb_rgba_base, int row_offset, int row_stride);
+int rt_progress_advance(rt_context* ctx, int samples, void* stream);
+int rt_progress_resolve(rt_context* ctx, float* fb_rgba);
+int rt_progress_resolve_device(rt_context* ctx, void* d_fb, void* stream);
+int rt_progress_info(const rt_context* ctx, int info[8]);
+long rt_progress_save(rt_context* ctx, void* buf, long capacity);
+int rt_progress_load(rt_context* ctx, const void* buf, long bytes);
+void rt_progress_end(rt_context* ctx);
+
 /* Counters of the last render when enabled (RT_STAT_* order, rt_device.h);
  * with n up to 2 * RT_STAT_COUNT the second block is the share of the
  * gfx950 tail kernel (k_tail) in those totals. */

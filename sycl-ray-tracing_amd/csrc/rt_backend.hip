@@ -525,6 +525,113 @@ int rt_backend_render_pixels(rt_context* c, int w, int h, int spp, int bounces, 
     return RT_OK;
 }
 
+// ---- progressions (rt_progress_*): the base values and the paused state live in buffers of
+// their own on the context's device; a pass is run_wave with a WavePass (no k_tonemap), a
+// resolve is k_resolve over base and state. Single-device contexts (rt_capi_host.cpp).
+namespace {
+// the passes (ev_done) and device resolves (ev_pg) still in flight have finished with the buffers
+int progress_quiesce(rt_context* c, Backend* b)
+{
+    if (b->done_recorded) HIPCHK(c, hipEventSynchronize(b->ev_done));
+    if (b->pg_recorded) HIPCHK(c, hipEventSynchronize(b->ev_pg));
+    return RT_OK;
+}
+void release(DevBuf& d)
+{
+    if (d.p) (void)hipFree(d.p);
+    d.p = nullptr;
+    d.bytes = 0;
+}
+}  // namespace
+
+int rt_backend_progress_begin(rt_context* c, const float* base, const float* state)
+{
+    Backend* b = be(c);
+    DeviceScope sc;
+    if (int r = sc.enter(c, b->device)) return r;
+    if (int r = progress_quiesce(c, b)) return r;
+    const size_t n = c->prog.npx(), bytes = n * sizeof(float4_);
+    if (int r = ensure(c, b->pg_base, bytes)) return r;
+    if (int r = ensure(c, b->pg_state, bytes)) return r;
+    if (!b->ev_pg) HIPCHK(c, hipEventCreateWithFlags(&b->ev_pg.h, hipEventDisableTiming));
+    if (base) {
+        HIPCHK(c, hipMemcpy(b->pg_base.p, base, bytes, hipMemcpyHostToDevice));
+    } else {
+        const std::vector<float4_> one(n, float4_{0.0f, 0.0f, 0.0f, 1.0f});
+        HIPCHK(c, hipMemcpy(b->pg_base.p, one.data(), bytes, hipMemcpyHostToDevice));
+    }
+    if (state) HIPCHK(c, hipMemcpy(b->pg_state.p, state, bytes, hipMemcpyHostToDevice));
+    else HIPCHK(c, hipMemset(b->pg_state.p, 0, bytes));
+    HIPCHK(c, hipDeviceSynchronize());  // (a pass may start on any stream)
+    return RT_OK;
+}
+
+int rt_backend_progress_advance(rt_context* c, int first, int stop, void* stream)
+{
+    Backend* b = be(c);
+    const RtProgress& P = c->prog;
+    HIPCHK(c, hipSetDevice(b->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (b->pg_recorded) HIPCHK(c, hipStreamWaitEvent(s, b->ev_pg, 0));  // (a device resolve still reads the state)
+    const rtk::PixSrc src{P.w, P.off, P.stride, nullptr};
+    // (the framebuffer pointer of the pass is never used: it names the state, valid memory of the same size)
+    const WavePass pass{(float4_*)b->pg_state.p, first, P.total};
+    HIPCHK(c, hipEventRecord(b->ev0, s));
+    if (int r = run_wave(c, b, P.w, P.h, stop, P.bounces, src, (int)P.npx(), pass.state, s, &pass)) return r;
+    HIPCHK(c, hipEventRecord(b->ev1, s));
+    c->last_kernel_ms = -1.0;  // read with rt_device_last_kernel_ms after the caller synchronizes
+    return finish_stats(c, b, s);
+}
+
+int rt_backend_progress_resolve(rt_context* c, float* host_fb, void* dev_fb, void* stream)
+{
+    Backend* b = be(c);
+    const RtProgress& P = c->prog;
+    DeviceScope sc;
+    if (int r = sc.enter(c, b->device)) return r;
+    const int n = (int)P.npx();
+    hipStream_t s = host_fb ? (hipStream_t)b->own : (hipStream_t)stream;
+    float4_* out = (float4_*)dev_fb;
+    if (host_fb) {
+        if (int r = ensure(c, b->pg_out, (size_t)n * sizeof(float4_))) return r;
+        out = (float4_*)b->pg_out.p;
+    }
+    if (b->done_recorded) HIPCHK(c, hipStreamWaitEvent(s, b->ev_done, 0));  // (the last pass, on its own streams)
+    if (int r = rt_wave_resolve(c, (const float4_*)b->pg_base.p, (const float4_*)b->pg_state.p, out, n, P.done, s)) return r;
+    if (host_fb) {
+        HIPCHK(c, hipMemcpyAsync(host_fb, out, (size_t)n * sizeof(float4_), hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipStreamSynchronize(s));
+    } else {
+        HIPCHK(c, hipEventRecord(b->ev_pg, s));
+        b->pg_recorded = true;
+    }
+    return RT_OK;
+}
+
+int rt_backend_progress_read(rt_context* c, float* base, float* state)
+{
+    Backend* b = be(c);
+    DeviceScope sc;
+    if (int r = sc.enter(c, b->device)) return r;
+    if (int r = progress_quiesce(c, b)) return r;
+    const size_t bytes = c->prog.npx() * sizeof(float4_);
+    HIPCHK(c, hipMemcpy(base, b->pg_base.p, bytes, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(state, b->pg_state.p, bytes, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+void rt_backend_progress_end(rt_context* c)
+{
+    if (!c->backend) return;
+    Backend* b = be(c);
+    DeviceScope sc;
+    if (sc.enter(c, b->device)) return;
+    (void)progress_quiesce(c, b);
+    release(b->pg_base);
+    release(b->pg_state);
+    release(b->pg_out);
+}
+
 Backend* rt_backend_dev0(rt_context* c) { return be(c); }
 
 // The root device's state for the post stage (rt_denoise.hip) and the ray queries (rt_query.hip).

@@ -129,10 +129,13 @@ struct Backend {
     Stream fs;      // the fast lane's stream with 4 lanes (fewer: the first idle lane stream)
     DevBuf xy;        // pixel list (rt_render_pixels)
     DevBuf fb;        // host-fb staging
+    DevBuf pg_base, pg_state, pg_out;  // a progression (rt_progress_*): base values, paused state, host-resolve staging
     DevBuf shard;     // multi-device renders: the root's N blocks of rows_max rows (scatter source /
                       // gather target); device d >= 1: its block
     Pinned<int32_t> h_act[RT_MAX_LANES];  // per lane: live-slot counters (sharded) + 8 fallback counters
     Event ev0, ev1;
+    Event ev_pg;    // end of the last rt_progress_resolve_device: the next pass writes the state it reads
+    bool pg_recorded = false;
     Event ev_done;  // end of the last run_wave (all lanes joined): the next render waits for it
     bool done_recorded = false;
     Stream ls[RT_MAX_LANES];                // lanes 1.. streams (lane 0 runs on the caller's)
@@ -173,7 +176,15 @@ Backend* rt_backend_dev0(rt_context* c);             // rt_backend.hip: the root
 
 // rt_render.hip: the wavefront loop for n slots of `src` into fb (device, n float4) on b's
 // device (current), and the sizes of a lane's counters and of its pinned readback block.
+// A progressive pass (rt_progress_advance): samples first .. spp - 1 of every pixel of a frame
+// of seed_spp samples, each pixel paused into state (n float4, indexed like fb; fb unused).
+struct WavePass {
+    float4_* state;
+    int first, seed_spp;
+};
 int run_wave(rt_context* c, Backend* b, int w, int h, int spp, int bounces, const rtk::PixSrc& src, int n, float4_* fb,
-             hipStream_t s);
+             hipStream_t s, const WavePass* pass = nullptr);
+// rt_render.hip k_resolve: out[i] = the tone-mapped pixel of base[i] and state[i] after `done` samples
+int rt_wave_resolve(rt_context* c, const float4_* base, const float4_* state, float4_* out, int n, int done, hipStream_t s);
 size_t rt_wave_counter_bytes();
 size_t rt_wave_readback_bytes();

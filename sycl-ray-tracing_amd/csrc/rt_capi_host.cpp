@@ -23,6 +23,14 @@ void set_global_err(const std::string& m)
 
 void rt_err_sink(std::string* sink) { tl_sink = sink; }
 
+// A rebind ends the context's progression (rt_progress_*): its state was computed under the old binding.
+static void progress_drop(rt_context* c)
+{
+    if (!c || !c->prog.active) return;
+    rt_backend_progress_end(c);
+    c->prog = RtProgress{};
+}
+
 void rt_read_diag(rt_context* c)
 {
     if (const char* e = std::getenv("RT_TIMELINE")) c->diag.timeline = e;
@@ -291,6 +299,7 @@ int rt_set_scene(rt_context* c, const float* triangles, int n, const int* materi
                  const float* materials, int n_mats, const int* emissive, int n_em, const float* spheres, int n_sph)
 {
     if (!c) return rt_fail(nullptr, RT_ERR_ARG, "rt_set_scene: ctx is NULL");
+    progress_drop(c);
     if (n < 0 || (n > 0 && !triangles) || n_mats <= 0 || !materials || n_mi < n || (n_mi > 0 && !material_indices) ||
         n_em < 0 || (n_em > 0 && !emissive) || n_sph < 0 || (n_sph > 0 && !spheres))
         return rt_fail(c, RT_ERR_ARG, "rt_set_scene: bad buffer sizes");
@@ -329,6 +338,7 @@ int rt_set_scene(rt_context* c, const float* triangles, int n, const int* materi
 
 int rt_set_materials(rt_context* c, const float* materials, int n_mats)
 {
+    progress_drop(c);
     if (!c || !c->have_scene) return rt_fail(c, RT_ERR_STATE, "rt_set_materials: no scene");
     if (n_mats <= 0 || !materials) return rt_fail(c, RT_ERR_ARG, "rt_set_materials: bad buffer");
     for (int32_t mi : c->mat_idx)
@@ -344,6 +354,7 @@ int rt_set_materials(rt_context* c, const float* materials, int n_mats)
 
 int rt_build_bvh(rt_context* c, int max_depth, int leaf_max)
 {
+    progress_drop(c);
     if (!c || !c->have_scene) return rt_fail(c, RT_ERR_STATE, "rt_build_bvh: no scene");
     if (max_depth > 32 || max_depth < -1 || leaf_max < 1)
         return rt_fail(c, RT_ERR_ARG, "rt_build_bvh: max_depth must be -1..32 (device stack bound), leaf_max >= 1");
@@ -359,6 +370,7 @@ int rt_build_bvh(rt_context* c, int max_depth, int leaf_max)
 
 int rt_set_bvh_preorder(rt_context* c, const void* dump, long bytes)
 {
+    progress_drop(c);
     if (!c || !c->have_scene) return rt_fail(c, RT_ERR_STATE, "rt_set_bvh_preorder: no scene");
     if (!dump || bytes <= 0) return rt_fail(c, RT_ERR_ARG, "rt_set_bvh_preorder: empty dump");
     rt::Octree t;
@@ -401,6 +413,7 @@ int rt_bvh_info(const rt_context* c, long* info)
 int rt_set_env(rt_context* c, const float* px, int w, int h, int ch, const float* cdf)
 {
     if (!c) return rt_fail(nullptr, RT_ERR_ARG, "rt_set_env: ctx is NULL");
+    progress_drop(c);
     if (!px || w <= 0 || h <= 0 || (ch != 3 && ch != 4)) return rt_fail(c, RT_ERR_ARG, "rt_set_env: bad image");
     const size_t n = (size_t)w * h;
     c->ew = w;
@@ -441,6 +454,7 @@ extern "C" {
 
 int rt_set_camera(rt_context* c, const float view[16], float fov_dist)
 {
+    progress_drop(c);
     if (!c || !view) return rt_fail(c, RT_ERR_ARG, "rt_set_camera: bad arguments");
     std::memcpy(c->cam.m, view, 64);
     c->cam.fov_dist = fov_dist;
@@ -681,10 +695,145 @@ int rt_denoise_device(rt_context* c, int w, int h, const void* in, const void* a
 int rt_set_intersect_mode(rt_context* c, int use_bvh)
 {
     if (!c) return RT_ERR_ARG;
+    progress_drop(c);
     c->brute = use_bvh == 0;
     c->dirty = true;
     return RT_OK;
 }
+
+// ------------------------------------------------- progressive rendering
+#define RT_PROGRESS_MAGIC 0x47505452  // "RTPG"
+#define RT_PROGRESS_VERSION 1
+#define RT_PROGRESS_HEADER 10         // int32 words: magic, version, the eight info words
+
+static bool ctx_is_multi(const rt_context* c) { return c->devices.size() > 1 || (c->force_multi && !c->devices.empty()); }
+
+// The frame of a progression: begin's arguments, or a checkpoint's header (fn names the caller).
+static int progress_frame(rt_context* c, const char* fn, int w, int h, int total, int bounces, int off, int stride)
+{
+    const std::string f = fn;
+    if (!c) return rt_fail(nullptr, RT_ERR_ARG, f + ": ctx is NULL");
+    if (ctx_is_multi(c))
+        return rt_fail(c, RT_ERR_ARG, f + ": multi-device contexts are not supported (one process per GPU, each with its row shard)");
+    if (int r = check_ready(c, w, h, total, bounces)) return r;
+    if (stride <= 0 || off < 0 || off >= stride || off >= h) return rt_fail(c, RT_ERR_ARG, f + ": row shard outside the frame");
+    const int rows = (h - off + stride - 1) / stride;
+    if ((size_t)rows * w > 0x7fffffff / 8) return rt_fail(c, RT_ERR_ARG, f + ": too many pixels for one launch");
+    return RT_OK;
+}
+
+static void progress_install(rt_context* c, int w, int h, int total, int done, int bounces, int off, int stride)
+{
+    RtProgress& P = c->prog;
+    P.active = true;
+    P.w = w, P.h = h, P.total = total, P.done = done, P.bounces = bounces, P.off = off, P.stride = stride;
+    P.rows = (h - off + stride - 1) / stride;
+}
+
+int rt_progress_begin(rt_context* c, int w, int h, int total, int bounces, const float* base, int off, int stride)
+{
+    if (int r = progress_frame(c, "rt_progress_begin", w, h, total, bounces, off, stride)) return r;
+    progress_drop(c);
+    progress_install(c, w, h, total, 0, bounces, off, stride);
+    if (int r = rt_backend_progress_begin(c, base, nullptr)) {
+        progress_drop(c);
+        return r;
+    }
+    return RT_OK;
+}
+
+static int progress_active(rt_context* c, const char* fn)
+{
+    if (!c) return rt_fail(nullptr, RT_ERR_ARG, std::string(fn) + ": ctx is NULL");
+    if (!c->prog.active)
+        return rt_fail(c, RT_ERR_STATE, std::string(fn) + ": no progression (none begun, or a rebind ended it)");
+    return RT_OK;
+}
+
+int rt_progress_advance(rt_context* c, int samples, void* stream)
+{
+    if (int r = progress_active(c, "rt_progress_advance")) return r;
+    if (samples <= 0) return rt_fail(c, RT_ERR_ARG, "rt_progress_advance: samples must be positive");
+    RtProgress& P = c->prog;
+    const int stop = P.done + std::min(samples, P.total - P.done);
+    if (stop == P.done) return RT_OK;  // nothing left: no launch
+    // (rt_render_variants or rt_set_stats since the last pass: the bound tables go up again)
+    if (int r = check_ready(c, P.w, P.h, P.total, P.bounces)) return r;
+    if (int r = rt_backend_progress_advance(c, P.done, stop, stream)) return r;
+    P.done = stop;
+    return RT_OK;
+}
+
+static int progress_resolve(rt_context* c, const char* fn, float* host_fb, void* dev_fb, void* stream)
+{
+    if (int r = progress_active(c, fn)) return r;
+    if (!host_fb && !dev_fb) return rt_fail(c, RT_ERR_ARG, std::string(fn) + ": the output is NULL");
+    if (c->prog.done == 0) return rt_fail(c, RT_ERR_STATE, std::string(fn) + ": no sample done yet");
+    return rt_backend_progress_resolve(c, host_fb, dev_fb, stream);
+}
+
+int rt_progress_resolve(rt_context* c, float* fb) { return progress_resolve(c, "rt_progress_resolve", fb, nullptr, nullptr); }
+
+int rt_progress_resolve_device(rt_context* c, void* d_fb, void* stream)
+{
+    return progress_resolve(c, "rt_progress_resolve_device", nullptr, d_fb, stream);
+}
+
+int rt_progress_info(const rt_context* c, int info[8])
+{
+    if (!c || !info) return rt_fail(nullptr, RT_ERR_ARG, "rt_progress_info: bad arguments");
+    if (!c->prog.active) return RT_ERR_STATE;  // (const context: the message stays what it was)
+    const RtProgress& P = c->prog;
+    const int v[8] = {P.w, P.h, P.total, P.done, P.bounces, P.off, P.stride, P.rows};
+    std::memcpy(info, v, sizeof v);
+    return RT_OK;
+}
+
+long rt_progress_save(rt_context* c, void* buf, long capacity)
+{
+    if (int r = progress_active(c, "rt_progress_save")) return r;
+    const RtProgress& P = c->prog;
+    const size_t px = P.npx() * sizeof(float4_);
+    const long size = (long)(RT_PROGRESS_HEADER * 4 + 2 * px);
+    if (!buf || capacity < size) return size;
+    const int32_t hd[RT_PROGRESS_HEADER] = {RT_PROGRESS_MAGIC, RT_PROGRESS_VERSION, P.w, P.h, P.total, P.done, P.bounces,
+                                            P.off, P.stride, P.rows};
+    std::memcpy(buf, hd, sizeof hd);
+    // (the payload need not be aligned for float in the caller's buffer: staged)
+    std::vector<float> tmp(2 * px / 4);
+    if (int r = rt_backend_progress_read(c, tmp.data(), tmp.data() + px / 4)) return r;
+    std::memcpy((char*)buf + sizeof hd, tmp.data(), 2 * px);
+    return size;
+}
+
+int rt_progress_load(rt_context* c, const void* buf, long bytes)
+{
+    if (!c) return rt_fail(nullptr, RT_ERR_ARG, "rt_progress_load: ctx is NULL");
+    if (!c->have_scene || !c->have_bvh || !c->have_env || !c->have_cam)
+        return rt_fail(c, RT_ERR_STATE, "rt_progress_load: scene, BVH, environment map and camera must be bound first");
+    if (!buf || bytes < RT_PROGRESS_HEADER * 4) return rt_fail(c, RT_ERR_ARG, "rt_progress_load: no header");
+    int32_t hd[RT_PROGRESS_HEADER];
+    std::memcpy(hd, buf, sizeof hd);
+    if (hd[0] != RT_PROGRESS_MAGIC) return rt_fail(c, RT_ERR_ARG, "rt_progress_load: not a progression checkpoint (magic)");
+    if (hd[1] != RT_PROGRESS_VERSION) return rt_fail(c, RT_ERR_ARG, "rt_progress_load: unknown format version");
+    const int w = hd[2], h = hd[3], total = hd[4], done = hd[5], bounces = hd[6], off = hd[7], stride = hd[8], rows = hd[9];
+    if (int r = progress_frame(c, "rt_progress_load", w, h, total, bounces, off, stride)) return r;
+    if (done < 0 || done > total) return rt_fail(c, RT_ERR_ARG, "rt_progress_load: done is outside 0..total");
+    const size_t px = (size_t)((h - off + stride - 1) / stride) * w * sizeof(float4_);
+    if (rows != (h - off + stride - 1) / stride || (size_t)bytes != sizeof hd + 2 * px)
+        return rt_fail(c, RT_ERR_ARG, "rt_progress_load: the size does not match the header");
+    std::vector<float> tmp(2 * px / 4);
+    std::memcpy(tmp.data(), (const char*)buf + sizeof hd, 2 * px);
+    progress_drop(c);
+    progress_install(c, w, h, total, done, bounces, off, stride);
+    if (int r = rt_backend_progress_begin(c, tmp.data(), tmp.data() + px / 4)) {
+        progress_drop(c);
+        return r;
+    }
+    return RT_OK;
+}
+
+void rt_progress_end(rt_context* c) { progress_drop(c); }
 
 int rt_set_stats(rt_context* c, int enabled)
 {

@@ -53,9 +53,21 @@ struct RtDiag {
     long wlog_total = 0;      // walks that qualified (may exceed cap)
 };
 
+// A progression (rt_progress_*, include/rt_hip.h): a frame of `total` samples rendered in
+// passes. `done` is uniform over the pixels. The buffers (base values and paused state, one
+// float4 per pixel of the row shard each) belong to the backend: on the device for gfx950,
+// the two vectors here for the hostsim build.
+struct RtProgress {
+    bool active = false;
+    int w = 0, h = 0, total = 0, done = 0, bounces = 0, off = 0, stride = 1, rows = 0;
+    std::vector<float4_> base, state;  // (hostsim only)
+    size_t npx() const { return (size_t)rows * w; }
+};
+
 struct rt_context {
     int device = 0;
     RtSchedule sched;
+    RtProgress prog;
     RtDiag diag;
     // rt_create_multi: the devices a render shards over (rows y -> device y mod N, RCCL
     // scatter / gather through devices[0]); empty for a single-device context (rt_create).
@@ -130,6 +142,17 @@ int rt_backend_query(rt_context* ctx, bool any, bool all_exact, const void* rays
                      void* stream);
 // Queries of the last rt_backend_query that took the exact walk (waits for them); < 0: an error.
 long rt_backend_query_last_exact(rt_context* ctx);
+
+// Progressions (ctx->prog describes the frame; single-device contexts only, arguments validated).
+// begin: the backend's buffers for prog.npx() pixels; base / state: host float4 per pixel, or
+// null for (0, 0, 0, 1) / zeroes. advance: samples first .. stop - 1 of every pixel (device:
+// on `stream`, no wait). resolve: the image after prog.done samples into host_fb (waits) or
+// dev_fb (on `stream`). read: base and state back to the host (waits). end: frees the buffers.
+int rt_backend_progress_begin(rt_context* ctx, const float* base, const float* state);
+int rt_backend_progress_advance(rt_context* ctx, int first, int stop, void* stream);
+int rt_backend_progress_resolve(rt_context* ctx, float* host_fb, void* dev_fb, void* stream);
+int rt_backend_progress_read(rt_context* ctx, float* base, float* state);
+void rt_backend_progress_end(rt_context* ctx);
 
 int rt_fail(rt_context* ctx, int code, const std::string& msg);
 // RtDiag from the environment (rt_create*)

@@ -63,8 +63,11 @@ static void host_append(const rtk::WaveView& W, int32_t* act_count, int p, const
     if (e.active) W.act_out[__atomic_fetch_add(act_count, 1, __ATOMIC_RELAXED)] = p;
 }
 
+// prog: a progressive pass (rt_progress_advance): samples first .. spp - 1 of a frame of seed_spp
+// samples, every pixel paused into prog (indexed like fb); no tone-map.
 static int run_wave_host(rt_context* c, int w, int h, int spp, int bounces, const rtk::PixSrc& src, int n,
-                         float4_* fb, unsigned long long* stats_out, const RtMat* mats = nullptr)
+                         float4_* fb, unsigned long long* stats_out, const RtMat* mats = nullptr,
+                         float4_* prog = nullptr, int first = 0, int seed_spp = 0)
 {
     if (n <= 0) return RT_OK;
     rtk::WaveView W{};
@@ -84,6 +87,9 @@ static int run_wave_host(rt_context* c, int w, int h, int spp, int bounces, cons
     W.H = h;
     W.spp = spp;
     W.bounces = bounces;
+    W.prog = prog;
+    W.first = prog ? first : 0;
+    W.seed_spp = prog ? seed_spp : spp;
     rtk::set_view_consts(W);
     W.n_slots = n;
     W.bl_rays = rt_table_has_emissive_prim(c, W.S.mats) ? 1 : 0;
@@ -103,7 +109,8 @@ static int run_wave_host(rt_context* c, int w, int h, int spp, int bounces, cons
 #pragma omp parallel for schedule(static)
     for (int p = 0; p < n; p++) {
         rtk::Emit e;
-        rtk::path_init(W, p, e);
+        if (W.first > 0) rtk::path_resume(W, p, e);
+        else rtk::path_init(W, p, e);
         host_append(W, &act[0], p, e);
     }
     using FAST = rtk::ArrayStack<RT_HOSTSIM_SHORT_CAP>;
@@ -250,13 +257,15 @@ static int run_wave_host(rt_context* c, int w, int h, int spp, int bounces, cons
                 float col[6 * rtk::RK_COUNT];
                 rtk::EmitLds<1> e;
                 e.s = col;
-                rtk::path_step(W, p, e, ps);
+                rtk::path_step<true>(W, p, e, ps);
                 host_append(W, &act[par ^ 1], p, e);
             }
         }
     }
+    if (!prog) {
 #pragma omp parallel for schedule(static)
-    for (int p = 0; p < n; p++) rtk::tonemap_pixel(W, p);
+        for (int p = 0; p < n; p++) rtk::tonemap_pixel(W, p);
+    }
     merge_stats(stats_out, st);
     return RT_OK;
 }
@@ -359,6 +368,50 @@ int rt_backend_render_pixels(rt_context* c, int w, int h, int spp, int bounces, 
     std::fill(c->stats, c->stats + RT_STAT_COUNT, 0ull);
     return run_wave_host(c, w, h, spp, bounces, src, n, (float4_*)rgba, c->stats);
 }
+
+// ---- progressions (rt_progress_*): base and state are the context's own vectors here
+int rt_backend_progress_begin(rt_context* c, const float* base, const float* state)
+{
+    RtProgress& P = c->prog;
+    const size_t n = P.npx();
+    P.base.assign(n, float4_{0.0f, 0.0f, 0.0f, 1.0f});
+    P.state.assign(n, float4_{0.0f, 0.0f, 0.0f, 0.0f});
+    if (base) std::memcpy(P.base.data(), base, n * sizeof(float4_));
+    if (state) std::memcpy(P.state.data(), state, n * sizeof(float4_));
+    return RT_OK;
+}
+
+int rt_backend_progress_advance(rt_context* c, int first, int stop, void*)
+{
+    RtProgress& P = c->prog;
+    const rtk::PixSrc src{P.w, P.off, P.stride, nullptr};
+    std::fill(c->stats, c->stats + RT_STAT_COUNT, 0ull);
+    const double t0 = omp_get_wtime();
+    const int r = run_wave_host(c, P.w, P.h, stop, P.bounces, src, (int)P.npx(), P.state.data(), c->stats, nullptr,
+                                P.state.data(), first, P.total);
+    c->last_kernel_ms = (omp_get_wtime() - t0) * 1e3;
+    return r;
+}
+
+int rt_backend_progress_resolve(rt_context* c, float* host_fb, void* dev_fb, void*)
+{
+    const RtProgress& P = c->prog;
+    float4_* out = host_fb ? (float4_*)host_fb : (float4_*)dev_fb;  // ("device" pointers are host pointers here)
+    const long n = (long)P.npx();
+#pragma omp parallel for schedule(static)
+    for (long i = 0; i < n; i++) out[i] = rtk::resolve_pixel(P.base[i], P.state[i], P.done);
+    return RT_OK;
+}
+
+int rt_backend_progress_read(rt_context* c, float* base, float* state)
+{
+    const RtProgress& P = c->prog;
+    std::memcpy(base, P.base.data(), P.npx() * sizeof(float4_));
+    std::memcpy(state, P.state.data(), P.npx() * sizeof(float4_));
+    return RT_OK;
+}
+
+void rt_backend_progress_end(rt_context*) {}  // (the vectors go with c->prog)
 
 int rt_backend_intersect(rt_context* c, const float* rays, int n, void* out)
 {

@@ -392,6 +392,30 @@ __global__ __launch_bounds__(256) void k_init(rtk::WaveView W)
     append_emit(W, 0, p & ~63, W.n_slots, p, e);
 }
 
+// k_init of a progressive pass after the first: every slot goes on from its pixel's paused
+// state (rt_wave.h path_resume) and emits the camera ray of the pass's first sample.
+__global__ __launch_bounds__(256) void k_resume(rtk::WaveView W)
+{
+    rtlibm::lds_tables_init();
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;  // grid covers whole waves
+    rtk::Emit e;
+    e.mask = 0;
+    e.active = false;
+    e.heavy = false;
+    if (p < W.n_slots) rtk::path_resume(W, p, e);
+    append_emit(W, 0, p & ~63, W.n_slots, p, e);
+}
+
+// A progression's image after `done` samples: one thread per pixel of the shard, base and
+// paused state in, the tone-mapped pixel out (rt_wave.h resolve_pixel). Changes no state.
+__global__ __launch_bounds__(256) void k_resolve(const float4_* __restrict__ base, const float4_* __restrict__ state,
+                                                 float4_* __restrict__ out, int n, int done)
+{
+    rtlibm::lds_tables_init();
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = rtk::resolve_pixel(base[i], state[i], done);
+}
+
 // After a lane's last step: the tone-map of every pixel of the lane (rt_wave.h tonemap_pixel).
 __global__ __launch_bounds__(256) void k_tonemap(rtk::WaveView W)
 {
@@ -577,7 +601,8 @@ __device__ void exact_octets(const rtk::WaveView& W, int par, uint32_t* lds, int
 // the exact octree walks of this iteration's fallbacks and of the walks parked
 // last iteration (they need the registers this kernel has anyway; k_trace
 // stays small enough for 8 waves per SIMD).
-template <bool STATS>
+// PROG: the instantiation a progressive pass launches (rt_wave.h finish_pixel pauses the pixel).
+template <bool STATS, bool PROG = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_STEP_OCC, 8))) void k_step(rtk::WaveView W, int par, unsigned long long* stats)
 {
     // (the exact roles' stacks; in the path-step blocks, the emitted rays: rt_wave.h EmitLds)
@@ -641,7 +666,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_STEP_OCC
         if (idx < n) {
             const int sh = shard_find8<RT_QSHARDS>(s_pre, idx);
             p = W.act_in[(size_t)sh * W.seg_cap + (idx - s_pre[sh])];
-            rtk::path_step(W, p, e, ps);
+            rtk::path_step<PROG>(W, p, e, ps);
         }
         append_emit(W, par ^ 1, base, n, p, e);
     }
@@ -1062,7 +1087,7 @@ __device__ __noinline__ int tail_step(const rtk::WaveView& W, int my, int last_k
     e.mask = 0;
     e.active = false;
     e.heavy = false;
-    if (my >= 0) rtk::path_step(W, my, e, ps);
+    if (my >= 0) rtk::path_step<true>(W, my, e, ps);
     int nl[2];
     tail_lists(e, last_kind, l0, l1, nl);
     return (e.active ? 1 : 0) | (nl[0] << 1) | (nl[1] << 11);
@@ -1094,7 +1119,7 @@ __device__ __noinline__ int tail_step(const rtk::WaveView& W, int my, int last_k
     e.mask = 0;
     e.active = false;
     e.heavy = false;
-    if (my >= 0) rtk::path_step(W, my, e, ps);
+    if (my >= 0) rtk::path_step<true>(W, my, e, ps);
     int nl[2];
     tail_lists(e, my, last_kind, l0, l1, nl);
     return (e.active ? 1 : 0) | (nl[0] << 1) | (nl[1] << 11);
@@ -1531,7 +1556,9 @@ void launch_k_tail_fast(bool SEQ, bool S, dim3 g, hipStream_t s, const rtk::Wave
 }
 void launch_k_step(bool S, dim3 g, hipStream_t s, const rtk::WaveView& W, int par, unsigned long long* stats)
 {
-    if (S) RT_LAUNCH(k_step<true>);
+    if (W.prog && S) RT_LAUNCH((k_step<true, true>));  // (a progressive pass)
+    else if (W.prog) RT_LAUNCH((k_step<false, true>));
+    else if (S) RT_LAUNCH(k_step<true>);
     else RT_LAUNCH(k_step<false>);
 }
 void launch_k_tail(bool SEQ, bool S, bool rows, dim3 g, hipStream_t s, const rtk::WaveView& W, int par,
@@ -1582,6 +1609,7 @@ struct WaveRun {
     int n;
     float4_* fb;
     hipStream_t s;
+    const WavePass* pass;  // a progressive pass: samples pass->first .. spp - 1, paused into pass->state (else null)
     int dev_cus = 256;
     WavePlan P{};
     WaveLane L[RT_MAX_LANES];
@@ -1709,6 +1737,9 @@ int WaveRun::init_lane(int l)
     W.H = h;
     W.spp = spp;
     W.bounces = bounces;
+    W.prog = pass ? pass->state + lp.first : nullptr;
+    W.first = pass ? pass->first : 0;
+    W.seed_spp = pass ? pass->seed_spp : spp;
     rtk::set_view_consts(W);
     W.n_slots = La.n;
     W.bl_rays = b->bl_rays;
@@ -1748,7 +1779,10 @@ int WaveRun::init_lane(int l)
     HIPCHK(c, hipMemsetAsync(W.r_park, 0, (size_t)La.n * 4, La.s));
     W.act_in = La.lists[1];
     W.act_out = La.lists[0];
-    hipLaunchKernelGGL(k_init, dim3((La.n + threads - 1) / threads), dim3(threads), 0, La.s, W);
+    if (W.first > 0)
+        hipLaunchKernelGGL(k_resume, dim3((La.n + threads - 1) / threads), dim3(threads), 0, La.s, W);
+    else
+        hipLaunchKernelGGL(k_init, dim3((La.n + threads - 1) / threads), dim3(threads), 0, La.s, W);
     HIPCHK(c, hipGetLastError());
     return RT_OK;
 }
@@ -2013,6 +2047,7 @@ int WaveRun::finish()
     for (int l = 0; l < nl; l++) {
         if (fast_ran)
             HIPCHK(c, hipStreamWaitEvent(L[l].s, b->fev_done, 0));  // (and the fast lane's)
+        if (pass) continue;  // (a progressive pass leaves the pixels paused: rt_progress_resolve tone-maps)
         hipLaunchKernelGGL(k_tonemap, dim3((L[l].n + threads - 1) / threads), dim3(threads), 0, L[l].s, L[l].W);
         HIPCHK(c, hipGetLastError());
     }
@@ -2125,14 +2160,21 @@ int WaveRun::report()
 }  // namespace
 
 int run_wave(rt_context* c, Backend* b, int w, int h, int spp, int bounces, const rtk::PixSrc& src, int n, float4_* fb,
-             hipStream_t s)
+             hipStream_t s, const WavePass* pass)
 {
     if (n <= 0) return RT_OK;
-    WaveRun R{c, b, w, h, spp, bounces, src, n, fb, s};
+    WaveRun R{c, b, w, h, spp, bounces, src, n, fb, s, pass};
     if (int r = R.begin()) return r;
     if (int r = R.poll()) return r;
     if (int r = R.finish()) return r;
     return R.report();
+}
+
+int rt_wave_resolve(rt_context* c, const float4_* base, const float4_* state, float4_* out, int n, int done, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_resolve, dim3((n + threads - 1) / threads), dim3(threads), 0, s, base, state, out, n, done);
+    HIPCHK(c, hipGetLastError());
+    return RT_OK;
 }
 
 int rt_backend_intersect(rt_context* c, const float* rays, int n, void* out)

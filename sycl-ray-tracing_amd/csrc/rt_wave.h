@@ -141,6 +141,11 @@ struct WaveView {
     const int32_t* act_in;  // active slots this iteration
     int32_t* act_out;
     int n_act_in;
+    // progressive passes (rt_progress_*): a pass runs samples first .. spp - 1 of every pixel and
+    // pauses it there. An ordinary render: prog null, first 0, seed_spp = spp.
+    float4_* prog;          // paused state per pixel {final_color rgb, RNG bits}, indexed like fb (fb_at); else null
+    int first;              // the pass's first sample index
+    int seed_spp;           // the frame's whole sample count: the reference's seed 31 + x*y*samples
 };
 
 // Carves the path-slot buffers for n slots out of one allocation at `base`
@@ -449,8 +454,15 @@ RT_HD size_t fb_at(const WaveView& W, int p)
 // on the same values in the same order) runs once per pixel after the render's last
 // step, in its own converged pass (rt_render.hip k_tonemap, rt_hostsim.cpp), instead
 // of inside the divergent step code.
+// PROG false: the caller runs ordinary renders only (k_step's product instantiation: the
+// test below moved its register allocation, so progressive passes launch one of their own).
+template <bool PROG>
 RT_HD void finish_pixel(const WaveView& W, int p, PathReg& P)
 {
+    if (PROG && W.prog) {  // a progressive pass pauses here: the state the next pass (path_resume) or a resolve reads
+        W.prog[fb_at(W, p)] = f4(P.fin, rt_asfloat(P.rng.a));
+        return;
+    }
     const float k = (float)W.spp;
     Col fin = P.fin;
     fin.r /= k;  // Color /= float is a true division (color.h:69-76)
@@ -462,6 +474,32 @@ RT_HD void finish_pixel(const WaveView& W, int p, PathReg& P)
     px.y += fin.g;
     px.z += fin.b;
     dst = px;
+}
+
+// A progression's image after `done` samples (rt_progress_resolve): the pixel's end on its
+// base value and paused state, finish_pixel's true division and sum, then tonemap_pixel's
+// operations in their order. With done = the frame's sample count this is the render's pixel.
+RT_HD float4_ resolve_pixel(const float4_& base, const float4_& state, int done)
+{
+    const float k = (float)done;
+    Col fin = colof(state);
+    fin.r /= k;
+    fin.g /= k;
+    fin.b /= k;
+    float4_ px = base;
+    px.x += fin.r;
+    px.y += fin.g;
+    px.z += fin.b;
+    float* v = &px.x;
+    const float a = v[3] + 0.0f;
+    v[3] = 1.0f + (-((-a) * 1.5f));
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        float e = rt_expf((-v[c]) * 1.5f);
+        float tm = 1.0f + (-e);
+        v[c] = rt_powf(tm, 1.0f / 2.2f);
+    }
+    return px;
 }
 
 RT_HD void tonemap_pixel(const WaveView& W, int p)
@@ -487,7 +525,7 @@ RT_HD void path_init(const WaveView& W, int p, Emit& e)
     int x, y;
     pix_xy(W.src, p, x, y);
     PathReg P;
-    P.rng.a = (uint32_t)(31 + x * y * W.spp);
+    P.rng.a = (uint32_t)(31 + x * y * W.seed_spp);
     for (int i = 0; i < 10; i++) P.rng.next();
     P.fin = col(0.0f);
     P.sample = 0;
@@ -495,7 +533,24 @@ RT_HD void path_init(const WaveView& W, int p, Emit& e)
     e.mask = 0;
     e.heavy = false;
     e.active = start_sample(W, p, P, e);
-    if (!e.active) finish_pixel(W, p, P);
+    if (!e.active) finish_pixel<true>(W, p, P);
+    store_path(W, p, P, true);
+}
+
+// path_init for a progressive pass after the first: the pixel goes on from its paused state
+// with sample W.first (its camera ray is cast here: a pass never traces ahead across its end).
+RT_HD void path_resume(const WaveView& W, int p, Emit& e)
+{
+    const float4_ st = W.prog[fb_at(W, p)];
+    PathReg P;
+    P.rng.a = rt_asuint(st.w);
+    P.fin = colof(st);
+    P.sample = W.first;
+    P.last_end = -2;
+    e.mask = 0;
+    e.heavy = false;
+    e.active = start_sample(W, p, P, e);
+    if (!e.active) finish_pixel<true>(W, p, P);
     store_path(W, p, P, true);
 }
 
@@ -769,7 +824,7 @@ RT_HD void resolve(const WaveView& W, int p, PathReg& P, const ResolveRec& R, St
 // (next_camera), is consumed in the same step (shaded, or that sample ends too and
 // the next camera ray is cast), else its camera ray is cast. Fills `e` with the rays
 // for the next trace.
-template <class E>
+template <bool PROG, class E>
 RT_HD void path_step(const WaveView& W, int p, E& e, Stats* st)
 {
     e.mask = 0;
@@ -844,7 +899,7 @@ RT_HD void path_step(const WaveView& W, int p, E& e, Stats* st)
     if (do_shade) {
         shade(W, p, P, h, e, st);
     } else if (!e.active) {
-        finish_pixel(W, p, P);
+        finish_pixel<PROG>(W, p, P);
     }
     store_path(W, p, P, fin_changed);
 }

@@ -296,6 +296,64 @@ class RenderKernel:
                                               ctypes.c_void_p(stream) if stream else None), self.ctx,
               "rt_render_device")
 
+    # ---- progressive rendering (rt_progress_*, include/rt_hip.h)
+    def progress_begin(self, samples_total: int | None = None, row_offset: int = 0, row_stride: int = 1):
+        """Begin a frame of samples_total samples (default: render_samples) rendered in passes, over the
+        rows row_offset::row_stride of the bound Image, whose values are the base the frame adds to."""
+        self._sync_materials()
+        total = self.render_samples if samples_total is None else int(samples_total)
+        base = np.ascontiguousarray(self.frame_buffer.pixels[row_offset::row_stride], dtype=np.float32)
+        check(self.L, self.L.rt_progress_begin(self.ctx, self.width, self.height, total, self.max_bounces, ptr(base),
+                                               row_offset, row_stride), self.ctx, "rt_progress_begin")
+
+    def progress_advance(self, samples: int, stream: int | None = None):
+        """The next min(samples, remaining) samples of every pixel. Returns the samples done so far."""
+        check(self.L, self.L.rt_progress_advance(self.ctx, int(samples), ctypes.c_void_p(stream) if stream else None),
+              self.ctx, "rt_progress_advance")
+        return self.progress_info()["done"]
+
+    def progress_info(self) -> dict:
+        info = np.zeros(8, np.int32)
+        check(self.L, self.L.rt_progress_info(self.ctx, ptr(info)), self.ctx, "rt_progress_info")
+        keys = ("width", "height", "total", "done", "bounces", "row_offset", "row_stride", "rows_local")
+        return {k: int(v) for k, v in zip(keys, info)}
+
+    def progress_resolve(self, image: Image | None = None) -> Image:
+        """The image after the samples done so far into the shard's rows of `image` (default: the bound
+        Image). Before the last pass it is a preview: the mean of the first `done` samples of the
+        samples_total chain, not the frame a render of `done` samples gives."""
+        image = self.frame_buffer if image is None else image
+        i = self.progress_info()
+        out = np.empty((i["rows_local"], self.width, 4), np.float32)
+        check(self.L, self.L.rt_progress_resolve(self.ctx, ptr(out)), self.ctx, "rt_progress_resolve")
+        image.pixels[i["row_offset"]::i["row_stride"]] = out
+        return image
+
+    def progress_resolve_device(self, d_fb: int, stream: int | None = None):
+        check(self.L, self.L.rt_progress_resolve_device(self.ctx, ctypes.c_void_p(d_fb),
+                                                        ctypes.c_void_p(stream) if stream else None), self.ctx,
+              "rt_progress_resolve_device")
+
+    def progress_save(self) -> bytes:
+        """The checkpoint: header, base, state. It does not fingerprint the scene."""
+        n = int(self.L.rt_progress_save(self.ctx, None, 0))
+        if n < 0:
+            check(self.L, n, self.ctx, "rt_progress_save")
+        buf = ctypes.create_string_buffer(n)
+        got = int(self.L.rt_progress_save(self.ctx, buf, n))
+        if got != n:
+            check(self.L, got if got < 0 else RT_ERR_STATE, self.ctx, "rt_progress_save")
+        return buf.raw
+
+    def progress_load(self, data: bytes):
+        """Install a checkpoint of the same scene, env, camera and intersect mode at its `done`."""
+        self._sync_materials()
+        buf = ctypes.create_string_buffer(data, len(data))
+        check(self.L, self.L.rt_progress_load(self.ctx, buf, len(data)), self.ctx, "rt_progress_load")
+
+    def progress_end(self):
+        self.L.rt_progress_end(self.ctx)
+
     # ---- post stage (what replaces Utils::OIDN_denoise, utils.cpp:144-196)
     def camera_rays(self) -> np.ndarray:
         """rt_camera_rays: the feature pass's rays, [h, w, 6] = origin, direction (host only)."""

@@ -29,6 +29,8 @@ EXPORTS = [
     "rt_camera_rays", "rt_render_features", "rt_render_features_device", "rt_denoise_default_params", "rt_denoise",
     "rt_denoise_device",
     "rt_query", "rt_query_device", "rt_query_last_exact",
+    "rt_progress_begin", "rt_progress_advance", "rt_progress_resolve", "rt_progress_resolve_device",
+    "rt_progress_info", "rt_progress_save", "rt_progress_load", "rt_progress_end",
 ]
 
 # return codes (include/rt_hip.h)
@@ -98,6 +100,14 @@ _SIGS = {
     "rt_denoise_default_params": (None, [ctypes.POINTER(DenoiseParams)]),
     "rt_denoise": (I, [P, I, I, P, P, P, ctypes.POINTER(DenoiseParams), F, P]),
     "rt_denoise_device": (I, [P, I, I, P, P, P, ctypes.POINTER(DenoiseParams), F, P, P]),
+    "rt_progress_begin": (I, [P, I, I, I, I, P, I, I]),
+    "rt_progress_advance": (I, [P, I, P]),
+    "rt_progress_resolve": (I, [P, P]),
+    "rt_progress_resolve_device": (I, [P, P, P]),
+    "rt_progress_info": (I, [P, P]),
+    "rt_progress_save": (L, [P, P, L]),
+    "rt_progress_load": (I, [P, P, L]),
+    "rt_progress_end": (None, [P]),
     # product-only extras
     "rt_device_libm": (I, [I, I, P, P, P, I]),
     "rt_device_last_kernel_ms": (ctypes.c_double, [P]),

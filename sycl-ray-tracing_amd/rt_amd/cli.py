@@ -6,6 +6,12 @@ product library: ingest, RenderKernel.render(), the denoise stage at blend 1.0 /
 the dragon camera, main.cpp:110), --out=<directory> (default .) and --hostsim (the CPU
 build of the device code, for machines without a GPU). The filter runs once; the three
 images are blends of its output with the render (utils.cpp:184-186).
+
+Progressive rendering (RenderKernel.progress_*): --preview-every=K renders in passes of K samples
+and writes RT_preview_<done>.png after each (a preview is the mean of the first `done` samples of
+the --samples chain, not the frame --samples=<done> gives); --checkpoint=PATH saves the progression
+after each pass and resumes from PATH when it exists (same scene, sky, camera and size: the file
+does not fingerprint them). The four PNGs at the end are the same as without these flags.
 """
 from __future__ import annotations
 
@@ -20,16 +26,16 @@ import rt_amd
 
 def parse(argv):
     a = dict(obj="data/OBJs/cornell_pbr.obj", sky="data/Skyspheres/evening_road_01_puresky_2k.hdr", w=512, h=512,
-             samples=64, bounces=8, camera="dragon", out=".", hostsim=False)
+             samples=64, bounces=8, camera="dragon", out=".", hostsim=False, preview_every=0, checkpoint="")
     for s in argv:
         if s == "--hostsim":
             a["hostsim"] = True
-        elif s.startswith(("--sky=", "--camera=", "--out=")):
+        elif s.startswith(("--sky=", "--camera=", "--out=", "--checkpoint=")):
             k, v = s[2:].split("=", 1)
             a[k] = v
-        elif s.startswith(("--w=", "--h=", "--samples=", "--bounces=")):
+        elif s.startswith(("--w=", "--h=", "--samples=", "--bounces=", "--preview-every=")):
             k, v = s[2:].split("=", 1)
-            a[k] = int(v)
+            a[k.replace("-", "_")] = int(v)
         else:
             a["obj"] = s  # (assuming the OBJ file path, as main.cpp:57-59)
     return a
@@ -42,6 +48,33 @@ def blend(filtered: rt_amd.Image, image: rt_amd.Image, factor: float) -> rt_amd.
     out.pixels[..., :3] = f * filtered.pixels[..., :3] + (np.float32(1.0) - f) * image.pixels[..., :3]
     out.pixels[..., 3] = 1.0
     return out
+
+
+def render_progressive(rk: rt_amd.RenderKernel, fb: rt_amd.Image, a: dict):
+    """The frame in passes: previews and / or a checkpoint after each; fb ends as render() leaves it."""
+    step = a["preview_every"] if a["preview_every"] > 0 else a["samples"]
+    ck = a["checkpoint"]
+    if ck and os.path.exists(ck):
+        with open(ck, "rb") as f:
+            rk.progress_load(f.read())
+        print(f"Resuming {ck} at {rk.progress_info()['done']} samples")
+    else:
+        rk.progress_begin()
+    os.makedirs(a["out"], exist_ok=True)
+    preview = rt_amd.Image(a["w"], a["h"])
+    while True:
+        i = rk.progress_info()
+        if i["done"] >= i["total"]:
+            break
+        done = rk.progress_advance(step)
+        if ck:
+            with open(ck + ".tmp", "wb") as f:
+                f.write(rk.progress_save())
+            os.replace(ck + ".tmp", ck)
+        if a["preview_every"] > 0:
+            rt_amd.write_image_png(rk.progress_resolve(preview), os.path.join(a["out"], f"RT_preview_{done}.png"))
+    rk.progress_resolve(fb)
+    rk.progress_end()
 
 
 def main(argv=None) -> int:
@@ -57,7 +90,10 @@ def main(argv=None) -> int:
                              P.emissive_triangle_indices, P.material_indices, None, rt_amd.BVH(P.triangles), sky,
                              rt_amd.compute_env_map_cdf(sky), hostsim=a["hostsim"])
     rk.set_camera(rt_amd.Camera.preset(a["camera"]))
-    rk.render()
+    if a["preview_every"] > 0 or a["checkpoint"]:
+        render_progressive(rk, fb, a)
+    else:
+        rk.render()
     print(f"{int((time.perf_counter() - t0) * 1e3)}ms")
     with np.errstate(all="ignore"):
         filtered = rk.denoise(fb, 1.0)
