@@ -52,12 +52,17 @@ $(OBJ)/rt_query.o: $(SRC)/rt_query.hip $(HDRS)
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
+# the display stage (tone-map + 8-bit conversion, linear resolve) likewise
+$(OBJ)/rt_display.o: $(SRC)/rt_display.hip $(HDRS)
+	@mkdir -p $(OBJ)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
 # the kernel-free half of the backend: contexts, uploads, the drivers over run_wave, rt_build_id
 $(OBJ)/rt_backend.o: $(SRC)/rt_backend.hip $(HDRS) $(ALL_SRC)
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -DRT_BUILD_SRC='"$(SRC_HASH)"' -c $< -o $@
 
-$(LIB)/librt_hip.so: $(OBJ)/rt_render.o $(OBJ)/rt_backend.o $(OBJ)/rt_denoise.o $(OBJ)/rt_query.o $(OBJ)/rt_scene.host.o $(OBJ)/rt_imageio.host.o $(OBJ)/rt_capi_host.host.o
+$(LIB)/librt_hip.so: $(OBJ)/rt_render.o $(OBJ)/rt_backend.o $(OBJ)/rt_denoise.o $(OBJ)/rt_query.o $(OBJ)/rt_display.o $(OBJ)/rt_scene.host.o $(OBJ)/rt_imageio.host.o $(OBJ)/rt_capi_host.host.o
 	@mkdir -p $(LIB)
 	$(HIPCC) -shared --offload-arch=$(ARCH) -fPIC $^ -o $@
 
@@ -114,7 +119,8 @@ variant: $(OBJ)/rt_scene.host.o $(OBJ)/rt_imageio.host.o $(OBJ)/rt_capi_host.hos
 	$(HIPCC) $(HIPFLAGS) $(DEFS) -DRT_BUILD_SRC='"$(SRC_HASH)"' -DRT_BUILD_DEFS='"$(DEFS)"' -c $(SRC)/rt_backend.hip -o $(OBJ)/rt_backend_$(V).o
 	$(HIPCC) $(HIPFLAGS) $(DEFS) -c $(SRC)/rt_denoise.hip -o $(OBJ)/rt_denoise_$(V).o
 	$(HIPCC) $(HIPFLAGS) $(DEFS) -c $(SRC)/rt_query.hip -o $(OBJ)/rt_query_$(V).o
-	$(HIPCC) -shared --offload-arch=$(ARCH) -fPIC $(OBJ)/rt_render_$(V).o $(OBJ)/rt_backend_$(V).o $(OBJ)/rt_denoise_$(V).o $(OBJ)/rt_query_$(V).o $^ -o $(LIB)/librt_hip_$(V).so
+	$(HIPCC) $(HIPFLAGS) $(DEFS) -c $(SRC)/rt_display.hip -o $(OBJ)/rt_display_$(V).o
+	$(HIPCC) -shared --offload-arch=$(ARCH) -fPIC $(OBJ)/rt_render_$(V).o $(OBJ)/rt_backend_$(V).o $(OBJ)/rt_denoise_$(V).o $(OBJ)/rt_query_$(V).o $(OBJ)/rt_display_$(V).o $^ -o $(LIB)/librt_hip_$(V).so
 
 # the same for the hostsim build: make hostsim-variant V=name DEFS="-DRT_SLABS=0" ->
 # lib/librt_hostsim_name.so (RT_HOSTSIM_LIB=...; study probes such as tools/far_probe.py)
@@ -179,6 +185,21 @@ build/progress_shim_test: tests/native/progress_shim_test.cpp include/render_ker
 	  -L$(LIB) -lrt_hostsim -Wl,-rpath,'$$ORIGIN/../$(LIB)' -o $@
 
 build/progress_shim_test_hip: tests/native/progress_shim_test.cpp include/render_kernel_hip.h include/rt_hip.h $(LIB)/librt_hip.so
+	@mkdir -p build
+	$(CXX) -std=gnu++20 -O2 -fopenmp -Iinclude -I$(REFDIR)/include -I$(REFDIR)/rapidobj -I$(REFDIR) $< \
+	  $(REFOBJ)/bvh.o $(REFOBJ)/flattened_bvh.o $(REFOBJ)/triangle.o $(REFOBJ)/vec.o $(REFOBJ)/color.o \
+	  $(REFOBJ)/mat.o $(REFOBJ)/camera.o $(REFOBJ)/ray.o $(REFOBJ)/utils.o -Wl,--gc-sections \
+	  -L$(LIB) -lrt_hip -Wl,-rpath,'$$ORIGIN/../$(LIB)' -o $@
+
+# the drop-in's display(render_linear()) against its own render() (tests/test_display_shim.py), both links likewise
+build/display_shim_test: tests/native/display_shim_test.cpp include/render_kernel_hip.h include/rt_hip.h $(LIB)/librt_hostsim.so
+	@mkdir -p build
+	$(CXX) -std=gnu++20 -O2 -fopenmp -Iinclude -I$(REFDIR)/include -I$(REFDIR)/rapidobj -I$(REFDIR) $< \
+	  $(REFOBJ)/bvh.o $(REFOBJ)/flattened_bvh.o $(REFOBJ)/triangle.o $(REFOBJ)/vec.o $(REFOBJ)/color.o \
+	  $(REFOBJ)/mat.o $(REFOBJ)/camera.o $(REFOBJ)/ray.o $(REFOBJ)/utils.o -Wl,--gc-sections \
+	  -L$(LIB) -lrt_hostsim -Wl,-rpath,'$$ORIGIN/../$(LIB)' -o $@
+
+build/display_shim_test_hip: tests/native/display_shim_test.cpp include/render_kernel_hip.h include/rt_hip.h $(LIB)/librt_hip.so
 	@mkdir -p build
 	$(CXX) -std=gnu++20 -O2 -fopenmp -Iinclude -I$(REFDIR)/include -I$(REFDIR)/rapidobj -I$(REFDIR) $< \
 	  $(REFOBJ)/bvh.o $(REFOBJ)/flattened_bvh.o $(REFOBJ)/triangle.o $(REFOBJ)/vec.o $(REFOBJ)/color.o \

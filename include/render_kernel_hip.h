@@ -93,6 +93,40 @@ public:
         check(rt_render(m_ctx, m_width, m_height, m_render_samples, m_max_bounces, m_frame_buffer.data()));
     }
 
+    // render() without its tone-map (rt_render_linear): the Image& ends as entry.rgb +
+    // final_color / samples with the entry alpha, the reference's hdrColor (render_kernel.cpp:173).
+    // display() of it at the defaults is what render() would have left, bit for bit.
+    void render_linear()
+    {
+        std::lock_guard<std::mutex> lk(m_mu);
+        sync_materials();
+        check(rt_render_linear(m_ctx, m_width, m_height, m_render_samples, m_max_bounces, m_frame_buffer.data()));
+    }
+
+    // The exposure / gamma tone-map of render_kernel.cpp:171-180 on a linear frame of any size
+    // (rt_display): a new Image. The reference's literals are the defaults.
+    Image display(const Image& linear, float exposure = 1.5f, float gamma = 2.2f) const
+    {
+        std::lock_guard<std::mutex> lk(m_mu);
+        rt_display_params p;
+        rt_display_default_params(&p);
+        p.exposure = exposure;
+        p.gamma = gamma;
+        Image out(linear.width(), linear.height());
+        check(rt_display(m_ctx, linear.width(), linear.height(), linear.data(), &p, out.data(), nullptr));
+        return out;
+    }
+
+    // write_image_hdr (image_io.h:20, image_io.cpp:208-214) through rt_write_hdr: the rgb channels
+    // as a Radiance RGBE file. A member, so that it does not collide with the reference's own
+    // function when image_io.h is included too.
+    static bool write_image_hdr(const Image& image, const char* filename, const bool flipY = true)
+    {
+        if (image.width() * image.height() == 0) return false;
+        check(rt_write_hdr(filename, image.data(), image.width(), image.height(), flipY ? 1 : 0));
+        return true;
+    }
+
     // render() in passes of pass_samples samples (rt_progress_*): the Image& is the base the
     // frame adds to, and after each pass it holds the image so far and on_pass(image, done,
     // total) is called; returning false stops the progression there. After the last pass the

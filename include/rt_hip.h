@@ -53,6 +53,12 @@ typedef struct rt_denoise_params {
     float sigma_albedo;  /* ... albedo */
     float sigma_depth;   /* ... and relative depth (t_p - t_q) / max(t_p, t_q) */
 } rt_denoise_params;
+/* Parameters of rt_display (rt_display_default_params fills the defaults). */
+typedef struct rt_display_params {
+    float exposure;      /* finite; the reference's 1.5f (render_kernel.cpp:175) */
+    float gamma;         /* finite and > 0; the reference's 2.2f (render_kernel.cpp:178) */
+    int flip_y;          /* rows of the 8-bit output reversed, as write_image_png writes them */
+} rt_display_params;
 
 /* ---------------------------------------------------------------- context */
 int rt_create(int device, rt_context** out);
@@ -337,6 +343,55 @@ int rt_progress_info(const rt_context* ctx, int info[8]);
 long rt_progress_save(rt_context* ctx, void* buf, long capacity);
 int rt_progress_load(rt_context* ctx, const void* buf, long bytes);
 void rt_progress_end(rt_context* ctx);
+
+/* ------------------------------------------- linear radiance and the display stage
+ * The reference ends a pixel with hdrColor = entry + final_color / samples and then its
+ * exposure / gamma tone-map with the literals 1.5 and 2.2 (render_kernel.cpp:171-180).
+ * rt_render returns the tone-mapped frame; these calls return the linear one and apply the
+ * tone-map, with a caller's exposure and gamma, as a stage of its own.
+ *
+ * rt_render_linear / _device: rt_render / rt_render_device without the tone-map pass. On
+ *   return the buffer holds, per pixel, entry.rgb + final_color / (float)samples and the entry
+ *   alpha untouched. Same argument checks, row shards, multi-device support and
+ *   rt_last_kernel_ms conventions as their tone-mapped twins.
+ * rt_progress_resolve_linear / _device: base + state.rgb / (float)done, alpha = the base's:
+ *   rt_progress_resolve's division and sum, stopped before its tone-map. Changes no state;
+ *   RT_ERR_STATE without a progression or with done == 0.
+ * rt_display / _device: for every pixel of a w x h linear frame
+ *     rgb = powf(1 - expf(-x * exposure), 1 / gamma),  a = 1 - (-(a + 0)) * exposure
+ *   in the reference's operation order, so rt_display(rt_render_linear(fb)) at the defaults is
+ *   rt_render(fb), bit for bit. rgba_out (w*h*4 floats, frame order) may be the input (in
+ *   place). rgba8_out (w*h*4 bytes) is rt_image_to_rgba8 of that result, rows reversed when
+ *   params->flip_y; flip_y affects nothing else. Either output may be NULL, not both. params
+ *   NULL: the defaults (1.5, 2.2, 0). No scene has to be bound. RT_ERR_ARG: non-positive
+ *   sizes, an exposure that is not finite, a gamma that is not finite and > 0, both outputs
+ *   NULL, more than 2^27 - 1 pixels, rgba8_out overlapping the input or rgba_out, rgba_out
+ *   overlapping the input without being it. The device form takes device pointers and a
+ *   stream (NULL: default) and returns without waiting; d_linear and d_rgba_out must be 16-byte
+ *   aligned and d_rgba8_out 4-byte aligned (the kernel moves a pixel with one 16-byte access
+ *   and its four bytes with one 4-byte store; any hipMalloc pointer and any whole-pixel offset
+ *   into one is; RT_ERR_ARG otherwise), while the host form takes any alignment. A multi-device
+ *   context runs the stage on its root device and restores the caller's current device.
+ *   rt_last_kernel_ms reports the stage's time (the device form: -1, read
+ *   rt_device_last_kernel_ms after synchronizing).
+ * rt_write_hdr (host only): write_image_hdr (image_io.cpp:208-214): a Radiance RGBE file of
+ *   the rgb channels (alpha dropped), rows reversed when flip_y, that rt_read_hdr decodes.
+ *   Per pixel the exponent is frexp's of the largest channel and the mantissas are truncated
+ *   (each channel comes back within 2^(e - 8)); a largest channel below 1e-32 is four zero
+ *   bytes; negative and NaN channels are written as 0 and anything above the format's largest
+ *   value, 255 * 2^119, as that value. Flat (not run-length encoded) scanlines. RT_ERR_ARG for
+ *   a NULL path or image or a non-positive size, RT_ERR_IO if the path cannot be written. */
+void rt_display_default_params(rt_display_params* params);
+int rt_render_linear(rt_context* ctx, int width, int height, int samples, int max_bounces, float* fb_rgba);
+int rt_render_linear_device(rt_context* ctx, int width, int height, int samples, int max_bounces, void* d_fb,
+                            int row_offset, int row_stride, void* stream);
+int rt_progress_resolve_linear(rt_context* ctx, float* fb_rgba);
+int rt_progress_resolve_linear_device(rt_context* ctx, void* d_fb, void* stream);
+int rt_display(rt_context* ctx, int w, int h, const float* linear_rgba, const rt_display_params* params,
+               float* rgba_out, unsigned char* rgba8_out);
+int rt_display_device(rt_context* ctx, int w, int h, const void* d_linear, const rt_display_params* params,
+                      void* d_rgba_out, void* d_rgba8_out, void* stream);
+int rt_write_hdr(const char* path, const float* rgba, int width, int height, int flip_y);
 
 /* Counters of the last render when enabled (RT_STAT_* order, rt_device.h);
  * with n up to 2 * RT_STAT_COUNT the second block is the share of the

@@ -264,7 +264,7 @@ int finish_stats(rt_context* c, Backend* b, hipStream_t s)
 // thread per device: run_wave polls its lanes), and ncclGather brings the blocks back
 // for the un-permute. Pack and un-permute are strided 2-D copies on the root.
 int render_multi(rt_context* c, Group* g, int w, int h, int spp, int bounces, float4_* fb, int off, int stride,
-                 hipStream_t s)
+                 hipStream_t s, bool linear)
 {
     const int N = (int)g->dev.size();
     std::string err;
@@ -313,7 +313,7 @@ int render_multi(rt_context* c, Group* g, int w, int h, int spp, int bounces, fl
             HIPCHK(c, hipSetDevice(b->device));
             const rtk::PixSrc src{w, off + d * stride, N * stride, nullptr};
             float4_* dst = d == 0 ? stage : (float4_*)g->dev[d]->shard.p;
-            return run_wave(c, b, w, h, spp, bounces, src, rows_of(d) * w, dst, st[d]);
+            return run_wave(c, b, w, h, spp, bounces, src, rows_of(d) * w, dst, st[d], nullptr, linear);
         }))
         return r;
     HIPCHK(c, hipSetDevice(root->device));
@@ -355,7 +355,7 @@ int render_multi(rt_context* c, Group* g, int w, int h, int spp, int bounces, fl
 }  // namespace
 
 int rt_backend_render(rt_context* c, int w, int h, int spp, int bounces, float* host_fb, void* dev_fb, int row_offset,
-                      int row_stride, void* stream)
+                      int row_stride, void* stream, bool linear)
 {
     Group* g = grp(c);
     Backend* b = be(c);
@@ -371,11 +371,11 @@ int rt_backend_render(rt_context* c, int w, int h, int spp, int bounces, float* 
         HIPCHK(c, hipMemcpyAsync(fb, host_fb, npx * sizeof(float4_), hipMemcpyHostToDevice, s));
     }
     if (g->multi) {
-        if (int r = render_multi(c, g, w, h, spp, bounces, fb, row_offset, row_stride, s)) return r;
+        if (int r = render_multi(c, g, w, h, spp, bounces, fb, row_offset, row_stride, s, linear)) return r;
     } else {
         rtk::PixSrc src{w, row_offset, row_stride, nullptr};
         HIPCHK(c, hipEventRecord(b->ev0, s));
-        if (int r = run_wave(c, b, w, h, spp, bounces, src, (int)npx, fb, s)) return r;
+        if (int r = run_wave(c, b, w, h, spp, bounces, src, (int)npx, fb, s, nullptr, linear)) return r;
         HIPCHK(c, hipEventRecord(b->ev1, s));
     }
     if (host_fb) {
@@ -527,7 +527,8 @@ int rt_backend_render_pixels(rt_context* c, int w, int h, int spp, int bounces, 
 
 // ---- progressions (rt_progress_*): the base values and the paused state live in buffers of
 // their own on the context's device; a pass is run_wave with a WavePass (no k_tonemap), a
-// resolve is k_resolve over base and state. Single-device contexts (rt_capi_host.cpp).
+// resolve is k_resolve (linear: rt_display.hip's k_resolve_linear) over base and state.
+// Single-device contexts (rt_capi_host.cpp).
 namespace {
 // the passes (ev_done) and device resolves (ev_pg) still in flight have finished with the buffers
 int progress_quiesce(rt_context* c, Backend* b)
@@ -583,7 +584,7 @@ int rt_backend_progress_advance(rt_context* c, int first, int stop, void* stream
     return finish_stats(c, b, s);
 }
 
-int rt_backend_progress_resolve(rt_context* c, float* host_fb, void* dev_fb, void* stream)
+int rt_backend_progress_resolve(rt_context* c, float* host_fb, void* dev_fb, void* stream, bool linear)
 {
     Backend* b = be(c);
     const RtProgress& P = c->prog;
@@ -597,7 +598,10 @@ int rt_backend_progress_resolve(rt_context* c, float* host_fb, void* dev_fb, voi
         out = (float4_*)b->pg_out.p;
     }
     if (b->done_recorded) HIPCHK(c, hipStreamWaitEvent(s, b->ev_done, 0));  // (the last pass, on its own streams)
-    if (int r = rt_wave_resolve(c, (const float4_*)b->pg_base.p, (const float4_*)b->pg_state.p, out, n, P.done, s)) return r;
+    const float4_ *base = (const float4_*)b->pg_base.p, *state = (const float4_*)b->pg_state.p;
+    if (int r = linear ? rt_display_resolve_linear(c, base, state, out, n, P.done, s)
+                       : rt_wave_resolve(c, base, state, out, n, P.done, s))
+        return r;
     if (host_fb) {
         HIPCHK(c, hipMemcpyAsync(host_fb, out, (size_t)n * sizeof(float4_), hipMemcpyDeviceToHost, s));
         HIPCHK(c, hipStreamSynchronize(s));
@@ -644,6 +648,7 @@ int rt_backend_root(rt_context* c, RtRootDev* out)
     out->ev1 = b->ev1;
     out->post = &b->post;
     out->query = &b->query;
+    out->disp = &b->disp;
     return RT_OK;
 }
 

@@ -4,6 +4,7 @@
 //   rt_backend.hip  contexts, uploads, the multi-device / variant / pixel-list drivers
 //   rt_render.hip   the render kernels and the wavefront loop (run_wave)
 //   rt_denoise.hip  the post stage          rt_query.hip  the ray queries
+//   rt_display.hip  the display stage and the linear resolve
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -130,6 +131,7 @@ struct Backend {
     DevBuf xy;        // pixel list (rt_render_pixels)
     DevBuf fb;        // host-fb staging
     DevBuf pg_base, pg_state, pg_out;  // a progression (rt_progress_*): base values, paused state, host-resolve staging
+    DevBuf disp;      // rt_display with host pointers: the frame (in, float out in place), then the 8-bit output
     DevBuf shard;     // multi-device renders: the root's N blocks of rows_max rows (scatter source /
                       // gather target); device d >= 1: its block
     Pinned<int32_t> h_act[RT_MAX_LANES];  // per lane: live-slot counters (sharded) + 8 fallback counters
@@ -169,6 +171,7 @@ struct RtRootDev {
     hipEvent_t ev0, ev1;      // the events rt_last_kernel_ms / rt_device_last_kernel_ms read
     void** post;              // the post stage's state, created on first use; rt_post_free releases it
     void** query;             // the ray queries' workspace, likewise; rt_query_free releases it
+    DevBuf* disp;             // the display stage's staging buffer (freed with the Backend)
 };
 
 int rt_backend_root(rt_context* c, RtRootDev* out);  // rt_backend.hip
@@ -182,9 +185,14 @@ struct WavePass {
     float4_* state;
     int first, seed_spp;
 };
+// linear: an ordinary render whose k_tonemap launch is skipped (rt_render_linear): fb keeps
+// entry + final_color / spp.
 int run_wave(rt_context* c, Backend* b, int w, int h, int spp, int bounces, const rtk::PixSrc& src, int n, float4_* fb,
-             hipStream_t s, const WavePass* pass = nullptr);
+             hipStream_t s, const WavePass* pass = nullptr, bool linear = false);
 // rt_render.hip k_resolve: out[i] = the tone-mapped pixel of base[i] and state[i] after `done` samples
 int rt_wave_resolve(rt_context* c, const float4_* base, const float4_* state, float4_* out, int n, int done, hipStream_t s);
+// rt_display.hip k_resolve_linear: out[i] = base[i] + state[i].rgb / done, the base's alpha (not tone-mapped)
+int rt_display_resolve_linear(rt_context* c, const float4_* base, const float4_* state, float4_* out, int n, int done,
+                              hipStream_t s);
 size_t rt_wave_counter_bytes();
 size_t rt_wave_readback_bytes();

@@ -3,6 +3,7 @@
 // helpers. The compute half lives in rt_render.hip (gfx950).
 #include <algorithm>
 #include <cmath>
+#include <cstdint>
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
@@ -497,6 +498,23 @@ int rt_render_device(rt_context* c, int w, int h, int spp, int bounces, void* d_
     return rt_backend_render(c, w, h, spp, bounces, nullptr, d_fb, row_offset, row_stride, stream);
 }
 
+// rt_render / rt_render_device without the tone-map pass: the same checks, the same shards.
+int rt_render_linear(rt_context* c, int w, int h, int spp, int bounces, float* fb)
+{
+    if (int r = check_ready(c, w, h, spp, bounces)) return r;
+    if (!fb) return rt_fail(c, RT_ERR_ARG, "rt_render_linear: fb is NULL");
+    return rt_backend_render(c, w, h, spp, bounces, fb, nullptr, 0, 1, nullptr, true);
+}
+
+int rt_render_linear_device(rt_context* c, int w, int h, int spp, int bounces, void* d_fb, int row_offset,
+                            int row_stride, void* stream)
+{
+    if (int r = check_ready(c, w, h, spp, bounces)) return r;
+    if (!d_fb || row_stride <= 0 || row_offset < 0 || row_offset >= row_stride)
+        return rt_fail(c, RT_ERR_ARG, "rt_render_linear_device: bad shard");
+    return rt_backend_render(c, w, h, spp, bounces, nullptr, d_fb, row_offset, row_stride, stream, true);
+}
+
 int rt_render_variants(rt_context* c, int w, int h, int spp, int bounces, int n_var, const float* materials,
                        int n_mats, int row_offset, int row_stride, float* fb, void* const* d_fbs)
 {
@@ -692,6 +710,61 @@ int rt_denoise_device(rt_context* c, int w, int h, const void* in, const void* a
     return rt_backend_denoise(c, w, h, in, alb, nd, p, blend, out, true, stream);
 }
 
+// ---------------------------------------------------------- display stage
+// The reference's literals (render_kernel.cpp:175, :178).
+void rt_display_default_params(rt_display_params* p)
+{
+    if (!p) return;
+    p->exposure = 1.5f;
+    p->gamma = 2.2f;
+    p->flip_y = 0;
+}
+
+static int display_ready(rt_context* c, const char* fn, int w, int h, const void* in, const rt_display_params* params,
+                         const void* out, const void* out8, bool device, rt_display_params& p)
+{
+    const std::string f = fn;
+    if (!c) return rt_fail(nullptr, RT_ERR_ARG, f + ": ctx is NULL");
+    if (w <= 0 || h <= 0 || !in) return rt_fail(c, RT_ERR_ARG, f + ": bad buffers");
+    if ((double)w * (double)h > 134217727.0) return rt_fail(c, RT_ERR_ARG, f + ": too many pixels");
+    if (!out && !out8) return rt_fail(c, RT_ERR_ARG, f + ": rgba_out and rgba8_out are both NULL");
+    // (the float output may be the input, pixel for pixel; a pixel's bytes land at another pixel's place)
+    const size_t n = (size_t)w * h;
+    const char *i0 = (const char*)in, *b0 = (const char*)out8;
+    if (out8 && b0 < i0 + 16 * n && i0 < b0 + 4 * n) return rt_fail(c, RT_ERR_ARG, f + ": rgba8_out overlaps the input");
+    const char* o0 = (const char*)out;
+    if (out8 && out && b0 < o0 + 16 * n && o0 < b0 + 4 * n) return rt_fail(c, RT_ERR_ARG, f + ": rgba8_out overlaps rgba_out");
+    // (the float output is the input or apart from it: a partial overlap would read pixels already written)
+    if (out && o0 != i0 && o0 < i0 + 16 * n && i0 < o0 + 16 * n)
+        return rt_fail(c, RT_ERR_ARG, f + ": rgba_out overlaps the input without being it");
+    // (k_display moves a pixel with one 16-byte load / store and its bytes with one 4-byte store;
+    // the host form copies through buffers of its own and takes any alignment)
+    if (device && ((uintptr_t)in % 16 != 0 || (uintptr_t)out % 16 != 0 || (uintptr_t)out8 % 4 != 0))
+        return rt_fail(c, RT_ERR_ARG, f + ": d_linear and d_rgba_out must be 16-byte aligned, d_rgba8_out 4-byte aligned");
+    if (params) p = *params;
+    else rt_display_default_params(&p);
+    if (!std::isfinite(p.exposure)) return rt_fail(c, RT_ERR_ARG, f + ": the exposure is not finite");
+    if (!std::isfinite(p.gamma) || !(p.gamma > 0.0f)) return rt_fail(c, RT_ERR_ARG, f + ": the gamma is not finite and > 0");
+    return RT_OK;
+}
+
+int rt_display(rt_context* c, int w, int h, const float* linear, const rt_display_params* params, float* out,
+               unsigned char* out8)
+{
+    rt_display_params p;
+    if (int r = display_ready(c, "rt_display", w, h, linear, params, out, out8, false, p)) return r;
+    // (an IEEE division at run time: at 2.2f it is the float the literal 1.0f / 2.2f of tonemap_pixel is)
+    return rt_backend_display(c, w, h, linear, p.exposure, 1.0f / p.gamma, p.flip_y != 0, out, out8, false, nullptr);
+}
+
+int rt_display_device(rt_context* c, int w, int h, const void* d_linear, const rt_display_params* params, void* d_out,
+                      void* d_out8, void* stream)
+{
+    rt_display_params p;
+    if (int r = display_ready(c, "rt_display_device", w, h, d_linear, params, d_out, d_out8, true, p)) return r;
+    return rt_backend_display(c, w, h, d_linear, p.exposure, 1.0f / p.gamma, p.flip_y != 0, d_out, d_out8, true, stream);
+}
+
 int rt_set_intersect_mode(rt_context* c, int use_bvh)
 {
     if (!c) return RT_ERR_ARG;
@@ -764,12 +837,23 @@ int rt_progress_advance(rt_context* c, int samples, void* stream)
     return RT_OK;
 }
 
-static int progress_resolve(rt_context* c, const char* fn, float* host_fb, void* dev_fb, void* stream)
+static int progress_resolve(rt_context* c, const char* fn, float* host_fb, void* dev_fb, void* stream,
+                            bool linear = false)
 {
     if (int r = progress_active(c, fn)) return r;
     if (!host_fb && !dev_fb) return rt_fail(c, RT_ERR_ARG, std::string(fn) + ": the output is NULL");
     if (c->prog.done == 0) return rt_fail(c, RT_ERR_STATE, std::string(fn) + ": no sample done yet");
-    return rt_backend_progress_resolve(c, host_fb, dev_fb, stream);
+    return rt_backend_progress_resolve(c, host_fb, dev_fb, stream, linear);
+}
+
+int rt_progress_resolve_linear(rt_context* c, float* fb)
+{
+    return progress_resolve(c, "rt_progress_resolve_linear", fb, nullptr, nullptr, true);
+}
+
+int rt_progress_resolve_linear_device(rt_context* c, void* d_fb, void* stream)
+{
+    return progress_resolve(c, "rt_progress_resolve_linear_device", nullptr, d_fb, stream, true);
 }
 
 int rt_progress_resolve(rt_context* c, float* fb) { return progress_resolve(c, "rt_progress_resolve", fb, nullptr, nullptr); }
@@ -944,6 +1028,14 @@ int rt_image_to_rgba8(const float* rgba, long n_pixels, unsigned char* out)
 {
     if (n_pixels < 0 || (n_pixels > 0 && (!rgba || !out))) return rt_fail(nullptr, RT_ERR_ARG, "rt_image_to_rgba8: bad arguments");
     rt::rgba8(rgba, (size_t)n_pixels, out);
+    return RT_OK;
+}
+
+int rt_write_hdr(const char* path, const float* rgba, int width, int height, int flip_y)
+{
+    if (!path || width <= 0 || height <= 0 || !rgba) return rt_fail(nullptr, RT_ERR_ARG, "rt_write_hdr: bad arguments");
+    std::string err;
+    if (rt::write_hdr(path, rgba, width, height, flip_y != 0, err)) return rt_fail(nullptr, RT_ERR_IO, "rt_write_hdr: " + err);
     return RT_OK;
 }
 

@@ -118,8 +118,10 @@ struct rt_context {
 int rt_backend_create(rt_context* ctx);
 void rt_backend_destroy(rt_context* ctx);
 int rt_backend_upload(rt_context* ctx);
+// linear: the render stops before its tone-map pass (rt_render_linear: the framebuffer keeps
+// entry + final_color / samples); the flag travels with every shard of a multi-device render
 int rt_backend_render(rt_context* ctx, int w, int h, int spp, int bounces, float* host_fb, void* dev_fb, int row_offset,
-                      int row_stride, void* stream);
+                      int row_stride, void* stream, bool linear = false);
 // n_variants material tables (RtMat, n_mats each, back to back); variant v on device v mod N
 int rt_backend_render_variants(rt_context* ctx, int w, int h, int spp, int bounces, int n_variants,
                                const std::vector<RtMat>& tables, int n_mats, int row_offset, int row_stride,
@@ -134,6 +136,11 @@ int rt_backend_features(rt_context* ctx, int w, int h, void* albedo, void* norma
 // alb and nd both null: colour only. p is validated (rt_capi_host.cpp).
 int rt_backend_denoise(rt_context* ctx, int w, int h, const void* in, const void* alb, const void* nd,
                        const rt_denoise_params& p, float blend, void* out, bool device, void* stream);
+// The display stage (rt_display.h), on the root device like the post stage: in (w*h float4) ->
+// out (w*h float4, may be `in`, or null) and out8 (w*h RGBA bytes, rows reversed when flip, or
+// null). The arguments are validated and inv_gamma = 1.0f / gamma (rt_capi_host.cpp).
+int rt_backend_display(rt_context* ctx, int w, int h, const void* in, float exposure, float inv_gamma, bool flip,
+                       void* out, void* out8, bool device, void* stream);
 
 // The ray queries (rt_query.h): n > 0 rays[n][6] -> out (closest: int32[n][11], any: int32[n]);
 // all_exact: every query takes the exact walk. device = false: host buffers, synchronous;
@@ -147,10 +154,11 @@ long rt_backend_query_last_exact(rt_context* ctx);
 // begin: the backend's buffers for prog.npx() pixels; base / state: host float4 per pixel, or
 // null for (0, 0, 0, 1) / zeroes. advance: samples first .. stop - 1 of every pixel (device:
 // on `stream`, no wait). resolve: the image after prog.done samples into host_fb (waits) or
-// dev_fb (on `stream`). read: base and state back to the host (waits). end: frees the buffers.
+// dev_fb (on `stream`); linear: base + state / done, not tone-mapped. read: base and state back
+// to the host (waits). end: frees the buffers.
 int rt_backend_progress_begin(rt_context* ctx, const float* base, const float* state);
 int rt_backend_progress_advance(rt_context* ctx, int first, int stop, void* stream);
-int rt_backend_progress_resolve(rt_context* ctx, float* host_fb, void* dev_fb, void* stream);
+int rt_backend_progress_resolve(rt_context* ctx, float* host_fb, void* dev_fb, void* stream, bool linear = false);
 int rt_backend_progress_read(rt_context* ctx, float* base, float* state);
 void rt_backend_progress_end(rt_context* ctx);
 

@@ -16,6 +16,7 @@
 
 #include "rt_context.h"
 #include "rt_denoise.h"
+#include "rt_display.h"
 #include "rt_query.h"
 #include "rt_wave.h"
 
@@ -64,10 +65,11 @@ static void host_append(const rtk::WaveView& W, int32_t* act_count, int p, const
 }
 
 // prog: a progressive pass (rt_progress_advance): samples first .. spp - 1 of a frame of seed_spp
-// samples, every pixel paused into prog (indexed like fb); no tone-map.
+// samples, every pixel paused into prog (indexed like fb); no tone-map. linear: an ordinary
+// render that stops before its tone-map pass (rt_render_linear).
 static int run_wave_host(rt_context* c, int w, int h, int spp, int bounces, const rtk::PixSrc& src, int n,
                          float4_* fb, unsigned long long* stats_out, const RtMat* mats = nullptr,
-                         float4_* prog = nullptr, int first = 0, int seed_spp = 0)
+                         float4_* prog = nullptr, int first = 0, int seed_spp = 0, bool linear = false)
 {
     if (n <= 0) return RT_OK;
     rtk::WaveView W{};
@@ -262,7 +264,7 @@ static int run_wave_host(rt_context* c, int w, int h, int spp, int bounces, cons
             }
         }
     }
-    if (!prog) {
+    if (!prog && !linear) {
 #pragma omp parallel for schedule(static)
         for (int p = 0; p < n; p++) rtk::tonemap_pixel(W, p);
     }
@@ -276,13 +278,13 @@ static int run_wave_host(rt_context* c, int w, int h, int spp, int bounces, cons
 // off + d*stride + k*N*stride, and un-permuted (here with host copies instead of
 // ncclScatter / ncclGather).
 static int render_shard(rt_context* c, int w, int h, int spp, int bounces, int off, int stride, int rows,
-                        float4_* shard)
+                        float4_* shard, bool linear)
 {
     const int N = c->devices.empty() ? 1 : (int)c->devices.size();
     if (N == 1) {
         rtk::PixSrc src{w, off, stride, nullptr};
         std::fill(c->stats, c->stats + RT_STAT_COUNT, 0ull);
-        return run_wave_host(c, w, h, spp, bounces, src, rows * w, shard, c->stats);
+        return run_wave_host(c, w, h, spp, bounces, src, rows * w, shard, c->stats, nullptr, nullptr, 0, 0, linear);
     }
     // one host thread per "device", as render_multi (rt_for_devices: per-device error slots),
     // each with its share of the OpenMP threads (not a full team per device)
@@ -294,7 +296,9 @@ static int render_shard(rt_context* c, int w, int h, int spp, int bounces, int o
         std::vector<float4_> blk((size_t)rows_d * w);
         for (int k = 0; k < rows_d; k++) std::memcpy(&blk[(size_t)k * w], shard + (size_t)(d + k * N) * w, 16 * (size_t)w);
         rtk::PixSrc src{w, off + d * stride, N * stride, nullptr};
-        if (int e = run_wave_host(c, w, h, spp, bounces, src, rows_d * w, blk.data(), dst[d].data())) return e;
+        if (int e = run_wave_host(c, w, h, spp, bounces, src, rows_d * w, blk.data(), dst[d].data(), nullptr, nullptr, 0, 0,
+                                  linear))
+            return e;
         for (int k = 0; k < rows_d; k++) std::memcpy(shard + (size_t)(d + k * N) * w, &blk[(size_t)k * w], 16 * (size_t)w);
         return 0;
     });
@@ -307,7 +311,7 @@ static int render_shard(rt_context* c, int w, int h, int spp, int bounces, int o
 }
 
 int rt_backend_render(rt_context* c, int w, int h, int spp, int bounces, float* host_fb, void* dev_fb, int row_offset,
-                      int row_stride, void*)
+                      int row_stride, void*, bool linear)
 {
     // host_fb: the full frame (rt_render). dev_fb: in this build a host
     // pointer to a compacted row shard, row j = image row row_offset +
@@ -320,11 +324,11 @@ int rt_backend_render(rt_context* c, int w, int h, int spp, int bounces, float* 
         std::vector<float4_> shard((size_t)rows_local * w);
         for (int j = 0; j < rows_local; j++)
             std::memcpy(&shard[(size_t)j * w], host_fb + 4 * (size_t)(row_offset + j * row_stride) * w, 16 * (size_t)w);
-        r = render_shard(c, w, h, spp, bounces, row_offset, row_stride, rows_local, shard.data());
+        r = render_shard(c, w, h, spp, bounces, row_offset, row_stride, rows_local, shard.data(), linear);
         for (int j = 0; j < rows_local; j++)
             std::memcpy(host_fb + 4 * (size_t)(row_offset + j * row_stride) * w, &shard[(size_t)j * w], 16 * (size_t)w);
     } else {
-        r = render_shard(c, w, h, spp, bounces, row_offset, row_stride, rows_local, (float4_*)dev_fb);
+        r = render_shard(c, w, h, spp, bounces, row_offset, row_stride, rows_local, (float4_*)dev_fb, linear);
     }
     c->last_kernel_ms = (omp_get_wtime() - t0) * 1e3;
     return r;
@@ -393,13 +397,41 @@ int rt_backend_progress_advance(rt_context* c, int first, int stop, void*)
     return r;
 }
 
-int rt_backend_progress_resolve(rt_context* c, float* host_fb, void* dev_fb, void*)
+int rt_backend_progress_resolve(rt_context* c, float* host_fb, void* dev_fb, void*, bool linear)
 {
     const RtProgress& P = c->prog;
     float4_* out = host_fb ? (float4_*)host_fb : (float4_*)dev_fb;  // ("device" pointers are host pointers here)
     const long n = (long)P.npx();
+    if (linear) {
+#pragma omp parallel for schedule(static)
+        for (long i = 0; i < n; i++) out[i] = rtk::resolve_linear_pixel(P.base[i], P.state[i], P.done);
+        return RT_OK;
+    }
 #pragma omp parallel for schedule(static)
     for (long i = 0; i < n; i++) out[i] = rtk::resolve_pixel(P.base[i], P.state[i], P.done);
+    return RT_OK;
+}
+
+// The display stage on the host: the loop around rt_display.h's per-pixel functions that
+// k_display (rt_display.hip) runs one thread per pixel. "Device" pointers are host pointers in
+// this build; a caller's float buffer need not be aligned for float4_, so pixels move by memcpy.
+int rt_backend_display(rt_context* c, int w, int h, const void* in, float exposure, float inv_gamma, bool flip,
+                       void* out, void* out8, bool, void*)
+{
+    const double t0 = omp_get_wtime();
+#pragma omp parallel for schedule(static)
+    for (long i = 0; i < (long)w * h; i++) {
+        float4_ px;
+        std::memcpy(&px, (const char*)in + 16 * i, 16);
+        px = rtk::display_pixel(px, exposure, inv_gamma);
+        if (out) std::memcpy((char*)out + 16 * i, &px, 16);
+        if (out8) {
+            const long y = i / w, x = i - y * w;
+            const uint32_t word = rtk::pack_rgba8(px);
+            std::memcpy((char*)out8 + 4 * ((flip ? h - 1 - y : y) * w + x), &word, 4);
+        }
+    }
+    c->last_kernel_ms = (omp_get_wtime() - t0) * 1e3;
     return RT_OK;
 }
 

@@ -13,6 +13,11 @@
 //    flipY and PNG. stb_image_write's deflate is not reproduced: the file is
 //    a valid PNG with stored (uncompressed) deflate blocks whose decoded
 //    pixels equal the reference's.
+//  * write_hdr: write_image_hdr (image_io.cpp:208-214), i.e. a Radiance RGBE file of the
+//    rgb channels with stb_image_write's encoding rule (frexp of the largest channel,
+//    truncated mantissas, four zero bytes below 1e-32), written from the format's
+//    description; flat scanlines, which read_hdr and stb_image decode at any width.
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -20,6 +25,7 @@
 #include <string>
 #include <vector>
 
+#include "rt_display.h"
 #include "rt_fp.h"
 #include "rt_scene.h"
 
@@ -185,12 +191,56 @@ int read_hdr(const char* path, bool flip_y, int& width, int& height, std::vector
 // write_image_png's conversion loop (image_io.cpp:165-177).
 void rgba8(const float* rgba, size_t n_px, unsigned char* out)
 {
-    auto clamp = [](float x, float mn, float mx) {  // image_io.cpp:156-161
-        if (x < mn) return mn;
-        if (x > mx) return mx;
-        return x;
-    };
-    for (size_t i = 0; i < 4 * n_px; i++) out[i] = (unsigned char)rt_f2i(clamp(rgba[i] * 255, 0, 255));
+    // (rt_display.h to_u8: the conversion k_display runs per channel on the device)
+    for (size_t i = 0; i < 4 * n_px; i++) out[i] = rtk::to_u8(rgba[i]);
+}
+
+// One RGBE pixel: the shared exponent is frexp's of the largest channel, every mantissa is
+// channel * 2^(8 - e) truncated (no rounding, so the largest one is 128..255), the exponent
+// byte e + 128; a largest channel below 1e-32 (or NaN) gives four zero bytes.
+// What the format cannot hold is brought into range first: a negative or NaN channel is 0,
+// anything above the format's largest value, 255 * 2^119 (exponent byte 255), is that value
+// (the conversions below are then defined for every input).
+static void rgbe_of(const float* rgb, unsigned char* out)
+{
+    const float top = 0x1.fep126f;
+    float v[3];
+    for (int c = 0; c < 3; c++) v[c] = !(rgb[c] > 0.0f) ? 0.0f : rgb[c] > top ? top : rgb[c];
+    const float m = std::max(v[0], std::max(v[1], v[2]));
+    if (m < 1e-32f) {
+        out[0] = out[1] = out[2] = out[3] = 0;
+        return;
+    }
+    int e = 0;
+    const float scale = std::frexp(m, &e) * 256.0f / m;  // 2^(8 - e), exactly
+    for (int c = 0; c < 3; c++) out[c] = (unsigned char)(int)(v[c] * scale);
+    out[3] = (unsigned char)(e + 128);
+}
+
+int write_hdr(const char* path, const float* rgba, int w, int h, bool flip_y, std::string& err)
+{
+    if (w <= 0 || h <= 0) {
+        err = "empty image";
+        return -1;
+    }
+    char head[96];
+    const int hn = std::snprintf(head, sizeof head, "#?RADIANCE\nFORMAT=32-bit_rle_rgbe\n\n-Y %d +X %d\n", h, w);
+    std::vector<unsigned char> file(head, head + hn);
+    file.resize((size_t)hn + (size_t)w * h * 4);
+    unsigned char* px = file.data() + hn;
+    for (int y = 0; y < h; y++) {
+        const float* row = rgba + (size_t)(flip_y ? h - 1 - y : y) * w * 4;
+        for (int x = 0; x < w; x++) rgbe_of(row + 4 * (size_t)x, px + ((size_t)y * w + x) * 4);
+    }
+    FILE* f = std::fopen(path, "wb");
+    if (!f) {
+        err = std::string("cannot write ") + path;
+        return -1;
+    }
+    const bool ok = std::fwrite(file.data(), 1, file.size(), f) == file.size();
+    std::fclose(f);
+    if (!ok) err = "short write";
+    return ok ? 0 : -1;
 }
 
 namespace {

@@ -1610,6 +1610,7 @@ struct WaveRun {
     float4_* fb;
     hipStream_t s;
     const WavePass* pass;  // a progressive pass: samples pass->first .. spp - 1, paused into pass->state (else null)
+    bool linear;           // no tone-map pass after the last step (rt_render_linear)
     int dev_cus = 256;
     WavePlan P{};
     WaveLane L[RT_MAX_LANES];
@@ -2048,6 +2049,7 @@ int WaveRun::finish()
         if (fast_ran)
             HIPCHK(c, hipStreamWaitEvent(L[l].s, b->fev_done, 0));  // (and the fast lane's)
         if (pass) continue;  // (a progressive pass leaves the pixels paused: rt_progress_resolve tone-maps)
+        if (linear) continue;  // (rt_render_linear: the framebuffer keeps finish_pixel's sum)
         hipLaunchKernelGGL(k_tonemap, dim3((L[l].n + threads - 1) / threads), dim3(threads), 0, L[l].s, L[l].W);
         HIPCHK(c, hipGetLastError());
     }
@@ -2160,10 +2162,10 @@ int WaveRun::report()
 }  // namespace
 
 int run_wave(rt_context* c, Backend* b, int w, int h, int spp, int bounces, const rtk::PixSrc& src, int n, float4_* fb,
-             hipStream_t s, const WavePass* pass)
+             hipStream_t s, const WavePass* pass, bool linear)
 {
     if (n <= 0) return RT_OK;
-    WaveRun R{c, b, w, h, spp, bounces, src, n, fb, s, pass};
+    WaveRun R{c, b, w, h, spp, bounces, src, n, fb, s, pass, linear};
     if (int r = R.begin()) return r;
     if (int r = R.poll()) return r;
     if (int r = R.finish()) return r;

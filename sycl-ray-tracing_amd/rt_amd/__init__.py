@@ -25,13 +25,13 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _capi
-from ._capi import DenoiseParams  # noqa: F401
+from ._capi import DenoiseParams, DisplayParams  # noqa: F401
 from ._capi import (RT_ERR_ARG, RT_ERR_HIP, RT_ERR_IO, RT_ERR_NODEV, RT_ERR_STATE, RT_OK,  # noqa: F401
                     RtError, check, lib, ptr)
 
 __all__ = ["Camera", "Image", "ParsedOBJ", "parse_obj", "compute_env_map_cdf", "luminance_of_pixels", "BVH",
            "RenderKernel", "RtError", "octree_dump", "make_materials", "read_image_float", "write_image_png",
-           "image_to_rgba8", "DenoiseParams", "denoise_default_params"]
+           "image_to_rgba8", "DenoiseParams", "denoise_default_params", "DisplayParams", "write_image_hdr"]
 
 
 # ------------------------------------------------------------------ camera
@@ -123,6 +123,17 @@ def write_image_png(image: Image, filename: str, flipY: bool = True) -> bool:
         return False
     check(lib(), lib().rt_write_png(filename.encode(), ptr(image.pixels), image.width, image.height, int(flipY)), None,
           f"write_image_png({filename})")
+    return True
+
+
+def write_image_hdr(image: Image, filename: str, flipY: bool = True) -> bool:
+    """write_image_hdr (image_io.cpp:208-214): the rgb channels as a Radiance RGBE file that
+    read_image_float decodes (rt_write_hdr); False for an empty image."""
+    if image.width * image.height == 0:
+        return False
+    px = np.ascontiguousarray(image.pixels, dtype=np.float32)
+    check(lib(), lib().rt_write_hdr(filename.encode(), ptr(px), image.width, image.height, int(flipY)), None,
+          f"write_image_hdr({filename})")
     return True
 
 
@@ -296,6 +307,54 @@ class RenderKernel:
                                               ctypes.c_void_p(stream) if stream else None), self.ctx,
               "rt_render_device")
 
+    # ---- linear radiance and the display stage (rt_render_linear, rt_display; include/rt_hip.h)
+    def render_linear(self):
+        """render() without the tone-map: the bound Image ends as entry.rgb + final_color / samples, alpha
+        untouched (the reference's hdrColor). display() of it at the defaults is render()'s frame."""
+        self._sync_materials()
+        fb = self.frame_buffer.pixels
+        assert fb.flags.c_contiguous and fb.dtype == np.float32 and fb.shape == (self.height, self.width, 4)
+        check(self.L, self.L.rt_render_linear(self.ctx, self.width, self.height, self.render_samples,
+                                              self.max_bounces, ptr(fb)), self.ctx, "rt_render_linear")
+
+    def render_linear_device(self, d_fb: int, row_offset: int = 0, row_stride: int = 1, stream: int | None = None):
+        """rt_render_linear_device: the same into a device buffer; no host copies, no wait."""
+        self._sync_materials()
+        check(self.L, self.L.rt_render_linear_device(self.ctx, self.width, self.height, self.render_samples,
+                                                     self.max_bounces, ctypes.c_void_p(d_fb), row_offset, row_stride,
+                                                     ctypes.c_void_p(stream) if stream else None), self.ctx,
+              "rt_render_linear_device")
+
+    def display(self, linear: Image | None = None, exposure: float = 1.5, gamma: float = 2.2, flip_y: bool = False,
+                want=("rgba",)):
+        """rt_display: the exposure / gamma tone-map of a linear frame (default: the bound Image, after
+        render_linear()). want names the outputs: "rgba" a new Image, "rgba8" a [h, w, 4] uint8 array of
+        write_image_png's conversion (rows reversed when flip_y). One name: that output; both: the pair,
+        in want's order."""
+        linear = self.frame_buffer if linear is None else linear
+        want = (want,) if isinstance(want, str) else tuple(want)
+        if not want or any(k not in ("rgba", "rgba8") for k in want):
+            raise ValueError(f"display: want {want!r} must name 'rgba', 'rgba8' or both")
+        src = np.ascontiguousarray(linear.pixels, dtype=np.float32)
+        h, w = src.shape[:2]
+        out = Image(w, h) if "rgba" in want else None
+        out8 = np.empty((h, w, 4), np.uint8) if "rgba8" in want else None
+        p = DisplayParams(float(exposure), float(gamma), int(bool(flip_y)))
+        check(self.L, self.L.rt_display(self.ctx, w, h, ptr(src), ctypes.byref(p), None if out is None else ptr(out.pixels),
+                                        ptr(out8)), self.ctx, "rt_display")
+        got = tuple(out if k == "rgba" else out8 for k in want)
+        return got[0] if len(got) == 1 else got
+
+    def display_device(self, d_linear: int, d_rgba: int | None = None, d_rgba8: int | None = None, exposure: float = 1.5,
+                       gamma: float = 2.2, flip_y: bool = False, stream: int | None = None, width=None, height=None):
+        """rt_display_device: device buffers (w*h*4 floats in and out, w*h*4 bytes), no wait; d_rgba may be
+        d_linear (in place)."""
+        p = DisplayParams(float(exposure), float(gamma), int(bool(flip_y)))
+        vp = lambda a: ctypes.c_void_p(a) if a else None  # noqa: E731
+        check(self.L, self.L.rt_display_device(self.ctx, int(width or self.width), int(height or self.height),
+                                               vp(d_linear), ctypes.byref(p), vp(d_rgba), vp(d_rgba8), vp(stream)),
+              self.ctx, "rt_display_device")
+
     # ---- progressive rendering (rt_progress_*, include/rt_hip.h)
     def progress_begin(self, samples_total: int | None = None, row_offset: int = 0, row_stride: int = 1):
         """Begin a frame of samples_total samples (default: render_samples) rendered in passes, over the
@@ -333,6 +392,23 @@ class RenderKernel:
         check(self.L, self.L.rt_progress_resolve_device(self.ctx, ctypes.c_void_p(d_fb),
                                                         ctypes.c_void_p(stream) if stream else None), self.ctx,
               "rt_progress_resolve_device")
+
+    def progress_resolve_linear(self, image: Image | None = None) -> Image:
+        """progress_resolve without the tone-map: base + state.rgb / done, the base's alpha, into the
+        shard's rows of `image` (default: the bound Image)."""
+        image = self.frame_buffer if image is None else image
+        i = self.progress_info()
+        out = np.empty((i["rows_local"], self.width, 4), np.float32)
+        check(self.L, self.L.rt_progress_resolve_linear(self.ctx, ptr(out)), self.ctx, "rt_progress_resolve_linear")
+        image.pixels[i["row_offset"]::i["row_stride"]] = out
+        return image
+
+    def progress_resolve_linear_device(self, d_fb: int, stream: int | None = None):
+        """rt_progress_resolve_linear_device: the same into a device buffer (rows_local*w*4 floats) on
+        `stream`; no wait."""
+        check(self.L, self.L.rt_progress_resolve_linear_device(self.ctx, ctypes.c_void_p(d_fb),
+                                                               ctypes.c_void_p(stream) if stream else None), self.ctx,
+              "rt_progress_resolve_linear_device")
 
     def progress_save(self) -> bytes:
         """The checkpoint: header, base, state. It does not fingerprint the scene."""

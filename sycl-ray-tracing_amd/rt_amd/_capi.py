@@ -31,6 +31,8 @@ EXPORTS = [
     "rt_query", "rt_query_device", "rt_query_last_exact",
     "rt_progress_begin", "rt_progress_advance", "rt_progress_resolve", "rt_progress_resolve_device",
     "rt_progress_info", "rt_progress_save", "rt_progress_load", "rt_progress_end",
+    "rt_display_default_params", "rt_render_linear", "rt_render_linear_device", "rt_progress_resolve_linear",
+    "rt_progress_resolve_linear_device", "rt_display", "rt_display_device", "rt_write_hdr",
 ]
 
 # return codes (include/rt_hip.h)
@@ -46,6 +48,11 @@ class DenoiseParams(ctypes.Structure):
     """struct rt_denoise_params (include/rt_hip.h)."""
     _fields_ = [("passes", ctypes.c_int), ("sigma_color", F), ("sigma_normal", F), ("sigma_albedo", F),
                 ("sigma_depth", F)]
+
+
+class DisplayParams(ctypes.Structure):
+    """struct rt_display_params (include/rt_hip.h)."""
+    _fields_ = [("exposure", F), ("gamma", F), ("flip_y", ctypes.c_int)]
 
 
 _SIGS = {
@@ -108,6 +115,14 @@ _SIGS = {
     "rt_progress_save": (L, [P, P, L]),
     "rt_progress_load": (I, [P, P, L]),
     "rt_progress_end": (None, [P]),
+    "rt_display_default_params": (None, [ctypes.POINTER(DisplayParams)]),
+    "rt_render_linear": (I, [P, I, I, I, I, P]),
+    "rt_render_linear_device": (I, [P, I, I, I, I, P, I, I, P]),
+    "rt_progress_resolve_linear": (I, [P, P]),
+    "rt_progress_resolve_linear_device": (I, [P, P, P]),
+    "rt_display": (I, [P, I, I, P, ctypes.POINTER(DisplayParams), P, P]),
+    "rt_display_device": (I, [P, I, I, P, ctypes.POINTER(DisplayParams), P, P, P]),
+    "rt_write_hdr": (I, [ctypes.c_char_p, P, I, I, I]),
     # product-only extras
     "rt_device_libm": (I, [I, I, P, P, P, I]),
     "rt_device_last_kernel_ms": (ctypes.c_double, [P]),
@@ -117,6 +132,7 @@ _SIGS = {
     "rt_device_exact_handovers": (I, [P, P, I]),
     "rt_device_queries": (I, [P, I, P, I, I, P, P, P]),
     "rt_device_denoise_pass_ms": (I, [P, I, P, I]),
+    "rt_device_display_kernel_ms": (I, [P, I, I, P, P, P, P, I, P]),
     # hostsim-only extra
     "rt_hostsim_heap_order": (I, [P, I, P, P]),
     "rt_hostsim_fast_queries": (I, [P, P, I, P, P]),

@@ -12,6 +12,14 @@ and writes RT_preview_<done>.png after each (a preview is the mean of the first 
 the --samples chain, not the frame --samples=<done> gives); --checkpoint=PATH saves the progression
 after each pass and resumes from PATH when it exists (same scene, sky, camera and size: the file
 does not fingerprint them). The four PNGs at the end are the same as without these flags.
+
+Display stage (RenderKernel.render_linear / display): --exposure=E and --gamma=G tone-map with the
+caller's parameters instead of the reference's 1.5 and 2.2, and --hdr-out=PATH writes the linear
+radiance as a Radiance .hdr file. With any of the three the frame is rendered linear (or resolved
+linear at the end of a progression), written to --hdr-out, then displayed; the denoise stage and the
+four PNGs follow as before, and previews are displayed with the same parameters. --exposure=1.5
+--gamma=2.2 writes the bytes of a run without flags; with none of the three the run takes the
+tone-mapped render's path unchanged.
 """
 from __future__ import annotations
 
@@ -26,13 +34,17 @@ import rt_amd
 
 def parse(argv):
     a = dict(obj="data/OBJs/cornell_pbr.obj", sky="data/Skyspheres/evening_road_01_puresky_2k.hdr", w=512, h=512,
-             samples=64, bounces=8, camera="dragon", out=".", hostsim=False, preview_every=0, checkpoint="")
+             samples=64, bounces=8, camera="dragon", out=".", hostsim=False, preview_every=0, checkpoint="",
+             exposure=None, gamma=None, hdr_out="")
     for s in argv:
         if s == "--hostsim":
             a["hostsim"] = True
-        elif s.startswith(("--sky=", "--camera=", "--out=", "--checkpoint=")):
+        elif s.startswith(("--sky=", "--camera=", "--out=", "--checkpoint=", "--hdr-out=")):
             k, v = s[2:].split("=", 1)
-            a[k] = v
+            a[k.replace("-", "_")] = v
+        elif s.startswith(("--exposure=", "--gamma=")):
+            k, v = s[2:].split("=", 1)
+            a[k] = float(v)
         elif s.startswith(("--w=", "--h=", "--samples=", "--bounces=", "--preview-every=")):
             k, v = s[2:].split("=", 1)
             a[k.replace("-", "_")] = int(v)
@@ -50,8 +62,18 @@ def blend(filtered: rt_amd.Image, image: rt_amd.Image, factor: float) -> rt_amd.
     return out
 
 
+def display_stage(a: dict) -> bool:
+    """Any of --exposure, --gamma, --hdr-out: the run goes through render_linear and display."""
+    return a["exposure"] is not None or a["gamma"] is not None or bool(a["hdr_out"])
+
+
+def display_args(a: dict) -> dict:
+    return dict(exposure=1.5 if a["exposure"] is None else a["exposure"], gamma=2.2 if a["gamma"] is None else a["gamma"])
+
+
 def render_progressive(rk: rt_amd.RenderKernel, fb: rt_amd.Image, a: dict):
-    """The frame in passes: previews and / or a checkpoint after each; fb ends as render() leaves it."""
+    """The frame in passes: previews and / or a checkpoint after each; fb ends as render() leaves it
+    (display stage: as render_linear() leaves it)."""
     step = a["preview_every"] if a["preview_every"] > 0 else a["samples"]
     ck = a["checkpoint"]
     if ck and os.path.exists(ck):
@@ -72,8 +94,15 @@ def render_progressive(rk: rt_amd.RenderKernel, fb: rt_amd.Image, a: dict):
                 f.write(rk.progress_save())
             os.replace(ck + ".tmp", ck)
         if a["preview_every"] > 0:
-            rt_amd.write_image_png(rk.progress_resolve(preview), os.path.join(a["out"], f"RT_preview_{done}.png"))
-    rk.progress_resolve(fb)
+            if display_stage(a):
+                shown = rk.display(rk.progress_resolve_linear(preview), **display_args(a))
+            else:
+                shown = rk.progress_resolve(preview)
+            rt_amd.write_image_png(shown, os.path.join(a["out"], f"RT_preview_{done}.png"))
+    if display_stage(a):
+        rk.progress_resolve_linear(fb)
+    else:
+        rk.progress_resolve(fb)
     rk.progress_end()
 
 
@@ -92,8 +121,14 @@ def main(argv=None) -> int:
     rk.set_camera(rt_amd.Camera.preset(a["camera"]))
     if a["preview_every"] > 0 or a["checkpoint"]:
         render_progressive(rk, fb, a)
+    elif display_stage(a):
+        rk.render_linear()
     else:
         rk.render()
+    if display_stage(a):  # fb holds the linear radiance: the .hdr file, then the displayed frame
+        if a["hdr_out"]:
+            rt_amd.write_image_hdr(fb, a["hdr_out"])
+        fb = rk.display(fb, **display_args(a))
     print(f"{int((time.perf_counter() - t0) * 1e3)}ms")
     with np.errstate(all="ignore"):
         filtered = rk.denoise(fb, 1.0)
