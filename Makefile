@@ -37,23 +37,15 @@ $(OBJ)/rt_hostsim.o: $(SRC)/rt_hostsim.cpp $(HDRS) $(ALL_SRC)
 	@mkdir -p $(OBJ)
 	$(CXX) $(CXXFLAGS) -fopenmp -DRT_BUILD_SRC='"$(SRC_HASH)"' -c $< -o $@
 
-$(OBJ)/rt_render.o: $(SRC)/rt_render.hip $(HDRS)
-	@mkdir -p $(OBJ)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-# the post stage (feature pass + filter) in a translation unit of its own: the render
-# kernels' code generation does not depend on it
-$(OBJ)/rt_denoise.o: $(SRC)/rt_denoise.hip $(HDRS)
-	@mkdir -p $(OBJ)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-# the ray queries (rt_query / rt_query_device) likewise
-$(OBJ)/rt_query.o: $(SRC)/rt_query.hip $(HDRS)
-	@mkdir -p $(OBJ)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-# the display stage (tone-map + 8-bit conversion, linear resolve) likewise
-$(OBJ)/rt_display.o: $(SRC)/rt_display.hip $(HDRS)
+# The gfx950 units. rt_render holds the render kernels and nothing else; each of the others is a
+# translation unit of its own so that the render kernels' code generation does not depend on it:
+#   rt_wave_run  the host loop that launches them (run_wave; no device code)
+#   rt_probe     the kernels no render calls (rt_intersect's walk, query benchmark, self-tests)
+#   rt_denoise   the post stage (feature pass + filter)
+#   rt_query     the ray queries (rt_query / rt_query_device)
+#   rt_display   the display stage (tone-map + 8-bit conversion, linear resolve)
+HIP_UNITS := rt_render rt_wave_run rt_probe rt_denoise rt_query rt_display
+$(HIP_UNITS:%=$(OBJ)/%.o): $(OBJ)/%.o: $(SRC)/%.hip $(HDRS)
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
@@ -62,7 +54,7 @@ $(OBJ)/rt_backend.o: $(SRC)/rt_backend.hip $(HDRS) $(ALL_SRC)
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -DRT_BUILD_SRC='"$(SRC_HASH)"' -c $< -o $@
 
-$(LIB)/librt_hip.so: $(OBJ)/rt_render.o $(OBJ)/rt_backend.o $(OBJ)/rt_denoise.o $(OBJ)/rt_query.o $(OBJ)/rt_display.o $(OBJ)/rt_scene.host.o $(OBJ)/rt_imageio.host.o $(OBJ)/rt_capi_host.host.o
+$(LIB)/librt_hip.so: $(HIP_UNITS:%=$(OBJ)/%.o) $(OBJ)/rt_backend.o $(OBJ)/rt_scene.host.o $(OBJ)/rt_imageio.host.o $(OBJ)/rt_capi_host.host.o
 	@mkdir -p $(LIB)
 	$(HIPCC) -shared --offload-arch=$(ARCH) -fPIC $^ -o $@
 
@@ -115,12 +107,9 @@ clean:
 # experiment builds: make variant V=name DEFS="-DRT_TAIL_OCC=2" -> lib/librt_hip_name.so (RT_HIP_LIB=...)
 variant: $(OBJ)/rt_scene.host.o $(OBJ)/rt_imageio.host.o $(OBJ)/rt_capi_host.host.o
 	@mkdir -p $(LIB)
-	$(HIPCC) $(HIPFLAGS) $(DEFS) -c $(SRC)/rt_render.hip -o $(OBJ)/rt_render_$(V).o
+	for u in $(HIP_UNITS); do $(HIPCC) $(HIPFLAGS) $(DEFS) -c $(SRC)/$$u.hip -o $(OBJ)/$${u}_$(V).o || exit 1; done
 	$(HIPCC) $(HIPFLAGS) $(DEFS) -DRT_BUILD_SRC='"$(SRC_HASH)"' -DRT_BUILD_DEFS='"$(DEFS)"' -c $(SRC)/rt_backend.hip -o $(OBJ)/rt_backend_$(V).o
-	$(HIPCC) $(HIPFLAGS) $(DEFS) -c $(SRC)/rt_denoise.hip -o $(OBJ)/rt_denoise_$(V).o
-	$(HIPCC) $(HIPFLAGS) $(DEFS) -c $(SRC)/rt_query.hip -o $(OBJ)/rt_query_$(V).o
-	$(HIPCC) $(HIPFLAGS) $(DEFS) -c $(SRC)/rt_display.hip -o $(OBJ)/rt_display_$(V).o
-	$(HIPCC) -shared --offload-arch=$(ARCH) -fPIC $(OBJ)/rt_render_$(V).o $(OBJ)/rt_backend_$(V).o $(OBJ)/rt_denoise_$(V).o $(OBJ)/rt_query_$(V).o $(OBJ)/rt_display_$(V).o $^ -o $(LIB)/librt_hip_$(V).so
+	$(HIPCC) -shared --offload-arch=$(ARCH) -fPIC $(HIP_UNITS:%=$(OBJ)/%_$(V).o) $(OBJ)/rt_backend_$(V).o $^ -o $(LIB)/librt_hip_$(V).so
 
 # the same for the hostsim build: make hostsim-variant V=name DEFS="-DRT_SLABS=0" ->
 # lib/librt_hostsim_name.so (RT_HOSTSIM_LIB=...; study probes such as tools/far_probe.py)
@@ -133,77 +122,27 @@ hostsim-variant: $(OBJ)/rt_imageio.host.o
 
 # C++ drop-in check (container only): include/render_kernel_hip.h against the
 # reference's headers and objects (oracle/_ref, `make ref`), linked to the hostsim
-# build of the C ABI. tests/test_shim.py runs it.
+# build of the C ABI (build/X_test), and to the product library (build/X_test_hip: built here,
+# run on the GPU box, which has no reference tree; the binary carries what it needs).
+#   shim_test           render()                         tests/test_shim.py
+#   denoise_shim_test   denoise() against rt_render_features + rt_denoise   tests/test_denoise_shim.py
+#   query_shim_test     query_closest / query_any against rt_intersect      tests/test_query_shim.py
+#   progress_shim_test  render_progressive against render()                 tests/test_progress_shim.py
+#   display_shim_test   display(render_linear()) against render()           tests/test_display_shim.py
 REFDIR ?= /root/reference
 REFOBJ := oracle/_ref/objO2
-build/shim_test: tests/native/shim_test.cpp include/render_kernel_hip.h include/rt_hip.h $(LIB)/librt_hostsim.so
+REFOBJS := $(REFOBJ)/bvh.o $(REFOBJ)/flattened_bvh.o $(REFOBJ)/triangle.o $(REFOBJ)/vec.o $(REFOBJ)/color.o \
+  $(REFOBJ)/mat.o $(REFOBJ)/camera.o $(REFOBJ)/ray.o $(REFOBJ)/utils.o
+build/%_test: tests/native/%_test.cpp include/render_kernel_hip.h include/rt_hip.h $(LIB)/librt_hostsim.so
 	@mkdir -p build
 	$(CXX) -std=gnu++20 -O2 -fopenmp -Iinclude -I$(REFDIR)/include -I$(REFDIR)/rapidobj -I$(REFDIR) $< \
-	  $(REFOBJ)/bvh.o $(REFOBJ)/flattened_bvh.o $(REFOBJ)/triangle.o $(REFOBJ)/vec.o $(REFOBJ)/color.o \
-	  $(REFOBJ)/mat.o $(REFOBJ)/camera.o $(REFOBJ)/ray.o $(REFOBJ)/utils.o -Wl,--gc-sections \
+	  $(REFOBJS) -Wl,--gc-sections \
 	  -L$(LIB) -lrt_hostsim -Wl,-rpath,'$$ORIGIN/../$(LIB)' -o $@
 
-# the drop-in's denoise() against the C ABI's rt_render_features + rt_denoise (tests/test_denoise_shim.py)
-build/denoise_shim_test: tests/native/denoise_shim_test.cpp include/render_kernel_hip.h include/rt_hip.h $(LIB)/librt_hostsim.so
+build/%_test_hip: tests/native/%_test.cpp include/render_kernel_hip.h include/rt_hip.h $(LIB)/librt_hip.so
 	@mkdir -p build
 	$(CXX) -std=gnu++20 -O2 -fopenmp -Iinclude -I$(REFDIR)/include -I$(REFDIR)/rapidobj -I$(REFDIR) $< \
-	  $(REFOBJ)/bvh.o $(REFOBJ)/flattened_bvh.o $(REFOBJ)/triangle.o $(REFOBJ)/vec.o $(REFOBJ)/color.o \
-	  $(REFOBJ)/mat.o $(REFOBJ)/camera.o $(REFOBJ)/ray.o $(REFOBJ)/utils.o -Wl,--gc-sections \
-	  -L$(LIB) -lrt_hostsim -Wl,-rpath,'$$ORIGIN/../$(LIB)' -o $@
-
-# the same drop-in linked to the product library (gfx950): built here, run on the GPU box by
-# tests/test_shim.py's gpu test (the box has no /root/reference; the binary carries what it needs)
-build/shim_test_hip: tests/native/shim_test.cpp include/render_kernel_hip.h include/rt_hip.h $(LIB)/librt_hip.so
-	@mkdir -p build
-	$(CXX) -std=gnu++20 -O2 -fopenmp -Iinclude -I$(REFDIR)/include -I$(REFDIR)/rapidobj -I$(REFDIR) $< \
-	  $(REFOBJ)/bvh.o $(REFOBJ)/flattened_bvh.o $(REFOBJ)/triangle.o $(REFOBJ)/vec.o $(REFOBJ)/color.o \
-	  $(REFOBJ)/mat.o $(REFOBJ)/camera.o $(REFOBJ)/ray.o $(REFOBJ)/utils.o -Wl,--gc-sections \
-	  -L$(LIB) -lrt_hip -Wl,-rpath,'$$ORIGIN/../$(LIB)' -o $@
-
-# the drop-in's query_closest / query_any against rt_intersect (tests/test_query_shim.py): linked to the
-# hostsim build, and (run on the GPU box) to the product library
-build/query_shim_test: tests/native/query_shim_test.cpp include/render_kernel_hip.h include/rt_hip.h $(LIB)/librt_hostsim.so
-	@mkdir -p build
-	$(CXX) -std=gnu++20 -O2 -fopenmp -Iinclude -I$(REFDIR)/include -I$(REFDIR)/rapidobj -I$(REFDIR) $< \
-	  $(REFOBJ)/bvh.o $(REFOBJ)/flattened_bvh.o $(REFOBJ)/triangle.o $(REFOBJ)/vec.o $(REFOBJ)/color.o \
-	  $(REFOBJ)/mat.o $(REFOBJ)/camera.o $(REFOBJ)/ray.o $(REFOBJ)/utils.o -Wl,--gc-sections \
-	  -L$(LIB) -lrt_hostsim -Wl,-rpath,'$$ORIGIN/../$(LIB)' -o $@
-
-build/query_shim_test_hip: tests/native/query_shim_test.cpp include/render_kernel_hip.h include/rt_hip.h $(LIB)/librt_hip.so
-	@mkdir -p build
-	$(CXX) -std=gnu++20 -O2 -fopenmp -Iinclude -I$(REFDIR)/include -I$(REFDIR)/rapidobj -I$(REFDIR) $< \
-	  $(REFOBJ)/bvh.o $(REFOBJ)/flattened_bvh.o $(REFOBJ)/triangle.o $(REFOBJ)/vec.o $(REFOBJ)/color.o \
-	  $(REFOBJ)/mat.o $(REFOBJ)/camera.o $(REFOBJ)/ray.o $(REFOBJ)/utils.o -Wl,--gc-sections \
-	  -L$(LIB) -lrt_hip -Wl,-rpath,'$$ORIGIN/../$(LIB)' -o $@
-
-# the drop-in's render_progressive against its own render() (tests/test_progress_shim.py), both links likewise
-build/progress_shim_test: tests/native/progress_shim_test.cpp include/render_kernel_hip.h include/rt_hip.h $(LIB)/librt_hostsim.so
-	@mkdir -p build
-	$(CXX) -std=gnu++20 -O2 -fopenmp -Iinclude -I$(REFDIR)/include -I$(REFDIR)/rapidobj -I$(REFDIR) $< \
-	  $(REFOBJ)/bvh.o $(REFOBJ)/flattened_bvh.o $(REFOBJ)/triangle.o $(REFOBJ)/vec.o $(REFOBJ)/color.o \
-	  $(REFOBJ)/mat.o $(REFOBJ)/camera.o $(REFOBJ)/ray.o $(REFOBJ)/utils.o -Wl,--gc-sections \
-	  -L$(LIB) -lrt_hostsim -Wl,-rpath,'$$ORIGIN/../$(LIB)' -o $@
-
-build/progress_shim_test_hip: tests/native/progress_shim_test.cpp include/render_kernel_hip.h include/rt_hip.h $(LIB)/librt_hip.so
-	@mkdir -p build
-	$(CXX) -std=gnu++20 -O2 -fopenmp -Iinclude -I$(REFDIR)/include -I$(REFDIR)/rapidobj -I$(REFDIR) $< \
-	  $(REFOBJ)/bvh.o $(REFOBJ)/flattened_bvh.o $(REFOBJ)/triangle.o $(REFOBJ)/vec.o $(REFOBJ)/color.o \
-	  $(REFOBJ)/mat.o $(REFOBJ)/camera.o $(REFOBJ)/ray.o $(REFOBJ)/utils.o -Wl,--gc-sections \
-	  -L$(LIB) -lrt_hip -Wl,-rpath,'$$ORIGIN/../$(LIB)' -o $@
-
-# the drop-in's display(render_linear()) against its own render() (tests/test_display_shim.py), both links likewise
-build/display_shim_test: tests/native/display_shim_test.cpp include/render_kernel_hip.h include/rt_hip.h $(LIB)/librt_hostsim.so
-	@mkdir -p build
-	$(CXX) -std=gnu++20 -O2 -fopenmp -Iinclude -I$(REFDIR)/include -I$(REFDIR)/rapidobj -I$(REFDIR) $< \
-	  $(REFOBJ)/bvh.o $(REFOBJ)/flattened_bvh.o $(REFOBJ)/triangle.o $(REFOBJ)/vec.o $(REFOBJ)/color.o \
-	  $(REFOBJ)/mat.o $(REFOBJ)/camera.o $(REFOBJ)/ray.o $(REFOBJ)/utils.o -Wl,--gc-sections \
-	  -L$(LIB) -lrt_hostsim -Wl,-rpath,'$$ORIGIN/../$(LIB)' -o $@
-
-build/display_shim_test_hip: tests/native/display_shim_test.cpp include/render_kernel_hip.h include/rt_hip.h $(LIB)/librt_hip.so
-	@mkdir -p build
-	$(CXX) -std=gnu++20 -O2 -fopenmp -Iinclude -I$(REFDIR)/include -I$(REFDIR)/rapidobj -I$(REFDIR) $< \
-	  $(REFOBJ)/bvh.o $(REFOBJ)/flattened_bvh.o $(REFOBJ)/triangle.o $(REFOBJ)/vec.o $(REFOBJ)/color.o \
-	  $(REFOBJ)/mat.o $(REFOBJ)/camera.o $(REFOBJ)/ray.o $(REFOBJ)/utils.o -Wl,--gc-sections \
+	  $(REFOBJS) -Wl,--gc-sections \
 	  -L$(LIB) -lrt_hip -Wl,-rpath,'$$ORIGIN/../$(LIB)' -o $@
 
 # Host sanitizers: the hostsim build of the render path + the CPU oracle +

@@ -1,6 +1,6 @@
 // rt_backend.hip — the kernel-free half of the gfx950 backend: contexts and their devices
 // (create / destroy / upload, RCCL loading), the multi-device, variant and pixel-list
-// drivers over rt_render.hip's run_wave, and the rt_device_* accessors.
+// drivers over rt_wave_run.hip's run_wave, and the rt_device_* accessors.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>

@@ -2,7 +2,9 @@
 // check, the owners of device resources (freed by their destructors), the per-device
 // Backend, and the hooks between the units:
 //   rt_backend.hip  contexts, uploads, the multi-device / variant / pixel-list drivers
-//   rt_render.hip   the render kernels and the wavefront loop (run_wave)
+//   rt_render.hip   the render kernels and their launch helpers (rt_wave_kernels.h)
+//   rt_wave_run.hip the wavefront loop (run_wave) over them; rt_wave_layout.h: the counters both index
+//   rt_probe.hip    rt_intersect's kernel and the test / measurement kernels no render launches
 //   rt_denoise.hip  the post stage          rt_query.hip  the ray queries
 //   rt_display.hip  the display stage and the linear resolve
 #pragma once
@@ -177,7 +179,7 @@ struct RtRootDev {
 int rt_backend_root(rt_context* c, RtRootDev* out);  // rt_backend.hip
 Backend* rt_backend_dev0(rt_context* c);             // rt_backend.hip: the root device's Backend
 
-// rt_render.hip: the wavefront loop for n slots of `src` into fb (device, n float4) on b's
+// rt_wave_run.hip: the wavefront loop for n slots of `src` into fb (device, n float4) on b's
 // device (current), and the sizes of a lane's counters and of its pinned readback block.
 // A progressive pass (rt_progress_advance): samples first .. spp - 1 of every pixel of a frame
 // of seed_spp samples, each pixel paused into state (n float4, indexed like fb; fb unused).
@@ -189,7 +191,7 @@ struct WavePass {
 // entry + final_color / spp.
 int run_wave(rt_context* c, Backend* b, int w, int h, int spp, int bounces, const rtk::PixSrc& src, int n, float4_* fb,
              hipStream_t s, const WavePass* pass = nullptr, bool linear = false);
-// rt_render.hip k_resolve: out[i] = the tone-mapped pixel of base[i] and state[i] after `done` samples
+// rt_wave_run.hip (rt_render.hip k_resolve): out[i] = the tone-mapped pixel of base[i] and state[i] after `done` samples
 int rt_wave_resolve(rt_context* c, const float4_* base, const float4_* state, float4_* out, int n, int done, hipStream_t s);
 // rt_display.hip k_resolve_linear: out[i] = base[i] + state[i].rgb / done, the base's alpha (not tone-mapped)
 int rt_display_resolve_linear(rt_context* c, const float4_* base, const float4_* state, float4_* out, int n, int done,

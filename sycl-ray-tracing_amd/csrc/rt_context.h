@@ -14,7 +14,7 @@
 #include "rt_device.h"
 #include "rt_scene.h"
 
-// Schedule of the wavefront loop (rt_render.hip run_wave). The product runs the defaults
+// Schedule of the wavefront loop (rt_wave_run.hip run_wave). The product runs the defaults
 // (-1: the backend's own choice); rt_test_schedule (tests and measurement tools only,
 // include/rt_hip.h) overrides them per context. No parameter changes a pixel: the GPU
 // schedule tests render with each and compare the bits. Nothing here is read from the

@@ -248,7 +248,7 @@ int rt_backend_denoise(rt_context* c, int w, int h, const void* in, const void* 
     return RT_OK;
 }
 
-// MEASUREMENT HOOK, like rt_device_libm / rt_device_queries of rt_render.hip: exported by the
+// MEASUREMENT HOOK, like rt_device_libm / rt_device_queries of rt_probe.hip: exported by the
 // gfx950 library only, not part of include/rt_hip.h, never called by the product paths.
 // Per-pass GPU time of the filter (tools/denoise_bench.py): enable 1 / 0 turns the events
 // around each pass of the later rt_denoise calls on / off, -1 leaves it; with out_ms, the

@@ -54,7 +54,7 @@ struct OmpShare {
     ~OmpShare() { omp_set_num_threads(all); }
 };
 
-// The product's wavefront loop (rt_render.hip run_wave) on the host:
+// The product's wavefront loop (rt_wave_run.hip run_wave) on the host:
 // same stage functions, same queues; appends are plain atomics.
 template <class E>
 static void host_append(const rtk::WaveView& W, int32_t* act_count, int p, const E& e)
@@ -335,7 +335,7 @@ int rt_backend_render(rt_context* c, int w, int h, int spp, int bounces, float* 
 }
 
 // The material sweep as replicas: variant v on "device" v mod N (one host thread each,
-// rt_for_devices), every device walking its variants in order (rt_render.hip's driver).
+// rt_for_devices), every device walking its variants in order (rt_backend.hip's driver).
 int rt_backend_render_variants(rt_context* c, int w, int h, int spp, int bounces, int n_var,
                                const std::vector<RtMat>& tabs, int n_mats, int off, int stride, float* host_fb,
                                void* const* d_fbs)

@@ -1,4 +1,4 @@
-// rt_plan.h — what a wavefront render (rt_render.hip run_wave) decides before its first
+// rt_plan.h — what a wavefront render (rt_wave_run.hip run_wave) decides before its first
 // launch: the lane count, the tail and fast-lane figures and each lane's share of the
 // launch. Host only and free of HIP calls, so tests/native/plan_check.cpp runs it as it is.
 #pragma once
@@ -13,7 +13,7 @@
 #define RT_FAST_MAX_SPP 4096  // ... in renders of at most this many samples per pixel
 #define RT_LANES4_MAX 1572864  // auto lanes: 4 at most this many slots per launch, else 3
 
-// The kernels' build-time knobs the plan depends on (rt_render.hip fills them from its macros).
+// The kernels' build-time knobs the plan depends on (rt_wave_run.hip fills them from rt_wave_layout.h's macros).
 struct WaveKnobs {
     int trace_occ, tail_occ;  // RT_TRACE_OCC, RT_TAIL_OCC
     int heavy_calls;          // RT_HEAVY_CALLS

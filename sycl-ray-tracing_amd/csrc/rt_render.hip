@@ -1,9 +1,9 @@
-// rt_render.hip — gfx950 backend of librt_hip.so: device buffers, the
-// wavefront render kernels and their launches.
+// rt_render.hip — the wavefront render kernels of librt_hip.so (gfx950) and their launch
+// helpers (rt_wave_kernels.h), nothing else: this unit changes only when a render kernel
+// does. The host loop that launches them is rt_wave_run.hip; the counters and queue
+// segments both sides index are rt_wave_layout.h; the kernels no render calls are rt_probe.hip.
 //
-// A render (run_wave) is a loop of iterations over the in-flight path slots
-// (one slot per pixel of the launch), split into up to 3 independent lanes on
-// their own streams:
+// One iteration of a lane (rt_wave_run.hip run_wave) over its in-flight path slots:
 //   k_trace  every closest-hit and occlusion query of the iteration, walked
 //            by quads of lanes over the search BVH with octree verification
 //            (rt_quad.h), as a per-wave stream with quad refill; queries it
@@ -15,135 +15,20 @@
 //            per-kind queues (64-way sharded, wave-aggregated atomics)
 //   k_tail   once few paths are left: all of them in one launch, each wave
 //            stepping its own paths and tracing their rays with its quads
-// Queue sizes live in device memory; the host only launches and, every 8
-// iterations, reads the live-slot count.
+// k_init / k_resume start a lane's paths, k_tonemap / k_resolve write its pixels, k_hist and
+// k_hand select and move the fast lane's paths, k_tail_fast steps them.
 #include <hip/hip_runtime.h>
-
-#include <cstdio>
-#include <string>
-#include <vector>
-#include <algorithm>
-
-#include <chrono>
-#include <thread>
 
 #include "rt_backend_hip.h"
 #include "rt_wave.h"
+#include "rt_wave_kernels.h"
 #include "rt_quad.h"
 #include "rt_row.h"
 #include "rt_octet.h"
 
 namespace {
 
-#ifndef RT_STEP_OCC
-#define RT_STEP_OCC 3  // k_step waves per SIMD
-#endif
-#ifndef RT_STEP_FILL
-// k_step: blocks per CU at most, one grid-fill at its occupancy (one slot per thread below
-// that; above, each wave strides over 64-slot chunks). cfg2 over 4 A/B rounds on 2 boxes:
-// 8 / 4 / 3 / 2 -> 128.8-129.3 / 128.5-128.9 / 128.0-128.4 / 127.3-128.4 ms
-// (profiles/r06_step_fill_ab.json)
-#define RT_STEP_FILL RT_STEP_OCC
-#endif
-#ifndef RT_TAIL_ROWS
-#define RT_TAIL_ROWS 1  // k_tail walks with rows (rt_row.h)
-#endif
-
-// counters[] layout (int32). Iteration i (p = i & 1) runs k_trace(i) then
-// k_step(i); every set is zeroed by a launch between its last reader and its
-// next writer, so no reset launch is needed:
-//   Q[p]      queue sizes     filled by k_step(i-1) / k_init, read by k_trace(i); k_trace(i) zeroes Q[p^1]
-//   ACT[p]    live count      filled by k_step(i-1) / k_init, read by k_step(i);  k_trace(i) zeroes ACT[p^1]
-//   FB[p]     fallback lists  filled by k_trace(i) (queries the quad walk could not settle), walked
-//                             exactly by k_step(i); k_step(i) zeroes FB[p^1] for k_trace(i + 1)
-//   PARK[p]   parked walks    filled by k_step(i), resumed by k_step(i + 1); k_trace(i) zeroes PARK[p]
-//   DONE[p]   finished walks  slots, filled by k_step(i); k_trace(i + 1) releases them (r_park -= 1)
-//                             and k_step(i + 1) zeroes DONE[p]. The release waits for a kernel
-//                             boundary so the walk's results are visible before the path steps.
-//   TK        exact-walk work tickets of k_step(i); k_trace(i) zeroes them
-//
-// Q and ACT are sharded: the appends of a 64-item input chunk go to one of
-// RT_QSHARDS shards (append_emit), each a segment of W.seg_cap entries with
-// its own counter on its own 128-B line. One counter per queue took every
-// wave's atomic: ~630 us per 2 M appends on 6 counters against ~25 us
-// sharded 64 ways (tools/micro/atomics.hip on the MI355X).
-enum {
-    C_FBC0 = 0,
-    C_FBC1,
-    C_FBA0,
-    C_FBA1,
-    C_PARKC0,
-    C_PARKC1,
-    C_PARKA0,
-    C_PARKA1,
-    C_TK_EXACT_C,
-    C_TK_EXACT_A,
-    C_TK_TAIL,       // k_tail: next live-list entry to take
-    C_DONE0,
-    C_DONE1,
-    C_SHARDED = 64,  // sharded counters from here (qc_at / ac_at)
-};
-#define RT_QSHARDS 64
-#define RT_HSHARDS 8   // heavy-class shards per kind (input shard sh -> heavy shard sh % 8)
-#define RT_CSTRIDE 32  // ints from one sharded counter to the next (one 128-B line each)
-#define C_HEAVY (C_SHARDED + (2 * rtk::RK_COUNT + 2) * RT_QSHARDS * RT_CSTRIDE)
-#define C_COUNT (C_HEAVY + 2 * rtk::RK_COUNT * RT_HSHARDS * RT_CSTRIDE)
-#define C_ZERO (C_SHARDED - 1)  // never written: the count of a padding segment
-__host__ __device__ __forceinline__ int qc_at(int par, int kind, int shard)
-{
-    return C_SHARDED + ((par * rtk::RK_COUNT + kind) * RT_QSHARDS + shard) * RT_CSTRIDE;
-}
-__host__ __device__ __forceinline__ int ac_at(int par, int shard)
-{
-    return C_SHARDED + ((2 * rtk::RK_COUNT + par) * RT_QSHARDS + shard) * RT_CSTRIDE;
-}
-__host__ __device__ __forceinline__ int hc_at(int par, int kind, int shard)
-{
-    return C_HEAVY + ((par * rtk::RK_COUNT + kind) * RT_HSHARDS + shard) * RT_CSTRIDE;
-}
-
-// Queue segments in k_trace's stream order. Each role's heavy class comes first, so the
-// walks predicted long (their path's previous query of the kind took >= W.heavy_calls
-// trips) start at the head of every wave's stream instead of setting its drain:
-//   [closest kinds' heavy shards][closest kinds' shards][occlusion kinds' heavy][occlusion kinds']
-// then zero-count padding to a multiple of 64 (shard_prefix).
-#define RT_NCK 4  // closest kinds: CONT, LSH, BL, CAM
-#define RT_SEG_CH (RT_NCK * RT_HSHARDS)
-#define RT_SEG_AH (RT_SEG_CH + RT_NCK * RT_QSHARDS)
-#define RT_SEG_A (RT_SEG_AH + (rtk::RK_COUNT - RT_NCK) * RT_HSHARDS)
-#define RT_SEG_END (RT_SEG_A + (rtk::RK_COUNT - RT_NCK) * RT_QSHARDS)
-#define RT_NSEG ((RT_SEG_END + 63) / 64 * 64)
-struct SegId {
-    int kind, shard;
-    bool heavy;
-};
-__host__ __device__ __forceinline__ SegId seg_id(int j)
-{
-    SegId s;
-    if (j < RT_SEG_CH) {
-        s.heavy = true, s.kind = j / RT_HSHARDS, s.shard = j % RT_HSHARDS;
-    } else if (j < RT_SEG_AH) {
-        s.heavy = false, s.kind = (j - RT_SEG_CH) / RT_QSHARDS, s.shard = (j - RT_SEG_CH) % RT_QSHARDS;
-    } else if (j < RT_SEG_A) {
-        s.heavy = true, s.kind = RT_NCK + (j - RT_SEG_AH) / RT_HSHARDS, s.shard = (j - RT_SEG_AH) % RT_HSHARDS;
-    } else {
-        s.heavy = false, s.kind = RT_NCK + (j - RT_SEG_A) / RT_QSHARDS, s.shard = (j - RT_SEG_A) % RT_QSHARDS;
-    }
-    return s;
-}
-__host__ __device__ __forceinline__ int seg_counter(int par, int j)
-{
-    if (j >= RT_SEG_END) return C_ZERO;
-    const SegId s = seg_id(j);
-    return s.heavy ? hc_at(par, s.kind, s.shard) : qc_at(par, s.kind, s.shard);
-}
-
-
 // ------------------------------------------------------------ wave helpers
-#ifndef RT_DEBUG_FB
-#define RT_DEBUG_FB 0  // study builds: count k_trace's exact-walk hand-overs and the octet walks'
-                       // parks of the timed renders, printed on stderr after each run_wave
-#endif
 #if RT_DEBUG_FB
 __device__ unsigned long long rt_dbg_fb[8];  // k_trace closest fallbacks, octet parks, occlusion fallbacks, overflows, ties, chain fails, from rows, -
 #define RT_DBG(i) atomicAdd(&rt_dbg_fb[i], 1ull)
@@ -286,32 +171,16 @@ __device__ __forceinline__ void shard_prefix(const int32_t* cnt, int m, AT at, i
     __syncthreads();
 }
 
-// Segment j of a prefix table pre[0..m] holding global index g (pre[j] <= g < pre[j+1]).
-__device__ __forceinline__ int shard_find(const int* pre, int m, int g)
-{
-    int lo = 0, hi = m - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (pre[mid] <= g)
-            lo = mid;
-        else
-            hi = mid - 1;
-    }
-    return lo;
-}
-
-// The same search with M (a compile-time table size) as an 8-way search: each round reads 7
+// Segment j of a prefix table pre[0..M] holding global index g (pre[j] <= g < pre[j+1]), M a
+// compile-time table size, as an 8-way search: each round reads 7
 // entries at once (independent LDS reads, one round trip) and advances by the count at or below
 // g (the table is non-decreasing), so 448 entries take 3 dependent round trips instead of 9 and
 // 64 take 2 instead of 6. k_trace's refill (on ~4 of 5 wave trips, the whole wave waiting) and
-// every k_step / k_tail chunk start search these tables.
-#ifndef RT_FIND8
-#define RT_FIND8 1
-#endif
+// every k_step / k_tail chunk start search these tables. (Against the binary search it
+// replaced: cfg2 127.5 -> 125.3 ms, profiles/r06_refill_prefetch_ab.json.)
 template <int M>
 __device__ __forceinline__ int shard_find8(const int* pre, int g)
 {
-#if RT_FIND8
     constexpr int TOP = M > 512 ? 512 : M > 64 ? 64 : M > 8 ? 8 : 1;
     static_assert(M <= 4096, "three or four 8-way rounds");
     int lo = 0;
@@ -326,9 +195,6 @@ __device__ __forceinline__ int shard_find8(const int* pre, int g)
         lo += step * c;
     }
     return lo;
-#else
-    return shard_find(pre, M, g);
-#endif
 }
 
 // Where stream position g's queue record lives (segment table pre[0..RT_NSEG]) and its kind.
@@ -343,22 +209,12 @@ __device__ __forceinline__ const rtk::RayRec* queue_item_ptr(const rtk::WaveView
     return qk + qbase(s.heavy, s.shard, W.seg_cap) + (g - pre[j]);
 }
 
-// Queue item of stream position g (segment table pre[0..RT_NSEG], k_trace): the ray and its kind.
-__device__ __forceinline__ rtk::RayRec queue_item_at(const rtk::WaveView& W, const int* pre, int g, int& kind)
-{
-    // (the queue base by selects: W.q[kind] with a lane-varying kind would be a load; heavy
-    // shard h: after the kind's RT_QSHARDS segments, RT_QSHARDS / RT_HSHARDS seg_caps each)
-    return *queue_item_ptr(W, pre, g, kind);
-}
-
-// k_trace's look-ahead (RT_TRACE_PREFETCH): right after a refill, the wave's next 16 stream
+// k_trace's look-ahead (against reading each record from the queue at its refill: cfg2 -1.1 %,
+// the 8-way shard -2.4 %, profiles/r06_refill_prefetch_ab.json): right after a refill, the wave's next 16 stream
 // positions are copied into its LDS buffer by direct-to-LDS loads (lane 2i + h: half h of
 // record i, 16 B; the hardware puts lane L's 16 B at buf + 16 L), their kinds alongside; the next
 // refill takes its records from there (a refill needs at most 16 positions, all from the
 // cursor on, which the buffer starts at), so the refill no longer waits on the queue's memory.
-#ifndef RT_TRACE_PREFETCH
-#define RT_TRACE_PREFETCH 1
-#endif
 struct QPrefetch {
     float4_* buf;  // the wave's 64 x 16 B (records 0..15 in the first 512 B)
     int* kind;     // the wave's 16 kinds (-1: past the end of the stream)
@@ -440,55 +296,12 @@ __global__ __launch_bounds__(256) void k_tonemap(rtk::WaveView W)
 //    query whose answer needs the exact walk (or whose stack would overflow)
 //    goes to the fallback list for the next launch, and its slot's r_park
 //    count keeps k_step off the path until the walk has finished.
-#ifndef RT_STEP_EMIT_LDS
-#define RT_STEP_EMIT_LDS 1  // k_step's and k_tail's emitted rays wait in LDS (rt_wave.h EmitLds), not in VGPRs
-#endif
 #define RT_LDS_WORDS 16         // LDS words per lane of k_trace (16 KB per block of 256)
-#define RT_LDS_CAP_FAST 16      // search-BVH stack: node + key in LDS ...
-#define RT_SPILL_FAST RT_FAST_SPILL  // ... then in the lane's global spill area
-#define RT_LDS_CAP_CLOSEST 8    // exact walks: key + record (windows are powers of two)
-#define RT_LDS_CAP_ANY 16
 #define RT_REFILL 16
-#define RT_QSTACK 32            // quad walks (rt_quad.h): stack entries per quad (item + key, 64 quads per block)
-#define RT_RSTACK 64            // row walks (rt_row.h): stack entries per row (item + key, 16 rows per block)
 #ifndef RT_TRACE_REFILL
 #define RT_TRACE_REFILL 4       // k_trace: idle quads of a wave that trigger a refill from its query stream
                                 // (r02, cfg2: 4 / 8 -> 726 / 723 vs 678 Msamples/s with static 16-query chunks)
 #endif
-#ifndef RT_HEAVY_CALLS
-#define RT_HEAVY_CALLS 6        // heavy class (seg_id): quad_visit calls of a walk that flag its path (0: off).
-                                // cfg2 (r02): off / 3 / 6 / 10 / 16 -> 737 / 744 / 744-748 / 740 / 735 Msamples/s;
-                                // 1-lane k_trace 124.1 -> 117.2 ms, drain slots 838 M -> 737 M
-                                // (a dynamic, per-XCD-ticketed tail of the stream, 10-40 %: 684-691, rejected)
-#endif
-#ifndef RT_TRACE_OCC
-#define RT_TRACE_OCC 6          // k_trace waves per SIMD (8 fits the quad walks in 64 VGPRs but measured
-                                // 512 vs 539 Msamples/s: more trace waves crowd the other lanes k_step)
-#endif
-
-// Search-BVH stack of a fast query: entries [0, N) in LDS (entry i of
-// thread t at [i * 256 + t]: a wave at equal depth touches 64 consecutive
-// words), the rest in the lane's global spill area (deep stacks are rare).
-template <int N, int M>
-struct FastStack {
-    static constexpr int CAP = N + M;
-    uint32_t* r;
-    float* k;
-    uint32_t* gr;
-    float* gk;
-    __device__ __forceinline__ uint32_t rec(int i) const { return i < N ? r[i * 256] : gr[i - N]; }
-    __device__ __forceinline__ float key(int i) const { return i < N ? k[i * 256] : gk[i - N]; }
-    __device__ __forceinline__ void set(int i, uint32_t rv, float kv)
-    {
-        if (i < N) {
-            r[i * 256] = rv;
-            k[i * 256] = kv;
-        } else {
-            gr[i - N] = rv;
-            gk[i - N] = kv;
-        }
-    }
-};
 
 // Does this query skip the search-BVH walk for the exact octree walk? Its origin lies outside
 // the near box (rt_fast.h far_origin), or the force_fallback stressor's ray hash selects it.
@@ -606,7 +419,9 @@ template <bool STATS, bool PROG = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_STEP_OCC, 8))) void k_step(rtk::WaveView W, int par, unsigned long long* stats)
 {
     // (the exact roles' stacks; in the path-step blocks, the emitted rays: rt_wave.h EmitLds)
-    __shared__ uint32_t s_lds[(RT_STEP_EMIT_LDS ? 6 * rtk::RK_COUNT : RT_LDS_WORDS) * 256];
+    // (k_step's and k_tail's emitted rays wait in LDS, not in VGPRs: k_step's spill slots 27 -> 0,
+    // cfg2 -3.6 %, profiles/r06_emit_lds_ab.json)
+    __shared__ uint32_t s_lds[6 * rtk::RK_COUNT * 256];
     static_assert(6 * rtk::RK_COUNT >= RT_LDS_WORDS, "the exact roles' stacks fit the emit columns");
     __shared__ int s_pre[RT_QSHARDS + 1];
     rtlibm::lds_tables_init();
@@ -653,12 +468,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_STEP_OCC
     const int wn = nbs * (int)(blockDim.x >> 6);
     for (int base = wg * 64; base < n; base += wn * 64) {
         const int idx = base + lane_id();
-#if RT_STEP_EMIT_LDS
         rtk::EmitLds<256> e;
         e.s = reinterpret_cast<float*>(s_lds) + threadIdx.x;
-#else
-        rtk::Emit e;
-#endif
         e.mask = 0;
         e.active = false;
         e.heavy = false;
@@ -752,13 +563,6 @@ struct RowInQuadStack {
         __builtin_amdgcn_wave_barrier();                       \
     } while (0)
 #endif
-#ifndef RT_DRAIN_ROWS
-#define RT_DRAIN_ROWS 3  // k_trace: once a wave's stream is out and at most this many quads still walk,
-                         // their walks continue as rows (rt_row.h); 0 = off. cfg4 8-way shard, one
-                         // MI355X (profiles/r04i_drain_probe.json, r04j_probe.json): off / 4 / 3 / 2 / 1 ->
-                         // 370-373 / 362.6-362.9 / 359.9-361.4 / 360.5-363.6 / 366.5-367.3 ms, cfg2 148.0 /
-                         // 145.3-145.9 / 145.1-145.4 / 145.6-146.0 / 147.1-147.6 ms
-#endif
 
 // k_trace's fast roles with per-quad refill (RT_TRACE_REFILL > 0): see k_trace.
 // G = lanes per query: 4 (quads over the 4-wide BVH, rt_quad.h) or 16 (rows over the 16-wide
@@ -781,9 +585,7 @@ __device__ __forceinline__ void trace_stream(const rtk::WaveView& W, const RtSce
     bool active = false;
     uint32_t target = 0;
     rtk::QState q;  // (its ray is the query's: a fallback record is rebuilt from q.o, q.d and target)
-#if RT_TRACE_PREFETCH
     if (!exhausted) queue_prefetch(W, s_pre, pf, first, cursor, wg, wn, total);
-#endif
     // a walk's end: its answer, or the exact walk's list; gs = lanes of the group walking it
     auto finish = [&](int res, int gs) {
         // a long walk: the path's next rays go to the heavy class (head of the next streams)
@@ -832,7 +634,6 @@ __device__ __forceinline__ void trace_stream(const rtk::WaveView& W, const RtSce
                 const int j = cursor + __popcll(bidle & ((1ull << (qd * G)) - 1ull));  // this group's stream position
                 const int idx = (wg + (j >> 4) * wn) * 16 + (j & 15);
                 if (idx < total) {
-#if RT_TRACE_PREFETCH
                     const int slot = j - cursor;  // (0..15: the buffer starts at the cursor)
                     // (the compiler does not order LDS reads after direct-to-LDS loads: wait for
                     // the vector-memory counter here, vmcnt(0), before reading the buffer)
@@ -841,10 +642,6 @@ __device__ __forceinline__ void trace_stream(const rtk::WaveView& W, const RtSce
                     r.o = pf.buf[2 * slot];
                     r.d = pf.buf[2 * slot + 1];
                     const int kind = pf.kind[slot];
-#else
-                    int kind;
-                    rtk::RayRec r = queue_item_at(W, s_pre, first + idx, kind);
-#endif
                     target = (rt_asuint(r.o.w) << 3) | (uint32_t)kind;
                     if (forced_fallback(W, r.o, r.d)) {
                         if (sub == 0) {
@@ -865,12 +662,10 @@ __device__ __forceinline__ void trace_stream(const rtk::WaveView& W, const RtSce
             }
             cursor += __popcll(bidle);
             exhausted = (wg + (cursor >> 4) * wn) * 16 >= total;
-#if RT_TRACE_PREFETCH
             // (every lane has read its record: the buffer is free for the next 16 positions)
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
             __builtin_amdgcn_wave_barrier();
             if (!exhausted) queue_prefetch(W, s_pre, pf, first, cursor, wg, wn, total);
-#endif
             if (STATS && lane == 0) ps->c[RT_STAT_REFILLS]++;
         }
         const unsigned long long bact = __ballot(active && sub == 0);
@@ -973,9 +768,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_TRACE_OC
 {
     __shared__ uint32_t s_lds[RT_LDS_WORDS * 256];
     __shared__ int s_pre[RT_NSEG + 1];
-    __shared__ float4_ s_qbuf[RT_TRACE_PREFETCH ? 4 : 1][64];  // per wave: the next 16 stream records (queue_prefetch)
-    __shared__ int s_qkind[RT_TRACE_PREFETCH ? 4 : 1][16];
-    const QPrefetch pf{s_qbuf[RT_TRACE_PREFETCH ? threadIdx.x >> 6 : 0], s_qkind[RT_TRACE_PREFETCH ? threadIdx.x >> 6 : 0]};
+    __shared__ float4_ s_qbuf[4][64];  // per wave: the next 16 stream records (queue_prefetch)
+    __shared__ int s_qkind[4][16];
+    const QPrefetch pf{s_qbuf[threadIdx.x >> 6], s_qkind[threadIdx.x >> 6]};
     int32_t* cnt = W.counters;
     if (blockIdx.x == 0) {  // filled by k_step(i) next
         for (int j = threadIdx.x; j < (rtk::RK_COUNT + 1) * RT_QSHARDS; j += blockDim.x)
@@ -1053,14 +848,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_TRACE_OC
 // Entry condition (run_wave): no query is parked or waiting for the exact
 // walk, so every path is ready to step; a query the quad walk cannot answer
 // is answered here by the exact walk, inline, by lane 0 of its quad.
-#define RT_TAIL_MAXP 16  // paths per wave at most (RK_COUNT rays each per list)
-#ifndef RT_TAIL_EMIT_LDS
-#define RT_TAIL_EMIT_LDS RT_STEP_EMIT_LDS
-#endif
-#if RT_TAIL_EMIT_LDS
 // k_tail: a path's emitted rays stay in the wave's LDS columns (EmitLds<RT_TAIL_MAXP>, lane j
 // of the wave's paths in column j); the lists hold (j << 3 | kind) (l0: closest-hit kinds,
-// l1: occlusion)
+// l1: occlusion). (With the rays in registers and lists of whole 32-B records k_tail had fewer
+// spill slots, 28 / 20 against 34 / 24, and measured 0.8 % slower: profiles/r06_emit_lds_ab.json.)
 using TailEmit = rtk::EmitLds<RT_TAIL_MAXP>;
 __device__ __forceinline__ void tail_lists(const TailEmit& e, int last_kind, uint8_t* l0, uint8_t* l1, int* nl)
 {
@@ -1092,39 +883,6 @@ __device__ __noinline__ int tail_step(const rtk::WaveView& W, int my, int last_k
     tail_lists(e, last_kind, l0, l1, nl);
     return (e.active ? 1 : 0) | (nl[0] << 1) | (nl[1] << 11);
 }
-#else
-// k_tail: a path's emitted rays -> the wave's LDS lists (l0: closest-hit kinds, l1: occlusion)
-__device__ __forceinline__ void tail_lists(const rtk::Emit& e, int slot, int last_kind, rtk::RayRec* l0, rtk::RayRec* l1,
-                                           int* nl)
-{
-    const int lane = lane_id();
-    nl[0] = nl[1] = 0;
-#pragma unroll
-    for (int k = 0; k < rtk::RK_COUNT; k++) {
-        const bool want = (e.mask >> k) & 1u;
-        const unsigned long long b = __ballot(want);
-        const int l = k <= last_kind ? 0 : 1;
-        if (want) {
-            const int pos = nl[l] + __popcll(b & ((1ull << lane) - 1ull));
-            (l ? l1 : l0)[pos] = e.rec(k, slot, rt_asfloat(((uint32_t)slot << 3) | (uint32_t)k));
-        }
-        nl[l] += __popcll(b);
-    }
-}
-// (as above, the rays in registers and the lists of whole records)
-__device__ __noinline__ int tail_step(const rtk::WaveView& W, int my, int last_kind, rtk::RayRec* l0, rtk::RayRec* l1,
-                                      rtk::Stats* ps)
-{
-    rtk::Emit e;
-    e.mask = 0;
-    e.active = false;
-    e.heavy = false;
-    if (my >= 0) rtk::path_step<true>(W, my, e, ps);
-    int nl[2];
-    tail_lists(e, my, last_kind, l0, l1, nl);
-    return (e.active ? 1 : 0) | (nl[0] << 1) | (nl[1] << 11);
-}
-#endif
 // k_tail's inline exact walk (a query the quad walk cannot settle: ~1e-6 of them), kept
 // out of line so that its registers do not add to the tail loop's: inlined, k_tail
 // needed 468 VGPR spill slots at its 168-VGPR budget, out of line ~190.
@@ -1149,22 +907,15 @@ __device__ __noinline__ void tail_exact(const rtk::WaveView& W, int l, uint32_t 
 #ifndef RT_TAIL_DESCEND
 #define RT_TAIL_DESCEND RT_VISIT_DESCEND  // inner-node trips per quad_visit call in k_tail
 #endif
-#ifndef RT_TAIL_OCC
-#define RT_TAIL_OCC 3    // k_tail waves per SIMD (2: no spills but half the paths per launch; 3 measured faster)
-#endif
 // FAST: the fast lane's launch, one kernel over every lane's handed-over paths: blocks
 // [fparts[l], fparts[l + 1]) step lane l's (fviews[l]: its fast list as shard 0 of its own
 // counters, its own spill area).
 template <bool STATS, bool PAIR, int G, bool FAST>
 __device__ __forceinline__ void tail_body(const rtk::WaveView& W, int par, unsigned long long* stats, int blk)
 {
-#if RT_TAIL_EMIT_LDS
     __shared__ float s_em[4][6 * rtk::RK_COUNT * RT_TAIL_MAXP];        // per wave: its paths' rays (TailEmit columns)
     __shared__ uint8_t s_q[4][2][RT_TAIL_MAXP * rtk::RK_COUNT];        // per wave: closest list, occlusion list
     __shared__ int s_my[4][RT_TAIL_MAXP];                              // per wave: the slot of column j
-#else
-    __shared__ rtk::RayRec s_q[4][2][RT_TAIL_MAXP * rtk::RK_COUNT];  // per wave: closest list, occlusion list
-#endif
     __shared__ uint32_t s_stk[2 * RT_QSTACK * 64];
     __shared__ int s_pre[RT_QSHARDS + 1];
     rtlibm::lds_tables_init();
@@ -1218,12 +969,8 @@ __device__ __forceinline__ void tail_body(const rtk::WaveView& W, int par, unsig
         const long long t0 = probe ? wall_clock64() : 0;
         int nl[2];
         {
-#if RT_TAIL_EMIT_LDS
             if (lane < RT_TAIL_MAXP) s_my[wv][lane] = my;
             const int r = tail_step(W, my, last_kind, s_em[wv], s_q[wv][0], s_q[wv][1], ps);
-#else
-            const int r = tail_step(W, my, last_kind, s_q[wv][0], s_q[wv][1], ps);
-#endif
             if (!(r & 1)) my = -1;
             nl[0] = (r >> 1) & 0x3ff;
             nl[1] = r >> 11;
@@ -1252,7 +999,6 @@ __device__ __forceinline__ void tail_body(const rtk::WaveView& W, int par, unsig
                 const int qi = next + __popcll(bidle & ((1ull << (lane & ~(G - 1))) - 1ull));  // this group's query
                 if (!act && qi < nq) {
                     l = qi < nl[0] ? 0 : 1;
-#if RT_TAIL_EMIT_LDS
                     const int ent = s_q[wv][l][l ? qi - nl[0] : qi], j = ent >> 3, kind = ent & 7;
                     TailEmit ce;
                     ce.s = s_em[wv] + j;
@@ -1260,10 +1006,6 @@ __device__ __forceinline__ void tail_body(const rtk::WaveView& W, int par, unsig
                     r.o = rtk::f4(ce.o(kind), 0.0f);
                     r.d = rtk::f4(ce.d(kind), 0.0f);
                     target = ((uint32_t)s_my[wv][j] << 3) | (uint32_t)kind;
-#else
-                    const rtk::RayRec r = s_q[wv][l][l ? qi - nl[0] : qi];
-                    target = rt_asuint(r.d.w);
-#endif
                     q.o = rtk::v3of(r.o);
                     q.d = rtk::v3of(r.d);
                     if (forced_fallback(W, r.o, r.d)) {
@@ -1361,183 +1103,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_TAIL_OCC
     tail_body<STATS, PAIR, G, true>(fviews[fl], 0, stats, b - b0);
 }
 
-__global__ __launch_bounds__(256) void k_intersect(RtSceneView S, const float* __restrict__ rays, int32_t* __restrict__ out,
-                                                   int n)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    rtk::StackEnt stack[RT_STACK_CAP];
-    const float* r = rays + 6 * (size_t)i;
-    const rtk::V3 o = rtk::v3(r[0], r[1], r[2]), d = rtk::v3(r[3], r[4], r[5]);
-    float t;
-    int k;
-    rtk::query_closest(S, o, d, stack, t, k, nullptr);
-    rtk::Hit h;
-    const bool f = rtk::hit_from(S, o, d, t, k, h);
-    int32_t* ot = out + 11 * (size_t)i;
-    ot[0] = f ? 1 : 0;
-    ot[1] = h.prim;
-    ot[2] = (int32_t)rt_asuint(t);
-    const bool any = t != -1.0f;
-    ot[3] = any ? (int32_t)rt_asuint(h.p.x) : 0;
-    ot[4] = any ? (int32_t)rt_asuint(h.p.y) : 0;
-    ot[5] = any ? (int32_t)rt_asuint(h.p.z) : 0;
-    ot[6] = any ? (int32_t)rt_asuint(h.n.x) : 0;
-    ot[7] = any ? (int32_t)rt_asuint(h.n.y) : 0;
-    ot[8] = any ? (int32_t)rt_asuint(h.n.z) : 0;
-    ot[9] = (int32_t)rt_asuint(-1.0f);
-    ot[10] = (int32_t)rt_asuint(-1.0f);
-}
-
-// Search-BVH query micro-benchmark (tools/query_bench.py): one query per
-// lane, the k_trace stack layout. out_t = t (closest) or 0/1 (any), -2 when
-// the query needs the exact walk.
-template <bool ANY, int WALK>
-__global__ __launch_bounds__(256, 4) void k_query(RtSceneView S, const float4_* __restrict__ rays,
-                                                  float* __restrict__ out_t, int* __restrict__ out_k, int n,
-                                                  uint32_t* spill_r, float* spill_k)
-{
-    __shared__ uint32_t s_lds[2 * RT_LDS_CAP_FAST * 256];
-    const size_t gl = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    FastStack<RT_LDS_CAP_FAST, RT_SPILL_FAST> stk{s_lds + threadIdx.x, (float*)s_lds + RT_LDS_CAP_FAST * 256 + threadIdx.x,
-                                                  spill_r + gl * RT_SPILL_FAST, spill_k + gl * RT_SPILL_FAST};
-    const int stride = (int)(gridDim.x * blockDim.x);
-    for (int i = (int)gl; i < n; i += stride) {
-        const rtk::V3 o = rtk::v3of(rays[2 * i]), d = rtk::v3of(rays[2 * i + 1]);
-        if (ANY) {
-            const int a = rtk::fast_query_any<decltype(stk), WALK>(S, o, d, stk, nullptr);
-            out_t[i] = a < 0 ? -2.0f : (float)a;
-            out_k[i] = 0;
-        } else {
-            float t = 0;
-            int k = 0;
-            const bool ok = rtk::fast_query_closest<decltype(stk), WALK>(S, o, d, stk, t, k, nullptr);
-            out_t[i] = ok ? t : -2.0f;
-            out_k[i] = ok ? (k >= 0 ? (int)rt_asuint(S.tri4[3 * (size_t)k].w) : -1) : -2;  // (the original triangle index)
-        }
-    }
-}
-
-// The same through the product's quad walks (rt_quad.h quad_visit, k_trace's per-trip
-// code and answer): four lanes per query.
-template <bool ANY, int OCC>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OCC, 8))) void k_query_quad(RtSceneView S, const float4_* __restrict__ rays,
-                                                    float* __restrict__ out_t, int* __restrict__ out_k, int n)
-{
-    __shared__ uint32_t s_lds[2 * RT_QSTACK * 64];
-    const int q = (int)(threadIdx.x >> 2), sub = (int)(threadIdx.x & 3);
-    rtk::QuadStack<RT_QSTACK, 64> stk{s_lds + q, (float*)s_lds + RT_QSTACK * 64 + q};
-    const int stride = (int)(gridDim.x * blockDim.x) >> 2;
-    for (int i = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 2); i < n; i += stride) {
-        rtk::QState qs;
-        int res = 1;
-        if (rtk::far_origin(S, rtk::v3of(rays[2 * i])))
-            res = -1;  // (the exact walk's)
-        else if (rtk::qstate_begin<ANY>(qs, rtk::v3of(rays[2 * i]), rtk::v3of(rays[2 * i + 1]), sub, nullptr))
-            do {
-                res = rtk::quad_visit<ANY>(S, qs, stk, sub, nullptr);
-            } while (res == 0);
-        float t = -1.0f;
-        int k = -1;
-        const bool ok = res > 0 && (ANY || rtk::quad_closest_answer(S, qs, sub, t, k, nullptr));
-        if (sub == 0) {
-            if (ANY) {
-                out_t[i] = ok ? (float)(qs.h.k == 1 ? 1 : 0) : -2.0f;
-                out_k[i] = 0;
-            } else {
-                out_t[i] = ok ? t : -2.0f;
-                out_k[i] = ok ? (k >= 0 ? (int)rt_asuint(S.tri4[3 * (size_t)k].w) : -1) : -2;  // (the original triangle index)
-            }
-        }
-    }
-}
-
-// The same through the row walks (rt_row.h row_visit over the 16-wide BVH): 16 lanes per query.
-template <bool ANY>
-__global__ __launch_bounds__(256) void k_query_row(RtSceneView S, const float4_* __restrict__ rays,
-                                                   float* __restrict__ out_t, int* __restrict__ out_k, int n)
-{
-    __shared__ uint32_t s_lds[2 * RT_RSTACK * 16];
-    const int r = (int)(threadIdx.x >> 4), sub = (int)(threadIdx.x & 15);
-    rtk::QuadStack<RT_RSTACK, 16> stk{s_lds + r, (float*)s_lds + RT_RSTACK * 16 + r};
-    const int stride = (int)(gridDim.x * blockDim.x) >> 4;
-    for (int i = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 4); i < n; i += stride) {
-        rtk::QState qs;
-        int res = 1;
-        if (rtk::far_origin(S, rtk::v3of(rays[2 * i])))
-            res = -1;  // (the exact walk's)
-        else if (rtk::qstate_begin<ANY>(qs, rtk::v3of(rays[2 * i]), rtk::v3of(rays[2 * i + 1]), sub, nullptr))
-            do {
-                res = rtk::row_visit<ANY, RT_VISIT_DESCEND>(S, qs, stk, sub, nullptr);
-            } while (res == 0);
-        float t = -1.0f;
-        int k = -1;
-        const bool ok = res > 0 && (ANY || rtk::quad_closest_answer(S, qs, sub & 3, t, k, nullptr));
-        if (sub == 0) {
-            if (ANY) {
-                out_t[i] = ok ? (float)(qs.h.k == 1 ? 1 : 0) : -2.0f;
-                out_k[i] = 0;
-            } else {
-                out_t[i] = ok ? t : -2.0f;
-                out_k[i] = ok ? (k >= 0 ? (int)rt_asuint(S.tri4[3 * (size_t)k].w) : -1) : -2;  // (the original triangle index)
-            }
-        }
-    }
-}
-
-// numerics self-test kernel (tests/test_gpu_parity.py): out[i] = f(in[i])
-__global__ void k_libm(int fn, const float* __restrict__ in, const float* __restrict__ in2, float* __restrict__ out, int n)
-{
-    rtlibm::lds_tables_init();
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const float x = in[i];
-    float r;
-    switch (fn) {
-        case 0: r = rt_expf(x); break;
-        case 1: r = rt_powf(x, in2[i]); break;
-        case 2: r = rt_sinf(x); break;
-        case 3: r = rt_cosf(x); break;
-        case 4: r = rt_acosf(x); break;
-        case 5: r = rt_asinf(x); break;
-        case 6: r = rt_atan2f(x, in2[i]); break;
-        case 7: r = rt_sqrtf(x); break;
-        case 8: r = x / in2[i]; break;
-        case 9: r = (float)((double)x * 0.31830988618379067154 / (double)in2[i]); break;
-        default: r = rtk::slab_div(x, 1.0 / (double)in2[i]); break;  // the slab quotient
-    }
-    out[i] = r;
-}
-
-// TEST ONLY (rt_device_env_search): cdf_search alone over caller values. form 0: as the shading
-// kernels run it, after lds_shade_init's staging; form 1: every table from global memory.
-__global__ void k_env_search(RtSceneView S, int form, const float* __restrict__ values, int n, int* __restrict__ xy)
-{
-    if (form == 0) rtk::lds_shade_init(S);
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        int x, y;
-        if (form == 0)
-            rtk::cdf_search(S, values[i], x, y, nullptr);
-        else
-            rtk::cdf_search_global(S, values[i], x, y);
-        xy[2 * i] = x;
-        xy[2 * i + 1] = y;
-    }
-}
-
-// ------------------------------------------------------------- wave memory
+const int threads = rt_wave_threads;
 }  // namespace
 
-size_t rt_wave_counter_bytes() { return C_COUNT * sizeof(int32_t); }
-size_t rt_wave_readback_bytes() { return RT_QSHARDS * RT_CSTRIDE * 4 + 64; }
-
-namespace {
-const int threads = 256;
-const WaveKnobs knobs{RT_TRACE_OCC, RT_TAIL_OCC, RT_HEAVY_CALLS, RT_TAIL_ROWS, RT_DRAIN_ROWS, RT_TAIL_MAXP, RT_QSHARDS};
-
-// One launch helper per kernel family: (SEQ, S, brute / rows) -> the instantiation.
-// SEQ: counter renders with unpaired occlusion walks; S: counter renders; brute: USE_BVH 0
-// scenes (the walks that keep the triangles' original indices); rows: k_tail walks by rows.
+// ----------------------------------------------------------------- launches
+// (rt_wave_kernels.h) One launch helper per kernel family: (SEQ, S, brute / rows) -> the instantiation.
 #define RT_LAUNCH(K) hipLaunchKernelGGL(K, g, dim3(threads), 0, s, W, par, stats)
 void launch_k_trace(bool SEQ, bool S, bool brute, dim3 g, hipStream_t s, const rtk::WaveView& W, int par,
                     unsigned long long* stats)
@@ -1569,731 +1139,27 @@ void launch_k_tail(bool SEQ, bool S, bool rows, dim3 g, hipStream_t s, const rtk
     else RT_LAUNCH((rows ? k_tail<false, true, 16> : k_tail<false, true, 4>));
 }
 #undef RT_LAUNCH
-// The readback a lane waits for: none, the live count (read_live), or the fallback counts
-// (the tail entry check of issue).
-enum class Await { None, Live, Fallbacks };
-// A lane's share of the fast lane, in order of life:
-//   Waiting -> HistPending   process: the lane reached fast_iter; k_hist's histogram is on its way back
-//   HistPending -> HandNext  fast_threshold: the histogram has landed, the threshold is known
-//   HandNext -> Handed       launch_step: k_hand ran before this k_step
-//   Waiting / HistPending -> NoShare   process: the lane is done or enters its tail first
-// (NoShare from the start without a fast lane). fast_launch runs once no lane is before Handed.
-enum class Fast { Waiting, HistPending, HandNext, Handed, NoShare };
-
-// One wavefront run over a subset of the launch's pixels (a "lane"): its own
-// path slots, queues, counters and stream. run_wave drives RT_LANES lanes on
-// as many streams (row j of the launch -> lane j % lanes) so that one lane's
-// k_step and the tails of its launches overlap another lane's k_trace.
-struct WaveLane {
-    rtk::WaveView W{};
-    int32_t* lists[2] = {nullptr, nullptr};
-    int32_t* cnt = nullptr;
-    int32_t* h = nullptr;  // pinned readback: ACT shard counts, then 8 FB / PARK counters
-    hipStream_t s = nullptr;
-    hipEvent_t ev = nullptr;
-    int n = 0, it = 0, tail_iter = -1;
-    long live = 0;  // live paths at the last readback (an upper bound: paths only finish)
-    bool done = false, tail_next = false;
-    Await await = Await::None;
-    Fast fast = Fast::NoShare;
-    int fast_thr = 0, fast_n = 0;  // ... samples-done threshold, paths at most
-    Event (*tev)[RT_MAX_TIMED_ITERS] = nullptr;  // [3][RT_MAX_TIMED_ITERS]
-};
-
-// One call of run_wave: the plan, the lanes and the launches on their streams.
-struct WaveRun {
-    rt_context* c;
-    Backend* b;
-    int w, h, spp, bounces;
-    const rtk::PixSrc& src;
-    int n;
-    float4_* fb;
-    hipStream_t s;
-    const WavePass* pass;  // a progressive pass: samples pass->first .. spp - 1, paused into pass->state (else null)
-    bool linear;           // no tone-map pass after the last step (rt_render_linear)
-    int dev_cus = 256;
-    WavePlan P{};
-    WaveLane L[RT_MAX_LANES];
-    bool S = false, SEQ = false, wlog = false;
-    unsigned long long* stats = nullptr;
-    const char* iter_log = nullptr;  // per-iteration log of lane 0: counts (stats renders) / ms (timed)
-    hipStream_t fstream = nullptr;
-    bool fast_launched = false, fast_ran = false;
-    long max_iters = 0;
-    static constexpr size_t act_bytes = RT_QSHARDS * RT_CSTRIDE * 4;
-
-    int begin();
-    int init_lane(int l);
-    int launch_trace(WaveLane& La);
-    int fast_launch();
-    int fast_threshold(WaveLane& La);
-    int launch_step(WaveLane& La);
-    int launch_tail(WaveLane& La, int par);
-    int read_live(WaveLane& La);
-    int issue(WaveLane& La);
-    int process(WaveLane& La);
-    int start_hist(WaveLane& La);
-    int poll();
-    int finish();
-    int report();
-    int lane_of(const WaveLane& La) const { return (int)(&La - L); }
-    // grids sized by the last known live count: k_step one slot per thread; k_trace up to
-    // five queries per path, a quad each, over two grid-fills, never fewer blocks than the
-    // exact-walk roles can claim (dev_cus * 4) plus room for the fast roles
-    // (k_step: at least 3 blocks, one per exact-walk role and one for the path step, so a
-    // small live count with fallbacks or parked walks pending still steps its paths)
-    int step_blocks_of(const WaveLane& La) const
-    {
-        return (int)std::max(3l, std::min((La.live + threads - 1) / threads, (long)dev_cus * RT_STEP_FILL));
-    }
-    int trace_blocks_of(const WaveLane& La) const
-    {
-        const long want = (20 * La.live + 2 * threads - 1) / (2 * threads);
-        return (int)std::min((long)P.trace_blocks, std::max(want, (long)dev_cus * 4 + 64));
-    }
-};
-
-int WaveRun::begin()
+void launch_k_init(dim3 g, hipStream_t s, const rtk::WaveView& W) { hipLaunchKernelGGL(k_init, g, dim3(threads), 0, s, W); }
+void launch_k_resume(dim3 g, hipStream_t s, const rtk::WaveView& W) { hipLaunchKernelGGL(k_resume, g, dim3(threads), 0, s, W); }
+void launch_k_tonemap(dim3 g, hipStream_t s, const rtk::WaveView& W) { hipLaunchKernelGGL(k_tonemap, g, dim3(threads), 0, s, W); }
+void launch_k_hand(dim3 g, hipStream_t s, const rtk::WaveView& W, int par)
 {
-    // every render of a context reuses its lanes' slots and counters: the previous render
-    // (whose tail kernel may still run, on another stream) must finish first
-    if (b->done_recorded) HIPCHK(c, hipStreamWaitEvent(s, b->ev_done, 0));
-    (void)hipDeviceGetAttribute(&dev_cus, hipDeviceAttributeMultiprocessorCount, b->device);
-    const RtDiag& dg = c->diag;
-    S = c->stats_enabled;
-    SEQ = S && c->stats_seq;  // (counter renders with unpaired occlusion walks: rt_set_stats(ctx, 2))
-    stats = (unsigned long long*)b->stats.p;
-    if (S) HIPCHK(c, hipMemsetAsync(b->stats.p, 0, b->stats.bytes, s));
-    iter_log = dg.iter_log.empty() ? nullptr : dg.iter_log.c_str();
-    wlog = S && dg.wlog_cap > 0 && b->index == 0;
-    if (wlog) {
-        if (int r = ensure(c, b->wlog, 256 + (size_t)dg.wlog_cap * 48)) return r;
-        HIPCHK(c, hipMemsetAsync(b->wlog.p, 0, 256, s));
-    }
-    if (!b->handovers.p) {
-        if (int r = ensure(c, b->handovers, 8)) return r;
-        HIPCHK(c, hipMemsetAsync(b->handovers.p, 0, 8, s));
-    }
-    if (S && iter_log) {
-        if (int r = ensure(c, b->iterq, RT_MAX_TIMED_ITERS * 24)) return r;
-        HIPCHK(c, hipMemsetAsync(b->iterq.p, 0, RT_MAX_TIMED_ITERS * 24, s));
-    }
-    const int rows = src.xy ? 0 : n / src.W;
-    P = wave_plan(c->sched, knobs, WaveSource{src.xy != nullptr, src.W, src.off, src.stride}, n, rows, spp, dev_cus, SEQ,
-                  b->lanes, b->budget);
-    const int nl = P.lanes;
-    if (P.fast_k > 0 && nl == RT_MAX_LANES && !b->fs) HIPCHK(c, hipStreamCreateWithFlags(&b->fs.h, hipStreamNonBlocking));
-    fstream = P.fast_k > 0 ? (hipStream_t)(nl < RT_MAX_LANES ? b->ls[nl] : b->fs) : nullptr;
-    if (nl > 1) {
-        HIPCHK(c, hipEventRecord(b->ev_fork, s));
-        for (int l = 1; l < nl; l++) HIPCHK(c, hipStreamWaitEvent(b->ls[l], b->ev_fork, 0));
-    }
-    for (int l = 0; l < nl; l++)
-        if (int r = init_lane(l)) return r;
-    if (dg.verbose)
-        fprintf(stderr, "[rt] run_wave n=%d lanes=%d cus=%d trace_blocks=%d budget=%d\n", n, nl, dev_cus, P.trace_blocks,
-                L[0].W.budget);
-    // A sample takes at most bounces + 1 iterations without fallbacks; an
-    // exact walk delays its path by at least one iteration. The bound only
-    // guards against a runaway loop.
-    max_iters = 64l * spp * ((long)bounces + 1) + 4096;
-    for (int l = 0; l < nl; l++)
-        if (int r = issue(L[l])) return r;
-    return RT_OK;
+    hipLaunchKernelGGL(k_hand, g, dim3(threads), 0, s, W, par);
 }
-
-// The lane's buffers carved, its view filled, its counters zeroed and k_init on its stream.
-int WaveRun::init_lane(int l)
+void launch_k_hist(dim3 g, hipStream_t s, const rtk::WaveView& W, int par, int32_t* hist)
 {
-    WaveLane& La = L[l];
-    const LanePlan& lp = P.lane[l];
-    const RtDiag& dg = c->diag;
-    rtk::PixSrc ls = src;
-    if (src.xy) ls.xy = src.xy + 2 * (size_t)lp.first;
-    ls.off = lp.off;
-    ls.stride = lp.stride;
-    La.n = lp.n;
-    La.live = La.n;
-    La.s = l == 0 ? s : (hipStream_t)b->ls[l];
-    La.cnt = (int32_t*)b->counters[l].p;
-    La.h = b->h_act[l];
-    La.ev = b->ev_lane[l];
-    La.tev = b->tev[l];
-    rtk::WaveView& W = La.W;
-    W.park_cap = 1 << 16;
-    W.heavy_calls = P.heavy_calls;
-    W.spec_cam = P.spec_cam;
-    W.shards = RT_QSHARDS;
-    W.seg_cap = lp.seg_cap;
-    W.spill_lanes = dev_cus * 4 * threads;  // exact walks: up to dev_cus * 2 blocks per role
-    W.fspill_lanes = 0;
-    const size_t need = rtk::wave_carve(nullptr, (size_t)La.n, W);
-    if (int r = ensure(c, b->wave[l], need)) return r;
-    rtk::wave_carve((char*)b->wave[l].p, (size_t)La.n, W);
-    W.S = b->view;
-    rt_view_near(c, W.S);  // (rt_test_schedule may have changed it since the upload)
-    W.cam = c->cam;
-    W.src = ls;
-    W.W = w;
-    W.H = h;
-    W.spp = spp;
-    W.bounces = bounces;
-    W.prog = pass ? pass->state + lp.first : nullptr;
-    W.first = pass ? pass->first : 0;
-    W.seed_spp = pass ? pass->seed_spp : spp;
-    rtk::set_view_consts(W);
-    W.n_slots = La.n;
-    W.bl_rays = b->bl_rays;
-    W.any_rays = b->any_rays;
-    W.fb = fb + lp.first;
-    W.fb_rs = lp.fb_rs;
-    W.budget = P.budget;
-    W.counters = La.cnt;
-    W.tail_paths = P.tail_p;
-    W.drain_rows = P.drain_rows;
-    W.force_fb = c->sched.force_fallback;  // (test stressor, rt_test_schedule)
-    W.fast_cap = 0;
-    La.fast = P.fast_k > 0 ? Fast::Waiting : Fast::NoShare;
-    La.fast_n = lp.fast_n;
-    if (P.fast_k > 0) {  // the fast lane's buffers and events (first use)
-        if (int r = ensure(c, b->fast[l], (size_t)(La.fast_n + 1) * 4)) return r;
-        if (int r = ensure(c, b->fcnt[l], C_COUNT * sizeof(int32_t))) return r;
-        if (int r = ensure(c, b->fhist[l], (RT_FAST_MAX_SPP + 1) * 4)) return r;
-        if (int r = ensure(c, b->fspill[l], (size_t)((La.fast_n + 3) / 4) * threads * RT_STACK_CAP * 8)) return r;
-        if (!b->h_hist[l]) HIPCHK(c, hipHostMalloc((void**)&b->h_hist[l].h, (RT_FAST_MAX_SPP + 1) * 4, hipHostMallocDefault));
-        if (!b->fev[l]) HIPCHK(c, hipEventCreateWithFlags(&b->fev[l].h, hipEventDisableTiming));
-        if (!b->hev[l]) HIPCHK(c, hipEventCreateWithFlags(&b->hev[l].h, hipEventDisableTiming));
-        HIPCHK(c, hipMemsetAsync(b->fcnt[l].p, 0, C_COUNT * sizeof(int32_t), La.s));
-    }
-    W.iterq = (S && iter_log && l == 0) ? (int32_t*)b->iterq.p : nullptr;
-    W.handovers = (unsigned long long*)b->handovers.p;
-    if (wlog) {
-        W.wlog_n = (int32_t*)b->wlog.p;
-        W.wlog = (float4_*)((char*)b->wlog.p + 256);
-        W.wlog_min = dg.wlog_min;
-        W.wlog_cap = dg.wlog_cap;
-        W.wlog_every = dg.wlog_every;
-    }
-    La.lists[0] = (int32_t*)W.act_in;
-    La.lists[1] = W.act_out;
-    HIPCHK(c, hipMemsetAsync(La.cnt, 0, C_COUNT * sizeof(int32_t), La.s));
-    HIPCHK(c, hipMemsetAsync(W.r_park, 0, (size_t)La.n * 4, La.s));
-    W.act_in = La.lists[1];
-    W.act_out = La.lists[0];
-    if (W.first > 0)
-        hipLaunchKernelGGL(k_resume, dim3((La.n + threads - 1) / threads), dim3(threads), 0, La.s, W);
-    else
-        hipLaunchKernelGGL(k_init, dim3((La.n + threads - 1) / threads), dim3(threads), 0, La.s, W);
-    HIPCHK(c, hipGetLastError());
-    return RT_OK;
+    hipLaunchKernelGGL(k_hist, g, dim3(threads), 0, s, W, par, hist);
 }
-
-int WaveRun::launch_trace(WaveLane& La)
+void launch_k_resolve(dim3 g, hipStream_t s, const float4_* base, const float4_* state, float4_* out, int n, int done)
 {
-    rtk::WaveView& W = La.W;
-    const int par = La.it & 1;
-    W.iter = La.it;
-    W.act_in = La.lists[par];
-    W.act_out = La.lists[par ^ 1];
-    const bool T = b->timing && La.it < RT_MAX_TIMED_ITERS;
-    if (T)
-        for (int k = 0; k < 3; k++)
-            if (!La.tev[k][La.it]) HIPCHK(c, hipEventCreate(&La.tev[k][La.it].h));
-    if (T) HIPCHK(c, hipEventRecord(La.tev[0][La.it], La.s));
-    launch_k_trace(SEQ, S, W.S.brute, dim3(trace_blocks_of(La)), La.s, W, par, stats);
-    if (T) HIPCHK(c, hipEventRecord(La.tev[1][La.it], La.s));
-    HIPCHK(c, hipGetLastError());
-    return RT_OK;
+    hipLaunchKernelGGL(k_resolve, g, dim3(threads), 0, s, base, state, out, n, done);
 }
-
-// the fast lane's tail kernel, once every lane has handed its share over (or has none)
-int WaveRun::fast_launch()
-{
-    const int nl = P.lanes;
-    if (P.fast_k == 0 || fast_launched) return RT_OK;
-    bool any = false;
-    for (int l = 0; l < nl; l++) {
-        if (L[l].fast != Fast::Handed && L[l].fast != Fast::NoShare) return RT_OK;  // (a lane still to hand over)
-        any = any || L[l].fast == Fast::Handed;
-    }
-    fast_launched = true;
-    if (!any) return RT_OK;
-    if (!b->h_fviews)
-        HIPCHK(c, hipHostMalloc((void**)&b->h_fviews.h, sizeof(rtk::WaveView) * RT_MAX_LANES, hipHostMallocDefault));
-    if (!b->fev_done) HIPCHK(c, hipEventCreateWithFlags(&b->fev_done.h, hipEventDisableTiming));
-    if (b->fev_done_recorded) HIPCHK(c, hipEventSynchronize(b->fev_done));  // (the last render's copy of the views)
-    if (int r = ensure(c, b->fviews, sizeof(rtk::WaveView) * RT_MAX_LANES)) return r;
-    int start[RT_MAX_LANES + 1] = {}, tot = 0;
-    for (int l = 0; l < RT_MAX_LANES; l++) {
-        start[l] = tot;
-        if (l >= nl || L[l].fast != Fast::Handed) continue;
-        rtk::WaveView FW = L[l].W;
-        FW.act_in = (int32_t*)b->fast[l].p;
-        FW.counters = (int32_t*)b->fcnt[l].p;
-        FW.fast_cap = L[l].fast_n;
-        FW.tail_paths = 1;  // (one path per wave, its queries on the wave's rows)
-        const int blocks = (L[l].fast_n + 3) / 4;
-        FW.spill_r = (uint32_t*)b->fspill[l].p;
-        FW.spill_k = (float*)((uint32_t*)b->fspill[l].p + (size_t)blocks * threads * RT_STACK_CAP);
-        FW.iterq = nullptr;
-        FW.spec_cam = P.spec_cam ? P.tail_spec_cam : 0;
-        b->h_fviews.h[l] = FW;
-        tot += blocks;
-        HIPCHK(c, hipStreamWaitEvent(fstream, b->fev[l], 0));
-    }
-    HIPCHK(c, hipMemcpyAsync(b->fviews.p, b->h_fviews, sizeof(rtk::WaveView) * RT_MAX_LANES, hipMemcpyHostToDevice,
-                             fstream));
-    if (b->timing) {
-        for (Event& e : b->ftev)
-            if (!e) HIPCHK(c, hipEventCreate(&e.h));
-        HIPCHK(c, hipEventRecord(b->ftev[0], fstream));
-    }
-    launch_k_tail_fast(SEQ, S, dim3(tot), fstream, (const rtk::WaveView*)b->fviews.p,
-                       make_int4(start[0], start[1], start[2], start[3]), stats);
-    HIPCHK(c, hipGetLastError());
-    if (b->timing) HIPCHK(c, hipEventRecord(b->ftev[1], fstream));
-    HIPCHK(c, hipEventRecord(b->fev_done, fstream));
-    b->fev_done_recorded = fast_ran = true;
-    return RT_OK;
-}
-
-// the fast lane's threshold: the samples-done count of the lane's fast_n-th slowest live
-// path, from the histogram k_hist read back (polled: the host thread serving every lane
-// never blocks on it; the hand-over happens at the first k_step after it has landed)
-int WaveRun::fast_threshold(WaveLane& La)
-{
-    const int l = lane_of(La);
-    const hipError_t q = hipEventQuery(b->hev[l]);
-    if (q == hipErrorNotReady) return RT_OK;
-    HIPCHK(c, q);
-    long acc = 0;
-    int thr = spp;
-    for (int k = 0; k <= spp; k++)
-        if ((acc += b->h_hist[l].h[k]) >= La.fast_n) {
-            thr = k;
-            break;
-        }
-    La.fast_thr = thr;
-    La.fast = Fast::HandNext;
-    return RT_OK;
-}
-
-int WaveRun::launch_step(WaveLane& La)
-{
-    const int par = La.it & 1;
-    const int l = lane_of(La);
-    if (La.fast == Fast::HistPending)
-        if (int r = fast_threshold(La)) return r;
-    const bool hand = La.fast == Fast::HandNext;
-    int32_t* fl = (int32_t*)b->fast[l].p;
-    if (hand) {  // this step hands the lane's slowest paths to the fast lane
-        HIPCHK(c, hipMemsetAsync(fl + La.fast_n, 0, 4, La.s));
-        rtk::WaveView HW = La.W;
-        HW.fast_list = fl;
-        HW.fast_ticket = fl + La.fast_n;
-        HW.fast_cap = La.fast_n;
-        HW.fast_thr = La.fast_thr;
-        hipLaunchKernelGGL(k_hand, dim3((unsigned)std::min(1024l, (La.live + threads - 1) / threads)), dim3(threads), 0,
-                           La.s, HW, par);
-        HIPCHK(c, hipGetLastError());
-    }
-    launch_k_step(S, dim3(step_blocks_of(La)), La.s, La.W, par, stats);
-    if (hand) {  // (its list's length as shard 0 of the fast lane's counters)
-        La.fast = Fast::Handed;
-        HIPCHK(c, hipMemcpyAsync((int32_t*)b->fcnt[l].p + ac_at(0, 0), fl + La.fast_n, 4, hipMemcpyDeviceToDevice, La.s));
-        HIPCHK(c, hipEventRecord(b->fev[l], La.s));
-        if (int r = fast_launch()) return r;
-    }
-    if (b->timing && La.it < RT_MAX_TIMED_ITERS) HIPCHK(c, hipEventRecord(La.tev[2][La.it], La.s));
-    HIPCHK(c, hipGetLastError());
-    La.it++;
-    return RT_OK;
-}
-
-// few paths left and none waits: the tail kernel finishes them all
-int WaveRun::launch_tail(WaveLane& La, int par)
-{
-    HIPCHK(c, hipMemsetAsync(La.cnt + C_TK_TAIL, 0, 4, La.s));
-    La.W.spec_cam = P.spec_cam ? P.tail_spec_cam : 0;  // (the lane's last launch)
-    launch_k_tail(SEQ, S, P.tail_rows, dim3(P.tail_blocks), La.s, La.W, par, stats);
-    if (b->timing && La.it < RT_MAX_TIMED_ITERS) HIPCHK(c, hipEventRecord(La.tev[2][La.it], La.s));
-    HIPCHK(c, hipGetLastError());
-    La.tail_iter = La.it;
-    La.it++;
-    La.done = true;
-    return RT_OK;
-}
-
-int WaveRun::read_live(WaveLane& La)  // ACT counts of the next iteration
-{
-    HIPCHK(c, hipMemcpyAsync(La.h, La.cnt + ac_at(La.it & 1, 0), act_bytes, hipMemcpyDeviceToHost, La.s));
-    HIPCHK(c, hipEventRecord(La.ev, La.s));
-    La.await = Await::Live;
-    return RT_OK;
-}
-
-// enqueue up to 8 iterations, then a readback
-int WaveRun::issue(WaveLane& La)
-{
-    for (int k = 0; k < 8 && La.it < max_iters; k++) {
-        if (int r = launch_trace(La)) return r;
-        if (La.tail_next) {  // does any query wait for the exact walk?
-            HIPCHK(c, hipMemcpyAsync(La.h + act_bytes / 4, La.cnt, 8 * 4, hipMemcpyDeviceToHost, La.s));
-            HIPCHK(c, hipEventRecord(La.ev, La.s));
-            La.await = Await::Fallbacks;
-            return RT_OK;
-        }
-        if (int r = launch_step(La)) return r;
-        if ((La.it & 7) == 0) break;
-    }
-    return read_live(La);
-}
-
-int WaveRun::process(WaveLane& La)
-{
-    HIPCHK(c, hipEventSynchronize(La.ev));
-    const Await kind = La.await;
-    La.await = Await::None;
-    if (kind == Await::Fallbacks) {  // (a fallback pending: step, then the live count, checked again next iteration)
-        const int par = La.it & 1;
-        const int32_t* f = La.h + act_bytes / 4;
-        if (f[C_FBC0 + par] == 0 && f[C_FBA0 + par] == 0 && f[C_PARKC0 + (par ^ 1)] == 0 &&
-            f[C_PARKA0 + (par ^ 1)] == 0)  // (k_trace(i) released DONE[par ^ 1])
-            return launch_tail(La, par);
-        if (int r = launch_step(La)) return r;
-        return read_live(La);
-    }
-    long live = 0;
-    for (int j = 0; j < RT_QSHARDS; j++) live += La.h[j * RT_CSTRIDE];
-    La.live = live;
-    La.done = live == 0;
-    La.tail_next = !La.done && live <= P.tail_max;
-    const bool before_hand = La.fast == Fast::Waiting || La.fast == Fast::HistPending;
-    if (before_hand && (La.done || La.tail_next)) {  // (no hand-over from this lane)
-        if (La.fast == Fast::HistPending) HIPCHK(c, hipEventSynchronize(b->hev[lane_of(La)]));  // (its readback is done with h_hist)
-        La.fast = Fast::NoShare;
-        return fast_launch();
-    }
-    if (La.fast == Fast::Waiting && La.it >= P.fast_iter) return start_hist(La);
-    return RT_OK;
-}
-
-// the samples-done histogram of the lane's live paths, read back asynchronously
-// (fast_threshold picks it up from a later k_step launch)
-int WaveRun::start_hist(WaveLane& La)
-{
-    const int l = lane_of(La);
-    int32_t* hh = (int32_t*)b->fhist[l].p;
-    HIPCHK(c, hipMemsetAsync(hh, 0, (size_t)(spp + 1) * 4, La.s));
-    rtk::WaveView HW = La.W;
-    HW.act_in = La.lists[La.it & 1];
-    hipLaunchKernelGGL(k_hist, dim3((unsigned)std::min(1024l, (La.live + threads - 1) / threads)), dim3(threads), 0, La.s,
-                       HW, La.it & 1, hh);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(b->h_hist[l], hh, (size_t)(spp + 1) * 4, hipMemcpyDeviceToHost, La.s));
-    HIPCHK(c, hipEventRecord(b->hev[l], La.s));
-    La.fast = Fast::HistPending;
-    return RT_OK;
-}
-
-// The host serves whichever lane's readback has completed (hipEventQuery), so a lane whose
-// batch is done is refilled at once instead of idling while the host blocks on another
-// lane's event (blocking in lane order left lanes idle 17-34 ms of a 367-ms cfg4 8-way
-// shard: profiles/r04e_tl.json; 379.5-380.2 -> 370.5-373.2 ms, cfg2 148.5-149.7 -> 148.0,
-// profiles/r04i_drain_probe.json).
-// (a thread that finds no lane done for a while sleeps between polls: in a multi-device
-// render every device thread polls like this, and the caller's host work shares the cores)
-int WaveRun::poll()
-{
-    auto idle_since = std::chrono::steady_clock::now();
-    for (;;) {
-        bool any = false, moved = false;
-        for (int l = 0; l < P.lanes; l++) {
-            WaveLane& La = L[l];
-            if (La.await != Await::None) {
-                any = true;
-                const hipError_t q = hipEventQuery(La.ev);
-                if (q == hipErrorNotReady) continue;
-                HIPCHK(c, q);
-                if (int r = process(La)) return r;
-                moved = true;
-            }
-            if (!La.done && La.await == Await::None) {
-                if (La.it >= max_iters) {
-                    HIPCHK(c, hipStreamSynchronize(La.s));
-                    return rt_fail(c, RT_ERR_STATE, "render: wavefront loop did not drain in " +
-                                                            std::to_string(max_iters) + " iterations (step budget " +
-                                                            std::to_string(b->budget) + ")");
-                }
-                if (int r = issue(La)) return r;
-                any = moved = true;
-            }
-        }
-        if (!any) break;
-        if (moved) {
-            idle_since = std::chrono::steady_clock::now();
-        } else if (std::chrono::steady_clock::now() - idle_since > std::chrono::microseconds(200)) {
-            std::this_thread::sleep_for(std::chrono::microseconds(10));
-        } else {
-            std::this_thread::yield();
-        }
-    }
-    return RT_OK;
-}
-
-// each lane's pixels tone-mapped after its last step; the lanes joined back into s
-int WaveRun::finish()
-{
-    const int nl = P.lanes;
-    for (int l = 0; l < nl; l++) {
-        if (fast_ran)
-            HIPCHK(c, hipStreamWaitEvent(L[l].s, b->fev_done, 0));  // (and the fast lane's)
-        if (pass) continue;  // (a progressive pass leaves the pixels paused: rt_progress_resolve tone-maps)
-        if (linear) continue;  // (rt_render_linear: the framebuffer keeps finish_pixel's sum)
-        hipLaunchKernelGGL(k_tonemap, dim3((L[l].n + threads - 1) / threads), dim3(threads), 0, L[l].s, L[l].W);
-        HIPCHK(c, hipGetLastError());
-    }
-    b->last_iters = 0;
-    for (int l = 0; l < nl; l++) {
-        b->last_iters = std::max(b->last_iters, L[l].it);
-        if (l > 0) {
-            HIPCHK(c, hipEventRecord(b->ev_join[l], b->ls[l]));
-            HIPCHK(c, hipStreamWaitEvent(s, b->ev_join[l], 0));
-        }
-    }
-    b->tail_iter = L[0].tail_iter;
-    HIPCHK(c, hipEventRecord(b->ev_done, s));
-    b->done_recorded = true;
-    return RT_OK;
-}
-
-// The run's diagnostics: walk log, iteration counts, per-kernel ms, timeline, RT_DEBUG_FB.
-int WaveRun::report()
-{
-    const int nl = P.lanes;
-    const RtDiag& dg = c->diag;
-    if (wlog) {  // (diagnostics: device 0's records of this render replace the last render's)
-        int32_t nw = 0;
-        HIPCHK(c, hipMemcpyAsync(&nw, b->wlog.p, 4, hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipStreamSynchronize(s));
-        RtDiag& d = c->diag;
-        d.wlog_total = nw;
-        d.wlog.assign((size_t)std::min(nw, d.wlog_cap) * RT_WLOG_FLOATS, 0.0f);
-        if (!d.wlog.empty())
-            HIPCHK(c, hipMemcpy(d.wlog.data(), (char*)b->wlog.p + 256, d.wlog.size() * 4, hipMemcpyDeviceToHost));
-    }
-    if (S && iter_log) {
-        std::vector<int32_t> hq((size_t)6 * RT_MAX_TIMED_ITERS);
-        HIPCHK(c, hipMemcpyAsync(hq.data(), b->iterq.p, hq.size() * 4, hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipStreamSynchronize(s));
-        if (FILE* f = fopen((std::string(iter_log) + ".counts").c_str(), "w")) {
-            const int32_t* h2 = hq.data() + 2 * RT_MAX_TIMED_ITERS;
-            for (int i = 0; i <= L[0].it && i < RT_MAX_TIMED_ITERS; i++)
-                fprintf(f, "%d %d %d %d %d %d %d\n", i, hq[2 * i], hq[2 * i + 1], h2[4 * i], h2[4 * i + 1], h2[4 * i + 2],
-                        h2[4 * i + 3]);
-            fclose(f);
-        }
-    }
-    if (b->timing) {  // per-kernel-class time of this render (HIP events on the launch streams)
-        HIPCHK(c, hipStreamSynchronize(s));
-        FILE* lf = iter_log ? fopen((std::string(iter_log) + ".ms").c_str(), "w") : nullptr;
-        for (int l = 0; l < nl; l++)
-            for (int i = 0; i < L[l].it && i < RT_MAX_TIMED_ITERS; i++)
-                for (int k = 0; k < 2; k++) {
-                    float ms = 0;
-                    HIPCHK(c, hipEventElapsedTime(&ms, L[l].tev[k][i], L[l].tev[k + 1][i]));
-                    const int cls = (k == 1 && i == L[l].tail_iter) ? 2 : k;  // the tail kernel: class "other"
-                    b->kms[cls] += ms;
-                    b->klaunch[cls] += 1;
-                    if (lf && l == 0) {
-                        if (k == 0)
-                            fprintf(lf, "%d %.4f", i, ms);
-                        else
-                            fprintf(lf, " %.4f\n", ms);
-                    }
-                }
-        if (lf) fclose(lf);
-        // RT_TIMELINE=file: every lane's launches on one clock (ms from lane 0's first
-        // k_trace): lane, iteration, k_trace start, k_trace end = k_step start, k_step end,
-        // 1 for the tail kernel (tools/timeline.py); the fast lane's kernel as lane `lanes`,
-        // iteration 0, flag 2
-        // (device index d > 0 of a multi-device context writes file.d: the device threads run concurrently)
-        if (!dg.timeline.empty()) {
-            const char* tl = dg.timeline.c_str();
-            std::string rows;
-            char line[128];
-            for (int l = 0; l < nl; l++)
-                for (int i = 0; i < L[l].it && i < RT_MAX_TIMED_ITERS; i++) {
-                    float t[3];
-                    for (int k = 0; k < 3; k++) HIPCHK(c, hipEventElapsedTime(&t[k], L[0].tev[0][0], L[l].tev[k][i]));
-                    snprintf(line, sizeof line, "%d %d %.4f %.4f %.4f %d\n", l, i, t[0], t[1], t[2],
-                             i == L[l].tail_iter ? 1 : 0);
-                    rows += line;
-                }
-            if (fast_ran) {
-                float t[2];
-                for (int k = 0; k < 2; k++) HIPCHK(c, hipEventElapsedTime(&t[k], L[0].tev[0][0], b->ftev[k]));
-                snprintf(line, sizeof line, "%d 0 %.4f %.4f %.4f 2\n", nl, t[0], t[1], t[1]);
-                rows += line;
-            }
-            const std::string path = b->index > 0 ? std::string(tl) + "." + std::to_string(b->index) : std::string(tl);
-            if (FILE* f = fopen(path.c_str(), "w")) {
-                fwrite(rows.data(), 1, rows.size(), f);
-                fclose(f);
-            }
-        }
-    }
 #if RT_DEBUG_FB
-    {
-        unsigned long long v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        HIPCHK(c, hipStreamSynchronize(s));
-        for (int l = 0; l < nl; l++) HIPCHK(c, hipStreamSynchronize(L[l].s));
-        HIPCHK(c, hipMemcpyFromSymbol(v, HIP_SYMBOL(rt_dbg_fb), sizeof v));
-        int its = 0;
-        for (int l = 0; l < nl; l++) its = std::max(its, L[l].it);
-        fprintf(stderr, "[rt dbg] n=%d iters=%d k_trace fallbacks closest=%llu any=%llu (overflow %llu tie %llu chain %llu; rows %llu) octet parks=%llu closest row drains=%llu\n",
-                n, its, v[0], v[2], v[3], v[4], v[5], v[6], v[1], v[7]);
-        const unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        HIPCHK(c, hipMemcpyToSymbol(HIP_SYMBOL(rt_dbg_fb), z, sizeof z));
-    }
+hipError_t rt_wave_dbg_fb_take(unsigned long long v[8])
+{
+    if (hipError_t e = hipMemcpyFromSymbol(v, HIP_SYMBOL(rt_dbg_fb), 8 * sizeof v[0])) return e;
+    const unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    return hipMemcpyToSymbol(HIP_SYMBOL(rt_dbg_fb), z, sizeof z);
+}
 #endif
-    return RT_OK;
-}
-}  // namespace
 
-int run_wave(rt_context* c, Backend* b, int w, int h, int spp, int bounces, const rtk::PixSrc& src, int n, float4_* fb,
-             hipStream_t s, const WavePass* pass, bool linear)
-{
-    if (n <= 0) return RT_OK;
-    WaveRun R{c, b, w, h, spp, bounces, src, n, fb, s, pass, linear};
-    if (int r = R.begin()) return r;
-    if (int r = R.poll()) return r;
-    if (int r = R.finish()) return r;
-    return R.report();
-}
-
-int rt_wave_resolve(rt_context* c, const float4_* base, const float4_* state, float4_* out, int n, int done, hipStream_t s)
-{
-    hipLaunchKernelGGL(k_resolve, dim3((n + threads - 1) / threads), dim3(threads), 0, s, base, state, out, n, done);
-    HIPCHK(c, hipGetLastError());
-    return RT_OK;
-}
-
-int rt_backend_intersect(rt_context* c, const float* rays, int n, void* out)
-{
-    Backend* b = rt_backend_dev0(c);
-    HIPCHK(c, hipSetDevice(b->device));
-    const size_t br = (size_t)n * 24, bo = (size_t)n * 44;
-    if (int r = ensure(c, b->xy, br + bo)) return r;
-    float* dr = (float*)b->xy.p;
-    int32_t* dout = (int32_t*)((char*)b->xy.p + br);
-    HIPCHK(c, hipMemcpy(dr, rays, br, hipMemcpyHostToDevice));
-    const int threads = 256, blocks = (n + threads - 1) / threads;
-    HIPCHK(c, hipEventRecord(b->ev0, 0));
-    hipLaunchKernelGGL(k_intersect, dim3(blocks), dim3(threads), 0, 0, b->view, dr, dout, n);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(b->ev1, 0));
-    HIPCHK(c, hipEventSynchronize(b->ev1));
-    float ms = 0;
-    HIPCHK(c, hipEventElapsedTime(&ms, b->ev0, b->ev1));
-    c->last_kernel_ms = ms;
-    HIPCHK(c, hipMemcpy(out, dout, bo, hipMemcpyDeviceToHost));
-    return RT_OK;
-}
-
-// Device self-tests of the numerics (libm restatement, IEEE div/sqrt/f64).
-extern "C" int rt_device_libm(int device, int fn, const float* in, const float* in2, float* out, int n)
-{
-    if (hipSetDevice(device) != hipSuccess) return RT_ERR_NODEV;
-    const size_t b = (size_t)n * 4;
-    DevBuf d_in, d_in2, d_out;
-    if (ensure(nullptr, d_in, b) || ensure(nullptr, d_in2, b) || ensure(nullptr, d_out, b)) return RT_ERR_HIP;
-    (void)hipMemcpy(d_in.p, in, b, hipMemcpyHostToDevice);
-    if (in2) (void)hipMemcpy(d_in2.p, in2, b, hipMemcpyHostToDevice);
-    hipLaunchKernelGGL(k_libm, dim3((n + 255) / 256), dim3(256), 0, 0, fn, (const float*)d_in.p, (const float*)d_in2.p,
-                       (float*)d_out.p, n);
-    return hipMemcpy(out, d_out.p, b, hipMemcpyDeviceToHost) == hipSuccess ? RT_OK : RT_ERR_HIP;
-}
-
-// TEST ONLY (include/rt_hip.h): the env-CDF search alone on the context's env, several blocks
-// (each stages its own LDS copy in form 0).
-extern "C" int rt_device_env_search(rt_context* c, int form, const float* values, int n, int* xy_out)
-{
-    if (!c || !c->backend || n <= 0 || !values || !xy_out || form < 0 || form > 1) return RT_ERR_ARG;
-    if (!c->have_env) return RT_ERR_STATE;
-    Backend* b = rt_backend_dev0(c);
-    HIPCHK(c, hipSetDevice(b->device));
-    if (c->dirty) {
-        if (int r = rt_backend_upload(c)) return r;
-        c->dirty = false;
-    }
-    DevBuf v, xy;
-    if (int r = ensure(c, v, (size_t)n * 4)) return r;
-    if (int r = ensure(c, xy, (size_t)n * 8)) return r;
-    HIPCHK(c, hipMemcpy(v.p, values, (size_t)n * 4, hipMemcpyHostToDevice));
-    const int threads = 256, blocks = std::min((n + threads - 1) / threads, 64);
-    hipLaunchKernelGGL(k_env_search, dim3(blocks), dim3(threads), 0, 0, b->view, form, (const float*)v.p, n, (int*)xy.p);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpy(xy_out, xy.p, (size_t)n * 8, hipMemcpyDeviceToHost));
-    return RT_OK;
-}
-
-// Search-BVH query micro-benchmark: rays[n][8] (origin xyz _, direction xyz _),
-// mode bit 0 = any (else closest), bits 1.. = walk variant (0-1 one lane, 2-3 lane + spill,
-// 4-5 quads, 6-7 quads at 8 waves/SIMD, 8-9 rows);
-// reps timed launches (HIP events), mean ms per launch into *ms.
-extern "C" int rt_device_queries(rt_context* c, int mode, const float* rays, int n, int reps, float* out_t,
-                                 int* out_k, double* ms)
-{
-    if (!c || !c->backend || n <= 0 || reps < 1 || mode < 0 || mode > 9) return RT_ERR_ARG;
-    Backend* b = rt_backend_dev0(c);
-    HIPCHK(c, hipSetDevice(b->device));
-    if (c->dirty) {
-        if (int r = rt_backend_upload(c)) return r;
-        c->dirty = false;
-    }
-    int cus = 256;
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, b->device);
-    const int threads = 256, blocks = std::min((n + threads - 1) / threads, cus * 8);
-    const int qblocks = std::min((4 * n + threads - 1) / threads, cus * 16);
-    const int rblocks = std::min((16 * n + threads - 1) / threads, cus * 16);
-    const size_t lanes = (size_t)blocks * threads;
-    DevBuf b_rays, b_t, b_k, b_sr, b_sk;
-    if (int r = ensure(c, b_rays, (size_t)n * 32)) return r;
-    if (int r = ensure(c, b_t, (size_t)n * 4)) return r;
-    if (int r = ensure(c, b_k, (size_t)n * 4)) return r;
-    if (int r = ensure(c, b_sr, lanes * RT_SPILL_FAST * 4)) return r;
-    if (int r = ensure(c, b_sk, lanes * RT_SPILL_FAST * 4)) return r;
-    float4_* d_rays = (float4_*)b_rays.p;
-    float* d_t = (float*)b_t.p;
-    int* d_k = (int*)b_k.p;
-    uint32_t* sr = (uint32_t*)b_sr.p;
-    float* sk = (float*)b_sk.p;
-    HIPCHK(c, hipMemcpy(d_rays, rays, (size_t)n * 32, hipMemcpyHostToDevice));
-    auto launch = [&]() {
-        switch (mode) {
-            case 0: hipLaunchKernelGGL((k_query<false, 0>), dim3(blocks), dim3(threads), 0, 0, b->view, d_rays, d_t, d_k, n, sr, sk); break;
-            case 1: hipLaunchKernelGGL((k_query<true, 0>), dim3(blocks), dim3(threads), 0, 0, b->view, d_rays, d_t, d_k, n, sr, sk); break;
-            case 2: hipLaunchKernelGGL((k_query<false, 1>), dim3(blocks), dim3(threads), 0, 0, b->view, d_rays, d_t, d_k, n, sr, sk); break;
-            case 3: hipLaunchKernelGGL((k_query<true, 1>), dim3(blocks), dim3(threads), 0, 0, b->view, d_rays, d_t, d_k, n, sr, sk); break;
-            case 4: hipLaunchKernelGGL((k_query_quad<false, 1>), dim3(qblocks), dim3(threads), 0, 0, b->view, d_rays, d_t, d_k, n); break;
-            case 5: hipLaunchKernelGGL((k_query_quad<true, 1>), dim3(qblocks), dim3(threads), 0, 0, b->view, d_rays, d_t, d_k, n); break;
-            case 6: hipLaunchKernelGGL((k_query_quad<false, 8>), dim3(qblocks), dim3(threads), 0, 0, b->view, d_rays, d_t, d_k, n); break;
-            case 7: hipLaunchKernelGGL((k_query_quad<true, 8>), dim3(qblocks), dim3(threads), 0, 0, b->view, d_rays, d_t, d_k, n); break;
-            case 8: hipLaunchKernelGGL((k_query_row<false>), dim3(rblocks), dim3(threads), 0, 0, b->view, d_rays, d_t, d_k, n); break;
-            default: hipLaunchKernelGGL((k_query_row<true>), dim3(rblocks), dim3(threads), 0, 0, b->view, d_rays, d_t, d_k, n); break;
-        }
-    };
-    launch();  // warm-up
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(b->ev0, 0));
-    for (int r = 0; r < reps; r++) launch();
-    HIPCHK(c, hipEventRecord(b->ev1, 0));
-    HIPCHK(c, hipEventSynchronize(b->ev1));
-    float t = 0;
-    HIPCHK(c, hipEventElapsedTime(&t, b->ev0, b->ev1));
-    if (ms) *ms = t / reps;
-    HIPCHK(c, hipMemcpy(out_t, d_t, (size_t)n * 4, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(out_k, d_k, (size_t)n * 4, hipMemcpyDeviceToHost));
-    return RT_OK;
-}

@@ -106,7 +106,7 @@ struct WaveView {
     uint8_t* r_heavy;       // [n_slots] (heavy class on) a query of the slot took >= heavy_calls quad trips
     int heavy_calls;        // k_trace's heavy threshold (0: heavy class off; set before wave_carve)
     int spec_cam;           // 1: trace the next sample's camera ray ahead (next_camera); 0: at the sample's start
-    int32_t* counters;      // queue sizes, tickets, live counts (rt_render.hip C_*)
+    int32_t* counters;      // queue sizes, tickets, live counts (rt_wave_layout.h C_*)
     int32_t* r_park;        // [n_slots] queries of the slot parked (the step skips the slot while > 0)
     RayRec* fb_c[2];        // [RK_COUNT n_slots] closest-hit queries left to the exact walk (d.w = kind), by parity
     RayRec* fb_a[2];        // [2 n_slots] occlusion queries left to the exact walk, by parity
@@ -137,7 +137,7 @@ struct WaveView {
     int fast_cap, fast_thr; // fast_cap 0: off (k_tail: the list's length cap)
     int force_fb;           // test knob (RT_FORCE_FALLBACK): a query whose ray hashes to 0 mod force_fb
                             // skips the quad walk and takes the exact octree walk (0: off)
-    int shards, seg_cap;    // queues and live lists: `shards` segments of seg_cap entries (device: rt_render.hip)
+    int shards, seg_cap;    // queues and live lists: `shards` segments of seg_cap entries (device: rt_wave_layout.h)
     const int32_t* act_in;  // active slots this iteration
     int32_t* act_out;
     int n_act_in;

@@ -1,5 +1,6 @@
 """Resource usage (VGPRs, spills, occupancy, LDS) of the product's kernels from the compiler's
-kernel-resource-usage remarks:  python tools/kernel_regs.py [rt_render.hip] [--all] [-- extra hipcc flags]"""
+kernel-resource-usage remarks:  python tools/kernel_regs.py [unit.hip] [--all] [-- extra hipcc flags]
+(default unit: rt_render.hip, the render kernels; the probe kernels are rt_probe.hip)"""
 import os
 import re
 import subprocess
@@ -34,7 +35,7 @@ if __name__ == "__main__":
     args = sys.argv[1:]
     extra = args[args.index("--") + 1:] if "--" in args else []
     args = args[:args.index("--")] if "--" in args else args
-    # --all: every kernel of the unit (rt_display.hip, rt_denoise.hip), not only the wavefront's three classes
+    # --all: every kernel of the unit (rt_probe.hip, rt_display.hip, rt_denoise.hip), not only the wavefront's three classes
     pattern = r"k_" if "--all" in args else r"k_(trace|step|tail)"
     args = [a for a in args if a != "--all"]
     src = args[0] if args else None

@@ -1,4 +1,4 @@
-"""Static instruction split of k_trace (no GPU): compiles rt_render.hip to gfx950 assembly with line
+"""Static instruction split of k_trace (no GPU): compiles rt_render.hip (the render kernels' unit) to gfx950 assembly with line
 tables, attributes every instruction of one kernel to the source function its line lies in (the
 innermost inlined frame the compiler recorded) and sums the functions into the parts of a query's
 life: setup, refill/begin, visit, walk-end (verify, store) and drain. A helper that many callers share
@@ -32,7 +32,7 @@ FLAGS = [*HIPCC_FLAGS, "--cuda-device-only", "-gline-tables-only", "-S"]
 
 # source function -> part of a query's life
 PARTS = {
-    "begin": {"qstate_begin", "rayb_setup", "forced_fallback", "far_origin", "queue_item_at", "queue_item_ptr", "qbase", "queue_prefetch",
+    "begin": {"qstate_begin", "rayb_setup", "forced_fallback", "far_origin", "queue_item_ptr", "qbase", "queue_prefetch",
               "trace_stream:refill", "v3of"},
     "visit": {"quad_visit", "quad_child", "child_record", "box_hit2", "box_hit", "slab_ok", "rt_half", "quad_tri",
               "tri_test_v", "tri_test", "leaf_item", "qdpp", "qdppf", "qor", "qsum", "s_lower", "rec", "key", "set",
