@@ -725,3 +725,95 @@ extern "C" int rt_hostsim_heap_order(const float* keys, int m, int* order_emul, 
 #define RT_BUILD_DEFS ""
 #endif
 extern "C" const char* rt_build_id(void) { return "src=" RT_BUILD_SRC " defs=" RT_BUILD_DEFS " (hostsim)"; }
+
+// What a ray's closest-hit search-BVH walk meets, trip by trip (tests/test_trip_code.py checks with it that
+// its inputs produce the cases they are for): rt_fast.h fast_closest_u with counters, over a stack of
+// RT_HOSTSIM_FAST_CAP entries (32: the quads' RT_HOSTSIM_FAST_CAP). One trip = one item, as a quad takes them. out[n][10]:
+//   [0..4] inner trips with 0, 1, 2, 3, 4 children hit (4 hit: 3 pushed)
+//   [5]    inner trips where two hit children have equal keys (the tie rule decides the push order)
+//   [6]    the deepest stack (entries) the walk reached; with [8] set, the depth at the overflow
+//   [7]    pops that found the stack empty (the walk's end included)
+//   [8]    1 when the bounded stack overflowed (the walk stops: the exact walk answers)
+//   [9]    leaf visits
+extern "C" int rt_hostsim_trip_cases(rt_context* c, const float* rays, int n, int* out)
+{
+    if (!c || n < 0 || (n > 0 && (!rays || !out))) return RT_ERR_ARG;
+    if (!c->have_bvh) return RT_ERR_STATE;
+    const RtSceneView S = rt_host_view(c);
+#pragma omp parallel
+    {
+        rtk::IdxStack<RT_HOSTSIM_FAST_CAP> stk;
+#pragma omp for schedule(dynamic, 64)
+        for (int i = 0; i < n; i++) {
+            const float* r = rays + 6 * (size_t)i;
+            const rtk::V3 o = rtk::v3(r[0], r[1], r[2]), d = rtk::v3(r[3], r[4], r[5]);
+            int* w = out + 10 * (size_t)i;
+            for (int j = 0; j < 10; j++) w[j] = 0;
+            if (rt_isnan(o.x) || rt_isnan(o.y) || rt_isnan(o.z) || rt_isnan(d.x) || rt_isnan(d.y) || rt_isnan(d.z)) continue;
+            rtk::FastHit h;
+            h.t = h.t2 = __builtin_inff();
+            h.k = -1, h.leaf = -1, h.prim = 0x7fffffff, h.tie = false, h.ovf = false;
+            const rtk::RayB rb = rtk::rayb_setup(o, d);
+            int sp = 0, cur = 0;
+            for (;;) {
+                rtk::ItemRecs R;
+                rtk::load_item(S, cur, R);
+                if (cur >= 0) {
+                    const rtk::Bvh4R nd = rtk::node_of(R);
+                    float tn[4], kk[4];
+                    bool hit[4];
+                    int v[4], ix[4] = {0, 1, 2, 3}, nv = 0;
+                    const float tmax = h.t + h.t * RT_T2_WINDOW;
+                    rtk::box4(S, cur, nd, rb, o, d, tmax, tn, hit);
+                    for (int ch = 0; ch < 4; ch++) {
+                        const bool ok = hit[ch] && tn[ch] <= tmax;
+                        kk[ch] = ok ? tn[ch] : __builtin_inff();
+                        v[ch] = nd.cnt[ch] > 0 ? rtk::leaf_item(nd.ref[ch], nd.cnt[ch]) : nd.ref[ch];
+                        nv += ok ? 1 : 0;
+                    }
+                    rtk::sort4(kk, ix);
+                    w[nv]++;
+                    for (int j = 1; j < nv; j++)
+                        if (kk[j] == kk[j - 1]) {
+                            w[5]++;
+                            break;
+                        }
+                    if (sp + nv - 1 > RT_HOSTSIM_FAST_CAP) {
+                        w[6] = sp + nv - 1;
+                        w[8] = 1;
+                        break;
+                    }
+                    for (int j = nv - 1; j >= 1; j--) stk.set(sp++, (uint32_t)v[ix[j]], kk[j]);
+                    if (sp > w[6]) w[6] = sp;
+                    if (nv > 0) {
+                        cur = v[ix[0]];
+                        continue;
+                    }
+                } else {
+                    const int cnt = ((~cur) & 3) + 1;
+                    w[9]++;
+                    for (int j = 0; j < cnt; j++) {
+                        float t;
+                        if (rtk::tri_test_v(rtk::ld3(R.q[3 * j]), rtk::ld3(R.q[3 * j + 1]), rtk::ld3(R.q[3 * j + 2]), o, d, t))
+                            rtk::fast_take(h, t, (int)rt_asuint(R.q[3 * j].w), (int)rt_asuint(R.q[3 * j + 1].w),
+                                           (int)rt_asuint(R.q[3 * j + 2].w), S.brute != 0);
+                    }
+                }
+                const float tmax = h.t + h.t * RT_T2_WINDOW;
+                cur = 0x7fffffff;
+                while (sp > 0) {
+                    --sp;
+                    if (stk.key(sp) <= tmax) {
+                        cur = (int)stk.rec(sp);
+                        break;
+                    }
+                }
+                if (cur == 0x7fffffff) {
+                    w[7]++;
+                    break;
+                }
+            }
+        }
+    }
+    return RT_OK;
+}

@@ -133,6 +133,35 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OCC, 8))) v
     }
 }
 
+// The quad walks' visit counts per query (rt_device_query_trips; tests pin them: the same nodes in the same
+// order take the same counts): out[3 i] = quad_visit calls, out[3 i + 1] = child boxes of the inner trips
+// (4 per node), out[3 i + 2] = triangles of the leaf visits. A far origin (no walk) leaves zeros.
+template <bool ANY>
+__global__ __launch_bounds__(256) void k_query_quad_trips(RtSceneView S, const float4_* __restrict__ rays, int* __restrict__ out, int n)
+{
+    __shared__ uint32_t s_lds[2 * RT_QSTACK * 64];
+    const int q = (int)(threadIdx.x >> 2), sub = (int)(threadIdx.x & 3);
+    rtk::QuadStack<RT_QSTACK, 64> stk{s_lds + q, (float*)s_lds + RT_QSTACK * 64 + q};
+    const int stride = (int)(gridDim.x * blockDim.x) >> 2;
+    for (int i = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 2); i < n; i += stride) {
+        rtk::QState qs;
+        rtk::Stats st;
+        for (int j = 0; j < RT_STAT_COUNT; j++) st.c[j] = 0;
+        int calls = 0, res = 1;
+        if (!rtk::far_origin(S, rtk::v3of(rays[2 * i])) &&
+            rtk::qstate_begin<ANY>(qs, rtk::v3of(rays[2 * i]), rtk::v3of(rays[2 * i + 1]), sub, &st))
+            do {
+                res = rtk::quad_visit<ANY>(S, qs, stk, sub, &st);
+                calls++;
+            } while (res == 0);
+        if (sub == 0) {
+            out[3 * i] = calls;
+            out[3 * i + 1] = (int)st.c[ANY ? RT_STAT_ANY_VOL : RT_STAT_VOL];
+            out[3 * i + 2] = (int)st.c[ANY ? RT_STAT_ANY_TRI : RT_STAT_TRI];
+        }
+    }
+}
+
 // The same through the row walks (rt_row.h row_visit over the 16-wide BVH): 16 lanes per query.
 template <bool ANY>
 __global__ __launch_bounds__(256) void k_query_row(RtSceneView S, const float4_* __restrict__ rays,
@@ -324,5 +353,31 @@ extern "C" int rt_device_queries(rt_context* c, int mode, const float* rays, int
     if (ms) *ms = t / reps;
     HIPCHK(c, hipMemcpy(out_t, d_t, (size_t)n * 4, hipMemcpyDeviceToHost));
     HIPCHK(c, hipMemcpy(out_k, d_k, (size_t)n * 4, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+// TEST ONLY. The quad walks' visit counts (k_query_quad_trips): rays[n][8] as rt_device_queries, any = 0 the
+// closest-hit walk, 1 the occlusion walk; out[n][3] = quad_visit calls, child boxes, leaf triangles.
+extern "C" int rt_device_query_trips(rt_context* c, int any, const float* rays, int n, int* out)
+{
+    if (!c || !c->backend || n <= 0 || !rays || !out || (any != 0 && any != 1)) return RT_ERR_ARG;
+    Backend* b = rt_backend_dev0(c);
+    HIPCHK(c, hipSetDevice(b->device));
+    if (c->dirty) {
+        if (int r = rt_backend_upload(c)) return r;
+        c->dirty = false;
+    }
+    const int threads = 256, qblocks = std::min((4 * n + threads - 1) / threads, 4096);
+    DevBuf b_rays, b_out;
+    if (int r = ensure(c, b_rays, (size_t)n * 32)) return r;
+    if (int r = ensure(c, b_out, (size_t)n * 12)) return r;
+    HIPCHK(c, hipMemcpy(b_rays.p, rays, (size_t)n * 32, hipMemcpyHostToDevice));
+    if (any)
+        hipLaunchKernelGGL((k_query_quad_trips<true>), dim3(qblocks), dim3(threads), 0, 0, b->view, (const float4_*)b_rays.p, (int*)b_out.p, n);
+    else
+        hipLaunchKernelGGL((k_query_quad_trips<false>), dim3(qblocks), dim3(threads), 0, 0, b->view, (const float4_*)b_rays.p, (int*)b_out.p, n);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipDeviceSynchronize());
+    HIPCHK(c, hipMemcpy(out, b_out.p, (size_t)n * 12, hipMemcpyDeviceToHost));
     return RT_OK;
 }

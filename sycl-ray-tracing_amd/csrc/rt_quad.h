@@ -109,9 +109,13 @@ __device__ __forceinline__ QChild quad_child(const RtSceneView& S, int node, int
     const float mn[3] = {a.x, a.y, a.z}, mx[3] = {a.w, b.x, b.y};
     QChild c;
     float tf;
-    c.ok = cnt >= 0 && box_hit2(mn, mx, rb, tmax, c.tn, tf) && c.tn <= tmax;
+    // (every term is evaluated, `&` not `&&`: a wave issues the box and slab arithmetic whatever its
+    // lanes' masks, and the exec-mask regions that skipped it cost more than it does; an empty
+    // child's record only ever feeds comparisons that `cnt >= 0` overrides)
+    const bool box = box_hit2(mn, mx, rb, tmax, c.tn, tf);
+    c.ok = (cnt >= 0) & box & (c.tn <= tmax);
 #if RT_SLAB_QUAD
-    c.ok = c.ok && slab_ok(sl, o, d, c.tn, tf);
+    c.ok = c.ok & slab_ok(sl, o, d, c.tn, tf);
 #else
     (void)o, (void)d;
 #endif
@@ -292,13 +296,44 @@ __device__ __forceinline__ bool scene_brute(const RtSceneView& S)
 {
     return BRUTE == RT_BRUTE_SCENE ? S.brute != 0 : BRUTE == RT_BRUTE_ON;
 }
+// Values of QState.cur that are no item (inner nodes are small non-negative indices, leaf items negative):
+constexpr int RT_CUR_OVF = 0x7ffffffd;   // the bounded stack overflowed: the visit returns -1
+constexpr int RT_CUR_POP = 0x7ffffffe;   // no child hit: pop
+constexpr int RT_CUR_NONE = 0x7fffffff;  // the stack is empty: the walk is over
+// Is cur an inner node (the trip loops go on)?
+__device__ __forceinline__ bool cur_inner(int cur) { return (unsigned)cur < (unsigned)RT_CUR_OVF; }
+
+// The closest-hit walks' pop (quads and rows): the topmost entry whose key lies within the window becomes
+// the next item, the entries above it are dropped; RT_CUR_NONE when none is left. The loop's body is
+// straight-line: the entry at a clamped depth is read whatever sp is (depth 0 of an empty stack is the
+// group's own word, read and ignored) and selected by compare, so a trip of the loop is one LDS round
+// trip (key and item together, profiles/r06_pop_pairing_ab.json) and no divergent region.
+template <class STK>
+__device__ __forceinline__ int pop_within(const STK& stk, int& sp, float tmax)
+{
+    int nxt = RT_CUR_NONE;
+    bool more;
+    do {
+        const bool has = sp > 0;
+        const int d = has ? sp - 1 : 0;
+        const float kk = stk.key(d);
+        const int rr = (int)stk.rec(d);
+        rt_pin(rr);  // (else the compiler sinks the item's read past the loop: two round trips)
+        const bool take = has & (kk <= tmax);
+        nxt = take ? rr : nxt;
+        sp = d;
+        more = has & !take;
+    } while (more);
+    return nxt;
+}
+
 template <bool ANY, int DESC = RT_VISIT_DESCEND, bool PAIR = true, int BRUTE = RT_BRUTE_SCENE, class QSTK>
 __device__ __forceinline__ int quad_visit(const RtSceneView& S, QState& q, QSTK& stk, int sub, Stats* st)
 {
     FastHit& h = q.h;
     const bool brute = scene_brute<BRUTE>(S);
 #pragma unroll 1
-    for (int dd = 0; dd < DESC && q.cur >= 0; dd++) {
+    for (int dd = 0; dd < DESC && cur_inner(q.cur); dd++) {
         if (ANY) {
             // the current node and the stack top's inner node in one trip
             constexpr int NW = PAIR ? 2 : 1;
@@ -307,15 +342,12 @@ __device__ __forceinline__ int quad_visit(const RtSceneView& S, QState& q, QSTK&
             int m = 1;
 #pragma unroll
             for (int j = 1; j < NW; j++) {
-                nd[j] = -1;
-                if (m == j && q.sp > 0) {
-                    const int t = (int)stk.rec(q.sp - 1);
-                    if (t >= 0) {
-                        nd[j] = t;
-                        q.sp--;
-                        m++;
-                    }
-                }
+                // (the top entry read at a clamped depth and taken by select: no divergent region)
+                const int t = (int)stk.rec(q.sp > 0 ? q.sp - 1 : 0);
+                const bool tk = (m == j) & (q.sp > 0) & (t >= 0);
+                nd[j] = tk ? t : -1;
+                q.sp -= tk ? 1 : 0;
+                m += tk ? 1 : 0;
             }
             if (st && sub == 0) st->c[RT_STAT_ANY_VOL] += 4 * m;
             float4_ r0[NW], r1[NW];
@@ -340,42 +372,35 @@ __device__ __forceinline__ int quad_visit(const RtSceneView& S, QState& q, QSTK&
 #endif
             }
             int base = 0, first = 0;
-            bool any_first = false;
 #pragma unroll
             for (int j = 0; j < NW; j++) {
                 const int ref = (int)rt_asuint(r1[j].z), cnt = (int)rt_asuint(r1[j].w);
                 const float mn[3] = {r0[j].x, r0[j].y, r0[j].z}, mx[3] = {r0[j].w, r1[j].x, r1[j].y};
                 float tn, tf;
+                // (every term evaluated, quad_child)
+                bool ok = (j < m) & (cnt >= 0) & box_hit2(mn, mx, q.rb, __builtin_inff(), tn, tf);
 #if RT_SLAB_QUAD
-                const bool ok = j < m && cnt >= 0 && box_hit2(mn, mx, q.rb, __builtin_inff(), tn, tf) &&
-                                slab_ok(sl[j], q.o, q.d, tn, tf);
-#else
-                const bool ok = j < m && cnt >= 0 && box_hit2(mn, mx, q.rb, __builtin_inff(), tn, tf);
+                ok = ok & slab_ok(sl[j], q.o, q.d, tn, tf);
 #endif
                 const int item = cnt > 0 ? leaf_item(ref, cnt) : ref;
                 const int o = ok ? 1 : 0;
                 const int o1 = qdpp<RT_QX1>(o), o2 = qdpp<RT_QX2>(o), o3 = qdpp<RT_QX3>(o);
                 const int pre = base + (s_lower(sub, 1) ? o1 : 0) + (s_lower(sub, 2) ? o2 : 0) + (s_lower(sub, 3) ? o3 : 0);
                 // hit k of the 4 * NW slots (node 0's children, then node 1's, ...) goes to
-                // stack position sp + k - 1; hit 0 is next
-                if (ok && pre > 0) {
-                    if (q.sp + pre - 1 < QSTK::CAP) stk.set_rec(q.sp + pre - 1, (uint32_t)item);
-                }
-                if (ok && pre == 0) {
-                    first = item;
-                    any_first = true;
-                }
+                // stack position sp + k - 1; hit 0 is next. The store is the only predicated
+                // instruction: one condition, no nested region.
+                if (ok & (pre > 0) & (q.sp + pre - 1 < QSTK::CAP)) stk.set_rec(q.sp + pre - 1, (uint32_t)item);
+                // (at most one of a lane's slots is hit 0: a hit in an earlier node makes base > 0)
+                first |= (ok & (pre == 0)) ? item : 0;
                 base += o + o1 + o2 + o3;
             }
             const int nv = base;
-            if (q.sp + nv - 1 > QSTK::CAP) return -1;
-            if (nv > 0) {
-                q.sp += nv - 1;
-                q.cur = qor(any_first ? first : 0);
-                continue;
-            }
-            q.cur = 0x7ffffffe;
-            break;
+            // the trip's outcome by selects: overflow (-1 below), the next item, or a pop
+            const bool ovf = q.sp + nv - 1 > QSTK::CAP;
+            const int nxt = qor(first);
+            q.sp += ((nv > 0) & !ovf) ? nv - 1 : 0;
+            q.cur = ovf ? RT_CUR_OVF : nv > 0 ? nxt : RT_CUR_POP;
+            continue;  // (the loop goes on while cur is an inner node)
         }
         if (st && sub == 0) st->c[RT_STAT_VOL] += 4;
         const float tmax = h.t + h.t * RT_T2_WINDOW;
@@ -387,19 +412,17 @@ __device__ __forceinline__ int quad_visit(const RtSceneView& S, QState& q, QSTK&
         const int rank = (k1 < key || (k1 == key && s1 < sub) ? 1 : 0) + (k2 < key || (k2 == key && s2 < sub) ? 1 : 0) +
                          (k3 < key || (k3 == key && s3 < sub) ? 1 : 0);
         const int nv = qsum(c.ok ? 1 : 0);
-        if (q.sp + nv - 1 > QSTK::CAP) return -1;
-        // far children on the stack, nearest of them on top (rank 1 at sp + nv - 2)
-        if (c.ok && rank > 0) stk.set(q.sp + nv - 1 - rank, (uint32_t)c.item, key);
-        if (nv > 0) {
-            q.sp += nv - 1;
-            q.cur = qor(c.ok && rank == 0 ? c.item : 0);
-            continue;
-        }
-        // no child hit: pop (below)
-        q.cur = 0x7ffffffe;
-        break;
+        const bool ovf = q.sp + nv - 1 > QSTK::CAP;
+        // far children on the stack, nearest of them on top (rank 1 at sp + nv - 2): every lane has its
+        // entry and its position, and the store is the only predicated instruction of the push
+        if (c.ok & (rank > 0) & !ovf) stk.set(q.sp + nv - 1 - rank, (uint32_t)c.item, key);
+        // the trip's outcome by selects: overflow (-1 below), the nearest child, or no child hit (pop below)
+        const int nxt = qor((c.ok & (rank == 0)) ? c.item : 0);
+        q.sp += ((nv > 0) & !ovf) ? nv - 1 : 0;
+        q.cur = ovf ? RT_CUR_OVF : nv > 0 ? nxt : RT_CUR_POP;
     }
-    if (q.cur >= 0 && q.cur != 0x7ffffffe) return 0;  // (descended DESC times; still inner)
+    if (cur_inner(q.cur)) return 0;  // (descended DESC times; still inner)
+    if (q.cur == RT_CUR_OVF) return -1;
     if (q.cur < 0) {
         if (st && sub == 0) st->c[ANY ? RT_STAT_ANY_TRI : RT_STAT_TRI] += ((~q.cur) & 3) + 1;
         int k, leaf, prim;
@@ -475,22 +498,10 @@ __device__ __forceinline__ int quad_visit(const RtSceneView& S, QState& q, QSTK&
         q.cur = (int)stk.rec(--q.sp);
         return 0;
     }
-    const float tmax = h.t + h.t * RT_T2_WINDOW;
-    int nxt = 0x7fffffff;
-    while (q.sp > 0) {
-        --q.sp;
-        // the entry's key and item read together: one LDS round trip per pop, not two (cfg2 -0.4
-        // to -0.7 %; two entries per round trip measured no better: profiles/r06_pop_pairing_ab.json)
-        const float kk = stk.key(q.sp);
-        const int rr = (int)stk.rec(q.sp);
-        rt_pin(rr);  // (else the compiler sinks the item's read past the loop: two round trips)
-        if (kk <= tmax) {
-            nxt = rr;
-            break;
-        }
-    }
-    q.cur = nxt;
-    return nxt == 0x7fffffff ? 1 : 0;
+    // the entry's key and item read together: one LDS round trip per pop, not two (cfg2 -0.4
+    // to -0.7 %; two entries per round trip measured no better: profiles/r06_pop_pairing_ab.json)
+    q.cur = pop_within(stk, q.sp, h.t + h.t * RT_T2_WINDOW);
+    return q.cur == RT_CUR_NONE ? 1 : 0;
 }
 
 // The closest-hit answer of a finished walk: true with (t, k), false when the exact

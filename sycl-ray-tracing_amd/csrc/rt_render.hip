@@ -576,7 +576,6 @@ __device__ __forceinline__ void trace_stream(const rtk::WaveView& W, const RtSce
                                              rtk::Stats* ps, const QPrefetch& pf)
 {
     static_assert(G == 4 || G == 16, "quads or rows");
-    constexpr unsigned long long ALL_IDLE = G == 4 ? 0x1111111111111111ull : 0x0001000100010001ull;
     constexpr int REFILL = G == 4 ? RT_TRACE_REFILL : 1;  // idle groups that trigger a refill
     const int lane = lane_id(), qd = lane / G;
     int sub = lane & (G - 1);
@@ -627,53 +626,66 @@ __device__ __forceinline__ void trace_stream(const rtk::WaveView& W, const RtSce
             }
         }
     };
+    // The common trip is one ballot and one branch around the visit: `trig` is the number of idle groups
+    // at which the wave has something else to do, and it changes only where `exhausted` does, at a refill.
+    //   stream not exhausted: REFILL idle groups (all groups idle is at least that many) -> refill;
+    //   stream exhausted: every group idle -> done, or, with quads, few enough walking (W.drain_rows) -> rows.
+    // (a group is idle or walking: popcount(idle) + popcount(walking) = NGROUPS, so "at most drain_rows walking"
+    // is "at least NGROUPS - drain_rows idle")
+    constexpr int NGROUPS = 64 / G;
+    static_assert(REFILL <= NGROUPS, "all groups idle triggers a refill");
+    const int trig_done = NGROUPS - (G == 4 && W.drain_rows > 0 ? min(W.drain_rows, NGROUPS) : 0);
+    int trig = exhausted ? trig_done : REFILL;  // (uniform)
     for (;;) {
         const unsigned long long bidle = __ballot(!active && sub == 0);
-        if (!exhausted && (__popcll(bidle) >= REFILL || bidle == ALL_IDLE)) {
-            if (!active) {
-                const int j = cursor + __popcll(bidle & ((1ull << (qd * G)) - 1ull));  // this group's stream position
-                const int idx = (wg + (j >> 4) * wn) * 16 + (j & 15);
-                if (idx < total) {
-                    const int slot = j - cursor;  // (0..15: the buffer starts at the cursor)
-                    // (the compiler does not order LDS reads after direct-to-LDS loads: wait for
-                    // the vector-memory counter here, vmcnt(0), before reading the buffer)
-                    __builtin_amdgcn_s_waitcnt(0x0F70);
-                    rtk::RayRec r;
-                    r.o = pf.buf[2 * slot];
-                    r.d = pf.buf[2 * slot + 1];
-                    const int kind = pf.kind[slot];
-                    target = (rt_asuint(r.o.w) << 3) | (uint32_t)kind;
-                    if (forced_fallback(W, r.o, r.d)) {
-                        if (sub == 0) {
-                            r.d.w = rt_asfloat(target & 7u);
-                            fbl[atomicAdd(fbn, 1)] = r;
-                            atomicAdd(&W.r_park[target >> 3], 1);
+        if (__popcll(bidle) >= trig) {
+            if (!exhausted) {
+                if (!active) {
+                    const int j = cursor + __popcll(bidle & ((1ull << (qd * G)) - 1ull));  // this group's stream position
+                    const int idx = (wg + (j >> 4) * wn) * 16 + (j & 15);
+                    if (idx < total) {
+                        const int slot = j - cursor;  // (0..15: the buffer starts at the cursor)
+                        // (the compiler does not order LDS reads after direct-to-LDS loads: wait for
+                        // the vector-memory counter here, vmcnt(0), before reading the buffer)
+                        __builtin_amdgcn_s_waitcnt(0x0F70);
+                        rtk::RayRec r;
+                        r.o = pf.buf[2 * slot];
+                        r.d = pf.buf[2 * slot + 1];
+                        const int kind = pf.kind[slot];
+                        target = (rt_asuint(r.o.w) << 3) | (uint32_t)kind;
+                        if (forced_fallback(W, r.o, r.d)) {
+                            if (sub == 0) {
+                                r.d.w = rt_asfloat(target & 7u);
+                                fbl[atomicAdd(fbn, 1)] = r;
+                                atomicAdd(&W.r_park[target >> 3], 1);
+                            }
+                        } else if (rtk::qstate_begin<ANY>(q, rtk::v3of(r.o), rtk::v3of(r.d), sub, ps)) {
+                            active = true;
+                            q.calls = 0;
+                        } else if (sub == 0) {  // (a NaN ray: no hit)
+                            if (ANY)
+                                rtk::finish_any(W, target, false);
+                            else
+                                rtk::finish_closest(W, target, q.o, q.d, -1.0f, -1);
                         }
-                    } else if (rtk::qstate_begin<ANY>(q, rtk::v3of(r.o), rtk::v3of(r.d), sub, ps)) {
-                        active = true;
-                        q.calls = 0;
-                    } else if (sub == 0) {  // (a NaN ray: no hit)
-                        if (ANY)
-                            rtk::finish_any(W, target, false);
-                        else
-                            rtk::finish_closest(W, target, q.o, q.d, -1.0f, -1);
                     }
                 }
+                cursor += __popcll(bidle);
+                exhausted = (wg + (cursor >> 4) * wn) * 16 >= total;
+                // (every lane has read its record: the buffer is free for the next 16 positions)
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                if (!exhausted) queue_prefetch(W, s_pre, pf, first, cursor, wg, wn, total);
+                if (STATS && lane == 0) ps->c[RT_STAT_REFILLS]++;
+                trig = exhausted ? trig_done : REFILL;
             }
-            cursor += __popcll(bidle);
-            exhausted = (wg + (cursor >> 4) * wn) * 16 >= total;
-            // (every lane has read its record: the buffer is free for the next 16 positions)
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            if (!exhausted) queue_prefetch(W, s_pre, pf, first, cursor, wg, wn, total);
-            if (STATS && lane == 0) ps->c[RT_STAT_REFILLS]++;
+            const unsigned long long bact = __ballot(active && sub == 0);
+            if (!bact) {
+                if (exhausted) break;
+                continue;
+            }
+            if (G == 4 && W.drain_rows > 0 && exhausted && __popcll(bact) <= W.drain_rows) break;  // to rows (below)
         }
-        const unsigned long long bact = __ballot(active && sub == 0);
-        if (!bact) {
-            if (exhausted) break;
-            continue;
-        }
-        if (G == 4 && W.drain_rows > 0 && exhausted && __popcll(bact) <= W.drain_rows) break;  // to rows (below)
         if (STATS) {  // SIMT slots of this trip: 16 quads, the active ones used
             if (active && sub == 0) ps->c[exhausted ? RT_STAT_DRAIN_VISITS : RT_STAT_QUAD_VISITS]++;
             if (lane == 0) ps->c[exhausted ? RT_STAT_DRAIN_SLOTS : RT_STAT_WAVE_SLOTS] += 64 / G;
@@ -732,7 +744,7 @@ __device__ __forceinline__ void trace_stream(const rtk::WaveView& W, const RtSce
         active = ract;
 #if RT_DRAIN_RESTART == 1  // (study build: the row walk restarts at the root, the quad's stack dropped)
         q.sp = 0;
-        if (q.cur != 0x7fffffff) q.cur = 0;
+        if (q.cur != rtk::RT_CUR_NONE) q.cur = 0;
 #elif RT_DRAIN_RESTART == 2  // (study build: a new walk of the same ray, nothing of the quad's kept)
         if (ract) rtk::qstate_begin<ANY>(q, q.o, q.d, sub, nullptr);
 #elif RT_DRAIN_RESTART == 3  // (study build: the ray's box-test form recomputed from o and d)
@@ -741,7 +753,7 @@ __device__ __forceinline__ void trace_stream(const rtk::WaveView& W, const RtSce
         q.h.t = __builtin_inff(), q.h.t2 = __builtin_inff(), q.h.k = ANY ? 0 : -1, q.h.leaf = -1;
         q.h.prim = 0x7fffffff, q.h.tie = false, q.h.ovf = false;
         q.sp = 0;
-        if (q.cur != 0x7fffffff) q.cur = 0;
+        if (q.cur != rtk::RT_CUR_NONE) q.cur = 0;
 #endif
         while (__any(active)) {
             if (STATS) {

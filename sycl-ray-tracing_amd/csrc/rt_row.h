@@ -99,7 +99,7 @@ __device__ __forceinline__ int row_visit(const RtSceneView& S, QState& q, RSTK& 
     FastHit& h = q.h;
     const bool brute = scene_brute<BRUTE>(S);
 #pragma unroll 1
-    for (int dd = 0; dd < DESC && q.cur >= 0; dd++) {
+    for (int dd = 0; dd < DESC && cur_inner(q.cur); dd++) {
         const float4_* p = (const float4_*)(S.bvh16 + (size_t)q.cur * RT_BVH16_W + sub);
         const float4_ a = p[0], b = p[1];
 #if RT_SLAB_ROW
@@ -144,10 +144,10 @@ __device__ __forceinline__ int row_visit(const RtSceneView& S, QState& q, RSTK& 
             q.cur = row_or(first ? item : 0);
             continue;
         }
-        q.cur = 0x7ffffffe;  // no child hit: pop (below)
+        q.cur = RT_CUR_POP;  // no child hit: pop (below)
         break;
     }
-    if (q.cur >= 0 && q.cur != 0x7ffffffe) return 0;  // (descended DESC times; still inner)
+    if (cur_inner(q.cur)) return 0;  // (descended DESC times; still inner)
     if (q.cur < 0) {
         // this leaf and up to three leaves right below it on the stack: four lanes each
         int l0 = q.cur, l1 = 0, l2 = 0, l3 = 0, nl = 1;
@@ -233,21 +233,9 @@ __device__ __forceinline__ int row_visit(const RtSceneView& S, QState& q, RSTK& 
         q.cur = (int)stk.rec(--q.sp);
         return 0;
     }
-    const float tmax = h.t + h.t * RT_T2_WINDOW;
-    int nxt = 0x7fffffff;
-    while (q.sp > 0) {
-        --q.sp;
-        // the entry's key and item read together: one LDS round trip per pop, not two (rt_quad.h)
-        const float kk = stk.key(q.sp);
-        const int rr = (int)stk.rec(q.sp);
-        rt_pin(rr);  // (else the compiler sinks the item's read past the loop: two round trips)
-        if (kk <= tmax) {
-            nxt = rr;
-            break;
-        }
-    }
-    q.cur = nxt;
-    return nxt == 0x7fffffff ? 1 : 0;
+    // (rt_quad.h pop_within: key and item in one LDS round trip, a straight-line loop body)
+    q.cur = pop_within(stk, q.sp, h.t + h.t * RT_T2_WINDOW);
+    return q.cur == RT_CUR_NONE ? 1 : 0;
 }
 
 }  // namespace rtk

@@ -131,12 +131,14 @@ _SIGS = {
     "rt_device_last_iterations": (I, [P]),
     "rt_device_exact_handovers": (I, [P, P, I]),
     "rt_device_queries": (I, [P, I, P, I, I, P, P, P]),
+    "rt_device_query_trips": (I, [P, I, P, I, P]),
     "rt_device_denoise_pass_ms": (I, [P, I, P, I]),
     "rt_device_display_kernel_ms": (I, [P, I, I, P, P, P, P, I, P]),
     # hostsim-only extra
     "rt_hostsim_heap_order": (I, [P, I, P, P]),
     "rt_hostsim_fast_queries": (I, [P, P, I, P, P]),
     "rt_hostsim_leaf_hits": (I, [P, P, I, P]),
+    "rt_hostsim_trip_cases": (I, [P, P, I, P]),
 }
 
 # rt_query modes (include/rt_hip.h)

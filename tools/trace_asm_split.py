@@ -4,7 +4,13 @@ innermost inlined frame the compiler recorded) and sums the functions into the p
 life: setup, refill/begin, visit, walk-end (verify, store) and drain. A helper that many callers share
 (dot, rt_max, a ballot) and compiler-generated code without a line count with the part around them.
 
-  python tools/trace_asm_split.py [--kernel SUBSTR] [--json OUT] [--functions] [-- extra hipcc flags]
+  python tools/trace_asm_split.py [--kernel SUBSTR] [--json OUT] [--functions] [--csrc DIR] [-- extra hipcc flags]
+
+The visit is split further into the pieces of a trip ("visit_parts"): box test, ranking, push, pop,
+leaf and loop control (quad_visit's own loop and returns, and trace_stream's trip loop around it), by
+marker strings in quad_visit (VISIT_MARKS; --csrc DIR splits another checkout's csrc/ with the same
+markers). A marker that is not found in quad_visit is reported on stderr: the pieces after it are
+then counted with the piece before.
 
 The counts are static (instructions in the code object, each once), not executed counts: they say
 how long each region is for a wave that enters it, which is what a divergent region costs however
@@ -22,6 +28,7 @@ import json
 import os
 import re
 import subprocess
+import sys
 import tempfile
 
 from kernel_regs import HIPCC, HIPCC_FLAGS
@@ -46,18 +53,39 @@ PARTS = {
               "row_bits", "rdpp", "rdppf", "RowInQuadStack"},
 }
 FUNC_PART = {f: p for p, fs in PARTS.items() for f in fs}
+# the visit's pieces: helper functions by name, quad_visit's own lines by marker (VISIT_MARKS, in source order)
+VISIT_SUB = {
+    "box": {"quad_child", "child_record", "box_hit2", "box_hit", "slab_ok", "rt_half", "leaf_item", "quad_visit:box"},
+    "rank": {"s_lower", "quad_visit:rank"},
+    "push": {"set", "set_rec", "quad_visit:push"},
+    "pop": {"pop_within", "rec", "key", "quad_visit:pop"},
+    "leaf": {"quad_tri", "tri_test_v", "tri_test", "fuzzy_tri", "quad_visit:leaf"},
+    "loopctl": {"trace_stream:loop", "quad_visit:loopctl", "cur_inner"},
+}
+FUNC_SUB = {f: p for p, fs in VISIT_SUB.items() for f in fs}
+VISIT_MARKS = [("for (int dd = 0;", "loopctl"), ("int nd[NW];", "pop"), ("float4_ r0[NW], r1[NW];", "box"),
+               ("const int o = ok ? 1 : 0;", "rank"), ("stack position sp + k - 1", "push"),
+               ("st->c[RT_STAT_VOL] += 4;", "box"), ("rank by (key, lane)", "rank"), ("const int nv = qsum(", "push"),
+               ("// (descended DESC times; still inner)", "loopctl"), ("if (q.cur < 0) {", "leaf"),
+               ("// (h.k = 0: no occluder)", "pop")]
 DEF = re.compile(r"^(?!\s|#|//|namespace|struct|class|template|using|typedef|static_assert|\}|\{)[^;]*?\b([A-Za-z_]\w*)\s*\(")
 
 
 def function_map(path):
     """line number -> enclosing function (column-0 definitions; trace_stream split into its phases)."""
-    out, cur, phase = {}, None, None
+    out, cur, phase, seen = {}, None, None, set()
     with open(path, errors="replace") as f:
         for n, line in enumerate(f, 1):
             m = DEF.match(line) or re.match(r"^struct\s+(\w+)[^;]*$", line)  # (a struct's members count with it)
             if m and not line.rstrip().endswith(";"):
                 cur, phase = m.group(1), None
-            if cur == "trace_stream":
+            if cur == "quad_visit":
+                for mark, ph in VISIT_MARKS:
+                    if mark in line:
+                        phase = ph
+                        seen.add(mark)
+                out[n] = "quad_visit:" + (phase or "loopctl")
+            elif cur == "trace_stream":
                 if "auto finish = [&]" in line:
                     phase = "finish"
                 elif phase == "finish" and line.startswith("    };"):
@@ -73,11 +101,15 @@ def function_map(path):
                 out[n] = "trace_stream:" + (phase or "setup")
             else:
                 out[n] = cur
+    if "quad_visit" in out.values() or any(str(v).startswith("quad_visit:") for v in out.values()):
+        for mark, ph in VISIT_MARKS:
+            if mark not in seen:
+                print(f"trace_asm_split: marker {mark!r} ({ph}) not found in quad_visit of {path}", file=sys.stderr)
     return out
 
 
-def split(kernel, extra):
-    src = os.path.join(CSRC, "rt_render.hip")
+def split(kernel, extra, csrc=CSRC):
+    src = os.path.join(csrc, "rt_render.hip")
     with tempfile.TemporaryDirectory() as td:
         asm = os.path.join(td, "k.s")
         subprocess.run([HIPCC, *FLAGS, *extra, src, "-o", asm], check=True, stderr=subprocess.DEVNULL)
@@ -95,7 +127,9 @@ def split(kernel, extra):
     parts = collections.Counter()
     spill = collections.Counter()
     kinds = collections.defaultdict(collections.Counter)
-    func, part = "?", "setup"  # (helpers such as dot or rt_max, and line-0 code, count with the part around them)
+    func, part, sub = "?", "setup", "loopctl"  # (helpers such as dot or rt_max, and line-0 code, count with the part around them)
+    vparts = collections.Counter()
+    vkinds = collections.defaultdict(collections.Counter)
     for l in lines[start + 1:end]:
         s = l.strip()
         m = re.match(r"\.loc\s+(\d+)\s+(\d+)", s)
@@ -104,18 +138,24 @@ def split(kernel, extra):
             if os.path.isfile(path) and path not in maps:
                 maps[path] = function_map(path)
             func = maps.get(path, {}).get(int(m.group(2))) or os.path.basename(path) + ":?"
-            part = FUNC_PART.get(func, part)
+            part = FUNC_PART.get(func.split(":")[0] if func.startswith("quad_visit:") else func, part)
+            sub = FUNC_SUB.get(func, sub)
             continue
         if not s or s.startswith((".", ";", "//")) or s.endswith(":"):
             continue
         op = s.split()[0]
         cnt[func] += 1
         parts[part] += 1
-        kinds[part]["valu" if op.startswith("v_") else "salu" if op.startswith("s_") else "mem"] += 1
+        kind = "valu" if op.startswith("v_") else "salu" if op.startswith("s_") else "mem"
+        kinds[part][kind] += 1
+        if part == "visit":
+            vparts[sub] += 1
+            vkinds[sub]["branch" if op.startswith(("s_cbranch", "s_branch")) else kind] += 1
         if op.startswith(("scratch_load", "scratch_store")):
             spill[part + (":load" if "load" in op else ":store")] += 1
     return {"kernel": name, "instructions": sum(cnt.values()), "parts": dict(parts),
             "kinds": {p: dict(k) for p, k in kinds.items()}, "spill_ops": dict(spill),
+            "visit_parts": dict(vparts), "visit_kinds": {p: dict(k) for p, k in vkinds.items()},
             "functions": dict(cnt.most_common())}
 
 
@@ -124,11 +164,14 @@ if __name__ == "__main__":
     ap.add_argument("--kernel", default="k_traceILb0ELb1ELi4ELi0E")
     ap.add_argument("--json")
     ap.add_argument("--functions", action="store_true")
+    ap.add_argument("--csrc", default=CSRC, help="the csrc/ directory to compile (default: this checkout's)")
     args, rest = ap.parse_known_args()
-    r = split(args.kernel, [a for a in rest if a != "--"])
+    r = split(args.kernel, [a for a in rest if a != "--"], args.csrc)
     print(r["kernel"], "instructions", r["instructions"])
     for p, n in sorted(r["parts"].items(), key=lambda x: -x[1]):
         print(f"  {p:8s} {n:6d}  {100.0 * n / r['instructions']:5.1f} %  {r['kinds'][p]}")
+    for p, n in sorted(r["visit_parts"].items(), key=lambda x: -x[1]):
+        print(f"    visit/{p:8s} {n:6d}  {100.0 * n / r['instructions']:5.1f} %  {r['visit_kinds'][p]}")
     print("  spill ops", r["spill_ops"])
     if args.functions:
         for f, n in r["functions"].items():
