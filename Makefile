@@ -72,7 +72,7 @@ $(LIB)/librt_hostsim.so: $(OBJ)/rt_hostsim.o $(OBJ)/rt_scene.host.o $(OBJ)/rt_im
 oracle/liboracle.so: oracle/cpu_oracle.cpp
 	$(MAKE) -C oracle liboracle.so
 
-build/libm_check: tests/native/libm_check.cpp $(SRC)/rt_libm.h $(SRC)/rt_fp.h
+build/libm_check: tests/native/libm_check.cpp $(SRC)/rt_libm.h $(SRC)/rt_fp.h $(SRC)/rt_digest.h
 	@mkdir -p build
 	$(CXX) -std=c++17 -O2 -fopenmp -ffp-contract=off -I$(SRC) $< -o $@ -lm
 

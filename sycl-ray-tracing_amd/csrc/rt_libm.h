@@ -27,9 +27,14 @@
 // __powf_log2_data, __sincosf_table, __inv_pio4, fdlibm coefficients).
 //
 // Validation: tests/native/libm_check.cpp compares every function with the
-// host libm over all 2^32 float inputs (powf over all x at the two
-// exponents the kernel uses; atan2f over dense structured pairs), and the
-// GPU test tests/test_gpu_libm.py re-checks the device build.
+// host libm over all 2^32 float inputs (powf over all x at eight fixed
+// exponents and over y at twelve fixed bases; atan2f over x at eighteen
+// fixed y, over y at the same values as x, and over random pairs). The
+// device build is held to the same glibc by digest: tests/test_gpu_libm.py
+// sums a hash of (result, input) over each block of 2^22 inputs of the same
+// sweeps on the GPU (rt_digest.h, k_libm_digest) and compares the 1024 words
+// per sweep with tests/golden/libm_digests.npz, which tools/gen_golden_libm.py
+// recorded from glibc; tests/test_numerics.py re-derives some of its blocks.
 #pragma once
 
 #include "rt_fp.h"

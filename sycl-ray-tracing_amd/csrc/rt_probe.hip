@@ -1,13 +1,15 @@
 // rt_probe.hip — kernels no render launches, with their C hooks: rt_intersect's exact walk
 // (k_intersect, rt_backend_intersect: product API), the search-BVH query micro-benchmark
 // (k_query*, rt_device_queries) and the device self-tests of the numerics and the env-CDF
-// search (k_libm, k_env_search). A translation unit of its own, so that an edit here leaves
+// search (k_libm, k_libm_digest, k_env_search). A translation unit of its own, so that an edit here leaves
 // the render kernels of rt_render.hip compiled exactly as they were.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <vector>
 
 #include "rt_backend_hip.h"
+#include "rt_digest.h"
 #include "rt_wave.h"
 #include "rt_wave_layout.h"
 #include "rt_quad.h"
@@ -214,9 +216,48 @@ __global__ void k_libm(int fn, const float* __restrict__ in, const float* __rest
         case 7: r = rt_sqrtf(x); break;
         case 8: r = x / in2[i]; break;
         case 9: r = (float)((double)x * 0.31830988618379067154 / (double)in2[i]); break;
+        case 11: {  // rt_sincosf's sine
+            float c;
+            rt_sincosf(x, r, c);
+            break;
+        }
+        case 12: {  // rt_sincosf's cosine
+            float s;
+            rt_sincosf(x, s, r);
+            break;
+        }
+        case 13: r = rt_atan2f(x, 1.0f); break;  // atanf
         default: r = rtk::slab_div(x, 1.0 / (double)in2[i]); break;  // the slab quotient
     }
     out[i] = r;
+}
+
+// Digest of a whole sweep of rt_libm.h (rt_digest.h; tests/test_gpu_libm.py): RT_DIGEST_SPLIT workgroups
+// per digest block of 2^22 indices, each over its own 2^19 consecutive indices. A thread sums the terms
+// of its indices (every stride-th, 256 stride apart: a wave's lanes take neighbouring arguments, so they
+// mostly take one branch) in a register; the workgroup's total goes to partial[blockIdx.x], and the host
+// adds the partials of a block.
+#define RT_DIGEST_SPLIT 8
+template <int FN>
+__global__ __launch_bounds__(256) void k_libm_digest(uint32_t param, uint32_t stride, uint64_t* __restrict__ partial)
+{
+    __shared__ uint64_t s_sum[256];
+    rtlibm::lds_tables_init();
+    const float p = rt_asfloat(param);
+    const uint32_t span = (1u << rtdigest::BLOCK_BITS) / RT_DIGEST_SPLIT;
+    const uint32_t base = blockIdx.x * span;  // (gridDim.x = 1024 * RT_DIGEST_SPLIT: below 2^32)
+    uint64_t sum = 0;
+    for (uint32_t k = threadIdx.x * stride; k < span; k += 256 * stride) {
+        const uint32_t i = base + k;
+        sum += rtdigest::term(i, rtdigest::eval<FN>(i, p));
+    }
+    s_sum[threadIdx.x] = sum;
+    __syncthreads();
+    for (uint32_t h = 128; h > 0; h >>= 1) {
+        if (threadIdx.x < h) s_sum[threadIdx.x] += s_sum[threadIdx.x + h];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) partial[blockIdx.x] = s_sum[0];
 }
 
 // TEST ONLY (rt_device_env_search): cdf_search alone over caller values. form 0: as the shading
@@ -271,6 +312,35 @@ extern "C" int rt_device_libm(int device, int fn, const float* in, const float* 
     hipLaunchKernelGGL(k_libm, dim3((n + 255) / 256), dim3(256), 0, 0, fn, (const float*)d_in.p, (const float*)d_in2.p,
                        (float*)d_out.p, n);
     return hipMemcpy(out, d_out.p, b, hipMemcpyDeviceToHost) == hipSuccess ? RT_OK : RT_ERR_HIP;
+}
+
+// TEST ONLY, like rt_device_libm (gfx950 library only, not in include/rt_hip.h): the digest words
+// out[1024] of one sweep of rt_libm.h on the device (rt_digest.h): sweep = the function code
+// (rtdigest::Fn), param = the fixed argument's bits, stride = a power of two, every stride-th index summed.
+extern "C" int rt_device_libm_digest(int device, int sweep, uint32_t param, int stride, uint64_t* out)
+{
+    if (!out || sweep < 0 || sweep >= rtdigest::FN_COUNT || stride < 1 || stride > 256 || (stride & (stride - 1))) return RT_ERR_ARG;
+    if (hipSetDevice(device) != hipSuccess) return RT_ERR_NODEV;
+    const int groups = rtdigest::BLOCKS * RT_DIGEST_SPLIT;
+    DevBuf d_part;
+    if (ensure(nullptr, d_part, (size_t)groups * 8)) return RT_ERR_HIP;
+    uint64_t* part = (uint64_t*)d_part.p;
+#define RT_DIGEST_CASE(FN) \
+    case FN: hipLaunchKernelGGL((k_libm_digest<FN>), dim3(groups), dim3(256), 0, 0, param, (uint32_t)stride, part); break;
+    switch (sweep) {
+        RT_DIGEST_CASE(0) RT_DIGEST_CASE(1) RT_DIGEST_CASE(2) RT_DIGEST_CASE(3) RT_DIGEST_CASE(4) RT_DIGEST_CASE(5)
+        RT_DIGEST_CASE(6) RT_DIGEST_CASE(7) RT_DIGEST_CASE(8) RT_DIGEST_CASE(9) RT_DIGEST_CASE(10) RT_DIGEST_CASE(11)
+    }
+#undef RT_DIGEST_CASE
+    if (hipGetLastError() != hipSuccess) return RT_ERR_HIP;
+    std::vector<uint64_t> h((size_t)groups);
+    if (hipMemcpy(h.data(), part, h.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) return RT_ERR_HIP;
+    for (int b = 0; b < rtdigest::BLOCKS; b++) {
+        uint64_t s = 0;
+        for (int k = 0; k < RT_DIGEST_SPLIT; k++) s += h[(size_t)b * RT_DIGEST_SPLIT + k];
+        out[b] = s;
+    }
+    return RT_OK;
 }
 
 // TEST ONLY (include/rt_hip.h): the env-CDF search alone on the context's env, several blocks

@@ -125,6 +125,7 @@ _SIGS = {
     "rt_write_hdr": (I, [ctypes.c_char_p, P, I, I, I]),
     # product-only extras
     "rt_device_libm": (I, [I, I, P, P, P, I]),
+    "rt_device_libm_digest": (I, [I, I, ctypes.c_uint32, I, P]),
     "rt_device_last_kernel_ms": (ctypes.c_double, [P]),
     "rt_device_kernel_timing": (I, [P, I, P, P]),
     "rt_device_set_lanes": (I, [P, I]),

@@ -39,7 +39,7 @@ def test_library_exports_every_symbol(which):
 
 def test_product_exports_device_extras():
     L = _capi.lib()
-    for s in ("rt_device_libm", "rt_device_last_kernel_ms"):
+    for s in ("rt_device_libm", "rt_device_libm_digest", "rt_device_last_kernel_ms"):
         assert getattr(L, s, None) is not None
 
 

@@ -57,6 +57,31 @@ def test_edge_values():
     dc.case_edges(True)
 
 
+@pytest.mark.parametrize("gamma", dc.GAMMAS + (1.8,))
+@pytest.mark.parametrize("exposure", dc.EXPOSURES)
+@pytest.mark.parametrize("buffer", ["model", "edge"])
+def test_display_against_glibc(buffer, exposure, gamma):
+    """rt_display's rgb is display_pixel's operations in numpy float32, in its order, with glibc's expf and powf
+    (through ctypes) where it calls rt_libm's, and 1 / gamma the float division rt_display forms: bit for bit, NaN
+    matching NaN. The gfx950 kernel is held to this build bitwise (tests/test_display_gpu.py), so the display stage
+    is chained to glibc at caller-chosen parameters."""
+    import libm_cases as lc
+    m = lc.glibc()
+    lin = dc.model_buffer() if buffer == "model" else dc.edge_buffer()
+    s = dc.unbound(True)
+    got, _ = dc.display(s, lin, exposure, gamma, want=("rgba",))
+    s.close()
+    e = np.float32(exposure)
+    inv_gamma = float(np.float32(1.0) / np.float32(gamma))
+    with np.errstate(all="ignore"):
+        arg = (-lin[..., :3]) * e
+        ex = np.array([m.expf(float(v)) for v in arg.ravel()], np.float32).reshape(arg.shape)
+        tm = np.float32(1.0) + (-ex)
+        want = np.array([m.powf(float(v), inv_gamma) for v in tm.ravel()], np.float32).reshape(tm.shape)
+    assert np.array_equal(lc.np_canon(got[..., :3]), lc.np_canon(want)), f"{buffer} e={exposure} g={gamma}: rgb vs glibc"
+    dc.assert_bits(got[..., 3], dc.model_alpha(lin, exposure), "alpha vs numpy float32")
+
+
 @pytest.mark.parametrize("shape", dc.SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
 def test_rgba8_and_shapes(shape):
     dc.case_shape(True, *shape)
