@@ -44,7 +44,8 @@ $(OBJ)/rt_hostsim.o: $(SRC)/rt_hostsim.cpp $(HDRS) $(ALL_SRC)
 #   rt_denoise   the post stage (feature pass + filter)
 #   rt_query     the ray queries (rt_query / rt_query_device)
 #   rt_display   the display stage (tone-map + 8-bit conversion, linear resolve)
-HIP_UNITS := rt_render rt_wave_run rt_probe rt_denoise rt_query rt_display
+#   rt_noise     a tracked progression's fold and noise estimate
+HIP_UNITS := rt_render rt_wave_run rt_probe rt_denoise rt_query rt_display rt_noise
 $(HIP_UNITS:%=$(OBJ)/%.o): $(OBJ)/%.o: $(SRC)/%.hip $(HDRS)
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
@@ -129,6 +130,7 @@ hostsim-variant: $(OBJ)/rt_imageio.host.o
 #   query_shim_test     query_closest / query_any against rt_intersect      tests/test_query_shim.py
 #   progress_shim_test  render_progressive against render()                 tests/test_progress_shim.py
 #   display_shim_test   display(render_linear()) against render()           tests/test_display_shim.py
+#   noise_test          progress_track_noise / progress_noise against the C ABI tests/test_noise_shim.py
 REFDIR ?= /root/reference
 REFOBJ := oracle/_ref/objO2
 REFOBJS := $(REFOBJ)/bvh.o $(REFOBJ)/flattened_bvh.o $(REFOBJ)/triangle.o $(REFOBJ)/vec.o $(REFOBJ)/color.o \

@@ -29,6 +29,7 @@
 #include <mutex>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "rt_hip.h"
@@ -139,6 +140,7 @@ public:
         std::lock_guard<std::mutex> lk(m_mu);
         sync_materials();
         check(rt_progress_begin(m_ctx, m_width, m_height, m_render_samples, m_max_bounces, m_frame_buffer.data(), 0, 1));
+        if (m_track) check(rt_progress_noise_track(m_ctx));
         for (int done = 0; done < m_render_samples;) {
             int info[8];
             if (rt_progress_advance(m_ctx, pass_samples, nullptr) != RT_OK ||
@@ -151,6 +153,35 @@ public:
             if (!on_pass(static_cast<const Image&>(m_frame_buffer), done, m_render_samples)) break;
         }
         rt_progress_end(m_ctx);
+    }
+
+    // The noise estimate of a progression (rt_progress_noise_track, rt_progress_noise), for the
+    // on_pass callback of render_progressive_tracked below. progress_track_noise: while a
+    // progression has no sample yet (render_progressive_tracked calls it). progress_noise: after at
+    // least two passes; stats.tiles_over == 0 means every 8x8 tile's error is at or below the
+    // threshold. Neither takes the kernel's lock: on_pass runs under it.
+    // context(): the C ABI's handle, for the calls the class does not wrap (rt_progress_noise's pixel
+    // and tile maps, the device forms); on_pass may use it, other threads must not meanwhile.
+    rt_context* context() const { return m_ctx; }
+    void progress_track_noise() { check(rt_progress_noise_track(m_ctx)); }
+    void progress_noise(float threshold, rt_noise_stats& stats) const
+    {
+        check(rt_progress_noise(m_ctx, threshold, &stats, nullptr, nullptr));
+    }
+
+    // render_progressive with the progression tracked: on_pass may call progress_noise from the
+    // second pass on and return false to stop at a threshold.
+    template <class F>
+    void render_progressive_tracked(int pass_samples, F&& on_pass)
+    {
+        m_track = true;
+        try {
+            render_progressive(pass_samples, std::forward<F>(on_pass));
+        } catch (...) {
+            m_track = false;
+            throw;
+        }
+        m_track = false;
     }
 
     // Thread-safe like the reference's (whose render() calls it from an OpenMP parallel-for,
@@ -270,6 +301,7 @@ private:
     Image& m_frame_buffer;
     const std::vector<SimpleMaterial>& m_materials_buffer;
     std::vector<char> m_materials_sent;
+    bool m_track = false;     // render_progressive_tracked: the progression render_progressive begins is tracked
     mutable std::mutex m_mu;  // one call on the context at a time (ray_trace_pixel is const and may be threaded)
 };
 

@@ -59,6 +59,16 @@ typedef struct rt_display_params {
     float gamma;         /* finite and > 0; the reference's 2.2f (render_kernel.cpp:178) */
     int flip_y;          /* rows of the 8-bit output reversed, as write_image_png writes them */
 } rt_display_params;
+/* What rt_progress_noise reports about the frame. */
+typedef struct rt_noise_stats {
+    float max_tile;      /* the largest tile error */
+    int tiles;           /* 8x8 tiles of the row shard */
+    int tiles_over;      /* tiles whose error is > threshold */
+    int nonfinite;       /* in-frame pixels whose error is not finite (they count 0 in their tile) */
+    int samples_a;       /* samples in the A passes (the even-numbered ones) */
+    int samples_b;       /* ... and in the B passes */
+    int passes;          /* passes so far */
+} rt_noise_stats;
 
 /* ---------------------------------------------------------------- context */
 int rt_create(int device, rt_context** out);
@@ -392,6 +402,46 @@ int rt_display(rt_context* ctx, int w, int h, const float* linear_rgba, const rt
 int rt_display_device(rt_context* ctx, int w, int h, const void* d_linear, const rt_display_params* params,
                       void* d_rgba_out, void* d_rgba8_out, void* stream);
 int rt_write_hdr(const char* path, const float* rgba, int width, int height, int flip_y);
+
+/* ------------------------------------------- noise estimate of a progression
+ * How noisy the preview is, so that a caller can stop at a threshold instead of guessing the
+ * sample count. A tracked progression keeps one more float4 per pixel, `half`: the rgb sum of
+ * the samples rendered by its A passes (fourth word 0). Passes are counted from 0 over the
+ * rt_progress_advance calls that rendered a sample; the even ones are A passes, the odd ones B
+ * passes, with nA and nB samples. Around an A pass, on the pass's stream:
+ *     before   half.c = half.c - state.c        after   half.c = half.c + state.c
+ * so half gains what the pass added to the state. With N = nA + nB, in float32, no contraction,
+ * IEEE division and square root, per pixel:
+ *     m.c = state.c / (float)N          a.c = half.c / (float)nA
+ *     d   = (|m.r - a.r| + |m.g - a.g|) + |m.b - a.b|
+ *     e   = (k * d) / sqrtf(0.01f + ((m.r + m.g) + m.b)),     k = sqrtf((float)nA / (float)nB)
+ * The base plays no part. Tiles are 8x8 pixels of the shard's local rows (tile (tx, ty): columns
+ * 8tx.., local rows 8ty..; th = ceil(rows_local / 8), tw = ceil(w / 8)); element l of a tile is
+ * pixel (8tx + l % 8, 8ty + l / 8), 0 when outside the frame or when e is not finite; the 64
+ * elements are summed pairwise (v = v[0::2] + v[1::2], six times) and divided by the tile's
+ * in-frame pixel count.
+ *
+ * rt_progress_noise_track: turns tracking on for the running progression. RT_ERR_STATE without
+ *   one or once a sample is done; a second call is harmless. Whatever ends a progression ends
+ *   its tracking.
+ * rt_progress_noise: stats (required), pixel_err (rows_local*w floats: e as computed, non-finite
+ *   values included; or NULL) and tile_err (th*tw floats, or NULL). Waits. RT_ERR_STATE when the
+ *   progression is not tracked or nA == 0 or nB == 0 (fewer than two passes); RT_ERR_ARG for a
+ *   threshold that is not finite and >= 0 or a NULL stats.
+ * rt_progress_noise_device: device buffers (4-byte aligned) on `stream`, no wait. d_stats is
+ *   eight int32 words {tiles, tiles_over, nonfinite, bits of max_tile, nA, nB, passes, 0}.
+ * Neither form changes any state. rt_last_kernel_ms reports the query's time (the device form:
+ * -1, read rt_device_last_kernel_ms after synchronizing).
+ *
+ * Checkpoints: rt_progress_save of a tracked progression writes format version 2: the 10-word
+ * header with version 2, {passes, nA} as two int32 words, then base, state and half. An
+ * untracked one writes version 1 as before. rt_progress_load takes both; a version-2 checkpoint
+ * loads as a tracked progression and continues as the uninterrupted one would. RT_ERR_ARG for a
+ * size that does not match, nA outside 0..done or passes < 0. */
+int rt_progress_noise_track(rt_context* ctx);
+int rt_progress_noise(rt_context* ctx, float threshold, rt_noise_stats* stats, float* pixel_err, float* tile_err);
+int rt_progress_noise_device(rt_context* ctx, float threshold, void* d_stats, void* d_pixel_err, void* d_tile_err,
+                             void* stream);
 
 /* Counters of the last render when enabled (RT_STAT_* order, rt_device.h);
  * with n up to 2 * RT_STAT_COUNT the second block is the share of the

@@ -577,8 +577,18 @@ int rt_backend_progress_advance(rt_context* c, int first, int stop, void* stream
     const rtk::PixSrc src{P.w, P.off, P.stride, nullptr};
     // (the framebuffer pointer of the pass is never used: it names the state, valid memory of the same size)
     const WavePass pass{(float4_*)b->pg_state.p, first, P.total};
+    // a tracked progression's A pass: half -= state ahead of it and half += state behind it, on its stream
+    const bool fold = P.next_is_a();
     HIPCHK(c, hipEventRecord(b->ev0, s));
+    if (fold) {
+        if (b->done_recorded) HIPCHK(c, hipStreamWaitEvent(s, b->ev_done, 0));  // (the last pass wrote the state)
+        if (int r = rt_noise_fold(c, (float4_*)b->pg_half.p, pass.state, (int)P.npx(), false, s)) return r;
+    }
     if (int r = run_wave(c, b, P.w, P.h, stop, P.bounces, src, (int)P.npx(), pass.state, s, &pass)) return r;
+    if (fold) {
+        if (int r = rt_noise_fold(c, (float4_*)b->pg_half.p, pass.state, (int)P.npx(), true, s)) return r;
+        HIPCHK(c, hipEventRecord(b->ev_done, s));  // (resolves, queries and the next pass wait for the fold too)
+    }
     HIPCHK(c, hipEventRecord(b->ev1, s));
     c->last_kernel_ms = -1.0;  // read with rt_device_last_kernel_ms after the caller synchronizes
     return finish_stats(c, b, s);
@@ -634,6 +644,32 @@ void rt_backend_progress_end(rt_context* c)
     release(b->pg_base);
     release(b->pg_state);
     release(b->pg_out);
+    release(b->pg_half);
+    release(b->pg_noise);
+}
+
+int rt_backend_progress_track(rt_context* c, const float* half)
+{
+    Backend* b = be(c);
+    DeviceScope sc;
+    if (int r = sc.enter(c, b->device)) return r;
+    if (int r = progress_quiesce(c, b)) return r;
+    const size_t bytes = c->prog.npx() * sizeof(float4_);
+    if (int r = ensure(c, b->pg_half, bytes)) return r;
+    if (half) HIPCHK(c, hipMemcpy(b->pg_half.p, half, bytes, hipMemcpyHostToDevice));
+    else HIPCHK(c, hipMemset(b->pg_half.p, 0, bytes));
+    HIPCHK(c, hipDeviceSynchronize());  // (a pass may start on any stream)
+    return RT_OK;
+}
+
+int rt_backend_progress_read_half(rt_context* c, float* half)
+{
+    Backend* b = be(c);
+    DeviceScope sc;
+    if (int r = sc.enter(c, b->device)) return r;
+    if (int r = progress_quiesce(c, b)) return r;
+    HIPCHK(c, hipMemcpy(half, b->pg_half.p, c->prog.npx() * sizeof(float4_), hipMemcpyDeviceToHost));
+    return RT_OK;
 }
 
 Backend* rt_backend_dev0(rt_context* c) { return be(c); }

@@ -7,6 +7,7 @@
 //   rt_probe.hip    rt_intersect's kernel and the test / measurement kernels no render launches
 //   rt_denoise.hip  the post stage          rt_query.hip  the ray queries
 //   rt_display.hip  the display stage and the linear resolve
+//   rt_noise.hip    a tracked progression's fold and noise estimate
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -133,6 +134,7 @@ struct Backend {
     DevBuf xy;        // pixel list (rt_render_pixels)
     DevBuf fb;        // host-fb staging
     DevBuf pg_base, pg_state, pg_out;  // a progression (rt_progress_*): base values, paused state, host-resolve staging
+    DevBuf pg_half, pg_noise;          // a tracked one: the A passes' sum; the host noise query's stat words and maps
     DevBuf disp;      // rt_display with host pointers: the frame (in, float out in place), then the 8-bit output
     DevBuf shard;     // multi-device renders: the root's N blocks of rows_max rows (scatter source /
                       // gather target); device d >= 1: its block
@@ -196,5 +198,7 @@ int rt_wave_resolve(rt_context* c, const float4_* base, const float4_* state, fl
 // rt_display.hip k_resolve_linear: out[i] = base[i] + state[i].rgb / done, the base's alpha (not tone-mapped)
 int rt_display_resolve_linear(rt_context* c, const float4_* base, const float4_* state, float4_* out, int n, int done,
                               hipStream_t s);
+// rt_noise.hip k_noise_fold: half[i].rgb -= state[i].rgb (add: +=), half[i].w = 0
+int rt_noise_fold(rt_context* c, float4_* half, const float4_* state, int n, bool add, hipStream_t s);
 size_t rt_wave_counter_bytes();
 size_t rt_wave_readback_bytes();

@@ -10,6 +10,7 @@
 
 #include "rt_context.h"
 #include "rt_denoise.h"
+#include "rt_noise.h"
 
 namespace {
 std::mutex g_err_mu;
@@ -776,7 +777,8 @@ int rt_set_intersect_mode(rt_context* c, int use_bvh)
 
 // ------------------------------------------------- progressive rendering
 #define RT_PROGRESS_MAGIC 0x47505452  // "RTPG"
-#define RT_PROGRESS_VERSION 1
+#define RT_PROGRESS_VERSION 1         // an untracked progression: header, base, state
+#define RT_PROGRESS_VERSION_TRACKED 2 // a tracked one: header, {passes, nA}, base, state, half
 #define RT_PROGRESS_HEADER 10         // int32 words: magic, version, the eight info words
 
 static bool ctx_is_multi(const rt_context* c) { return c->devices.size() > 1 || (c->force_multi && !c->devices.empty()); }
@@ -833,6 +835,10 @@ int rt_progress_advance(rt_context* c, int samples, void* stream)
     // (rt_render_variants or rt_set_stats since the last pass: the bound tables go up again)
     if (int r = check_ready(c, P.w, P.h, P.total, P.bounces)) return r;
     if (int r = rt_backend_progress_advance(c, P.done, stop, stream)) return r;
+    if (P.tracked) {  // (the backend folded this pass into half if it was an A pass)
+        if (P.next_is_a()) P.n_a += stop - P.done;
+        P.passes++;
+    }
     P.done = stop;
     return RT_OK;
 }
@@ -878,15 +884,22 @@ long rt_progress_save(rt_context* c, void* buf, long capacity)
     if (int r = progress_active(c, "rt_progress_save")) return r;
     const RtProgress& P = c->prog;
     const size_t px = P.npx() * sizeof(float4_);
-    const long size = (long)(RT_PROGRESS_HEADER * 4 + 2 * px);
+    const size_t extra = P.tracked ? 8 : 0, nbuf = P.tracked ? 3 : 2;
+    const long size = (long)(RT_PROGRESS_HEADER * 4 + extra + nbuf * px);
     if (!buf || capacity < size) return size;
-    const int32_t hd[RT_PROGRESS_HEADER] = {RT_PROGRESS_MAGIC, RT_PROGRESS_VERSION, P.w, P.h, P.total, P.done, P.bounces,
-                                            P.off, P.stride, P.rows};
+    const int32_t hd[RT_PROGRESS_HEADER] = {RT_PROGRESS_MAGIC, P.tracked ? RT_PROGRESS_VERSION_TRACKED : RT_PROGRESS_VERSION,
+                                            P.w, P.h, P.total, P.done, P.bounces, P.off, P.stride, P.rows};
     std::memcpy(buf, hd, sizeof hd);
+    if (P.tracked) {
+        const int32_t tr[2] = {P.passes, P.n_a};
+        std::memcpy((char*)buf + sizeof hd, tr, sizeof tr);
+    }
     // (the payload need not be aligned for float in the caller's buffer: staged)
-    std::vector<float> tmp(2 * px / 4);
+    std::vector<float> tmp(nbuf * px / 4);
     if (int r = rt_backend_progress_read(c, tmp.data(), tmp.data() + px / 4)) return r;
-    std::memcpy((char*)buf + sizeof hd, tmp.data(), 2 * px);
+    if (P.tracked)
+        if (int r = rt_backend_progress_read_half(c, tmp.data() + 2 * px / 4)) return r;
+    std::memcpy((char*)buf + sizeof hd + extra, tmp.data(), nbuf * px);
     return size;
 }
 
@@ -899,22 +912,90 @@ int rt_progress_load(rt_context* c, const void* buf, long bytes)
     int32_t hd[RT_PROGRESS_HEADER];
     std::memcpy(hd, buf, sizeof hd);
     if (hd[0] != RT_PROGRESS_MAGIC) return rt_fail(c, RT_ERR_ARG, "rt_progress_load: not a progression checkpoint (magic)");
-    if (hd[1] != RT_PROGRESS_VERSION) return rt_fail(c, RT_ERR_ARG, "rt_progress_load: unknown format version");
+    if (hd[1] != RT_PROGRESS_VERSION && hd[1] != RT_PROGRESS_VERSION_TRACKED)
+        return rt_fail(c, RT_ERR_ARG, "rt_progress_load: unknown format version");
+    const bool tracked = hd[1] == RT_PROGRESS_VERSION_TRACKED;
+    const size_t extra = tracked ? 8 : 0, nbuf = tracked ? 3 : 2;
     const int w = hd[2], h = hd[3], total = hd[4], done = hd[5], bounces = hd[6], off = hd[7], stride = hd[8], rows = hd[9];
     if (int r = progress_frame(c, "rt_progress_load", w, h, total, bounces, off, stride)) return r;
     if (done < 0 || done > total) return rt_fail(c, RT_ERR_ARG, "rt_progress_load: done is outside 0..total");
     const size_t px = (size_t)((h - off + stride - 1) / stride) * w * sizeof(float4_);
-    if (rows != (h - off + stride - 1) / stride || (size_t)bytes != sizeof hd + 2 * px)
+    if (rows != (h - off + stride - 1) / stride || (size_t)bytes != sizeof hd + extra + nbuf * px)
         return rt_fail(c, RT_ERR_ARG, "rt_progress_load: the size does not match the header");
-    std::vector<float> tmp(2 * px / 4);
-    std::memcpy(tmp.data(), (const char*)buf + sizeof hd, 2 * px);
+    int32_t tr[2] = {0, 0};  // passes, nA
+    if (tracked) {
+        std::memcpy(tr, (const char*)buf + sizeof hd, sizeof tr);
+        if (tr[0] < 0) return rt_fail(c, RT_ERR_ARG, "rt_progress_load: a negative pass count");
+        if (tr[1] < 0 || tr[1] > done) return rt_fail(c, RT_ERR_ARG, "rt_progress_load: the A passes' samples are outside 0..done");
+    }
+    std::vector<float> tmp(nbuf * px / 4);
+    std::memcpy(tmp.data(), (const char*)buf + sizeof hd + extra, nbuf * px);
     progress_drop(c);
     progress_install(c, w, h, total, done, bounces, off, stride);
-    if (int r = rt_backend_progress_begin(c, tmp.data(), tmp.data() + px / 4)) {
+    int r = rt_backend_progress_begin(c, tmp.data(), tmp.data() + px / 4);
+    if (!r && tracked) r = rt_backend_progress_track(c, tmp.data() + 2 * px / 4);
+    if (r) {
         progress_drop(c);
         return r;
     }
+    c->prog.tracked = tracked;
+    c->prog.passes = tr[0], c->prog.n_a = tr[1];
     return RT_OK;
+}
+
+// ---- the noise estimate of a tracked progression (rt_noise.h)
+int rt_progress_noise_track(rt_context* c)
+{
+    if (int r = progress_active(c, "rt_progress_noise_track")) return r;
+    RtProgress& P = c->prog;
+    if (P.tracked) return RT_OK;
+    if (P.done > 0)
+        return rt_fail(c, RT_ERR_STATE, "rt_progress_noise_track: samples are done already (track before the first pass)");
+    if (int r = rt_backend_progress_track(c, nullptr)) return r;
+    P.tracked = true;
+    P.passes = P.n_a = 0;
+    return RT_OK;
+}
+
+static int noise_ready(rt_context* c, const char* fn, float threshold, rtk::NoiseArgs& A)
+{
+    const std::string f = fn;
+    if (int r = progress_active(c, fn)) return r;
+    const RtProgress& P = c->prog;
+    if (!P.tracked) return rt_fail(c, RT_ERR_STATE, f + ": the progression is not tracked (rt_progress_noise_track)");
+    const int n_a = P.n_a, n_b = P.done - P.n_a;
+    if (n_a <= 0 || n_b <= 0) return rt_fail(c, RT_ERR_STATE, f + ": needs a sample in both halves (two passes)");
+    if (!std::isfinite(threshold) || !(threshold >= 0.0f)) return rt_fail(c, RT_ERR_ARG, f + ": the threshold is not finite and >= 0");
+    A.n_all = (float)(n_a + n_b);
+    A.n_a = (float)n_a;
+    A.k = rt_sqrtf((float)n_a / (float)n_b);
+    A.threshold = threshold;
+    A.samples_a = n_a, A.samples_b = n_b, A.passes = P.passes;
+    return RT_OK;
+}
+
+int rt_progress_noise(rt_context* c, float threshold, rt_noise_stats* stats, float* pixel_err, float* tile_err)
+{
+    rtk::NoiseArgs A;
+    if (int r = noise_ready(c, "rt_progress_noise", threshold, A)) return r;
+    if (!stats) return rt_fail(c, RT_ERR_ARG, "rt_progress_noise: stats is NULL");
+    int32_t st[8];
+    if (int r = rt_backend_progress_noise(c, A, st, pixel_err, tile_err, false, nullptr)) return r;
+    stats->max_tile = rt_asfloat((uint32_t)st[3]);
+    stats->tiles = st[0], stats->tiles_over = st[1], stats->nonfinite = st[2];
+    stats->samples_a = st[4], stats->samples_b = st[5], stats->passes = st[6];
+    return RT_OK;
+}
+
+int rt_progress_noise_device(rt_context* c, float threshold, void* d_stats, void* d_pixel_err, void* d_tile_err,
+                             void* stream)
+{
+    rtk::NoiseArgs A;
+    if (int r = noise_ready(c, "rt_progress_noise_device", threshold, A)) return r;
+    if (!d_stats) return rt_fail(c, RT_ERR_ARG, "rt_progress_noise_device: d_stats is NULL");
+    if ((uintptr_t)d_stats % 4 != 0 || (uintptr_t)d_pixel_err % 4 != 0 || (uintptr_t)d_tile_err % 4 != 0)
+        return rt_fail(c, RT_ERR_ARG, "rt_progress_noise_device: the buffers must be 4-byte aligned");
+    return rt_backend_progress_noise(c, A, (int32_t*)d_stats, (float*)d_pixel_err, (float*)d_tile_err, true, stream);
 }
 
 void rt_progress_end(rt_context* c) { progress_drop(c); }

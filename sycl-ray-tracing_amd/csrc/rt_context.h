@@ -57,11 +57,19 @@ struct RtDiag {
 // passes. `done` is uniform over the pixels. The buffers (base values and paused state, one
 // float4 per pixel of the row shard each) belong to the backend: on the device for gfx950,
 // the two vectors here for the hostsim build.
+// Tracked (rt_progress_noise_track): the backend keeps one more buffer, `half`, the rgb sum of the
+// samples of the A passes (rt_noise.h). `passes` counts the advances that rendered a sample, from
+// 0; the even ones are A passes and n_a is their samples, so the B passes' are done - n_a.
 struct RtProgress {
     bool active = false;
     int w = 0, h = 0, total = 0, done = 0, bounces = 0, off = 0, stride = 1, rows = 0;
-    std::vector<float4_> base, state;  // (hostsim only)
+    bool tracked = false;
+    int passes = 0, n_a = 0;
+    std::vector<float4_> base, state, half;  // (hostsim only)
     size_t npx() const { return (size_t)rows * w; }
+    int tiles_w() const { return (w + 7) / 8; }
+    int tiles_h() const { return (rows + 7) / 8; }
+    bool next_is_a() const { return tracked && (passes & 1) == 0; }
 };
 
 struct rt_context {
@@ -161,6 +169,19 @@ int rt_backend_progress_advance(rt_context* ctx, int first, int stop, void* stre
 int rt_backend_progress_resolve(rt_context* ctx, float* host_fb, void* dev_fb, void* stream, bool linear = false);
 int rt_backend_progress_read(rt_context* ctx, float* base, float* state);
 void rt_backend_progress_end(rt_context* ctx);
+// A tracked progression (ctx->prog.tracked is set by the caller once track succeeds). track: the
+// half buffer, prog.npx() float4 from `half` (host) or zeroes for null. advance folds the state into
+// it around a pass for which prog.next_is_a() holds, on the pass's stream. read_half: back to the
+// host (waits). noise: the estimate of rt_noise.h from the state and half; stats: 8 int32 words;
+// pixel_err (rows * w floats) and tile_err (tiles_h * tiles_w floats) may be null. device = false:
+// host buffers, waits; true: device buffers on `stream`, no wait (hostsim: host pointers).
+namespace rtk {
+struct NoiseArgs;
+}
+int rt_backend_progress_track(rt_context* ctx, const float* half);
+int rt_backend_progress_read_half(rt_context* ctx, float* half);
+int rt_backend_progress_noise(rt_context* ctx, const rtk::NoiseArgs& args, int32_t* stats, float* pixel_err,
+                              float* tile_err, bool device, void* stream);
 
 int rt_fail(rt_context* ctx, int code, const std::string& msg);
 // RtDiag from the environment (rt_create*)

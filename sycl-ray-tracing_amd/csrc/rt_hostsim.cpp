@@ -17,6 +17,7 @@
 #include "rt_context.h"
 #include "rt_denoise.h"
 #include "rt_display.h"
+#include "rt_noise.h"
 #include "rt_query.h"
 #include "rt_wave.h"
 
@@ -391,10 +392,65 @@ int rt_backend_progress_advance(rt_context* c, int first, int stop, void*)
     const rtk::PixSrc src{P.w, P.off, P.stride, nullptr};
     std::fill(c->stats, c->stats + RT_STAT_COUNT, 0ull);
     const double t0 = omp_get_wtime();
+    const bool fold = P.next_is_a();  // (a tracked progression's A pass: rt_noise.h)
+    const long n = (long)P.npx();
+    if (fold)
+        for (long i = 0; i < n; i++) P.half[i] = rtk::fold_pixel(P.half[i], P.state[i], false);
     const int r = run_wave_host(c, P.w, P.h, stop, P.bounces, src, (int)P.npx(), P.state.data(), c->stats, nullptr,
                                 P.state.data(), first, P.total);
+    if (fold && !r)
+        for (long i = 0; i < n; i++) P.half[i] = rtk::fold_pixel(P.half[i], P.state[i], true);
     c->last_kernel_ms = (omp_get_wtime() - t0) * 1e3;
     return r;
+}
+
+int rt_backend_progress_track(rt_context* c, const float* half)
+{
+    RtProgress& P = c->prog;
+    P.half.assign(P.npx(), float4_{0.0f, 0.0f, 0.0f, 0.0f});
+    if (half) std::memcpy(P.half.data(), half, P.npx() * sizeof(float4_));
+    return RT_OK;
+}
+
+int rt_backend_progress_read_half(rt_context* c, float* half)
+{
+    std::memcpy(half, c->prog.half.data(), c->prog.npx() * sizeof(float4_));
+    return RT_OK;
+}
+
+// The noise estimate on the host: the loops around rt_noise.h's per-pixel function that
+// k_noise_tiles (rt_noise.hip) runs one wave per tile. "Device" pointers are host pointers here; a
+// caller's buffers need not be aligned, so words move by memcpy.
+int rt_backend_progress_noise(rt_context* c, const rtk::NoiseArgs& A, int32_t* stats, float* pixel_err, float* tile_err,
+                              bool, void*)
+{
+    const RtProgress& P = c->prog;
+    const double t0 = omp_get_wtime();
+    const int tw = P.tiles_w(), th = P.tiles_h();
+    int32_t tiles_over = 0, nonfinite = 0;
+    float max_tile = 0.0f;
+    for (int ty = 0; ty < th; ty++)
+        for (int tx = 0; tx < tw; tx++) {
+            float v[64];
+            for (int l = 0; l < 64; l++) {
+                const int x = rtk::NOISE_TILE * tx + (l & 7), y = rtk::NOISE_TILE * ty + (l >> 3);
+                v[l] = 0.0f;
+                if (x >= P.w || y >= P.rows) continue;
+                const size_t i = (size_t)y * P.w + x;
+                const float e = rtk::noise_pixel(P.state[i], P.half[i], A);
+                if (pixel_err) std::memcpy((char*)pixel_err + 4 * i, &e, 4);
+                if (rtk::noise_finite(e)) v[l] = e;
+                else nonfinite++;
+            }
+            const float tile = rtk::noise_tree64(v) / (float)rtk::noise_tile_count(tx, ty, P.w, P.rows);
+            if (tile_err) std::memcpy((char*)tile_err + 4 * ((size_t)ty * tw + tx), &tile, 4);
+            if (tile > A.threshold) tiles_over++;
+            if (rt_asuint(tile) > rt_asuint(max_tile)) max_tile = tile;
+        }
+    const int32_t st[8] = {tw * th, tiles_over, nonfinite, (int32_t)rt_asuint(max_tile), A.samples_a, A.samples_b, A.passes, 0};
+    std::memcpy(stats, st, sizeof st);
+    c->last_kernel_ms = (omp_get_wtime() - t0) * 1e3;
+    return RT_OK;
 }
 
 int rt_backend_progress_resolve(rt_context* c, float* host_fb, void* dev_fb, void*, bool linear)

@@ -25,7 +25,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _capi
-from ._capi import DenoiseParams, DisplayParams  # noqa: F401
+from ._capi import DenoiseParams, DisplayParams, NoiseStats  # noqa: F401
 from ._capi import (RT_ERR_ARG, RT_ERR_HIP, RT_ERR_IO, RT_ERR_NODEV, RT_ERR_STATE, RT_OK,  # noqa: F401
                     RtError, check, lib, ptr)
 
@@ -429,6 +429,31 @@ class RenderKernel:
 
     def progress_end(self):
         self.L.rt_progress_end(self.ctx)
+
+    # ---- noise estimate of a progression (rt_progress_noise_track, rt_progress_noise; include/rt_hip.h)
+    def progress_track_noise(self):
+        """Track the running progression (before its first pass): it keeps the sum of the samples of its
+        even-numbered passes, which progress_noise compares with the sum of all of them."""
+        check(self.L, self.L.rt_progress_noise_track(self.ctx), self.ctx, "rt_progress_noise_track")
+
+    def progress_noise(self, threshold: float, pixel_map: bool = False, tile_map: bool = False) -> dict:
+        """rt_progress_noise after at least two passes: the stats as a dict (max_tile, tiles, tiles_over,
+        nonfinite, samples_a, samples_b, passes), with "pixel_err" [rows_local, w] and "tile_err"
+        [ceil(rows_local / 8), ceil(w / 8)] float32 arrays when asked for. tiles_over == 0: every 8x8 tile's
+        error is at or below the threshold."""
+        i = self.progress_info()
+        rows, w = i["rows_local"], self.width
+        px = np.empty((rows, w), np.float32) if pixel_map else None
+        tl = np.empty(((rows + 7) // 8, (w + 7) // 8), np.float32) if tile_map else None
+        st = NoiseStats()
+        check(self.L, self.L.rt_progress_noise(self.ctx, float(threshold), ctypes.byref(st), ptr(px), ptr(tl)), self.ctx,
+              "rt_progress_noise")
+        out = {k: getattr(st, k) for k, _ in NoiseStats._fields_}
+        if pixel_map:
+            out["pixel_err"] = px
+        if tile_map:
+            out["tile_err"] = tl
+        return out
 
     # ---- post stage (what replaces Utils::OIDN_denoise, utils.cpp:144-196)
     def camera_rays(self) -> np.ndarray:

@@ -33,6 +33,7 @@ EXPORTS = [
     "rt_progress_info", "rt_progress_save", "rt_progress_load", "rt_progress_end",
     "rt_display_default_params", "rt_render_linear", "rt_render_linear_device", "rt_progress_resolve_linear",
     "rt_progress_resolve_linear_device", "rt_display", "rt_display_device", "rt_write_hdr",
+    "rt_progress_noise_track", "rt_progress_noise", "rt_progress_noise_device",
 ]
 
 # return codes (include/rt_hip.h)
@@ -53,6 +54,12 @@ class DenoiseParams(ctypes.Structure):
 class DisplayParams(ctypes.Structure):
     """struct rt_display_params (include/rt_hip.h)."""
     _fields_ = [("exposure", F), ("gamma", F), ("flip_y", ctypes.c_int)]
+
+
+class NoiseStats(ctypes.Structure):
+    """struct rt_noise_stats (include/rt_hip.h)."""
+    _fields_ = [("max_tile", F), ("tiles", I), ("tiles_over", I), ("nonfinite", I), ("samples_a", I), ("samples_b", I),
+                ("passes", I)]
 
 
 _SIGS = {
@@ -123,6 +130,9 @@ _SIGS = {
     "rt_display": (I, [P, I, I, P, ctypes.POINTER(DisplayParams), P, P]),
     "rt_display_device": (I, [P, I, I, P, ctypes.POINTER(DisplayParams), P, P, P]),
     "rt_write_hdr": (I, [ctypes.c_char_p, P, I, I, I]),
+    "rt_progress_noise_track": (I, [P]),
+    "rt_progress_noise": (I, [P, F, ctypes.POINTER(NoiseStats), P, P]),
+    "rt_progress_noise_device": (I, [P, F, P, P, P, P]),
     # product-only extras
     "rt_device_libm": (I, [I, I, P, P, P, I]),
     "rt_device_libm_digest": (I, [I, I, ctypes.c_uint32, I, P]),
@@ -135,6 +145,7 @@ _SIGS = {
     "rt_device_query_trips": (I, [P, I, P, I, P]),
     "rt_device_denoise_pass_ms": (I, [P, I, P, I]),
     "rt_device_display_kernel_ms": (I, [P, I, I, P, P, P, P, I, P]),
+    "rt_device_noise_kernel_ms": (I, [P, I, I, P, P, P, P, P, I, P]),
     # hostsim-only extra
     "rt_hostsim_heap_order": (I, [P, I, P, P]),
     "rt_hostsim_fast_queries": (I, [P, P, I, P, P]),

@@ -20,6 +20,12 @@ linear at the end of a progression), written to --hdr-out, then displayed; the d
 four PNGs follow as before, and previews are displayed with the same parameters. --exposure=1.5
 --gamma=2.2 writes the bytes of a run without flags; with none of the three the run takes the
 tone-mapped render's path unchanged.
+
+Noise estimate (RenderKernel.progress_track_noise / progress_noise): --noise-threshold=T, with
+--preview-every=K, tracks the progression, and from the second pass on prints one line per pass
+(done, max_tile, tiles_over) and stops the passes once no 8x8 tile's error is above T. The four PNGs
+(and --hdr-out) then come from the samples done so far. A progression resumed from an untracked
+--checkpoint stays untracked and runs to the end. Without the flag a run writes the bytes it writes today.
 """
 from __future__ import annotations
 
@@ -35,16 +41,16 @@ import rt_amd
 def parse(argv):
     a = dict(obj="data/OBJs/cornell_pbr.obj", sky="data/Skyspheres/evening_road_01_puresky_2k.hdr", w=512, h=512,
              samples=64, bounces=8, camera="dragon", out=".", hostsim=False, preview_every=0, checkpoint="",
-             exposure=None, gamma=None, hdr_out="")
+             exposure=None, gamma=None, hdr_out="", noise_threshold=None)
     for s in argv:
         if s == "--hostsim":
             a["hostsim"] = True
         elif s.startswith(("--sky=", "--camera=", "--out=", "--checkpoint=", "--hdr-out=")):
             k, v = s[2:].split("=", 1)
             a[k.replace("-", "_")] = v
-        elif s.startswith(("--exposure=", "--gamma=")):
+        elif s.startswith(("--exposure=", "--gamma=", "--noise-threshold=")):
             k, v = s[2:].split("=", 1)
-            a[k] = float(v)
+            a[k.replace("-", "_")] = float(v)
         elif s.startswith(("--w=", "--h=", "--samples=", "--bounces=", "--preview-every=")):
             k, v = s[2:].split("=", 1)
             a[k.replace("-", "_")] = int(v)
@@ -82,7 +88,10 @@ def render_progressive(rk: rt_amd.RenderKernel, fb: rt_amd.Image, a: dict):
         print(f"Resuming {ck} at {rk.progress_info()['done']} samples")
     else:
         rk.progress_begin()
+        if a["noise_threshold"] is not None:
+            rk.progress_track_noise()
     os.makedirs(a["out"], exist_ok=True)
+    passes = 0
     preview = rt_amd.Image(a["w"], a["h"])
     while True:
         i = rk.progress_info()
@@ -99,6 +108,15 @@ def render_progressive(rk: rt_amd.RenderKernel, fb: rt_amd.Image, a: dict):
             else:
                 shown = rk.progress_resolve(preview)
             rt_amd.write_image_png(shown, os.path.join(a["out"], f"RT_preview_{done}.png"))
+        passes += 1
+        if a["noise_threshold"] is not None and passes >= 2:
+            try:
+                n = rk.progress_noise(a["noise_threshold"])
+            except rt_amd.RtError:  # (resumed from an untracked checkpoint, or one pass into a tracked one)
+                continue
+            print(f"noise: done {done} max_tile {n['max_tile']:.6g} tiles_over {n['tiles_over']}")
+            if n["tiles_over"] == 0:
+                break
     if display_stage(a):
         rk.progress_resolve_linear(fb)
     else:
@@ -108,6 +126,9 @@ def render_progressive(rk: rt_amd.RenderKernel, fb: rt_amd.Image, a: dict):
 
 def main(argv=None) -> int:
     a = parse(sys.argv[1:] if argv is None else argv)
+    if a["noise_threshold"] is not None and a["preview_every"] <= 0:
+        print("--noise-threshold needs --preview-every=K (the estimate compares passes)", file=sys.stderr)
+        return 2
     print(f"Reading OBJ {a['obj']} ...")
     P = rt_amd.parse_obj(a["obj"])
     print(f"Reading Environment Map {a['sky']} ...")
