@@ -96,6 +96,22 @@ build/stackless_probe: tools/probe/stackless_probe.cpp $(OBJ)/rt_scene.host.o $(
 	@mkdir -p build
 	$(CXX) -std=c++17 -O2 -fopenmp -ffp-contract=off -I$(SRC) $< $(OBJ)/rt_scene.host.o -o $@ -lpthread
 
+# A host-only change leaves the kernels alone: make device-diff PARENT=<checkout of the commit before it>
+# compiles the device side of every unit that has one (rt_wave_run and rt_backend have none) from both
+# trees and fails on any differing assembly line besides the one naming the unit's __hip_cuid_ symbol.
+DEV_UNITS := $(filter-out rt_wave_run,$(HIP_UNITS))
+build/devasm/%.s: $(SRC)/%.hip $(HDRS)
+	@mkdir -p build/devasm
+	$(HIPCC) $(HIPFLAGS) --cuda-device-only -S $< -o $@
+build/devasm/%.parent.s: $(PARENT)/$(SRC)/%.hip
+	@mkdir -p build/devasm
+	$(HIPCC) $(HIPFLAGS) --cuda-device-only -S $< -o $@
+device-diff: $(DEV_UNITS:%=build/devasm/%.s) $(DEV_UNITS:%=build/devasm/%.parent.s)
+	@for u in $(DEV_UNITS); do \
+	  n=$$(diff build/devasm/$$u.parent.s build/devasm/$$u.s | grep '^[<>]' | grep -vc __hip_cuid_); \
+	  echo "$$u: $$(grep -c . build/devasm/$$u.s) lines, $$n differ besides __hip_cuid_"; [ $$n -eq 0 ] || exit 1; done
+.PHONY: device-diff
+
 # the reference build (container only; needs /root/reference)
 ref:
 	$(MAKE) -C oracle/ref OPT=-O2

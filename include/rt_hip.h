@@ -329,7 +329,8 @@ int rt_denoise_device(rt_context* ctx, int w, int h, const void* d_rgba_in, cons
  *   the total was split. It changes no state. Before that point it is a preview: the mean of
  *   the first `done` samples of the N-sample chain, which is not the reference's
  *   `done`-sample frame (except where x*y == 0: there the seed is 31 for every count).
- *   done == 0: RT_ERR_STATE.
+ *   done == 0: RT_ERR_STATE. rt_last_kernel_ms reports the resolve's time (the device form: -1,
+ *   read rt_device_last_kernel_ms after synchronizing), as for every stage with both forms.
  * rt_progress_info: info = {w, h, total, done, bounces, row_offset, row_stride, rows_local}.
  * rt_progress_save: header (magic, format version, the eight info words; 10 int32), then
  *   the base, then the state; returns the size (buf NULL or capacity too small: only the

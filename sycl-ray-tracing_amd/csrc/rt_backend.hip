@@ -8,6 +8,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include <dlfcn.h>
@@ -100,7 +101,7 @@ int create_one(rt_context* c, int device, Backend** out)
     }
     HIPCHK(c, hipStreamCreateWithFlags(&b->own.h, hipStreamNonBlocking));
     HIPCHK(c, hipEventCreateWithFlags(&b->ev_fork.h, hipEventDisableTiming));
-    HIPCHK(c, hipEventCreateWithFlags(&b->ev_done.h, hipEventDisableTiming));
+    HIPCHK(c, hipEventCreateWithFlags(&b->ev_done.ev.h, hipEventDisableTiming));
     return RT_OK;
 }
 
@@ -117,7 +118,7 @@ int upload_one(rt_context* c, Backend* b, const std::vector<int32_t>& matk, bool
     HIPCHK(c, hipSetDevice(b->device));
     // the previous render may still run (rt_render_device returns at once, its kernels on
     // non-blocking streams that a null-stream copy does not wait for): it reads these tables
-    if (b->done_recorded) HIPCHK(c, hipEventSynchronize(b->ev_done));
+    if (int r = b->ev_done.sync(c)) return r;
     int r = 0;
     if (mats_only) {  // rt_set_materials: the material table (and what depends on it) alone
         if ((r = upload(c, b->mats, c->mats))) return r;
@@ -129,55 +130,25 @@ int upload_one(rt_context* c, Backend* b, const std::vector<int32_t>& matk, bool
     // device triangle records carry the material index in e1.w (rt_wave.h hit_from)
     std::vector<float4_> tri4 = c->flat.tri4;
     for (size_t k = 0; k < matk.size(); k++) std::memcpy(&tri4[3 * k + 1].w, &matk[k], 4);
-    if ((r = upload(c, b->nodes, c->flat.nodes)) || (r = upload(c, b->tri4, tri4)) ||
-        (r = upload(c, b->prim2k, c->flat.prim2k)) || (r = upload(c, b->mat_idx, c->mat_idx)) ||
-        (r = upload(c, b->mats, c->mats)) || (r = upload(c, b->emissive, c->emissive)) ||
-        (r = upload(c, b->spheres, c->spheres)) || (r = upload(c, b->env, c->env)) ||
-        (r = upload(c, b->env_lum, c->env_lum)) || (r = upload(c, b->cdf, c->cdf)) ||
-        (r = upload(c, b->bvh4, c->flat.bvh4)) || (r = upload(c, b->bvh16, c->flat.bvh16)) ||
-        (r = upload(c, b->bvh4s, c->flat.bvh4s)) || (r = upload(c, b->bvh16s, c->flat.bvh16s)) ||
-        (r = upload(c, b->bvh_tri4, c->flat.bvh_tri4)) ||
-        (r = upload(c, b->parent, c->flat.parent)) || (r = upload(c, b->leaf_of, c->flat.leaf_of)) ||
-        (r = upload(c, b->cdf_row, c->cdf_row)) || (r = upload(c, b->cdf_coarse, c->cdf_coarse)) ||
-        (r = upload(c, b->cdf_fence, c->cdf_fence)) || (r = upload(c, b->matk, matk)) ||
+    if ((r = upload(c, b->tri4, tri4)) || (r = upload(c, b->mats, c->mats)) || (r = upload(c, b->matk, matk)) ||
         (r = ensure(c, b->stats, 2 * RT_STAT_COUNT * sizeof(unsigned long long))))
         return r;
     for (int l = 0; l < RT_MAX_LANES; l++)
         if ((r = ensure(c, b->counters[l], rt_wave_counter_bytes()))) return r;
     RtSceneView v{};
-    v.nodes = (const RtNode*)b->nodes.p;
+    rt_view_scalars(c, v);
+    int i = 0;
+    rt_scene_tables(c, v, [&](const auto& table, auto& field) {
+        DevBuf& d = b->tables[i++ % RT_SCENE_TABLES];
+        if (!r) r = upload(c, d, table);
+        field = (std::remove_reference_t<decltype(field)>)d.p;
+    });
+    if (r) return r;
     v.tri4 = (const float4_*)b->tri4.p;
-    v.prim2k = (const int32_t*)b->prim2k.p;
-    v.mat_idx = (const int32_t*)b->mat_idx.p;
-    v.matk = (const int32_t*)b->matk.p;
     v.mats = (const RtMat*)b->mats.p;
-    v.n_mats = (int)c->mats.size();
-    v.emissive = (const int32_t*)b->emissive.p;
-    v.spheres = (const float4_*)b->spheres.p;
-    v.env = (const float4_*)b->env.p;
-    v.env_lum = (const float*)b->env_lum.p;
-    v.cdf = (const float*)b->cdf.p;
-    v.cdf_row = (const float*)b->cdf_row.p;
-    v.cdf_coarse = (const float*)b->cdf_coarse.p;
-    v.cdf_fence = c->cdf_fence.empty() ? nullptr : (const float*)b->cdf_fence.p;
-    v.cdf_cw = c->cdf_cw;
-    v.cdf_total = c->cdf.empty() ? 0.0f : c->cdf.back();
-    v.n_emissive = (int)c->emissive.size();
-    v.n_spheres = (int)(c->spheres.size() / 2);
-    v.ew = c->ew;
-    v.eh = c->eh;
-    v.n_tris = (int)(c->tris.size() / 9);
-    v.chain_monotone = rt_view_chain_monotone(c);
-    v.brute = c->brute ? 1 : 0;
-    v.bvh4 = (const Bvh4Node*)b->bvh4.p;
-    v.bvh16 = (const Bvh4Child*)b->bvh16.p;
-    v.bvh4s = (const float4_*)b->bvh4s.p;
-    v.bvh16s = (const float4_*)b->bvh16s.p;
-    v.bvh_tri4 = (const float4_*)b->bvh_tri4.p;
-    v.parent = (const int32_t*)b->parent.p;
-    v.leaf_of = (const int32_t*)b->leaf_of.p;
+    v.matk = (const int32_t*)b->matk.p;
+    if (c->cdf_fence.empty()) v.cdf_fence = nullptr;
     v.tri_mat = 1;
-    rt_view_near(c, v);
     b->view = v;
     b->bl_rays = rt_scene_has_emissive_prim(c) ? 1 : 0;
     b->any_rays = v.n_spheres == 0 ? 1 : 0;
@@ -359,35 +330,24 @@ int rt_backend_render(rt_context* c, int w, int h, int spp, int bounces, float* 
 {
     Group* g = grp(c);
     Backend* b = be(c);
-    HIPCHK(c, hipSetDevice(b->device));
-    hipStream_t s = (hipStream_t)stream;
+    StagedCall st;  // (the host form runs on `stream` too: rt_render passes the null stream)
+    if (int r = st.enter(c, b, host_fb == nullptr, stream, (hipStream_t)stream)) return r;
+    hipStream_t s = st.s;
     const int rows_local = (h - row_offset + row_stride - 1) / row_stride;
     const size_t npx = (size_t)rows_local * w;
     if (npx > 0x7fffffff / 8) return rt_fail(c, RT_ERR_ARG, "render: too many pixels for one launch");
-    float4_* fb = (float4_*)dev_fb;
-    if (host_fb) {
-        if (int r = ensure(c, b->fb, npx * sizeof(float4_))) return r;
-        fb = (float4_*)b->fb.p;
-        HIPCHK(c, hipMemcpyAsync(fb, host_fb, npx * sizeof(float4_), hipMemcpyHostToDevice, s));
-    }
-    if (g->multi) {
+    if (int r = st.staging(b->fb, npx * sizeof(float4_))) return r;
+    float4_* fb = (float4_*)st.inout(host_fb ? (void*)host_fb : dev_fb, host_fb, npx * sizeof(float4_));
+    if (g->multi) {  // (render_multi records the root's ev0 and ev1 itself, around its pack and un-permute)
+        if (st.err) return st.err;
         if (int r = render_multi(c, g, w, h, spp, bounces, fb, row_offset, row_stride, s, linear)) return r;
-    } else {
-        rtk::PixSrc src{w, row_offset, row_stride, nullptr};
-        HIPCHK(c, hipEventRecord(b->ev0, s));
-        if (int r = run_wave(c, b, w, h, spp, bounces, src, (int)npx, fb, s, nullptr, linear)) return r;
-        HIPCHK(c, hipEventRecord(b->ev1, s));
+        return st.finish();
     }
-    if (host_fb) {
-        HIPCHK(c, hipMemcpyAsync(host_fb, fb, npx * sizeof(float4_), hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipStreamSynchronize(s));
-        float ms = 0;
-        HIPCHK(c, hipEventElapsedTime(&ms, b->ev0, b->ev1));
-        c->last_kernel_ms = ms;
-    } else {
-        c->last_kernel_ms = -1.0;  // read with rt_device_last_kernel_ms after the caller synchronizes
-    }
-    return g->multi ? RT_OK : finish_stats(c, b, s);
+    rtk::PixSrc src{w, row_offset, row_stride, nullptr};
+    if (int r = st.begin()) return r;
+    if (int r = run_wave(c, b, w, h, spp, bounces, src, (int)npx, fb, s, nullptr, linear)) return r;
+    if (int r = st.end()) return r;
+    return finish_stats(c, b, s);
 }
 
 // The material sweep as replicas (rt_render_variants): variant v on device v mod N, one
@@ -411,7 +371,7 @@ int rt_backend_render_variants(rt_context* c, int w, int h, int spp, int bounces
         Backend* b = g->dev[d];
         HIPCHK(c, hipSetDevice(b->device));
         hipStream_t s = b->own;
-        if (b->done_recorded) HIPCHK(c, hipEventSynchronize(b->ev_done));  // (the table and buffers are reused)
+        if (int e = b->ev_done.sync(c)) return e;  // (the table and buffers are reused)
         if (int e = ensure(c, b->mats, (size_t)n_mats * sizeof(RtMat))) return e;
         b->view.mats = (const RtMat*)b->mats.p;
         b->view.n_mats = n_mats;
@@ -460,25 +420,20 @@ int rt_backend_render_variants(rt_context* c, int w, int h, int spp, int bounces
 static int render_pixels_one(rt_context* c, Backend* b, int w, int h, int spp, int bounces, const int* xy, int n,
                              float* rgba, float* ms_out)
 {
-    HIPCHK(c, hipSetDevice(b->device));
+    StagedCall st;
+    if (int r = st.enter(c, b, false, nullptr, b->own)) return r;
     if (n == 0) return RT_OK;
     const size_t bxy = (size_t)n * 8, brgba = (size_t)n * 16;
-    if (int r = ensure(c, b->xy, bxy)) return r;
-    if (int r = ensure(c, b->fb, brgba)) return r;
-    hipStream_t s = b->own;
+    hipStream_t s = st.s;
+    if (int r = ensure(c, b->xy, bxy)) return r;  // (the list: a buffer of its own beside the staged pixels)
+    if (int r = st.staging(b->fb, brgba)) return r;
     HIPCHK(c, hipMemcpyAsync(b->xy.p, xy, bxy, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(b->fb.p, rgba, brgba, hipMemcpyHostToDevice, s));
+    float4_* fb = (float4_*)st.inout(rgba, rgba, brgba);
     if (c->stats_enabled) HIPCHK(c, hipMemsetAsync(b->stats.p, 0, b->stats.bytes, s));
     rtk::PixSrc src{w, 0, 1, (const int32_t*)b->xy.p};
-    HIPCHK(c, hipEventRecord(b->ev0, s));
-    if (int r = run_wave(c, b, w, h, spp, bounces, src, n, (float4_*)b->fb.p, s)) return r;
-    HIPCHK(c, hipEventRecord(b->ev1, s));
-    HIPCHK(c, hipMemcpyAsync(rgba, b->fb.p, brgba, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    float ms = 0;
-    HIPCHK(c, hipEventElapsedTime(&ms, b->ev0, b->ev1));
-    *ms_out = ms;
-    return RT_OK;
+    if (int r = st.begin()) return r;
+    if (int r = run_wave(c, b, w, h, spp, bounces, src, n, fb, s)) return r;
+    return st.end(nullptr, ms_out);
 }
 
 int rt_backend_render_pixels(rt_context* c, int w, int h, int spp, int bounces, const int* xy, int n, float* rgba)
@@ -533,9 +488,8 @@ namespace {
 // the passes (ev_done) and device resolves (ev_pg) still in flight have finished with the buffers
 int progress_quiesce(rt_context* c, Backend* b)
 {
-    if (b->done_recorded) HIPCHK(c, hipEventSynchronize(b->ev_done));
-    if (b->pg_recorded) HIPCHK(c, hipEventSynchronize(b->ev_pg));
-    return RT_OK;
+    if (int r = b->ev_done.sync(c)) return r;
+    return b->ev_pg.sync(c);
 }
 void release(DevBuf& d)
 {
@@ -554,7 +508,7 @@ int rt_backend_progress_begin(rt_context* c, const float* base, const float* sta
     const size_t n = c->prog.npx(), bytes = n * sizeof(float4_);
     if (int r = ensure(c, b->pg_base, bytes)) return r;
     if (int r = ensure(c, b->pg_state, bytes)) return r;
-    if (!b->ev_pg) HIPCHK(c, hipEventCreateWithFlags(&b->ev_pg.h, hipEventDisableTiming));
+    if (!b->ev_pg.ev) HIPCHK(c, hipEventCreateWithFlags(&b->ev_pg.ev.h, hipEventDisableTiming));
     if (base) {
         HIPCHK(c, hipMemcpy(b->pg_base.p, base, bytes, hipMemcpyHostToDevice));
     } else {
@@ -573,7 +527,7 @@ int rt_backend_progress_advance(rt_context* c, int first, int stop, void* stream
     const RtProgress& P = c->prog;
     HIPCHK(c, hipSetDevice(b->device));
     hipStream_t s = (hipStream_t)stream;
-    if (b->pg_recorded) HIPCHK(c, hipStreamWaitEvent(s, b->ev_pg, 0));  // (a device resolve still reads the state)
+    if (int r = b->ev_pg.wait(c, s)) return r;  // (a device resolve still reads the state)
     const rtk::PixSrc src{P.w, P.off, P.stride, nullptr};
     // (the framebuffer pointer of the pass is never used: it names the state, valid memory of the same size)
     const WavePass pass{(float4_*)b->pg_state.p, first, P.total};
@@ -581,16 +535,16 @@ int rt_backend_progress_advance(rt_context* c, int first, int stop, void* stream
     const bool fold = P.next_is_a();
     HIPCHK(c, hipEventRecord(b->ev0, s));
     if (fold) {
-        if (b->done_recorded) HIPCHK(c, hipStreamWaitEvent(s, b->ev_done, 0));  // (the last pass wrote the state)
+        if (int r = b->ev_done.wait(c, s)) return r;  // (the last pass wrote the state)
         if (int r = rt_noise_fold(c, (float4_*)b->pg_half.p, pass.state, (int)P.npx(), false, s)) return r;
     }
     if (int r = run_wave(c, b, P.w, P.h, stop, P.bounces, src, (int)P.npx(), pass.state, s, &pass)) return r;
     if (fold) {
         if (int r = rt_noise_fold(c, (float4_*)b->pg_half.p, pass.state, (int)P.npx(), true, s)) return r;
-        HIPCHK(c, hipEventRecord(b->ev_done, s));  // (resolves, queries and the next pass wait for the fold too)
+        if (int r = b->ev_done.record(c, s)) return r;  // (resolves, queries and the next pass wait for the fold too)
     }
     HIPCHK(c, hipEventRecord(b->ev1, s));
-    c->last_kernel_ms = -1.0;  // read with rt_device_last_kernel_ms after the caller synchronizes
+    c->last_kernel_ms = -1.0;  // (a device call: StagedCall's convention)
     return finish_stats(c, b, s);
 }
 
@@ -598,28 +552,19 @@ int rt_backend_progress_resolve(rt_context* c, float* host_fb, void* dev_fb, voi
 {
     Backend* b = be(c);
     const RtProgress& P = c->prog;
-    DeviceScope sc;
-    if (int r = sc.enter(c, b->device)) return r;
+    StagedCall st;
+    if (int r = st.enter(c, b, host_fb == nullptr, stream, b->own)) return r;
     const int n = (int)P.npx();
-    hipStream_t s = host_fb ? (hipStream_t)b->own : (hipStream_t)stream;
-    float4_* out = (float4_*)dev_fb;
-    if (host_fb) {
-        if (int r = ensure(c, b->pg_out, (size_t)n * sizeof(float4_))) return r;
-        out = (float4_*)b->pg_out.p;
-    }
-    if (b->done_recorded) HIPCHK(c, hipStreamWaitEvent(s, b->ev_done, 0));  // (the last pass, on its own streams)
+    hipStream_t s = st.s;
+    if (int r = st.staging(b->pg_out, (size_t)n * sizeof(float4_))) return r;
+    float4_* out = (float4_*)st.out(host_fb ? (void*)host_fb : dev_fb, (size_t)n * sizeof(float4_));
+    if (int r = b->ev_done.wait(c, s)) return r;  // (the last pass, on its own streams)
     const float4_ *base = (const float4_*)b->pg_base.p, *state = (const float4_*)b->pg_state.p;
+    if (int r = st.begin()) return r;
     if (int r = linear ? rt_display_resolve_linear(c, base, state, out, n, P.done, s)
                        : rt_wave_resolve(c, base, state, out, n, P.done, s))
         return r;
-    if (host_fb) {
-        HIPCHK(c, hipMemcpyAsync(host_fb, out, (size_t)n * sizeof(float4_), hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipStreamSynchronize(s));
-    } else {
-        HIPCHK(c, hipEventRecord(b->ev_pg, s));
-        b->pg_recorded = true;
-    }
-    return RT_OK;
+    return st.end(&b->ev_pg);  // (device form: the next pass writes the state this reads)
 }
 
 int rt_backend_progress_read(rt_context* c, float* base, float* state)
@@ -673,20 +618,6 @@ int rt_backend_progress_read_half(rt_context* c, float* half)
 }
 
 Backend* rt_backend_dev0(rt_context* c) { return be(c); }
-
-// The root device's state for the post stage (rt_denoise.hip) and the ray queries (rt_query.hip).
-int rt_backend_root(rt_context* c, RtRootDev* out)
-{
-    Backend* b = be(c);
-    out->device = b->device;
-    out->view = &b->view;
-    out->ev0 = b->ev0;
-    out->ev1 = b->ev1;
-    out->post = &b->post;
-    out->query = &b->query;
-    out->disp = &b->disp;
-    return RT_OK;
-}
 
 // Time between the events around the last rt_render_device launch sequence
 // (recorded on its stream); call after synchronizing that stream.

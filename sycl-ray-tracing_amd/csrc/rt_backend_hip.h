@@ -1,6 +1,7 @@
 // rt_backend_hip.h — what the translation units of the gfx950 backend share: the HIP error
-// check, the owners of device resources (freed by their destructors), the per-device
-// Backend, and the hooks between the units:
+// check, the owners of device resources (freed by their destructors), the recorded-event
+// Marker, the per-device Backend (every unit reaches the root's through rt_backend_dev0), the
+// StagedCall that runs a stage in its host or its device form, and the hooks between the units:
 //   rt_backend.hip  contexts, uploads, the multi-device / variant / pixel-list drivers
 //   rt_render.hip   the render kernels and their launch helpers (rt_wave_kernels.h)
 //   rt_wave_run.hip the wavefront loop (run_wave) over them; rt_wave_layout.h: the counters both index
@@ -12,6 +13,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -100,8 +102,38 @@ struct DeviceScope {
     }
 };
 
-void rt_post_free(void* post);    // rt_denoise.hip (the device is current)
-void rt_query_free(void* query);  // rt_query.hip (the device is current)
+// An event and whether it has been recorded: waiting for one never recorded is a no-op.
+struct Marker {
+    Event ev;
+    bool recorded = false;
+    int record(rt_context* c, hipStream_t s)
+    {
+        HIPCHK(c, hipEventRecord(ev, s));
+        recorded = true;
+        return RT_OK;
+    }
+    int wait(rt_context* c, hipStream_t s) const  // s waits for it
+    {
+        if (recorded) HIPCHK(c, hipStreamWaitEvent(s, ev, 0));
+        return RT_OK;
+    }
+    int sync(rt_context* c) const  // the host waits for it
+    {
+        if (recorded) HIPCHK(c, hipEventSynchronize(ev));
+        return RT_OK;
+    }
+};
+
+// The post stage's buffers (rt_denoise.hip) and the ray queries' workspace (rt_query.hip),
+// created on first use and deleted with their Backend (its device current).
+struct Post;
+struct Query;
+struct PostDelete {
+    void operator()(Post* p) const;
+};
+struct QueryDelete {
+    void operator()(Query* q) const;
+};
 
 namespace rtk {
 struct WaveView;
@@ -113,8 +145,8 @@ struct Backend {
     int device = 0;
     int index = 0;    // position in the context's device list (0: the root)
     Stream own;       // device-side work not on a caller's stream (multi-device shards, pixel lists)
-    DevBuf nodes, tri4, prim2k, mat_idx, mats, emissive, spheres, env, env_lum, cdf;
-    DevBuf bvh4, bvh16, bvh4s, bvh16s, bvh_tri4, parent, leaf_of, cdf_row, cdf_coarse, cdf_fence, matk;
+    DevBuf tables[RT_SCENE_TABLES];  // the uploads of rt_scene_tables' vectors, in its order
+    DevBuf tri4, mats, matk;         // the patched triangle records, the material table, leaf-order k -> material
     DevBuf stats;     // 2 x RT_STAT_COUNT u64: all kernels, then the tail kernel's share
     DevBuf handovers; // u64: queries k_trace handed to the exact walk, every render since the last reset
     DevBuf iterq;     // stats renders: per-iteration {queries, live slots} (RT_ITER_LOG)
@@ -126,9 +158,9 @@ struct Backend {
     DevBuf fast[RT_MAX_LANES], fcnt[RT_MAX_LANES], fhist[RT_MAX_LANES], fspill[RT_MAX_LANES], fviews;
     Pinned<int32_t> h_hist[RT_MAX_LANES];
     Pinned<rtk::WaveView> h_fviews;
-    Event fev[RT_MAX_LANES], fev_done;
+    Event fev[RT_MAX_LANES];
+    Marker fev_done;          // end of the last fast-lane kernel: it read the views the next one overwrites
     Event hev[RT_MAX_LANES];  // fast lane: each lane's samples-done histogram readback
-    bool fev_done_recorded = false;
     Event ftev[2];  // (timed renders: around the fast lane's kernel)
     Stream fs;      // the fast lane's stream with 4 lanes (fewer: the first idle lane stream)
     DevBuf xy;        // pixel list (rt_render_pixels)
@@ -140,10 +172,8 @@ struct Backend {
                       // gather target); device d >= 1: its block
     Pinned<int32_t> h_act[RT_MAX_LANES];  // per lane: live-slot counters (sharded) + 8 fallback counters
     Event ev0, ev1;
-    Event ev_pg;    // end of the last rt_progress_resolve_device: the next pass writes the state it reads
-    bool pg_recorded = false;
-    Event ev_done;  // end of the last run_wave (all lanes joined): the next render waits for it
-    bool done_recorded = false;
+    Marker ev_pg;    // end of the last device resolve or noise query: the next pass writes the state it reads
+    Marker ev_done;  // end of the last run_wave (all lanes joined): the next render waits for it
     Stream ls[RT_MAX_LANES];                // lanes 1.. streams (lane 0 runs on the caller's)
     Event ev_fork, ev_join[RT_MAX_LANES], ev_lane[RT_MAX_LANES];
     int lanes = 0;                          // RT_LANES; 0: auto, 4 lanes for launches of at most RT_LANES4_MAX
@@ -160,26 +190,125 @@ struct Backend {
     Event tev[RT_MAX_LANES][3][RT_MAX_TIMED_ITERS];
     double kms[3] = {0, 0, 0};      // k_trace, k_step, k_tail
     long klaunch[3] = {0, 0, 0};
-    void* post = nullptr;           // the post stage's buffers (rt_denoise.hip owns them: rt_post_free)
-    void* query = nullptr;          // the ray-query workspace (rt_query.hip owns it: rt_query_free)
-    ~Backend()
+    std::unique_ptr<Post, PostDelete> post;     // (rt_denoise.hip)
+    std::unique_ptr<Query, QueryDelete> query;  // (rt_query.hip)
+};
+
+Backend* rt_backend_dev0(rt_context* c);  // rt_backend.hip: the root device's Backend
+
+// One call of a stage, in its device form (the caller's device buffers on the caller's stream,
+// no wait; rt_last_kernel_ms is -1 until rt_device_last_kernel_ms reads ev0 / ev1 once the caller
+// has synchronized) or its host form (host buffers through regions of the stage's staging
+// DevBuf, each at a 16-byte boundary; waits; rt_last_kernel_ms is the time between ev0 and ev1):
+//   enter, [staging], in / out / inout per buffer, begin, the stage's launches, end
+// b's device is current until the StagedCall leaves scope, then the caller's again.
+// The host forms' streams are inherited from the stages as they were written, not chosen here:
+//   null stream   features, denoise (Post::io), display (disp), queries (Query::io), rt_render (fb)
+//   Backend::own  noise (pg_noise), progressive resolves (pg_out), pixel lists (fb)
+struct StagedCall {
+    rt_context* c = nullptr;
+    Backend* b = nullptr;
+    bool device = false;
+    hipStream_t s = nullptr;
+    DeviceScope sc;
+    char* base = nullptr;  // host form: the staging buffer, what it holds and what is taken
+    size_t cap = 0, used = 0;
+    struct Out {
+        void* host;
+        const void* dev;
+        size_t bytes;
+    } outs[4];
+    int n_out = 0;
+    int err = RT_OK;  // the first failure of a region; begin returns it
+
+    static size_t pad(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
+    int enter(rt_context* ctx, Backend* be, bool device_form, void* caller_stream, hipStream_t host_stream)
     {
-        if (post) rt_post_free(post);
-        if (query) rt_query_free(query);
+        c = ctx, b = be, device = device_form;
+        s = device ? (hipStream_t)caller_stream : host_stream;
+        return sc.enter(c, b->device);
+    }
+    // host form: the regions come from d, grown to `bytes` (the padded sizes of all of them)
+    int staging(DevBuf& d, size_t bytes)
+    {
+        if (device) return RT_OK;
+        if (int r = ensure(c, d, bytes)) return r;
+        base = (char*)d.p, cap = d.bytes, used = 0;
+        return RT_OK;
+    }
+    // A buffer of the call. Device form: the caller's pointer (src, or dst for an output). Host
+    // form: the next region, filled from src now and copied to dst by end; neither: no region.
+    void* inout(const void* src, void* dst, size_t bytes)
+    {
+        if (device) return src ? (void*)src : dst;
+        if ((!src && !dst) || err) return nullptr;
+        if (used + bytes > cap || (dst && n_out == 4)) {
+            err = rt_fail(c, RT_ERR_ARG, "StagedCall: a region beyond the staging buffer");
+            return nullptr;
+        }
+        void* p = base + used;
+        used += pad(bytes);
+        if (src) {
+            const hipError_t e = hipMemcpyAsync(p, src, bytes, hipMemcpyHostToDevice, s);
+            if (e != hipSuccess) err = rt_fail(c, RT_ERR_HIP, std::string("hipMemcpyAsync: ") + hipGetErrorString(e));
+        }
+        if (dst) outs[n_out++] = Out{dst, p, bytes};
+        return p;
+    }
+    void* in(const void* src, size_t bytes) { return inout(src, nullptr, bytes); }
+    void* out(void* dst, size_t bytes) { return inout(nullptr, dst, bytes); }
+    int begin()
+    {
+        if (err) return err;
+        HIPCHK(c, hipEventRecord(b->ev0, s));
+        return RT_OK;
+    }
+    int stop()
+    {
+        HIPCHK(c, hipEventRecord(b->ev1, s));
+        return RT_OK;
+    }
+    // mark: recorded in the device form (the call's end, for whoever overwrites what it read).
+    // ms_out: the host form's time goes there instead of the context (one device's thread of many).
+    int finish(Marker* mark = nullptr, float* ms_out = nullptr)
+    {
+        if (device) {
+            if (mark)
+                if (int r = mark->record(c, s)) return r;
+            c->last_kernel_ms = -1.0;
+            return RT_OK;
+        }
+        for (int i = 0; i < n_out; i++)
+            HIPCHK(c, hipMemcpyAsync(outs[i].host, outs[i].dev, outs[i].bytes, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipStreamSynchronize(s));
+        float ms = 0;
+        HIPCHK(c, hipEventElapsedTime(&ms, b->ev0, b->ev1));
+        if (ms_out) *ms_out = ms;
+        else c->last_kernel_ms = ms;
+        return RT_OK;
+    }
+    int end(Marker* mark = nullptr, float* ms_out = nullptr)
+    {
+        if (int r = stop()) return r;
+        return finish(mark, ms_out);
     }
 };
 
-struct RtRootDev {
-    int device;               // HIP ordinal of the context's root device
-    const RtSceneView* view;  // its scene view (valid after rt_backend_upload)
-    hipEvent_t ev0, ev1;      // the events rt_last_kernel_ms / rt_device_last_kernel_ms read
-    void** post;              // the post stage's state, created on first use; rt_post_free releases it
-    void** query;             // the ray queries' workspace, likewise; rt_query_free releases it
-    DevBuf* disp;             // the display stage's staging buffer (freed with the Backend)
-};
-
-int rt_backend_root(rt_context* c, RtRootDev* out);  // rt_backend.hip
-Backend* rt_backend_dev0(rt_context* c);             // rt_backend.hip: the root device's Backend
+// The measurement hooks' loop body (rt_device_display_kernel_ms, rt_device_noise_kernel_ms): one
+// launch alone on the default stream between e0 and e1, waited for; its GPU time into *ms.
+template <class F>
+int rt_time_alone(rt_context* c, hipEvent_t e0, hipEvent_t e1, F launch, double* ms)
+{
+    HIPCHK(c, hipEventRecord(e0, nullptr));
+    const int rc = launch();
+    HIPCHK(c, hipEventRecord(e1, nullptr));
+    if (rc) return rc;
+    HIPCHK(c, hipEventSynchronize(e1));
+    float f = 0;
+    HIPCHK(c, hipEventElapsedTime(&f, e0, e1));
+    *ms = f;
+    return RT_OK;
+}
 
 // rt_wave_run.hip: the wavefront loop for n slots of `src` into fb (device, n float4) on b's
 // device (current), and the sizes of a lane's counters and of its pinned readback block.

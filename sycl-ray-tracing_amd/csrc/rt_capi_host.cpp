@@ -54,24 +54,52 @@ int rt_fail(rt_context* ctx, int code, const std::string& msg)
     return code;
 }
 
+// One material of the C ABI (10 floats: emission rgba, diffuse rgba, metalness, roughness) as the device's record.
+static RtMat unpack_mat(const float* p) { return RtMat{p[0], p[1], p[2], p[8], p[4], p[5], p[6], p[9]}; }
+
+// The tail of rt_create*: the backend for a filled-in context, which is destroyed if that fails.
+static int create_finish(rt_context* c, rt_context** out)
+{
+    rt_read_diag(c);
+    int r = rt_backend_create(c);
+    if (r) {
+        set_global_err(c->err);
+        rt_backend_destroy(c);
+        delete c;
+        return r;
+    }
+    *out = c;
+    return RT_OK;
+}
+
+// The device tables made current. mats_too: a changed material table alone (rt_set_materials,
+// rt_render_variants) is a reason too; env_stub: bind the placeholder env first (the calls that need no env).
+static void placeholder_env(rt_context* c);
+static int tables_current(rt_context* c, bool mats_too, bool env_stub)
+{
+    if (!c->dirty && !(mats_too && c->mats_dirty_only)) return RT_OK;
+    if (env_stub) placeholder_env(c);
+    if (int r = rt_backend_upload(c)) return r;
+    c->dirty = false;
+    c->mats_dirty_only = false;
+    return RT_OK;
+}
+
 RtSceneView rt_host_view(const rt_context* c)
 {
     RtSceneView v{};
-    v.nodes = c->flat.nodes.data();
+    rt_view_scalars(c, v);
+    rt_scene_tables(c, v, [](const auto& table, auto& field) { field = table.data(); });
     v.tri4 = c->flat.tri4.data();
-    v.prim2k = c->flat.prim2k.data();
-    v.mat_idx = c->mat_idx.data();
     v.mats = c->mats.data();
+    if (c->cdf_fence.empty()) v.cdf_fence = nullptr;
+    v.tri_mat = 0;
+    return v;
+}
+
+void rt_view_scalars(const rt_context* c, RtSceneView& v)
+{
     v.n_mats = (int)c->mats.size();
-    v.emissive = c->emissive.data();
-    v.spheres = c->spheres.data();
-    v.env = c->env.data();
-    v.env_lum = c->env_lum.data();
-    v.cdf = c->cdf.data();
-    v.brute = c->brute ? 1 : 0;
-    v.cdf_row = c->cdf_row.data();
-    v.cdf_fence = c->cdf_fence.empty() ? nullptr : c->cdf_fence.data();
-    v.cdf_coarse = c->cdf_coarse.data();
     v.cdf_cw = c->cdf_cw;
     v.cdf_total = c->cdf.empty() ? 0.0f : c->cdf.back();
     v.n_emissive = (int)c->emissive.size();
@@ -80,16 +108,8 @@ RtSceneView rt_host_view(const rt_context* c)
     v.eh = c->eh;
     v.n_tris = (int)(c->tris.size() / 9);
     v.chain_monotone = rt_view_chain_monotone(c);
-    v.bvh4 = c->flat.bvh4.data();
-    v.bvh16 = c->flat.bvh16.data();
-    v.bvh4s = c->flat.bvh4s.data();
-    v.bvh16s = c->flat.bvh16s.data();
-    v.bvh_tri4 = c->flat.bvh_tri4.data();
-    v.parent = c->flat.parent.data();
-    v.leaf_of = c->flat.leaf_of.data();
-    v.tri_mat = 0;
+    v.brute = c->brute ? 1 : 0;
     rt_view_near(c, v);
-    return v;
 }
 
 int rt_view_chain_monotone(const rt_context* c) { return c->flat.chain_monotone && !c->sched.chain_full ? 1 : 0; }
@@ -150,16 +170,7 @@ int rt_create(int device, rt_context** out)
     *out = nullptr;
     rt_context* c = new rt_context();
     c->device = device;
-    rt_read_diag(c);
-    int r = rt_backend_create(c);
-    if (r) {
-        set_global_err(c->err);
-        rt_backend_destroy(c);
-        delete c;
-        return r;
-    }
-    *out = c;
-    return RT_OK;
+    return create_finish(c, out);
 }
 
 }  // extern "C"
@@ -189,16 +200,7 @@ int create_multi(int n_devices, const int* devices, bool loopback, rt_context** 
     c->device = c->devices[0];
     c->loopback = loopback;
     c->force_multi = rccl;
-    rt_read_diag(c);
-    int r = rt_backend_create(c);
-    if (r) {
-        set_global_err(c->err);
-        rt_backend_destroy(c);
-        delete c;
-        return r;
-    }
-    *out = c;
-    return RT_OK;
+    return create_finish(c, out);
 }
 }  // namespace
 
@@ -318,10 +320,7 @@ int rt_set_scene(rt_context* c, const float* triangles, int n, const int* materi
     c->tris.assign(triangles, triangles + 9 * (size_t)n);
     c->mat_idx.assign(material_indices, material_indices + n_mi);
     c->mats.resize(n_mats);
-    for (int i = 0; i < n_mats; i++) {
-        const float* p = materials + 10 * (size_t)i;
-        c->mats[i] = RtMat{p[0], p[1], p[2], p[8], p[4], p[5], p[6], p[9]};
-    }
+    for (int i = 0; i < n_mats; i++) c->mats[i] = unpack_mat(materials + 10 * (size_t)i);
     c->emissive.assign(emissive, emissive + n_em);
     c->spheres.clear();
     for (int i = 0; i < n_sph; i++) {
@@ -346,10 +345,7 @@ int rt_set_materials(rt_context* c, const float* materials, int n_mats)
     for (int32_t mi : c->mat_idx)
         if (mi >= n_mats) return rt_fail(c, RT_ERR_ARG, "rt_set_materials: a material index is out of range");
     c->mats.resize(n_mats);
-    for (int i = 0; i < n_mats; i++) {
-        const float* p = materials + 10 * (size_t)i;
-        c->mats[i] = RtMat{p[0], p[1], p[2], p[8], p[4], p[5], p[6], p[9]};
-    }
+    for (int i = 0; i < n_mats; i++) c->mats[i] = unpack_mat(materials + 10 * (size_t)i);
     c->mats_dirty_only = true;  // the octree, search BVH, triangles and env stay on the device
     return RT_OK;
 }
@@ -474,13 +470,7 @@ static int check_ready(rt_context* c, int w, int h, int spp, int bounces)
     // the reference seeds with the int 31 + x*y*spp (render_kernel.cpp:77)
     if ((double)(w - 1) * (double)(h - 1) * (double)spp + 31.0 > 2147483647.0)
         return rt_fail(c, RT_ERR_ARG, "31 + x*y*spp overflows int (reference seed)");
-    if (c->dirty || c->mats_dirty_only) {
-        int r = rt_backend_upload(c);
-        if (r) return r;
-        c->dirty = false;
-        c->mats_dirty_only = false;
-    }
-    return RT_OK;
+    return tables_current(c, true, false);
 }
 
 int rt_render(rt_context* c, int w, int h, int spp, int bounces, float* fb)
@@ -530,10 +520,7 @@ int rt_render_variants(rt_context* c, int w, int h, int spp, int bounces, int n_
         for (int v = 0; v < n_var; v++)
             if (!d_fbs[v]) return rt_fail(c, RT_ERR_ARG, "rt_render_variants: null device buffer");
     std::vector<RtMat> tabs((size_t)n_var * n_mats);
-    for (size_t i = 0; i < tabs.size(); i++) {
-        const float* p = materials + 10 * i;
-        tabs[i] = RtMat{p[0], p[1], p[2], p[8], p[4], p[5], p[6], p[9]};
-    }
+    for (size_t i = 0; i < tabs.size(); i++) tabs[i] = unpack_mat(materials + 10 * i);
     const int r = rt_backend_render_variants(c, w, h, spp, bounces, n_var, tabs, n_mats, row_offset, row_stride, fb, d_fbs);
     c->mats_dirty_only = true;  // the devices' tables hold the last variants: the next render re-sends the bound one
     return r;
@@ -555,13 +542,7 @@ int rt_intersect(rt_context* c, const float* rays, int n, void* out)
     if (!c || !c->have_scene || !c->have_bvh) return rt_fail(c, RT_ERR_STATE, "rt_intersect: scene/BVH not set");
     if (n < 0 || (n > 0 && (!rays || !out))) return rt_fail(c, RT_ERR_ARG, "rt_intersect: bad buffers");
     if (n == 0) return RT_OK;
-    if (c->dirty) {
-        placeholder_env(c);
-        int r = rt_backend_upload(c);
-        if (r) return r;
-        c->dirty = false;
-        c->mats_dirty_only = false;
-    }
+    if (int r = tables_current(c, false, true)) return r;
     return rt_backend_intersect(c, rays, n, out);
 }
 
@@ -581,13 +562,7 @@ static int query_ready(rt_context* c, const char* fn, int mode, const void* rays
         c->query_on_device = false;
         return RT_OK;
     }
-    if (c->dirty) {
-        placeholder_env(c);
-        if (int r = rt_backend_upload(c)) return r;
-        c->dirty = false;
-        c->mats_dirty_only = false;
-    }
-    return RT_OK;
+    return tables_current(c, false, true);
 }
 
 // Spheres and the brute-force mode take k_intersect's path for every query (rt_query.h).
@@ -642,13 +617,7 @@ static int features_ready(rt_context* c, int w, int h, const void* alb, const vo
     if (!c->have_cam) return rt_fail(c, RT_ERR_STATE, "rt_render_features: camera not set");
     if (w <= 0 || h <= 0 || !alb || !nd || alb == nd) return rt_fail(c, RT_ERR_ARG, "rt_render_features: bad buffers");
     if ((double)w * (double)h > 268435455.0) return rt_fail(c, RT_ERR_ARG, "rt_render_features: too many pixels");
-    if (c->dirty || c->mats_dirty_only) {
-        placeholder_env(c);
-        if (int r = rt_backend_upload(c)) return r;
-        c->dirty = false;
-        c->mats_dirty_only = false;
-    }
-    return RT_OK;
+    return tables_current(c, true, true);
 }
 
 int rt_render_features(rt_context* c, int w, int h, float* albedo, float* normal_depth)

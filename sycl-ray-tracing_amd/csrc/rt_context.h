@@ -217,6 +217,23 @@ int rt_for_devices(rt_context* c, int n, F fn)
     return 0;
 }
 RtSceneView rt_host_view(const rt_context* ctx);  // host-memory view (hostsim)
+// The view's fields that do not depend on where the tables live: the counts, the env's size and
+// CDF scalars, chain_monotone, brute and the near box. Both builds start their view with it.
+void rt_view_scalars(const rt_context* ctx, RtSceneView& v);
+// The context's host tables, each with the view's pointer to it: f(vector, field) for every one.
+// The host view points at the vectors, the device view at its upload of each. Not listed, because
+// the builds differ there: tri4 and mats (the device patches the one and re-sends the other alone),
+// matk (device only), tri_mat, and cdf_fence's null when the table is empty.
+#define RT_SCENE_TABLES 18
+template <class F>
+void rt_scene_tables(const rt_context* c, RtSceneView& v, F f)
+{
+    f(c->flat.nodes, v.nodes), f(c->flat.prim2k, v.prim2k), f(c->mat_idx, v.mat_idx), f(c->emissive, v.emissive);
+    f(c->spheres, v.spheres), f(c->env, v.env), f(c->env_lum, v.env_lum), f(c->cdf, v.cdf);
+    f(c->cdf_row, v.cdf_row), f(c->cdf_coarse, v.cdf_coarse), f(c->cdf_fence, v.cdf_fence);
+    f(c->flat.bvh4, v.bvh4), f(c->flat.bvh16, v.bvh16), f(c->flat.bvh4s, v.bvh4s), f(c->flat.bvh16s, v.bvh16s);
+    f(c->flat.bvh_tri4, v.bvh_tri4), f(c->flat.parent, v.parent), f(c->flat.leaf_of, v.leaf_of);
+}
 // The view's near box (rt_fast.h far_origin): the octree root's axis planes (the scene's box)
 // widened on every side by RT_NEAR_SCALE (or sched.near_scale) x the box's largest extent;
 // unbounded for an empty scene.

@@ -112,25 +112,6 @@ bool dn_use_lds(int variant, int step)
     return step <= 2;
 }
 
-// The post stage's buffers on the root device, cached across calls like the render's.
-struct Post {
-    DevBuf io;    // host-pointer calls: input, output, albedo, normal_depth
-    DevBuf pp;    // ping-pong colour buffers between passes
-    // optional per-pass timing (rt_device_denoise_pass_ms): an event before each pass and after the last
-    bool timing = false;
-    Event pev[11];
-    int timed_passes = 0;
-};
-
-int enter(rt_context* c, RtRootDev& R, DeviceScope& sc, Post** post)
-{
-    if (int r = rt_backend_root(c, &R)) return r;
-    if (int r = sc.enter(c, R.device)) return r;
-    if (!*R.post) *R.post = new Post();
-    *post = (Post*)*R.post;
-    return RT_OK;
-}
-
 int launch_pass(rt_context* c, const rtk::DnPass& P, float4_* out, const float4_* orig, float blend, bool lds,
                 hipStream_t s)
 {
@@ -151,68 +132,58 @@ int launch_pass(rt_context* c, const rtk::DnPass& P, float4_* out, const float4_
 
 }  // namespace
 
-void rt_post_free(void* post) { delete (Post*)post; }
+// The post stage's buffers on the root device, cached across calls like the render's.
+struct Post {
+    DevBuf io;    // host-pointer calls: input, output, albedo, normal_depth
+    DevBuf pp;    // ping-pong colour buffers between passes
+    // optional per-pass timing (rt_device_denoise_pass_ms): an event before each pass and after the last
+    bool timing = false;
+    Event pev[11];
+    int timed_passes = 0;
+};
+
+void PostDelete::operator()(Post* p) const { delete p; }
+
+static Post* post_of(Backend* b)  // (created on first use)
+{
+    if (!b->post) b->post.reset(new Post());
+    return b->post.get();
+}
 
 int rt_backend_features(rt_context* c, int w, int h, void* albedo, void* normal_depth, bool device, void* stream)
 {
-    RtRootDev R;
-    DeviceScope sc;
-    Post* post = nullptr;
-    if (int r = enter(c, R, sc, &post)) return r;
+    Backend* b = rt_backend_dev0(c);
+    StagedCall st;
+    if (int r = st.enter(c, b, device, stream, nullptr)) return r;
     const size_t n = (size_t)w * h, bytes = n * sizeof(float4_);
-    hipStream_t s = device ? (hipStream_t)stream : nullptr;
-    float4_ *d_alb = (float4_*)albedo, *d_nd = (float4_*)normal_depth;
-    if (!device) {
-        if (int r = ensure(c, post->io, 4 * bytes)) return r;
-        d_alb = (float4_*)post->io.p + 2 * n;
-        d_nd = (float4_*)post->io.p + 3 * n;
-    }
+    if (int r = st.staging(post_of(b)->io, 4 * bytes)) return r;  // (rt_denoise's four regions: one size for both)
+    float4_* d_alb = (float4_*)st.out(albedo, bytes);
+    float4_* d_nd = (float4_*)st.out(normal_depth, bytes);
     const rtk::CamView V = rtk::cam_view(c->cam, w, h);
-    HIPCHK(c, hipEventRecord(R.ev0, s));
-    hipLaunchKernelGGL(k_features, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, *R.view, V, d_alb, d_nd);
+    if (int r = st.begin()) return r;
+    hipLaunchKernelGGL(k_features, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st.s, b->view, V, d_alb, d_nd);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(R.ev1, s));
-    if (device) {
-        c->last_kernel_ms = -1.0;  // read with rt_device_last_kernel_ms after the caller synchronizes
-        return RT_OK;
-    }
-    HIPCHK(c, hipMemcpyAsync(albedo, d_alb, bytes, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipMemcpyAsync(normal_depth, d_nd, bytes, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    float ms = 0;
-    HIPCHK(c, hipEventElapsedTime(&ms, R.ev0, R.ev1));
-    c->last_kernel_ms = ms;
-    return RT_OK;
+    return st.end();
 }
 
 int rt_backend_denoise(rt_context* c, int w, int h, const void* in, const void* alb, const void* nd,
                        const rt_denoise_params& p, float blend, void* out, bool device, void* stream)
 {
-    RtRootDev R;
-    DeviceScope sc;
-    Post* post = nullptr;
-    if (int r = enter(c, R, sc, &post)) return r;
+    Backend* b = rt_backend_dev0(c);
+    StagedCall st;
+    if (int r = st.enter(c, b, device, stream, nullptr)) return r;
+    Post* post = post_of(b);
     const size_t n = (size_t)w * h, bytes = n * sizeof(float4_);
-    hipStream_t s = device ? (hipStream_t)stream : nullptr;
-    const float4_ *d_in = (const float4_*)in, *d_alb = (const float4_*)alb, *d_nd = (const float4_*)nd;
-    float4_* d_out = (float4_*)out;
     if (int r = ensure(c, post->pp, 2 * bytes)) return r;
-    if (!device) {
-        if (int r = ensure(c, post->io, 4 * bytes)) return r;
-        float4_* io = (float4_*)post->io.p;
-        HIPCHK(c, hipMemcpyAsync(io, in, bytes, hipMemcpyHostToDevice, s));
-        d_in = io;
-        d_out = io + n;
-        if (alb) {
-            HIPCHK(c, hipMemcpyAsync(io + 2 * n, alb, bytes, hipMemcpyHostToDevice, s));
-            HIPCHK(c, hipMemcpyAsync(io + 3 * n, nd, bytes, hipMemcpyHostToDevice, s));
-            d_alb = io + 2 * n;
-            d_nd = io + 3 * n;
-        }
-    }
+    if (int r = st.staging(post->io, 4 * bytes)) return r;
+    const float4_* d_in = (const float4_*)st.in(in, bytes);
+    float4_* d_out = (float4_*)st.out(out, bytes);
+    const float4_* d_alb = (const float4_*)st.in(alb, bytes);  // (both null: colour only)
+    const float4_* d_nd = (const float4_*)st.in(nd, bytes);
+    hipStream_t s = st.s;
     float4_* pp[2] = {(float4_*)post->pp.p, (float4_*)post->pp.p + n};
     const float4_* src = d_in;
-    HIPCHK(c, hipEventRecord(R.ev0, s));
+    if (int r = st.begin()) return r;
     for (int i = 0; i < p.passes; i++) {
         const bool last = i + 1 == p.passes;
         const rtk::DnPass P{w,
@@ -235,17 +206,7 @@ int rt_backend_denoise(rt_context* c, int w, int h, const void* in, const void* 
         HIPCHK(c, hipEventRecord(post->pev[p.passes], s));
         post->timed_passes = p.passes;
     }
-    HIPCHK(c, hipEventRecord(R.ev1, s));
-    if (device) {
-        c->last_kernel_ms = -1.0;  // read with rt_device_last_kernel_ms after the caller synchronizes
-        return RT_OK;
-    }
-    HIPCHK(c, hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    float ms = 0;
-    HIPCHK(c, hipEventElapsedTime(&ms, R.ev0, R.ev1));
-    c->last_kernel_ms = ms;
-    return RT_OK;
+    return st.end();
 }
 
 // MEASUREMENT HOOK, like rt_device_libm / rt_device_queries of rt_probe.hip: exported by the
@@ -256,10 +217,10 @@ int rt_backend_denoise(rt_context* c, int w, int h, const void* in, const void* 
 extern "C" int rt_device_denoise_pass_ms(rt_context* c, int enable, double* out_ms, int n)
 {
     if (!c || !c->backend) return RT_ERR_ARG;
-    RtRootDev R;
+    Backend* b = rt_backend_dev0(c);
     DeviceScope sc;
-    Post* post = nullptr;
-    if (int r = enter(c, R, sc, &post)) return r;
+    if (int r = sc.enter(c, b->device)) return r;
+    Post* post = post_of(b);
     if (enable == 1 && !post->pev[0])
         for (Event& e : post->pev) HIPCHK(c, hipEventCreate(&e.h));
     if (enable >= 0) {

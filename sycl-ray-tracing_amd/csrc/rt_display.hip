@@ -72,37 +72,18 @@ int launch_display(rt_context* c, const float4_* in, float4_* out, uint32_t* out
 int rt_backend_display(rt_context* c, int w, int h, const void* in, float exposure, float inv_gamma, bool flip,
                        void* out, void* out8, bool device, void* stream)
 {
-    RtRootDev R;
-    DeviceScope sc;
-    if (int r = rt_backend_root(c, &R)) return r;
-    if (int r = sc.enter(c, R.device)) return r;
+    Backend* b = rt_backend_dev0(c);
+    StagedCall st;
+    if (int r = st.enter(c, b, device, stream, nullptr)) return r;
     const size_t n = (size_t)w * h, fbytes = n * sizeof(float4_), bbytes = n * 4;
-    hipStream_t s = device ? (hipStream_t)stream : nullptr;
-    const float4_* d_in = (const float4_*)in;
-    float4_* d_out = (float4_*)out;
-    uint32_t* d_out8 = (uint32_t*)out8;
-    if (!device) {  // the frame, tone-mapped in place when the float output is asked for; the bytes behind it
-        if (int r = ensure(c, *R.disp, fbytes + bbytes)) return r;
-        float4_* io = (float4_*)R.disp->p;
-        HIPCHK(c, hipMemcpyAsync(io, in, fbytes, hipMemcpyHostToDevice, s));
-        d_in = io;
-        d_out = out ? io : nullptr;
-        d_out8 = out8 ? (uint32_t*)(io + n) : nullptr;
-    }
-    HIPCHK(c, hipEventRecord(R.ev0, s));
-    if (int r = launch_display(c, d_in, d_out, d_out8, w, h, flip, exposure, inv_gamma, s)) return r;
-    HIPCHK(c, hipEventRecord(R.ev1, s));
-    if (device) {
-        c->last_kernel_ms = -1.0;  // read with rt_device_last_kernel_ms after the caller synchronizes
-        return RT_OK;
-    }
-    if (out) HIPCHK(c, hipMemcpyAsync(out, d_out, fbytes, hipMemcpyDeviceToHost, s));
-    if (out8) HIPCHK(c, hipMemcpyAsync(out8, d_out8, bbytes, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    float ms = 0;
-    HIPCHK(c, hipEventElapsedTime(&ms, R.ev0, R.ev1));
-    c->last_kernel_ms = ms;
-    return RT_OK;
+    if (int r = st.staging(b->disp, fbytes + bbytes)) return r;
+    // host form: the frame, tone-mapped in place when the float output is asked for; the bytes behind it
+    const float4_* d_in = (const float4_*)st.inout(in, out, fbytes);
+    float4_* d_out = device ? (float4_*)out : out ? (float4_*)d_in : nullptr;
+    uint32_t* d_out8 = (uint32_t*)st.out(out8, bbytes);
+    if (int r = st.begin()) return r;
+    if (int r = launch_display(c, d_in, d_out, d_out8, w, h, flip, exposure, inv_gamma, st.s)) return r;
+    return st.end();
 }
 
 int rt_display_resolve_linear(rt_context* c, const float4_* base, const float4_* state, float4_* out, int n, int done,
@@ -128,10 +109,8 @@ extern "C" int rt_device_display_kernel_ms(rt_context* c, int w, int h, const vo
     if (!c || !c->backend || w <= 0 || h <= 0 || (double)w * (double)h > 134217727.0 || !d_in || !d_state || !d_out ||
         !d_out8 || reps <= 0 || !out_ms)
         return rt_fail(c, RT_ERR_ARG, "rt_device_display_kernel_ms: bad arguments");
-    RtRootDev R;
     DeviceScope sc;
-    if (int r = rt_backend_root(c, &R)) return r;
-    if (int r = sc.enter(c, R.device)) return r;
+    if (int r = sc.enter(c, rt_backend_dev0(c)->device)) return r;
     Event e0, e1;
     HIPCHK(c, hipEventCreate(&e0.h));
     HIPCHK(c, hipEventCreate(&e1.h));
@@ -142,22 +121,17 @@ extern "C" int rt_device_display_kernel_ms(rt_context* c, int w, int h, const vo
     const float ex = 1.5f, ig = 1.0f / 2.2f;
     for (int r = 0; r < reps; r++)
         for (int k = 0; k < 6; k++) {
-            HIPCHK(c, hipEventRecord(e0, nullptr));
-            int rc = RT_OK;
-            switch (k) {
-            case 0: rc = rt_wave_resolve(c, in, state, out, n, 1, nullptr); break;
-            case 1: rc = rt_display_resolve_linear(c, in, state, out, n, 1, nullptr); break;
-            case 2: rc = launch_display(c, in, out, nullptr, w, h, false, ex, ig, nullptr); break;
-            case 3: rc = launch_display(c, in, nullptr, out8, w, h, false, ex, ig, nullptr); break;
-            case 4: rc = launch_display(c, in, nullptr, out8, w, h, true, ex, ig, nullptr); break;
-            default: rc = launch_display(c, in, out, out8, w, h, false, ex, ig, nullptr); break;
-            }
-            HIPCHK(c, hipEventRecord(e1, nullptr));
-            if (rc) return rc;
-            HIPCHK(c, hipEventSynchronize(e1));
-            float ms = 0;
-            HIPCHK(c, hipEventElapsedTime(&ms, e0, e1));
-            out_ms[(size_t)k * reps + r] = ms;
+            auto launch = [&]() -> int {
+                switch (k) {
+                case 0: return rt_wave_resolve(c, in, state, out, n, 1, nullptr);
+                case 1: return rt_display_resolve_linear(c, in, state, out, n, 1, nullptr);
+                case 2: return launch_display(c, in, out, nullptr, w, h, false, ex, ig, nullptr);
+                case 3: return launch_display(c, in, nullptr, out8, w, h, false, ex, ig, nullptr);
+                case 4: return launch_display(c, in, nullptr, out8, w, h, true, ex, ig, nullptr);
+                default: return launch_display(c, in, out, out8, w, h, false, ex, ig, nullptr);
+                }
+            };
+            if (int e = rt_time_alone(c, e0, e1, launch, &out_ms[(size_t)k * reps + r])) return e;
         }
     return RT_OK;
 }

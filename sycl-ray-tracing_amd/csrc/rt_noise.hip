@@ -139,41 +139,23 @@ int rt_backend_progress_noise(rt_context* c, const rtk::NoiseArgs& A, int32_t* s
 {
     Backend* b = rt_backend_dev0(c);
     const RtProgress& P = c->prog;
-    DeviceScope sc;
-    if (int r = sc.enter(c, b->device)) return r;
+    StagedCall st;
+    if (int r = st.enter(c, b, device, stream, b->own)) return r;
     const size_t n = P.npx(), n_tiles = (size_t)P.tiles_w() * P.tiles_h();
-    hipStream_t s = device ? (hipStream_t)stream : (hipStream_t)b->own;
-    uint32_t* d_st = (uint32_t*)stats;
-    float *d_px = pixel_err, *d_tl = tile_err;
-    if (!device) {  // the stat words, then the maps asked for
-        if (int r = ensure(c, b->pg_noise, 32 + 4 * ((pixel_err ? n : 0) + (tile_err ? n_tiles : 0)))) return r;
-        d_st = (uint32_t*)b->pg_noise.p;
-        float* f = (float*)((char*)b->pg_noise.p + 32);
-        d_px = pixel_err ? f : nullptr;
-        d_tl = tile_err ? f + (pixel_err ? n : 0) : nullptr;
-    }
-    if (b->done_recorded) HIPCHK(c, hipStreamWaitEvent(s, b->ev_done, 0));  // (the last pass and its fold)
+    // host form: the stat words, then the maps asked for
+    if (int r = st.staging(b->pg_noise, 32 + (pixel_err ? st.pad(4 * n) : 0) + (tile_err ? 4 * n_tiles : 0))) return r;
+    uint32_t* d_st = (uint32_t*)st.out(stats, 32);
+    float* d_px = (float*)st.out(pixel_err, 4 * n);
+    float* d_tl = (float*)st.out(tile_err, 4 * n_tiles);
+    if (int r = b->ev_done.wait(c, st.s)) return r;  // (the last pass and its fold)
     // (a device query re-records ev_pg below: what an earlier device resolve recorded stays ahead of it)
-    if (device && b->pg_recorded) HIPCHK(c, hipStreamWaitEvent(s, b->ev_pg, 0));
-    HIPCHK(c, hipEventRecord(b->ev0, s));
+    if (device)
+        if (int r = b->ev_pg.wait(c, st.s)) return r;
+    if (int r = st.begin()) return r;
     if (int r = launch_tiles(c, (const float4_*)b->pg_state.p, (const float4_*)b->pg_half.p, P.w, P.rows, A, d_px, d_tl,
-                             d_st, s))
+                             d_st, st.s))
         return r;
-    HIPCHK(c, hipEventRecord(b->ev1, s));
-    if (device) {
-        HIPCHK(c, hipEventRecord(b->ev_pg, s));  // (the next pass writes what this reads)
-        b->pg_recorded = true;
-        c->last_kernel_ms = -1.0;  // read with rt_device_last_kernel_ms after the caller synchronizes
-        return RT_OK;
-    }
-    HIPCHK(c, hipMemcpyAsync(stats, d_st, 32, hipMemcpyDeviceToHost, s));
-    if (pixel_err) HIPCHK(c, hipMemcpyAsync(pixel_err, d_px, 4 * n, hipMemcpyDeviceToHost, s));
-    if (tile_err) HIPCHK(c, hipMemcpyAsync(tile_err, d_tl, 4 * n_tiles, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    float ms = 0;
-    HIPCHK(c, hipEventElapsedTime(&ms, b->ev0, b->ev1));
-    c->last_kernel_ms = ms;
-    return RT_OK;
+    return st.end(&b->ev_pg);  // (device form: the next pass writes what this reads)
 }
 
 // MEASUREMENT HOOK, like rt_device_display_kernel_ms of rt_display.hip: exported by the gfx950
@@ -200,25 +182,12 @@ extern "C" int rt_device_noise_kernel_ms(rt_context* c, int w, int h, const void
     const rtk::NoiseArgs A{4.0f, 2.0f, 1.0f, 0.05f, 2, 2, 2};
     for (int r = 0; r < reps; r++)
         for (int k = 0; k < 3; k++) {
-            HIPCHK(c, hipEventRecord(e0, nullptr));
-            int rc = RT_OK;
-            switch (k) {
-            case 0: rc = launch_fold(c, (float4_*)d_half, (const float4_*)d_state, w * h, (r & 1) != 0, nullptr); break;
-            case 1:
-                rc = launch_tiles(c, (const float4_*)d_state, (const float4_*)d_half, w, h, A, nullptr, (float*)d_tile,
-                                  (uint32_t*)d_stats, nullptr);
-                break;
-            default:
-                rc = launch_tiles(c, (const float4_*)d_state, (const float4_*)d_half, w, h, A, (float*)d_pixel,
-                                  (float*)d_tile, (uint32_t*)d_stats, nullptr);
-                break;
-            }
-            HIPCHK(c, hipEventRecord(e1, nullptr));
-            if (rc) return rc;
-            HIPCHK(c, hipEventSynchronize(e1));
-            float ms = 0;
-            HIPCHK(c, hipEventElapsedTime(&ms, e0, e1));
-            out_ms[(size_t)k * reps + r] = ms;
+            auto launch = [&]() -> int {
+                if (k == 0) return launch_fold(c, (float4_*)d_half, (const float4_*)d_state, w * h, (r & 1) != 0, nullptr);
+                return launch_tiles(c, (const float4_*)d_state, (const float4_*)d_half, w, h, A,
+                                    k == 1 ? nullptr : (float*)d_pixel, (float*)d_tile, (uint32_t*)d_stats, nullptr);
+            };
+            if (int e = rt_time_alone(c, e0, e1, launch, &out_ms[(size_t)k * reps + r])) return e;
         }
     return RT_OK;
 }

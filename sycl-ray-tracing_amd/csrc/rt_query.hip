@@ -161,36 +161,6 @@ __global__ __launch_bounds__(256) void k_rq_exact(RtSceneView S, const float* __
     }
 }
 
-// The queries' workspace on the root device, cached across calls and grown on demand like
-// the post stage's buffers.
-struct Query {
-    DevBuf list;     // 64 B (the fallback count in its first word), then n indices
-    DevBuf io;       // host-pointer calls: the rays, then the answers
-    Event done;  // the end of the last call's kernels (rt_query_last_exact waits for it)
-    int blocks[4] = {0, 0, 0, 0};  // resident blocks per CU of k_rq_fast<ANY, REFILL>, asked once
-    int cus = 0;
-};
-
-int enter(rt_context* c, RtRootDev& R, DeviceScope& sc, Query** query)
-{
-    if (int r = rt_backend_root(c, &R)) return r;
-    if (int r = sc.enter(c, R.device)) return r;
-    if (!*R.query) {
-        Query* q = new Query();
-        *R.query = q;
-        HIPCHK(c, hipEventCreate(&q->done.h));
-        HIPCHK(c, hipDeviceGetAttribute(&q->cus, hipDeviceAttributeMultiprocessorCount, R.device));
-        const void* fn[4] = {(const void*)k_rq_fast<false, false>, (const void*)k_rq_fast<false, true>,
-                             (const void*)k_rq_fast<true, false>, (const void*)k_rq_fast<true, true>};
-        for (int i = 0; i < 4; i++) {
-            HIPCHK(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&q->blocks[i], fn[i], 256, 0));
-            q->blocks[i] = std::max(1, std::min(8, q->blocks[i]));
-        }
-    }
-    *query = (Query*)*R.query;
-    return RT_OK;
-}
-
 // rq_variant (rt_test_schedule): 1 the plain rounds, 2 the per-quad refill, 0 the product's
 // choice: the refill (profiles/query_api_bench.json), plain / refill ms for 2 M
 // rays over the cfg2 dragon on the MI355X: bounce rays closest 0.419 / 0.356, any 0.373 / 0.268;
@@ -201,36 +171,62 @@ bool use_refill(int variant) { return variant != 1; }
 
 }  // namespace
 
-void rt_query_free(void* query) { delete (Query*)query; }
+// The queries' workspace on the root device, cached across calls and grown on demand like
+// the post stage's buffers.
+struct Query {
+    DevBuf list;     // 64 B (the fallback count in its first word), then n indices
+    DevBuf io;       // host-pointer calls: the rays, then the answers
+    Event done;  // the end of the last call's kernels (rt_query_last_exact waits for it)
+    int blocks[4] = {0, 0, 0, 0};  // resident blocks per CU of k_rq_fast<ANY, REFILL>, asked once
+    int cus = 0;
+};
+
+void QueryDelete::operator()(Query* q) const { delete q; }
+
+// (created on first use; b's device is current)
+static int query_of(rt_context* c, Backend* b, Query** out)
+{
+    if (!b->query) {
+        Query* q = new Query();
+        b->query.reset(q);
+        HIPCHK(c, hipEventCreate(&q->done.h));
+        HIPCHK(c, hipDeviceGetAttribute(&q->cus, hipDeviceAttributeMultiprocessorCount, b->device));
+        const void* fn[4] = {(const void*)k_rq_fast<false, false>, (const void*)k_rq_fast<false, true>,
+                             (const void*)k_rq_fast<true, false>, (const void*)k_rq_fast<true, true>};
+        for (int i = 0; i < 4; i++) {
+            HIPCHK(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&q->blocks[i], fn[i], 256, 0));
+            q->blocks[i] = std::max(1, std::min(8, q->blocks[i]));
+        }
+    }
+    *out = b->query.get();
+    return RT_OK;
+}
 
 int rt_backend_query(rt_context* c, bool any, bool all_exact, const void* rays, long n, void* out, bool device,
                      void* stream)
 {
-    RtRootDev R;
-    DeviceScope sc;
+    Backend* b = rt_backend_dev0(c);
+    StagedCall st;
     Query* Q = nullptr;
-    if (int r = enter(c, R, sc, &Q)) return r;
-    hipStream_t s = device ? (hipStream_t)stream : nullptr;
+    if (int r = st.enter(c, b, device, stream, nullptr)) return r;
+    if (int r = query_of(c, b, &Q)) return r;
+    hipStream_t s = st.s;
     const size_t ray_bytes = (size_t)n * 24, out_bytes = (size_t)n * (any ? 4 : 4 * RQ_WORDS);
-    const float* d_rays = (const float*)rays;
-    int32_t* d_out = (int32_t*)out;
-    if (!device) {
-        if (int r = ensure(c, Q->io, ray_bytes + out_bytes)) return r;
-        HIPCHK(c, hipMemcpyAsync(Q->io.p, rays, ray_bytes, hipMemcpyHostToDevice, s));
-        d_rays = (const float*)Q->io.p;
-        d_out = (int32_t*)((char*)Q->io.p + ray_bytes);
-    }
+    if (int r = st.staging(Q->io, st.pad(ray_bytes) + out_bytes)) return r;
+    const float* d_rays = (const float*)st.in(rays, ray_bytes);
+    int32_t* d_out = (int32_t*)st.out(out, out_bytes);
     const int ni = (int)n;  // (n < 2^27, rt_capi_host.cpp)
     const unsigned per_thread = (unsigned)((n + 255) / 256);
     c->query_on_device = !all_exact;
     c->query_exact = n;
+    if (!all_exact)
+        if (int r = ensure(c, Q->list, 64 + (size_t)n * 4)) return r;
+    if (int r = st.begin()) return r;
     if (all_exact) {
-        HIPCHK(c, hipEventRecord(R.ev0, s));
-        hipLaunchKernelGGL(k_rq_exact, dim3(per_thread), dim3(256), 0, s, *R.view, d_rays, d_out, ni,
+        hipLaunchKernelGGL(k_rq_exact, dim3(per_thread), dim3(256), 0, s, b->view, d_rays, d_out, ni,
                            (const int32_t*)nullptr, (const int32_t*)nullptr, any ? 1 : 0);
         HIPCHK(c, hipGetLastError());
     } else {
-        if (int r = ensure(c, Q->list, 64 + (size_t)n * 4)) return r;
         int32_t* count = (int32_t*)Q->list.p;
         int32_t* list = count + 16;
         const bool refill = use_refill(c->sched.rq_variant);
@@ -240,44 +236,35 @@ int rt_backend_query(rt_context* c, bool any, bool all_exact, const void* rays, 
         // (the list's length is known on the device only: a grid for the near-box shares the
         // render sees, the rest by stride)
         const unsigned exact_blocks = std::min(per_thread, (unsigned)Q->cus * 8u);
-        HIPCHK(c, hipEventRecord(R.ev0, s));
         HIPCHK(c, hipMemsetAsync(count, 0, 4, s));
         if (any) {
             if (refill)
-                hipLaunchKernelGGL((k_rq_fast<true, true>), dim3(fast_blocks), dim3(256), 0, s, *R.view, d_rays, d_out, ni, list, count);
+                hipLaunchKernelGGL((k_rq_fast<true, true>), dim3(fast_blocks), dim3(256), 0, s, b->view, d_rays, d_out, ni, list, count);
             else
-                hipLaunchKernelGGL((k_rq_fast<true, false>), dim3(fast_blocks), dim3(256), 0, s, *R.view, d_rays, d_out, ni, list, count);
+                hipLaunchKernelGGL((k_rq_fast<true, false>), dim3(fast_blocks), dim3(256), 0, s, b->view, d_rays, d_out, ni, list, count);
         } else {
             if (refill)
-                hipLaunchKernelGGL((k_rq_fast<false, true>), dim3(fast_blocks), dim3(256), 0, s, *R.view, d_rays, d_out, ni, list, count);
+                hipLaunchKernelGGL((k_rq_fast<false, true>), dim3(fast_blocks), dim3(256), 0, s, b->view, d_rays, d_out, ni, list, count);
             else
-                hipLaunchKernelGGL((k_rq_fast<false, false>), dim3(fast_blocks), dim3(256), 0, s, *R.view, d_rays, d_out, ni, list, count);
+                hipLaunchKernelGGL((k_rq_fast<false, false>), dim3(fast_blocks), dim3(256), 0, s, b->view, d_rays, d_out, ni, list, count);
         }
         HIPCHK(c, hipGetLastError());
-        hipLaunchKernelGGL(k_rq_exact, dim3(exact_blocks), dim3(256), 0, s, *R.view, d_rays, d_out, ni,
+        hipLaunchKernelGGL(k_rq_exact, dim3(exact_blocks), dim3(256), 0, s, b->view, d_rays, d_out, ni,
                            (const int32_t*)list, (const int32_t*)count, any ? 1 : 0);
         HIPCHK(c, hipGetLastError());
     }
-    HIPCHK(c, hipEventRecord(R.ev1, s));
+    if (int r = st.stop()) return r;
     HIPCHK(c, hipEventRecord(Q->done, s));
-    if (device) {
-        c->last_kernel_ms = -1.0;  // read with rt_device_last_kernel_ms after the caller synchronizes
-        return RT_OK;
-    }
-    HIPCHK(c, hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    float ms = 0;
-    HIPCHK(c, hipEventElapsedTime(&ms, R.ev0, R.ev1));
-    c->last_kernel_ms = ms;
-    return RT_OK;
+    return st.finish();
 }
 
 long rt_backend_query_last_exact(rt_context* c)
 {
-    RtRootDev R;
+    Backend* b = rt_backend_dev0(c);
     DeviceScope sc;
     Query* Q = nullptr;
-    if (int r = enter(c, R, sc, &Q)) return r;
+    if (int r = sc.enter(c, b->device)) return r;
+    if (int r = query_of(c, b, &Q)) return r;
     if (!c->query_on_device) {
         // (every query took the exact walk, or no call yet: known on the host; wait all the same)
         if (c->query_exact > 0) HIPCHK(c, hipEventSynchronize(Q->done));

@@ -117,7 +117,7 @@ int WaveRun::begin()
 {
     // every render of a context reuses its lanes' slots and counters: the previous render
     // (whose tail kernel may still run, on another stream) must finish first
-    if (b->done_recorded) HIPCHK(c, hipStreamWaitEvent(s, b->ev_done, 0));
+    if (int r = b->ev_done.wait(c, s)) return r;
     (void)hipDeviceGetAttribute(&dev_cus, hipDeviceAttributeMultiprocessorCount, b->device);
     const RtDiag& dg = c->diag;
     S = c->stats_enabled;
@@ -280,8 +280,8 @@ int WaveRun::fast_launch()
     if (!any) return RT_OK;
     if (!b->h_fviews)
         HIPCHK(c, hipHostMalloc((void**)&b->h_fviews.h, sizeof(rtk::WaveView) * RT_MAX_LANES, hipHostMallocDefault));
-    if (!b->fev_done) HIPCHK(c, hipEventCreateWithFlags(&b->fev_done.h, hipEventDisableTiming));
-    if (b->fev_done_recorded) HIPCHK(c, hipEventSynchronize(b->fev_done));  // (the last render's copy of the views)
+    if (!b->fev_done.ev) HIPCHK(c, hipEventCreateWithFlags(&b->fev_done.ev.h, hipEventDisableTiming));
+    if (int r = b->fev_done.sync(c)) return r;  // (the last render's copy of the views)
     if (int r = ensure(c, b->fviews, sizeof(rtk::WaveView) * RT_MAX_LANES)) return r;
     int start[RT_MAX_LANES + 1] = {}, tot = 0;
     for (int l = 0; l < RT_MAX_LANES; l++) {
@@ -312,8 +312,8 @@ int WaveRun::fast_launch()
                        make_int4(start[0], start[1], start[2], start[3]), stats);
     HIPCHK(c, hipGetLastError());
     if (b->timing) HIPCHK(c, hipEventRecord(b->ftev[1], fstream));
-    HIPCHK(c, hipEventRecord(b->fev_done, fstream));
-    b->fev_done_recorded = fast_ran = true;
+    if (int r = b->fev_done.record(c, fstream)) return r;
+    fast_ran = true;
     return RT_OK;
 }
 
@@ -505,7 +505,7 @@ int WaveRun::finish()
     const int nl = P.lanes;
     for (int l = 0; l < nl; l++) {
         if (fast_ran)
-            HIPCHK(c, hipStreamWaitEvent(L[l].s, b->fev_done, 0));  // (and the fast lane's)
+            if (int r = b->fev_done.wait(c, L[l].s)) return r;  // (and the fast lane's)
         if (pass) continue;  // (a progressive pass leaves the pixels paused: rt_progress_resolve tone-maps)
         if (linear) continue;  // (rt_render_linear: the framebuffer keeps finish_pixel's sum)
         launch_k_tonemap(dim3((L[l].n + threads - 1) / threads), L[l].s, L[l].W);
@@ -520,9 +520,7 @@ int WaveRun::finish()
         }
     }
     b->tail_iter = L[0].tail_iter;
-    HIPCHK(c, hipEventRecord(b->ev_done, s));
-    b->done_recorded = true;
-    return RT_OK;
+    return b->ev_done.record(c, s);
 }
 
 // The run's diagnostics: walk log, iteration counts, per-kernel ms, timeline, RT_DEBUG_FB.
