@@ -45,7 +45,8 @@ $(OBJ)/rt_hostsim.o: $(SRC)/rt_hostsim.cpp $(HDRS) $(ALL_SRC)
 #   rt_query     the ray queries (rt_query / rt_query_device)
 #   rt_display   the display stage (tone-map + 8-bit conversion, linear resolve)
 #   rt_noise     a tracked progression's fold and noise estimate
-HIP_UNITS := rt_render rt_wave_run rt_probe rt_denoise rt_query rt_display rt_noise
+#   rt_adapt     an adaptive progression's selection, gather / scatter and resolves
+HIP_UNITS := rt_render rt_wave_run rt_probe rt_denoise rt_query rt_display rt_noise rt_adapt
 $(HIP_UNITS:%=$(OBJ)/%.o): $(OBJ)/%.o: $(SRC)/%.hip $(HDRS)
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
@@ -147,6 +148,8 @@ hostsim-variant: $(OBJ)/rt_imageio.host.o
 #   progress_shim_test  render_progressive against render()                 tests/test_progress_shim.py
 #   display_shim_test   display(render_linear()) against render()           tests/test_display_shim.py
 #   noise_test          progress_track_noise / progress_noise against the C ABI tests/test_noise_shim.py
+#   adaptive_shim_test  render_adaptive against the C ABI                   tests/test_adaptive_shim.py
+#                       (make sanitize-adaptive: the same program under ASan + UBSan over the hostsim sources)
 REFDIR ?= /root/reference
 REFOBJ := oracle/_ref/objO2
 REFOBJS := $(REFOBJ)/bvh.o $(REFOBJ)/flattened_bvh.o $(REFOBJ)/triangle.o $(REFOBJ)/vec.o $(REFOBJ)/color.o \
@@ -188,3 +191,11 @@ sanitize: build/san_asan/driver build/san_tsan/driver
 	  build/san_tsan/driver scenes tsan 2>&1 | tee profiles/r04_sanitize_tsan.log
 
 .PHONY: sanitize
+
+# render_adaptive and the adaptive C calls under ASan + UBSan: tests/native/adaptive_shim_test.cpp with the
+# hostsim sources of build/san_asan in one stand-alone executable (container only: the reference's objects).
+build/san_asan/adaptive_shim_test: tests/native/adaptive_shim_test.cpp include/render_kernel_hip.h build/san_asan/driver
+	$(CXX) -std=gnu++20 $(SAN_NUM) $(ASAN) -Iinclude -I$(REFDIR)/include -I$(REFDIR)/rapidobj -I$(REFDIR) $< \
+	  $(filter-out build/san_asan/cpu_oracle.o,$(wildcard build/san_asan/*.o)) $(REFOBJS) -Wl,--gc-sections -o $@
+sanitize-adaptive: build/san_asan/adaptive_shim_test
+.PHONY: sanitize-adaptive

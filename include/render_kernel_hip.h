@@ -184,6 +184,34 @@ public:
         m_track = false;
     }
 
+    // render() with the samples spent where the noise is (rt_progress_advance_adaptive): two uniform
+    // passes of pass_samples, then passes that advance only the 8x8 tiles whose noise estimate is
+    // above `threshold`, until none is (or none fits under render_samples any more: keep
+    // render_samples a multiple of pass_samples), or after max_passes adaptive passes (0: no limit).
+    // The Image& then holds every pixel's mean over its tile's samples, added to the base it held.
+    // Returns tile_n, the samples per tile, ceil(height / 8) rows of ceil(width / 8). A pixel whose
+    // tile has c samples is what render_progressive shows it to be after c samples. Single device only.
+    std::vector<int> render_adaptive(float threshold, int pass_samples, int max_passes = 0)
+    {
+        std::lock_guard<std::mutex> lk(m_mu);
+        sync_materials();
+        check(rt_progress_begin(m_ctx, m_width, m_height, m_render_samples, m_max_bounces, m_frame_buffer.data(), 0, 1));
+        std::vector<int> tile_n((size_t)((m_width + 7) / 8) * ((m_height + 7) / 8));
+        int rc = rt_progress_noise_track(m_ctx);
+        for (int p = 0; rc == RT_OK && p < 2; p++) rc = rt_progress_advance(m_ctx, pass_samples, nullptr);
+        for (int p = 0; rc == RT_OK && (max_passes <= 0 || p < max_passes); p++) {
+            int info[8];
+            rc = rt_progress_advance_adaptive(m_ctx, pass_samples, threshold, nullptr, info);
+            if (rc != RT_OK || info[0] == 0) break;
+        }
+        if (rc == RT_OK) rc = rt_progress_resolve(m_ctx, m_frame_buffer.data());
+        if (rc == RT_OK) rc = rt_progress_tile_counts(m_ctx, tile_n.data(), nullptr);
+        const std::string err = rc == RT_OK ? std::string() : std::string("librt_hip: ") + rt_last_error(nullptr);
+        rt_progress_end(m_ctx);
+        if (rc != RT_OK) throw std::runtime_error(err);
+        return tile_n;
+    }
+
     // Thread-safe like the reference's (whose render() calls it from an OpenMP parallel-for,
     // render_kernel.cpp:189-211): calls on one kernel are serialized, since they share the
     // context's device buffers and the material-sync state. For throughput, hand pixel

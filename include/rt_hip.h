@@ -444,6 +444,54 @@ int rt_progress_noise(rt_context* ctx, float threshold, rt_noise_stats* stats, f
 int rt_progress_noise_device(rt_context* ctx, float threshold, void* d_stats, void* d_pixel_err, void* d_tile_err,
                              void* stream);
 
+/* ------------------------------------------- adaptive sampling of a progression
+ * A frame that spends its samples where the noise is: a pass advances only the 8x8 tiles (the
+ * noise estimate's tiles, over the shard's local rows, t = ty*tw + tx) whose error is still above
+ * a threshold. Every pixel stays a bit-exact prefix of the chain rt_render runs for it: a pixel
+ * with c samples holds the state an untracked progression of the same total holds at done = c.
+ *
+ * An adaptive progression is a tracked progression plus two int32 per tile: tile_n[t], the
+ * samples done by every pixel of the tile, and tile_nA[t], how many of them fell in A passes.
+ *
+ * rt_progress_advance_adaptive: on a tracked progression; the first call makes it adaptive with
+ *   tile_n = done and tile_nA = nA in every tile. Tile t is active in the pass iff
+ *       tile_n[t] + samples <= total    and    (passes < 2  or  tile_err[t] > threshold)
+ *   where tile_err is the noise estimate's tile value computed with the tile's own counts
+ *   (N = tile_n[t], nA = tile_nA[t], nB = N - nA; a NaN compares false). While passes < 2 there is
+ *   no estimate and every tile that fits is active. A tile with tile_err > threshold that does not
+ *   fit under the total is capped, not active: choose a total that is a multiple of the pass size.
+ *   Active tiles get tile_n += samples and, on an A pass, tile_nA += samples; the half fold runs
+ *   over their pixels only, and no word of an inactive pixel is touched. Pass parity stays global:
+ *   the pass is an A pass iff `passes` is even; passes, nA and nB advance as for rt_progress_advance
+ *   when a pass is launched (they are what a tile active in every pass has, and rt_noise_stats keeps
+ *   reporting them). A tile that was active in A passes only has a lopsided split; k still
+ *   normalises it, the estimate is valid but less sharp.
+ *   The call waits for the work already queued on the progression, reads one small header back to
+ *   size the launch, enqueues the pass on `stream` and returns without waiting for it.
+ *   info = {active tiles, active pixels, capped tiles, min tile_n after, max tile_n after, tiles,
+ *   0, 0}. No active tile: RT_OK, nothing launched, passes unchanged.
+ *   The active pixels are listed by ascending tile, row-major inside a tile, so the pass is a pure
+ *   function of the state: runs, checkpoints and the two builds agree.
+ * On an adaptive progression:
+ *   rt_progress_resolve*, _linear*: divide by the pixel's tile count, same operations.
+ *   rt_progress_noise / _device: the tile's counts in k and both divisions; a tile with nA == 0 or
+ *     nB == 0 gives non-finite elements, which count 0.
+ *   rt_progress_info: done is the smallest tile_n.
+ *   rt_progress_advance: RT_ERR_STATE once the tile counts differ; with equal counts it behaves as
+ *     before and keeps the tile arrays in step.
+ *   rt_progress_save writes format version 3: the version-2 layout (its done word holds nA + nB),
+ *     then tile_n[th*tw], then tile_nA[th*tw]. It loads as an adaptive progression and continues to
+ *     the uninterrupted run's bits. RT_ERR_ARG for a size that does not match, tile_nA outside
+ *     0..tile_n, tile_n outside 0..total, or counts that mix zero and positive (no call leaves
+ *     such a state: a pass either starts its pixels' chains or resumes them). Versions 1 and 2 are
+ *     written and read as before.
+ * rt_progress_tile_counts: th*tw int32 each (either may be NULL); waits. A tracked progression that
+ *   is not adaptive yet reports done and nA in every tile.
+ * RT_ERR_STATE: no progression, or an untracked one. RT_ERR_ARG: samples <= 0, a threshold that
+ * is not finite and >= 0, a NULL info, a multi-device context. */
+int rt_progress_advance_adaptive(rt_context* ctx, int samples, float threshold, void* stream, int info[8]);
+int rt_progress_tile_counts(rt_context* ctx, int* tile_n, int* tile_nA);
+
 /* Counters of the last render when enabled (RT_STAT_* order, rt_device.h);
  * with n up to 2 * RT_STAT_COUNT the second block is the share of the
  * gfx950 tail kernel (k_tail) in those totals. */

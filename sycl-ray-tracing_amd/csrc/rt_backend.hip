@@ -15,6 +15,7 @@
 
 #include <rccl/rccl.h>
 
+#include "rt_adapt.h"
 #include "rt_backend_hip.h"
 #include "rt_wave.h"
 
@@ -561,8 +562,10 @@ int rt_backend_progress_resolve(rt_context* c, float* host_fb, void* dev_fb, voi
     if (int r = b->ev_done.wait(c, s)) return r;  // (the last pass, on its own streams)
     const float4_ *base = (const float4_*)b->pg_base.p, *state = (const float4_*)b->pg_state.p;
     if (int r = st.begin()) return r;
-    if (int r = linear ? rt_display_resolve_linear(c, base, state, out, n, P.done, s)
-                       : rt_wave_resolve(c, base, state, out, n, P.done, s))
+    if (P.adaptive) {  // (the pixel's tile count for `done`: rt_adapt.hip)
+        if (int r = rt_adapt_resolve(c, b, base, state, out, linear, s)) return r;
+    } else if (int r = linear ? rt_display_resolve_linear(c, base, state, out, n, P.done, s)
+                              : rt_wave_resolve(c, base, state, out, n, P.done, s))
         return r;
     return st.end(&b->ev_pg);  // (device form: the next pass writes the state this reads)
 }
@@ -591,6 +594,7 @@ void rt_backend_progress_end(rt_context* c)
     release(b->pg_out);
     release(b->pg_half);
     release(b->pg_noise);
+    b->adapt.reset();
 }
 
 int rt_backend_progress_track(rt_context* c, const float* half)
@@ -614,6 +618,82 @@ int rt_backend_progress_read_half(rt_context* c, float* half)
     if (int r = sc.enter(c, b->device)) return r;
     if (int r = progress_quiesce(c, b)) return r;
     HIPCHK(c, hipMemcpy(half, b->pg_half.p, c->prog.npx() * sizeof(float4_), hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+// ---- adaptive progressions (rt_adapt.h): the stages are rt_adapt.hip's, the pass is run_wave over
+// the compact pixel list with the compact state as its WavePass.
+int rt_backend_progress_adapt_begin(rt_context* c, const int32_t* tile_n, const int32_t* tile_nA)
+{
+    Backend* b = be(c);
+    const RtProgress& P = c->prog;
+    DeviceScope sc;
+    if (int r = sc.enter(c, b->device)) return r;
+    if (int r = progress_quiesce(c, b)) return r;
+    if (!b->adapt) b->adapt.reset(new Adapt);
+    const size_t n_tiles = (size_t)P.tiles_w() * P.tiles_h();
+    if (int r = ensure(c, b->adapt->tile_n, 4 * n_tiles)) return r;
+    if (int r = ensure(c, b->adapt->tile_nA, 4 * n_tiles)) return r;
+    const std::vector<int32_t> n(n_tiles, P.done), na(n_tiles, P.n_a);
+    HIPCHK(c, hipMemcpy(b->adapt->tile_n.p, tile_n ? tile_n : n.data(), 4 * n_tiles, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(b->adapt->tile_nA.p, tile_nA ? tile_nA : na.data(), 4 * n_tiles, hipMemcpyHostToDevice));
+    HIPCHK(c, hipDeviceSynchronize());  // (a pass may start on any stream)
+    return RT_OK;
+}
+
+int rt_backend_progress_adapt_bump(rt_context* c, int samples, bool a_pass, void* stream)
+{
+    Backend* b = be(c);
+    HIPCHK(c, hipSetDevice(b->device));
+    hipStream_t s = (hipStream_t)stream;
+    // Behind the uniform pass on its stream (which waited for ev_pg and ev_done); ev_done is recorded again
+    // behind the bump, so resolves, queries and the next pass wait for the counts too.
+    if (int r = rt_adapt_bump(c, b, samples, a_pass, s)) return r;
+    return b->ev_done.record(c, s);
+}
+
+int rt_backend_progress_adapt_advance(rt_context* c, int samples, float threshold, void* stream, int32_t* hdr)
+{
+    Backend* b = be(c);
+    const RtProgress& P = c->prog;
+    HIPCHK(c, hipSetDevice(b->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (int r = progress_quiesce(c, b)) return r;  // (the host sizes the launch: nothing of the progression in flight)
+    Adapt& ad = *b->adapt;
+    const bool a_pass = P.next_is_a();
+    if (int r = rt_adapt_select(c, b, samples, threshold, P.passes >= 2, a_pass, hdr, s)) return r;
+    const int n_act = hdr[rtk::AD_TILES_ACTIVE], n = hdr[rtk::AD_PIXELS];
+    c->last_kernel_ms = -1.0;
+    if (n_act == 0) return RT_OK;
+    if (int r = ensure(c, ad.xy, 8 * (size_t)n)) return r;
+    if (int r = ensure(c, ad.idx, 4 * (size_t)n)) return r;
+    if (int r = ensure(c, ad.cstate, 16 * (size_t)n)) return r;
+    HIPCHK(c, hipEventRecord(b->ev0, s));
+    if (int r = rt_adapt_gather(c, b, n_act, a_pass, s)) return r;
+    // Slot i of the list is its own pixel: fb_at is the identity for a list, and run_wave offsets the
+    // list, the framebuffer and the pass's state by a lane's first slot alike. The sample index is a
+    // counter only (the seed takes seed_spp), so pixels at different counts run as samples 1 .. samples.
+    // Only a pixel without a sample has no state to go on from: it starts at 0 (k_init seeds its chain), and
+    // the counts are then all 0 (rt_progress_load refuses a mix of zero and positive counts).
+    const int first = P.tile_max == 0 ? 0 : 1;
+    const rtk::PixSrc src{P.w, 0, 1, (const int32_t*)ad.xy.p};
+    const WavePass pass{(float4_*)ad.cstate.p, first, P.total};
+    if (int r = run_wave(c, b, P.w, P.h, first + samples, P.bounces, src, n, pass.state, s, &pass)) return r;
+    if (int r = rt_adapt_scatter(c, b, n, a_pass, s)) return r;
+    if (int r = b->ev_done.record(c, s)) return r;  // (resolves, queries and the next pass wait for the scatter too)
+    HIPCHK(c, hipEventRecord(b->ev1, s));
+    return finish_stats(c, b, s);
+}
+
+int rt_backend_progress_adapt_counts(rt_context* c, int32_t* tile_n, int32_t* tile_nA)
+{
+    Backend* b = be(c);
+    DeviceScope sc;
+    if (int r = sc.enter(c, b->device)) return r;
+    if (int r = progress_quiesce(c, b)) return r;
+    const size_t bytes = 4 * (size_t)c->prog.tiles_w() * c->prog.tiles_h();
+    if (tile_n) HIPCHK(c, hipMemcpy(tile_n, b->adapt->tile_n.p, bytes, hipMemcpyDeviceToHost));
+    if (tile_nA) HIPCHK(c, hipMemcpy(tile_nA, b->adapt->tile_nA.p, bytes, hipMemcpyDeviceToHost));
     return RT_OK;
 }
 

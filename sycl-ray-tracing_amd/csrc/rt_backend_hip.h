@@ -140,6 +140,17 @@ struct WaveView;
 struct PixSrc;
 }
 
+// An adaptive progression's buffers (rt_adapt.hip), created by its first adaptive pass or a
+// version-3 load and dropped with the progression.
+struct Adapt {
+    DevBuf tile_n, tile_nA;  // int32 per tile: samples done, and those of them in A passes
+    DevBuf err;              // float per tile: the selection's tile errors
+    DevBuf list, off;        // per active tile, ascending: its index; its first slot in the pixel list
+    DevBuf hdr;              // the selection's header (rtk::AD_WORDS int32)
+    DevBuf xy, idx, cstate;  // per slot: (x, image y); pixel index in the shard; the compact paused state
+    Pinned<int32_t> h_hdr;   // the header's readback
+};
+
 // One device's resources. Created and destroyed with its device current (rt_backend.hip).
 struct Backend {
     int device = 0;
@@ -192,6 +203,7 @@ struct Backend {
     long klaunch[3] = {0, 0, 0};
     std::unique_ptr<Post, PostDelete> post;     // (rt_denoise.hip)
     std::unique_ptr<Query, QueryDelete> query;  // (rt_query.hip)
+    std::unique_ptr<Adapt> adapt;               // (rt_adapt.hip)
 };
 
 Backend* rt_backend_dev0(rt_context* c);  // rt_backend.hip: the root device's Backend
@@ -329,5 +341,19 @@ int rt_display_resolve_linear(rt_context* c, const float4_* base, const float4_*
                               hipStream_t s);
 // rt_noise.hip k_noise_fold: half[i].rgb -= state[i].rgb (add: +=), half[i].w = 0
 int rt_noise_fold(rt_context* c, float4_* half, const float4_* state, int n, bool add, hipStream_t s);
+// rt_adapt.hip: the stages of an adaptive pass on s (P = c->prog; b->adapt holds the buffers).
+//   select   tile errors with per-tile counts (estimate), flags, the ascending list and offsets, the counts'
+//            update and the header, which it reads back: waits for s. hdr: rtk::AD_WORDS words.
+//   gather   the active tiles' pixels into xy / idx / cstate; on an A pass half -= state for them
+//   scatter  cstate back into the state; on an A pass half += state for them
+//   bump     a uniform pass keeps the counts in step: tile_n += samples, on an A pass tile_nA too
+//   resolve  k_resolve / k_resolve_linear with the pixel's tile count for `done`
+int rt_adapt_select(rt_context* c, Backend* b, int samples, float threshold, bool estimate, bool a_pass, int32_t* hdr,
+                    hipStream_t s);
+int rt_adapt_gather(rt_context* c, Backend* b, int n_tiles_active, bool a_pass, hipStream_t s);
+int rt_adapt_scatter(rt_context* c, Backend* b, int n_pixels, bool a_pass, hipStream_t s);
+int rt_adapt_bump(rt_context* c, Backend* b, int samples, bool a_pass, hipStream_t s);
+int rt_adapt_resolve(rt_context* c, Backend* b, const float4_* base, const float4_* state, float4_* out, bool linear,
+                     hipStream_t s);
 size_t rt_wave_counter_bytes();
 size_t rt_wave_readback_bytes();

@@ -8,6 +8,7 @@
 #include <cstring>
 #include <mutex>
 
+#include "rt_adapt.h"
 #include "rt_context.h"
 #include "rt_denoise.h"
 #include "rt_noise.h"
@@ -748,6 +749,7 @@ int rt_set_intersect_mode(rt_context* c, int use_bvh)
 #define RT_PROGRESS_MAGIC 0x47505452  // "RTPG"
 #define RT_PROGRESS_VERSION 1         // an untracked progression: header, base, state
 #define RT_PROGRESS_VERSION_TRACKED 2 // a tracked one: header, {passes, nA}, base, state, half
+#define RT_PROGRESS_VERSION_ADAPTIVE 3 // an adaptive one: version 2 (done = nA + nB), then tile_n, then tile_nA
 #define RT_PROGRESS_HEADER 10         // int32 words: magic, version, the eight info words
 
 static bool ctx_is_multi(const rt_context* c) { return c->devices.size() > 1 || (c->force_multi && !c->devices.empty()); }
@@ -799,16 +801,68 @@ int rt_progress_advance(rt_context* c, int samples, void* stream)
     if (int r = progress_active(c, "rt_progress_advance")) return r;
     if (samples <= 0) return rt_fail(c, RT_ERR_ARG, "rt_progress_advance: samples must be positive");
     RtProgress& P = c->prog;
+    if (P.adaptive && P.tile_max != P.done)
+        return rt_fail(c, RT_ERR_STATE, "rt_progress_advance: the tiles of this adaptive progression have different sample "
+                                        "counts (rt_progress_advance_adaptive)");
     const int stop = P.done + std::min(samples, P.total - P.done);
     if (stop == P.done) return RT_OK;  // nothing left: no launch
     // (rt_render_variants or rt_set_stats since the last pass: the bound tables go up again)
     if (int r = check_ready(c, P.w, P.h, P.total, P.bounces)) return r;
     if (int r = rt_backend_progress_advance(c, P.done, stop, stream)) return r;
+    if (P.adaptive)  // (equal counts: the tile arrays stay in step with the pass, once it is enqueued)
+        if (int r = rt_backend_progress_adapt_bump(c, stop - P.done, P.next_is_a(), stream)) return r;
     if (P.tracked) {  // (the backend folded this pass into half if it was an A pass)
         if (P.next_is_a()) P.n_a += stop - P.done;
+        else P.n_b += stop - P.done;
         P.passes++;
     }
-    P.done = stop;
+    P.done = P.tile_max = stop;
+    return RT_OK;
+}
+
+static bool threshold_ok(float t) { return std::isfinite(t) && t >= 0.0f; }
+
+int rt_progress_advance_adaptive(rt_context* c, int samples, float threshold, void* stream, int info[8])
+{
+    const char* fn = "rt_progress_advance_adaptive";
+    const std::string f = fn;
+    if (!c) return rt_fail(nullptr, RT_ERR_ARG, f + ": ctx is NULL");
+    if (ctx_is_multi(c)) return rt_fail(c, RT_ERR_ARG, f + ": multi-device contexts are not supported");
+    if (int r = progress_active(c, fn)) return r;
+    RtProgress& P = c->prog;
+    if (!P.tracked) return rt_fail(c, RT_ERR_STATE, f + ": the progression is not tracked (rt_progress_noise_track)");
+    if (samples <= 0) return rt_fail(c, RT_ERR_ARG, f + ": samples must be positive");
+    if (!threshold_ok(threshold)) return rt_fail(c, RT_ERR_ARG, f + ": the threshold is not finite and >= 0");
+    if (!info) return rt_fail(c, RT_ERR_ARG, f + ": info is NULL");
+    if (int r = check_ready(c, P.w, P.h, P.total, P.bounces)) return r;
+    if (!P.adaptive) {  // (the counts every tile has so far)
+        if (int r = rt_backend_progress_adapt_begin(c, nullptr, nullptr)) return r;
+        P.adaptive = true;
+        P.n_b = P.done - P.n_a;
+        P.tile_max = P.done;
+    }
+    int32_t hdr[rtk::AD_WORDS];
+    if (int r = rt_backend_progress_adapt_advance(c, samples, threshold, stream, hdr)) return r;
+    if (hdr[rtk::AD_TILES_ACTIVE] > 0) {
+        if (P.next_is_a()) P.n_a += samples;
+        else P.n_b += samples;
+        P.passes++;
+    }
+    P.done = hdr[rtk::AD_MIN];
+    P.tile_max = hdr[rtk::AD_MAX];
+    for (int i = 0; i < 8; i++) info[i] = hdr[i];
+    return RT_OK;
+}
+
+int rt_progress_tile_counts(rt_context* c, int* tile_n, int* tile_nA)
+{
+    if (int r = progress_active(c, "rt_progress_tile_counts")) return r;
+    const RtProgress& P = c->prog;
+    if (!P.tracked) return rt_fail(c, RT_ERR_STATE, "rt_progress_tile_counts: the progression is not tracked");
+    if (P.adaptive) return rt_backend_progress_adapt_counts(c, tile_n, tile_nA);
+    const size_t n_tiles = (size_t)P.tiles_w() * P.tiles_h();
+    if (tile_n) std::fill(tile_n, tile_n + n_tiles, P.done);
+    if (tile_nA) std::fill(tile_nA, tile_nA + n_tiles, P.n_a);
     return RT_OK;
 }
 
@@ -854,10 +908,12 @@ long rt_progress_save(rt_context* c, void* buf, long capacity)
     const RtProgress& P = c->prog;
     const size_t px = P.npx() * sizeof(float4_);
     const size_t extra = P.tracked ? 8 : 0, nbuf = P.tracked ? 3 : 2;
-    const long size = (long)(RT_PROGRESS_HEADER * 4 + extra + nbuf * px);
+    const size_t counts = P.adaptive ? 4 * (size_t)P.tiles_w() * P.tiles_h() : 0;  // bytes of each count array
+    const long size = (long)(RT_PROGRESS_HEADER * 4 + extra + nbuf * px + 2 * counts);
     if (!buf || capacity < size) return size;
-    const int32_t hd[RT_PROGRESS_HEADER] = {RT_PROGRESS_MAGIC, P.tracked ? RT_PROGRESS_VERSION_TRACKED : RT_PROGRESS_VERSION,
-                                            P.w, P.h, P.total, P.done, P.bounces, P.off, P.stride, P.rows};
+    const int version = P.adaptive ? RT_PROGRESS_VERSION_ADAPTIVE : P.tracked ? RT_PROGRESS_VERSION_TRACKED : RT_PROGRESS_VERSION;
+    const int32_t hd[RT_PROGRESS_HEADER] = {RT_PROGRESS_MAGIC, version, P.w, P.h, P.total, P.adaptive ? P.n_a + P.n_b : P.done,
+                                            P.bounces, P.off, P.stride, P.rows};
     std::memcpy(buf, hd, sizeof hd);
     if (P.tracked) {
         const int32_t tr[2] = {P.passes, P.n_a};
@@ -869,6 +925,11 @@ long rt_progress_save(rt_context* c, void* buf, long capacity)
     if (P.tracked)
         if (int r = rt_backend_progress_read_half(c, tmp.data() + 2 * px / 4)) return r;
     std::memcpy((char*)buf + sizeof hd + extra, tmp.data(), nbuf * px);
+    if (P.adaptive) {
+        std::vector<int32_t> tn(counts / 2);  // tile_n, then tile_nA
+        if (int r = rt_backend_progress_adapt_counts(c, tn.data(), tn.data() + counts / 4)) return r;
+        std::memcpy((char*)buf + sizeof hd + extra + nbuf * px, tn.data(), 2 * counts);
+    }
     return size;
 }
 
@@ -881,15 +942,19 @@ int rt_progress_load(rt_context* c, const void* buf, long bytes)
     int32_t hd[RT_PROGRESS_HEADER];
     std::memcpy(hd, buf, sizeof hd);
     if (hd[0] != RT_PROGRESS_MAGIC) return rt_fail(c, RT_ERR_ARG, "rt_progress_load: not a progression checkpoint (magic)");
-    if (hd[1] != RT_PROGRESS_VERSION && hd[1] != RT_PROGRESS_VERSION_TRACKED)
+    if (hd[1] != RT_PROGRESS_VERSION && hd[1] != RT_PROGRESS_VERSION_TRACKED && hd[1] != RT_PROGRESS_VERSION_ADAPTIVE)
         return rt_fail(c, RT_ERR_ARG, "rt_progress_load: unknown format version");
-    const bool tracked = hd[1] == RT_PROGRESS_VERSION_TRACKED;
+    const bool adaptive = hd[1] == RT_PROGRESS_VERSION_ADAPTIVE;
+    const bool tracked = hd[1] == RT_PROGRESS_VERSION_TRACKED || adaptive;
     const size_t extra = tracked ? 8 : 0, nbuf = tracked ? 3 : 2;
     const int w = hd[2], h = hd[3], total = hd[4], done = hd[5], bounces = hd[6], off = hd[7], stride = hd[8], rows = hd[9];
     if (int r = progress_frame(c, "rt_progress_load", w, h, total, bounces, off, stride)) return r;
-    if (done < 0 || done > total) return rt_fail(c, RT_ERR_ARG, "rt_progress_load: done is outside 0..total");
-    const size_t px = (size_t)((h - off + stride - 1) / stride) * w * sizeof(float4_);
-    if (rows != (h - off + stride - 1) / stride || (size_t)bytes != sizeof hd + extra + nbuf * px)
+    // (version 3: done is nA + nB, which a threshold that changed between passes can take past the total)
+    if (done < 0 || (done > total && !adaptive)) return rt_fail(c, RT_ERR_ARG, "rt_progress_load: done is outside 0..total");
+    const int rows_h = (h - off + stride - 1) / stride;
+    const size_t px = (size_t)rows_h * w * sizeof(float4_);
+    const size_t n_tiles = (size_t)((rows_h + 7) / 8) * ((w + 7) / 8), counts = adaptive ? 4 * n_tiles : 0;
+    if (rows != rows_h || (size_t)bytes != sizeof hd + extra + nbuf * px + 2 * counts)
         return rt_fail(c, RT_ERR_ARG, "rt_progress_load: the size does not match the header");
     int32_t tr[2] = {0, 0};  // passes, nA
     if (tracked) {
@@ -899,16 +964,34 @@ int rt_progress_load(rt_context* c, const void* buf, long bytes)
     }
     std::vector<float> tmp(nbuf * px / 4);
     std::memcpy(tmp.data(), (const char*)buf + sizeof hd + extra, nbuf * px);
+    std::vector<int32_t> tn(2 * n_tiles);  // tile_n, then tile_nA
+    int t_min = done, t_max = done;
+    if (adaptive) {
+        std::memcpy(tn.data(), (const char*)buf + sizeof hd + extra + nbuf * px, 2 * counts);
+        for (size_t t = 0; t < n_tiles; t++) {
+            if (tn[t] < 0 || tn[t] > total) return rt_fail(c, RT_ERR_ARG, "rt_progress_load: a tile count is outside 0..total");
+            if (tn[n_tiles + t] < 0 || tn[n_tiles + t] > tn[t])
+                return rt_fail(c, RT_ERR_ARG, "rt_progress_load: a tile's A samples are outside 0..its count");
+        }
+        t_min = *std::min_element(tn.begin(), tn.begin() + n_tiles);
+        t_max = *std::max_element(tn.begin(), tn.begin() + n_tiles);
+        // (a pass starts its pixels' chains or goes on from their states, not both: no API call leaves such counts)
+        if (t_min == 0 && t_max > 0) return rt_fail(c, RT_ERR_ARG, "rt_progress_load: tile counts mix zero and positive");
+    }
     progress_drop(c);
-    progress_install(c, w, h, total, done, bounces, off, stride);
+    progress_install(c, w, h, total, adaptive ? t_min : done, bounces, off, stride);
     int r = rt_backend_progress_begin(c, tmp.data(), tmp.data() + px / 4);
     if (!r && tracked) r = rt_backend_progress_track(c, tmp.data() + 2 * px / 4);
+    if (!r && adaptive) r = rt_backend_progress_adapt_begin(c, tn.data(), tn.data() + n_tiles);
     if (r) {
         progress_drop(c);
         return r;
     }
     c->prog.tracked = tracked;
     c->prog.passes = tr[0], c->prog.n_a = tr[1];
+    c->prog.adaptive = adaptive;
+    c->prog.n_b = done - tr[1];
+    c->prog.tile_max = t_max;
     return RT_OK;
 }
 
@@ -932,9 +1015,9 @@ static int noise_ready(rt_context* c, const char* fn, float threshold, rtk::Nois
     if (int r = progress_active(c, fn)) return r;
     const RtProgress& P = c->prog;
     if (!P.tracked) return rt_fail(c, RT_ERR_STATE, f + ": the progression is not tracked (rt_progress_noise_track)");
-    const int n_a = P.n_a, n_b = P.done - P.n_a;
+    const int n_a = P.n_a, n_b = P.adaptive ? P.n_b : P.done - P.n_a;
     if (n_a <= 0 || n_b <= 0) return rt_fail(c, RT_ERR_STATE, f + ": needs a sample in both halves (two passes)");
-    if (!std::isfinite(threshold) || !(threshold >= 0.0f)) return rt_fail(c, RT_ERR_ARG, f + ": the threshold is not finite and >= 0");
+    if (!threshold_ok(threshold)) return rt_fail(c, RT_ERR_ARG, f + ": the threshold is not finite and >= 0");
     A.n_all = (float)(n_a + n_b);
     A.n_a = (float)n_a;
     A.k = rt_sqrtf((float)n_a / (float)n_b);
@@ -949,7 +1032,9 @@ int rt_progress_noise(rt_context* c, float threshold, rt_noise_stats* stats, flo
     if (int r = noise_ready(c, "rt_progress_noise", threshold, A)) return r;
     if (!stats) return rt_fail(c, RT_ERR_ARG, "rt_progress_noise: stats is NULL");
     int32_t st[8];
-    if (int r = rt_backend_progress_noise(c, A, st, pixel_err, tile_err, false, nullptr)) return r;
+    if (int r = c->prog.adaptive ? rt_backend_progress_adapt_noise(c, A, st, pixel_err, tile_err, false, nullptr)
+                                 : rt_backend_progress_noise(c, A, st, pixel_err, tile_err, false, nullptr))
+        return r;
     stats->max_tile = rt_asfloat((uint32_t)st[3]);
     stats->tiles = st[0], stats->tiles_over = st[1], stats->nonfinite = st[2];
     stats->samples_a = st[4], stats->samples_b = st[5], stats->passes = st[6];
@@ -964,6 +1049,8 @@ int rt_progress_noise_device(rt_context* c, float threshold, void* d_stats, void
     if (!d_stats) return rt_fail(c, RT_ERR_ARG, "rt_progress_noise_device: d_stats is NULL");
     if ((uintptr_t)d_stats % 4 != 0 || (uintptr_t)d_pixel_err % 4 != 0 || (uintptr_t)d_tile_err % 4 != 0)
         return rt_fail(c, RT_ERR_ARG, "rt_progress_noise_device: the buffers must be 4-byte aligned");
+    if (c->prog.adaptive)  // (every tile with its own counts)
+        return rt_backend_progress_adapt_noise(c, A, (int32_t*)d_stats, (float*)d_pixel_err, (float*)d_tile_err, true, stream);
     return rt_backend_progress_noise(c, A, (int32_t*)d_stats, (float*)d_pixel_err, (float*)d_tile_err, true, stream);
 }
 

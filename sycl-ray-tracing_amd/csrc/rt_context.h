@@ -65,7 +65,13 @@ struct RtProgress {
     int w = 0, h = 0, total = 0, done = 0, bounces = 0, off = 0, stride = 1, rows = 0;
     bool tracked = false;
     int passes = 0, n_a = 0;
+    // Adaptive (rt_progress_advance_adaptive, rt_adapt.h): the backend keeps tile_n and tile_nA per 8x8
+    // tile. `done` is then the smallest tile_n and tile_max the largest (the host's copy of the last
+    // selection's header); n_a and n_b are what a tile active in every pass has.
+    bool adaptive = false;
+    int n_b = 0, tile_max = 0;
     std::vector<float4_> base, state, half;  // (hostsim only)
+    std::vector<int32_t> tile_n, tile_nA;    // (hostsim only)
     size_t npx() const { return (size_t)rows * w; }
     int tiles_w() const { return (w + 7) / 8; }
     int tiles_h() const { return (rows + 7) / 8; }
@@ -182,6 +188,22 @@ int rt_backend_progress_track(rt_context* ctx, const float* half);
 int rt_backend_progress_read_half(rt_context* ctx, float* half);
 int rt_backend_progress_noise(rt_context* ctx, const rtk::NoiseArgs& args, int32_t* stats, float* pixel_err,
                               float* tile_err, bool device, void* stream);
+// An adaptive progression (rt_adapt.h; ctx->prog.adaptive is set by the caller once adapt_begin succeeds).
+// adapt_begin: the two count arrays, tiles_h * tiles_w int32 each, from the host arrays or, for null,
+//   prog.done and prog.n_a in every tile. With prog.adaptive set, resolve divides by the pixel's tile count.
+// adapt_bump: a uniform pass of `samples` keeps the counts in step (on `stream`, behind the pass).
+// adapt_advance: one adaptive pass. Waits for the progression's queued work, selects (one small readback),
+//   then enqueues gather, the pass over the compact pixel list and scatter on `stream`; hdr: rtk::AD_WORDS
+//   words {active tiles, active pixels, capped, min and max count after, tiles, 0, 0}. No active tile: no pass.
+// adapt_counts: the arrays back to the host (waits); either may be null.
+// adapt_noise: rt_backend_progress_noise with the tile's counts in k and both divisions (args: the
+//   threshold and the stat words 4..6).
+int rt_backend_progress_adapt_begin(rt_context* ctx, const int32_t* tile_n, const int32_t* tile_nA);
+int rt_backend_progress_adapt_bump(rt_context* ctx, int samples, bool a_pass, void* stream);
+int rt_backend_progress_adapt_advance(rt_context* ctx, int samples, float threshold, void* stream, int32_t* hdr);
+int rt_backend_progress_adapt_counts(rt_context* ctx, int32_t* tile_n, int32_t* tile_nA);
+int rt_backend_progress_adapt_noise(rt_context* ctx, const rtk::NoiseArgs& args, int32_t* stats, float* pixel_err,
+                                    float* tile_err, bool device, void* stream);
 
 int rt_fail(rt_context* ctx, int code, const std::string& msg);
 // RtDiag from the environment (rt_create*)

@@ -14,6 +14,7 @@
 #include <cstring>
 #include <vector>
 
+#include "rt_adapt.h"
 #include "rt_context.h"
 #include "rt_denoise.h"
 #include "rt_display.h"
@@ -421,8 +422,23 @@ int rt_backend_progress_read_half(rt_context* c, float* half)
 // The noise estimate on the host: the loops around rt_noise.h's per-pixel function that
 // k_noise_tiles (rt_noise.hip) runs one wave per tile. "Device" pointers are host pointers here; a
 // caller's buffers need not be aligned, so words move by memcpy.
+static int noise_host(rt_context* c, const rtk::NoiseArgs& F, bool per_tile, int32_t* stats, float* pixel_err, float* tile_err);
+
 int rt_backend_progress_noise(rt_context* c, const rtk::NoiseArgs& A, int32_t* stats, float* pixel_err, float* tile_err,
                               bool, void*)
+{
+    return noise_host(c, A, false, stats, pixel_err, tile_err);
+}
+
+// (an adaptive progression: every tile with its own counts, k_adapt_tiles of rt_adapt.hip)
+int rt_backend_progress_adapt_noise(rt_context* c, const rtk::NoiseArgs& A, int32_t* stats, float* pixel_err, float* tile_err,
+                                    bool, void*)
+{
+    return noise_host(c, A, true, stats, pixel_err, tile_err);
+}
+
+// F: the frame's arguments; per_tile: n_all, n_a and k from the tile's counts instead. stats may be null.
+static int noise_host(rt_context* c, const rtk::NoiseArgs& F, bool per_tile, int32_t* stats, float* pixel_err, float* tile_err)
 {
     const RtProgress& P = c->prog;
     const double t0 = omp_get_wtime();
@@ -431,6 +447,8 @@ int rt_backend_progress_noise(rt_context* c, const rtk::NoiseArgs& A, int32_t* s
     float max_tile = 0.0f;
     for (int ty = 0; ty < th; ty++)
         for (int tx = 0; tx < tw; tx++) {
+            const int t = ty * tw + tx;
+            const rtk::NoiseArgs A = per_tile ? rtk::adapt_tile_args(P.tile_n[t], P.tile_nA[t], F) : F;
             float v[64];
             for (int l = 0; l < 64; l++) {
                 const int x = rtk::NOISE_TILE * tx + (l & 7), y = rtk::NOISE_TILE * ty + (l >> 3);
@@ -444,11 +462,108 @@ int rt_backend_progress_noise(rt_context* c, const rtk::NoiseArgs& A, int32_t* s
             }
             const float tile = rtk::noise_tree64(v) / (float)rtk::noise_tile_count(tx, ty, P.w, P.rows);
             if (tile_err) std::memcpy((char*)tile_err + 4 * ((size_t)ty * tw + tx), &tile, 4);
-            if (tile > A.threshold) tiles_over++;
+            if (tile > F.threshold) tiles_over++;
             if (rt_asuint(tile) > rt_asuint(max_tile)) max_tile = tile;
         }
-    const int32_t st[8] = {tw * th, tiles_over, nonfinite, (int32_t)rt_asuint(max_tile), A.samples_a, A.samples_b, A.passes, 0};
-    std::memcpy(stats, st, sizeof st);
+    const int32_t st[8] = {tw * th, tiles_over, nonfinite, (int32_t)rt_asuint(max_tile), F.samples_a, F.samples_b, F.passes, 0};
+    if (stats) std::memcpy(stats, st, sizeof st);
+    c->last_kernel_ms = (omp_get_wtime() - t0) * 1e3;
+    return RT_OK;
+}
+
+// ---- adaptive progressions: the stages of rt_adapt.hip as loops over rt_adapt.h's functions
+int rt_backend_progress_adapt_begin(rt_context* c, const int32_t* tile_n, const int32_t* tile_nA)
+{
+    RtProgress& P = c->prog;
+    const size_t n_tiles = (size_t)P.tiles_w() * P.tiles_h();
+    P.tile_n.assign(n_tiles, P.done);
+    P.tile_nA.assign(n_tiles, P.n_a);
+    if (tile_n) std::memcpy(P.tile_n.data(), tile_n, 4 * n_tiles);
+    if (tile_nA) std::memcpy(P.tile_nA.data(), tile_nA, 4 * n_tiles);
+    return RT_OK;
+}
+
+int rt_backend_progress_adapt_bump(rt_context* c, int samples, bool a_pass, void*)
+{
+    RtProgress& P = c->prog;
+    for (size_t t = 0; t < P.tile_n.size(); t++) {
+        P.tile_n[t] += samples;
+        if (a_pass) P.tile_nA[t] += samples;
+    }
+    return RT_OK;
+}
+
+int rt_backend_progress_adapt_counts(rt_context* c, int32_t* tile_n, int32_t* tile_nA)
+{
+    const RtProgress& P = c->prog;
+    if (tile_n) std::memcpy(tile_n, P.tile_n.data(), 4 * P.tile_n.size());
+    if (tile_nA) std::memcpy(tile_nA, P.tile_nA.data(), 4 * P.tile_nA.size());
+    return RT_OK;
+}
+
+int rt_backend_progress_adapt_advance(rt_context* c, int samples, float threshold, void*, int32_t* hdr)
+{
+    RtProgress& P = c->prog;
+    const double t0 = omp_get_wtime();
+    const int tw = P.tiles_w(), th = P.tiles_h(), n_tiles = tw * th;
+    const bool estimate = P.passes >= 2, a_pass = P.next_is_a();
+    // k_adapt_tiles, then k_adapt_select: flags, the ascending list, the offsets, the counts, the header
+    std::vector<float> err(n_tiles, 0.0f);
+    if (estimate) {
+        rtk::NoiseArgs F{};
+        F.threshold = threshold;
+        if (int r = noise_host(c, F, true, nullptr, nullptr, err.data())) return r;
+    }
+    std::vector<int32_t> list, off;
+    int n = 0, capped = 0, n_min = 0x7fffffff, n_max = (int)0x80000000;
+    for (int t = 0; t < n_tiles; t++) {
+        const int flags = rtk::adapt_flags(P.tile_n[t], samples, P.total, estimate, err[t], threshold);
+        if (flags & rtk::ADAPT_ACTIVE) {
+            list.push_back(t);
+            off.push_back(n);
+            n += rtk::noise_tile_count(t % tw, t / tw, P.w, P.rows);
+            P.tile_n[t] += samples;
+            if (a_pass) P.tile_nA[t] += samples;
+        }
+        if (flags & rtk::ADAPT_CAPPED) capped++;
+        n_min = std::min(n_min, P.tile_n[t]);
+        n_max = std::max(n_max, P.tile_n[t]);
+    }
+    const int32_t h[rtk::AD_WORDS] = {(int32_t)list.size(), n, capped, n_min, n_max, n_tiles, 0, 0};
+    std::memcpy(hdr, h, sizeof h);
+    std::fill(c->stats, c->stats + RT_STAT_COUNT, 0ull);
+    if (list.empty()) return RT_OK;
+    // k_adapt_gather: lane l of a tile is pixel (8tx + l % 8, 8ty + l / 8); in-frame lanes in lane order
+    std::vector<int32_t> xy(2 * (size_t)n), idx(n);
+    std::vector<float4_> cstate(n);
+    for (size_t a = 0; a < list.size(); a++) {
+        const int t = list[a], ty = t / tw, tx = t - ty * tw;
+        int slot = off[a];
+        for (int l = 0; l < 64; l++) {
+            const int x = rtk::NOISE_TILE * tx + (l & 7), y = rtk::NOISE_TILE * ty + (l >> 3);
+            if (x >= P.w || y >= P.rows) continue;
+            const int p = y * P.w + x;
+            xy[2 * (size_t)slot] = x;
+            xy[2 * (size_t)slot + 1] = P.off + y * P.stride;
+            idx[slot] = p;
+            cstate[slot] = P.state[p];
+            if (a_pass) P.half[p] = rtk::fold_pixel(P.half[p], P.state[p], false);
+            slot++;
+        }
+    }
+    // the pass: samples 1 .. samples of every listed pixel's own chain, paused into cstate (the index is a
+    // counter only; before any sample, when every count is 0, from 0: path_init seeds the chains)
+    const int first = P.tile_max == 0 ? 0 : 1;
+    const rtk::PixSrc src{P.w, 0, 1, xy.data()};
+    if (int r = run_wave_host(c, P.w, P.h, first + samples, P.bounces, src, n, cstate.data(), c->stats, nullptr, cstate.data(),
+                              first, P.total))
+        return r;
+    // k_adapt_scatter
+    for (int i = 0; i < n; i++) {
+        const int p = idx[i];
+        P.state[p] = cstate[i];
+        if (a_pass) P.half[p] = rtk::fold_pixel(P.half[p], cstate[i], true);
+    }
     c->last_kernel_ms = (omp_get_wtime() - t0) * 1e3;
     return RT_OK;
 }
@@ -458,13 +573,16 @@ int rt_backend_progress_resolve(rt_context* c, float* host_fb, void* dev_fb, voi
     const RtProgress& P = c->prog;
     float4_* out = host_fb ? (float4_*)host_fb : (float4_*)dev_fb;  // ("device" pointers are host pointers here)
     const long n = (long)P.npx();
+    const int tw = P.tiles_w();
+    // (an adaptive progression: the pixel's tile count, k_adapt_resolve of rt_adapt.hip)
+    auto done_of = [&](long i) { return P.adaptive ? P.tile_n[rtk::adapt_tile_of((int)i, P.w, tw)] : P.done; };
     if (linear) {
 #pragma omp parallel for schedule(static)
-        for (long i = 0; i < n; i++) out[i] = rtk::resolve_linear_pixel(P.base[i], P.state[i], P.done);
+        for (long i = 0; i < n; i++) out[i] = rtk::resolve_linear_pixel(P.base[i], P.state[i], done_of(i));
         return RT_OK;
     }
 #pragma omp parallel for schedule(static)
-    for (long i = 0; i < n; i++) out[i] = rtk::resolve_pixel(P.base[i], P.state[i], P.done);
+    for (long i = 0; i < n; i++) out[i] = rtk::resolve_pixel(P.base[i], P.state[i], done_of(i));
     return RT_OK;
 }
 

@@ -863,7 +863,7 @@ int octree_from_dump(const char* buf, size_t bytes, Octree& out)
         OctNode n;
         n.leaf = leaf != 0;
         n.tris.resize(nt);
-        std::memcpy(n.tris.data(), buf + o, 4 * (size_t)nt);
+        if (nt) std::memcpy(n.tris.data(), buf + o, 4 * (size_t)nt);  // (an empty vector's data() may be null)
         o += 4 * (size_t)nt;
         std::memcpy(n.mn, buf + o, 12);
         std::memcpy(n.mx, buf + o + 12, 12);

@@ -455,6 +455,28 @@ class RenderKernel:
             out["tile_err"] = tl
         return out
 
+    # ---- adaptive sampling (rt_progress_advance_adaptive, rt_progress_tile_counts; include/rt_hip.h)
+    def progress_advance_adaptive(self, samples: int, threshold: float, stream: int | None = None) -> dict:
+        """One adaptive pass of a tracked progression: `samples` more samples for every 8x8 tile whose noise
+        estimate is above `threshold` and that still fits under the total (every tile that fits during the first
+        two passes). Returns {"active_tiles", "active_pixels", "capped_tiles", "min_count", "max_count", "tiles"};
+        active_tiles == 0: nothing was rendered."""
+        info = np.zeros(8, np.int32)
+        check(self.L, self.L.rt_progress_advance_adaptive(self.ctx, int(samples), float(threshold),
+                                                          ctypes.c_void_p(stream) if stream else None, ptr(info)),
+              self.ctx, "rt_progress_advance_adaptive")
+        keys = ("active_tiles", "active_pixels", "capped_tiles", "min_count", "max_count", "tiles")
+        return {k: int(v) for k, v in zip(keys, info)}
+
+    def progress_tile_counts(self):
+        """(tile_n, tile_nA): [ceil(rows_local / 8), ceil(w / 8)] int32 arrays, the samples every pixel of the
+        tile has done and how many of them fell in A passes. Waits for the passes."""
+        i = self.progress_info()
+        shape = ((i["rows_local"] + 7) // 8, (self.width + 7) // 8)
+        n, na = np.zeros(shape, np.int32), np.zeros(shape, np.int32)
+        check(self.L, self.L.rt_progress_tile_counts(self.ctx, ptr(n), ptr(na)), self.ctx, "rt_progress_tile_counts")
+        return n, na
+
     # ---- post stage (what replaces Utils::OIDN_denoise, utils.cpp:144-196)
     def camera_rays(self) -> np.ndarray:
         """rt_camera_rays: the feature pass's rays, [h, w, 6] = origin, direction (host only)."""

@@ -34,6 +34,7 @@ EXPORTS = [
     "rt_display_default_params", "rt_render_linear", "rt_render_linear_device", "rt_progress_resolve_linear",
     "rt_progress_resolve_linear_device", "rt_display", "rt_display_device", "rt_write_hdr",
     "rt_progress_noise_track", "rt_progress_noise", "rt_progress_noise_device",
+    "rt_progress_advance_adaptive", "rt_progress_tile_counts",
 ]
 
 # return codes (include/rt_hip.h)
@@ -133,6 +134,8 @@ _SIGS = {
     "rt_progress_noise_track": (I, [P]),
     "rt_progress_noise": (I, [P, F, ctypes.POINTER(NoiseStats), P, P]),
     "rt_progress_noise_device": (I, [P, F, P, P, P, P]),
+    "rt_progress_advance_adaptive": (I, [P, I, F, P, P]),
+    "rt_progress_tile_counts": (I, [P, P, P]),
     # product-only extras
     "rt_device_libm": (I, [I, I, P, P, P, I]),
     "rt_device_libm_digest": (I, [I, I, ctypes.c_uint32, I, P]),
@@ -146,6 +149,7 @@ _SIGS = {
     "rt_device_denoise_pass_ms": (I, [P, I, P, I]),
     "rt_device_display_kernel_ms": (I, [P, I, I, P, P, P, P, I, P]),
     "rt_device_noise_kernel_ms": (I, [P, I, I, P, P, P, P, P, I, P]),
+    "rt_device_adapt_kernel_ms": (I, [P, F, I, P, P]),
     # hostsim-only extra
     "rt_hostsim_heap_order": (I, [P, I, P, P]),
     "rt_hostsim_fast_queries": (I, [P, P, I, P, P]),

@@ -26,6 +26,12 @@ Noise estimate (RenderKernel.progress_track_noise / progress_noise): --noise-thr
 (done, max_tile, tiles_over) and stops the passes once no 8x8 tile's error is above T. The four PNGs
 (and --hdr-out) then come from the samples done so far. A progression resumed from an untracked
 --checkpoint stays untracked and runs to the end. Without the flag a run writes the bytes it writes today.
+
+Adaptive sampling (RenderKernel.progress_advance_adaptive): --adaptive, with --noise-threshold=T and
+--preview-every=K. After two uniform passes every further pass advances only the 8x8 tiles whose error
+is still above T, until none is (or none fits under --samples any more: keep --samples a multiple of K).
+It also writes a fifth PNG, RT_samples.png: tile_n / samples in grey, so that one sees where the samples
+went. Without --adaptive nothing changes.
 """
 from __future__ import annotations
 
@@ -41,10 +47,12 @@ import rt_amd
 def parse(argv):
     a = dict(obj="data/OBJs/cornell_pbr.obj", sky="data/Skyspheres/evening_road_01_puresky_2k.hdr", w=512, h=512,
              samples=64, bounces=8, camera="dragon", out=".", hostsim=False, preview_every=0, checkpoint="",
-             exposure=None, gamma=None, hdr_out="", noise_threshold=None)
+             exposure=None, gamma=None, hdr_out="", noise_threshold=None, adaptive=False)
     for s in argv:
         if s == "--hostsim":
             a["hostsim"] = True
+        elif s == "--adaptive":
+            a["adaptive"] = True
         elif s.startswith(("--sky=", "--camera=", "--out=", "--checkpoint=", "--hdr-out=")):
             k, v = s[2:].split("=", 1)
             a[k.replace("-", "_")] = v
@@ -97,7 +105,15 @@ def render_progressive(rk: rt_amd.RenderKernel, fb: rt_amd.Image, a: dict):
         i = rk.progress_info()
         if i["done"] >= i["total"]:
             break
-        done = rk.progress_advance(step)
+        if a["adaptive"]:  # (the first two passes take every tile: there is no estimate yet)
+            n = rk.progress_advance_adaptive(step, a["noise_threshold"])
+            if n["active_tiles"] == 0:
+                break
+            done = (passes + 1) * step  # (previews are named by the samples a tile active in every pass has)
+            print(f"adaptive: {n['active_tiles']} of {n['tiles']} tiles, counts {n['min_count']} .. {n['max_count']}, "
+                  f"capped {n['capped_tiles']}")
+        else:
+            done = rk.progress_advance(step)
         if ck:
             with open(ck + ".tmp", "wb") as f:
                 f.write(rk.progress_save())
@@ -109,6 +125,8 @@ def render_progressive(rk: rt_amd.RenderKernel, fb: rt_amd.Image, a: dict):
                 shown = rk.progress_resolve(preview)
             rt_amd.write_image_png(shown, os.path.join(a["out"], f"RT_preview_{done}.png"))
         passes += 1
+        if a["adaptive"]:  # (an adaptive pass that finds no tile above the threshold ends the loop)
+            continue
         if a["noise_threshold"] is not None and passes >= 2:
             try:
                 n = rk.progress_noise(a["noise_threshold"])
@@ -121,6 +139,13 @@ def render_progressive(rk: rt_amd.RenderKernel, fb: rt_amd.Image, a: dict):
         rk.progress_resolve_linear(fb)
     else:
         rk.progress_resolve(fb)
+    if a["adaptive"]:  # where the samples went: tile_n / total in grey
+        tile_n, _ = rk.progress_tile_counts()
+        grey = np.repeat(np.repeat(tile_n, 8, 0), 8, 1)[:a["h"], :a["w"]].astype(np.float32) / np.float32(a["samples"])
+        counts = rt_amd.Image(a["w"], a["h"])
+        counts.pixels[..., :3] = grey[..., None]
+        counts.pixels[..., 3] = 1.0
+        rt_amd.write_image_png(counts, os.path.join(a["out"], "RT_samples.png"))
     rk.progress_end()
 
 
@@ -128,6 +153,9 @@ def main(argv=None) -> int:
     a = parse(sys.argv[1:] if argv is None else argv)
     if a["noise_threshold"] is not None and a["preview_every"] <= 0:
         print("--noise-threshold needs --preview-every=K (the estimate compares passes)", file=sys.stderr)
+        return 2
+    if a["adaptive"] and a["noise_threshold"] is None:
+        print("--adaptive needs --noise-threshold=T and --preview-every=K", file=sys.stderr)
         return 2
     print(f"Reading OBJ {a['obj']} ...")
     P = rt_amd.parse_obj(a["obj"])
