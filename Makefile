@@ -46,7 +46,8 @@ $(OBJ)/rt_hostsim.o: $(SRC)/rt_hostsim.cpp $(HDRS) $(ALL_SRC)
 #   rt_display   the display stage (tone-map + 8-bit conversion, linear resolve)
 #   rt_noise     a tracked progression's fold and noise estimate
 #   rt_adapt     an adaptive progression's selection, gather / scatter and resolves
-HIP_UNITS := rt_render rt_wave_run rt_probe rt_denoise rt_query rt_display rt_noise rt_adapt
+#   rt_dnv       the variance-guided filter and the absolute noise figure it takes
+HIP_UNITS := rt_render rt_wave_run rt_probe rt_denoise rt_query rt_display rt_noise rt_adapt rt_dnv
 $(HIP_UNITS:%=$(OBJ)/%.o): $(OBJ)/%.o: $(SRC)/%.hip $(HDRS)
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
@@ -100,7 +101,9 @@ build/stackless_probe: tools/probe/stackless_probe.cpp $(OBJ)/rt_scene.host.o $(
 # A host-only change leaves the kernels alone: make device-diff PARENT=<checkout of the commit before it>
 # compiles the device side of every unit that has one (rt_wave_run and rt_backend have none) from both
 # trees and fails on any differing assembly line besides the one naming the unit's __hip_cuid_ symbol.
-DEV_UNITS := $(filter-out rt_wave_run,$(HIP_UNITS))
+# A unit the parent does not have (a new translation unit) is left out of the comparison and named.
+DEV_UNITS := $(foreach u,$(filter-out rt_wave_run,$(HIP_UNITS)),$(if $(wildcard $(PARENT)/$(SRC)/$(u).hip),$(u)))
+NEW_UNITS := $(filter-out rt_wave_run $(DEV_UNITS),$(HIP_UNITS))
 build/devasm/%.s: $(SRC)/%.hip $(HDRS)
 	@mkdir -p build/devasm
 	$(HIPCC) $(HIPFLAGS) --cuda-device-only -S $< -o $@
@@ -111,6 +114,7 @@ device-diff: $(DEV_UNITS:%=build/devasm/%.s) $(DEV_UNITS:%=build/devasm/%.parent
 	@for u in $(DEV_UNITS); do \
 	  n=$$(diff build/devasm/$$u.parent.s build/devasm/$$u.s | grep '^[<>]' | grep -vc __hip_cuid_); \
 	  echo "$$u: $$(grep -c . build/devasm/$$u.s) lines, $$n differ besides __hip_cuid_"; [ $$n -eq 0 ] || exit 1; done
+	@for u in $(NEW_UNITS); do echo "$$u: not in the parent"; done
 .PHONY: device-diff
 
 # the reference build (container only; needs /root/reference)
@@ -150,6 +154,7 @@ hostsim-variant: $(OBJ)/rt_imageio.host.o
 #   noise_test          progress_track_noise / progress_noise against the C ABI tests/test_noise_shim.py
 #   adaptive_shim_test  render_adaptive against the C ABI                   tests/test_adaptive_shim.py
 #                       (make sanitize-adaptive: the same program under ASan + UBSan over the hostsim sources)
+#   dnv_shim_test       denoise_var / progress_noise_sigma against the C ABI     tests/test_dnv_shim.py
 REFDIR ?= /root/reference
 REFOBJ := oracle/_ref/objO2
 REFOBJS := $(REFOBJ)/bvh.o $(REFOBJ)/flattened_bvh.o $(REFOBJ)/triangle.o $(REFOBJ)/vec.o $(REFOBJ)/color.o \

@@ -243,6 +243,34 @@ public:
         return out;
     }
 
+    // denoise() with the colour edge-stop scaled per pixel by sigma (rt_denoise_var with its default
+    // parameters): sigma holds width * height standard deviations of the image's colour, such as
+    // progress_noise_sigma() gives for the linear frame of a tracked progression (from the on_pass
+    // callback of render_progressive_tracked, after at least two passes; it does not take the
+    // kernel's lock: on_pass runs under it). sigma_out, when given, receives the standard deviation
+    // left in the filtered colour.
+    std::vector<float> progress_noise_sigma() const
+    {
+        std::vector<float> sigma((size_t)m_width * m_height);
+        check(rt_progress_noise_sigma(m_ctx, sigma.data()));
+        return sigma;
+    }
+    Image denoise_var(const Image& image, const std::vector<float>& sigma, float blend_factor,
+                      std::vector<float>* sigma_out = nullptr) const
+    {
+        std::lock_guard<std::mutex> lk(m_mu);
+        const_cast<RenderKernel*>(this)->sync_materials();
+        const int w = image.width(), h = image.height();
+        if (sigma.size() != (size_t)w * h) throw std::runtime_error("librt_hip: denoise_var: sigma is not width * height floats");
+        std::vector<float> albedo((size_t)w * h * 4), normal_depth((size_t)w * h * 4);
+        check(rt_render_features(m_ctx, w, h, albedo.data(), normal_depth.data()));
+        if (sigma_out) sigma_out->assign((size_t)w * h, 0.0f);
+        Image out(w, h);
+        check(rt_denoise_var(m_ctx, w, h, image.data(), sigma.data(), albedo.data(), normal_depth.data(), nullptr,
+                             blend_factor, out.data(), sigma_out ? sigma_out->data() : nullptr));
+        return out;
+    }
+
     // INTERSECT_SCENE for a batch of rays through rt_query (the render's search-BVH walks, the
     // exact walk behind them): hits[i] as BVH::intersect + the sphere loop fill it (t = -1 and
     // primitive_index = -1 without a hit).

@@ -104,8 +104,8 @@ int rt_test_fail_device(rt_context* ctx, int device);
  * paths go to a tail kernel early; 0: off), "fast_spp" (... from iteration
  * fast_spp x spp on), "near_scale" (the near box, scene box widened by this x its
  * largest extent: queries from outside it take the exact octree walk), "dn_variant"
- * (rt_denoise's filter kernel: 0 the product's choice per step, 1 direct loads, 2 the
- * LDS-halo tile at every step that has one), "rq_variant" (rt_query's search-BVH kernel:
+ * (rt_denoise's and rt_denoise_var's filter kernel: 0 the product's choice per step, 1 direct
+ * loads, 2 the LDS-halo tile at every step that has one), "rq_variant" (rt_query's search-BVH kernel:
  * 0 the product's choice, 1 plain rounds of one query per quad, 2 per-quad refill),
  * "chain_full" (1: the scene view reports an unmonotone tree, so the leaf verification
  * walks the whole ancestor chain instead of one slab test), the
@@ -491,6 +491,71 @@ int rt_progress_noise_device(rt_context* ctx, float threshold, void* d_stats, vo
  * is not finite and >= 0, a NULL info, a multi-device context. */
 int rt_progress_advance_adaptive(rt_context* ctx, int samples, float threshold, void* stream, int info[8]);
 int rt_progress_tile_counts(rt_context* ctx, int* tile_n, int* tile_nA);
+
+/* ------------------------------------------- variance-guided denoise
+ * The a-trous filter of rt_denoise with its colour edge-stop scaled per pixel by an estimate
+ * of the input's variance (the spatial half of SVGF, Schied et al. 2017), and the query that
+ * gives a tracked or adaptive progression's estimate in the units of the linear frame.
+ * Float32 throughout, no contraction, IEEE division and square root, the library's expf.
+ *
+ * rt_progress_noise_sigma / _device: sigma (rows_local*w floats, required; device: 4-byte
+ *   aligned, on `stream`, no wait; host: waits) receives, per pixel of the shard,
+ *       s = k * d
+ *   with m, a, d and k exactly as the noise estimate above computes them (s is e's numerator,
+ *   before the division by sqrtf(0.01f + (m.r + m.g) + m.b)); in an adaptive progression with the
+ *   pixel's tile's own counts (N = tile_n[t], nA = tile_nA[t]) in k and both divisions. A pixel
+ *   whose tile has nA == 0 or nB == 0 gets what the arithmetic gives, which is not finite; it is
+ *   written as it is. Changes no state. RT_ERR_STATE and RT_ERR_ARG as rt_progress_noise (not
+ *   tracked, fewer than two passes; no progression on a multi-device context), RT_ERR_ARG for a
+ *   NULL or misaligned sigma.
+ *
+ * rt_denoise_var / _device: rt_denoise's buffers plus sigma (float[h][w], required: a per-pixel
+ *   standard deviation of rgba_in's colour, such as the query's) and sigma_out (float[h][w], or
+ *   NULL). Prep: v_p = sigma_p * sigma_p; a NaN v becomes 0, an infinite one the largest finite
+ *   float, so every v is finite and >= 0 from here on. Then `passes` iterations over the records
+ *   {r, g, b, v}; pass i has step s = 1 << i and, for pixel p:
+ *     g_p = sum b v_q / sum b over the 3x3 pixels q around p at unit spacing that lie inside the
+ *           image (dy outer), b = {1/4, 1/2, 1/4}[dy+1] * {1/4, 1/2, 1/4}[dx+1]; every such pixel
+ *           counts whatever its colour; a quotient above the largest finite float is that float
+ *     r_p = (1 / sigma_color^2) / (g_p + var_floor)        the same sigma_color in every pass
+ *     the taps q = p + s (dx, dy) of rt_denoise, in its order and with its skips, with
+ *     e   = |c_p - c_q|^2 * r_p + |n_p - n_q|^2 / sigma_normal^2 + |a_p - a_q|^2 / sigma_albedo^2
+ *         + ((t_p - t_q) / max(t_p, t_q))^2 / sigma_depth^2
+ *     w   = k expf(-e)                                     k = h[dy+2] h[dx+2] as in rt_denoise
+ *     out.rgb = sum w c_q / sum w      out.v = sum w (w v_q) / ((sum w) (sum w))
+ *   evaluated as written (w (w v_q): w w would leave the normal range from w = 1e-19 down)
+ *   (the four 1 / sigma^2 are floats computed once and multiplied in, clamped to the normal range).
+ *   A tap is skipped, in all five sums, when it is outside the image, its colour is not finite,
+ *   one of p and q is a hit and the other a miss, or e is not >= 0 (a NaN guide; a colour distance
+ *   that overflowed while r_p is 0, which it is once g_p + var_floor is infinite). A centre whose
+ *   colour is not finite, and a centre left without any tap (its own guide is NaN), keeps its
+ *   record, v included. The centre tap always has e = 0, so sum w >= 9/64 wherever it is > 0; an
+ *   out.v above the largest finite float is that float. After the last pass rgb = blend *
+ *   filtered + (1.0f - blend) * rgba_in and alpha 1.0f, as rt_denoise, and sigma_out = sqrtf(out.v):
+ *   the standard deviation left in the filtered colour, before the blend. rgba_in's alpha plays no
+ *   part. A finite colour input never gives a NaN colour.
+ *   RT_ERR_ARG as rt_denoise (passes outside 1..10, a sigma_* parameter that is not finite and
+ *   > 0, a non-finite blend, exactly one guide NULL, rgba_in == rgba_out, more than 262140 rows
+ *   or 2^27 - 1 pixels), and for a NULL sigma and a var_floor that is not finite and > 0. The
+ *   device form takes device pointers (the float4 buffers 16-byte aligned, sigma and sigma_out
+ *   4-byte aligned: RT_ERR_ARG otherwise) and a stream (NULL: default) and returns without
+ *   waiting. params NULL: the defaults (rt_denoise_var_default_params). Runs on the root device;
+ *   rt_last_kernel_ms as for rt_denoise. */
+typedef struct rt_denoise_var_params {
+    int passes;          /* a-trous iterations, 1..10 */
+    float sigma_color;   /* colour distance in standard deviations of the input */
+    float sigma_normal, sigma_albedo, sigma_depth; /* as rt_denoise_params */
+    float var_floor;     /* added to the variance estimate: the edge-stop's width where sigma is 0 */
+} rt_denoise_var_params;
+int rt_progress_noise_sigma(rt_context* ctx, float* sigma);
+int rt_progress_noise_sigma_device(rt_context* ctx, void* d_sigma, void* stream);
+void rt_denoise_var_default_params(rt_denoise_var_params* params);
+int rt_denoise_var(rt_context* ctx, int w, int h, const float* rgba_in, const float* sigma, const float* albedo,
+                   const float* normal_depth, const rt_denoise_var_params* params, float blend, float* rgba_out,
+                   float* sigma_out);
+int rt_denoise_var_device(rt_context* ctx, int w, int h, const void* d_rgba_in, const void* d_sigma, const void* d_albedo,
+                          const void* d_normal_depth, const rt_denoise_var_params* params, float blend, void* d_rgba_out,
+                          void* d_sigma_out, void* stream);
 
 /* Counters of the last render when enabled (RT_STAT_* order, rt_device.h);
  * with n up to 2 * RT_STAT_COUNT the second block is the share of the

@@ -9,6 +9,7 @@
 //   rt_denoise.hip  the post stage          rt_query.hip  the ray queries
 //   rt_display.hip  the display stage and the linear resolve
 //   rt_noise.hip    a tracked progression's fold and noise estimate
+//   rt_dnv.hip      the variance-guided post stage and the absolute noise figure it takes
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -127,9 +128,13 @@ struct Marker {
 // The post stage's buffers (rt_denoise.hip) and the ray queries' workspace (rt_query.hip),
 // created on first use and deleted with their Backend (its device current).
 struct Post;
+struct PostVar;  // (rt_dnv.hip: the variance-guided filter's buffers, Post's sibling)
 struct Query;
 struct PostDelete {
     void operator()(Post* p) const;
+};
+struct PostVarDelete {
+    void operator()(PostVar* p) const;
 };
 struct QueryDelete {
     void operator()(Query* q) const;
@@ -202,6 +207,7 @@ struct Backend {
     double kms[3] = {0, 0, 0};      // k_trace, k_step, k_tail
     long klaunch[3] = {0, 0, 0};
     std::unique_ptr<Post, PostDelete> post;     // (rt_denoise.hip)
+    std::unique_ptr<PostVar, PostVarDelete> post_var;  // (rt_dnv.hip)
     std::unique_ptr<Query, QueryDelete> query;  // (rt_query.hip)
     std::unique_ptr<Adapt> adapt;               // (rt_adapt.hip)
 };
@@ -215,8 +221,8 @@ Backend* rt_backend_dev0(rt_context* c);  // rt_backend.hip: the root device's B
 //   enter, [staging], in / out / inout per buffer, begin, the stage's launches, end
 // b's device is current until the StagedCall leaves scope, then the caller's again.
 // The host forms' streams are inherited from the stages as they were written, not chosen here:
-//   null stream   features, denoise (Post::io), display (disp), queries (Query::io), rt_render (fb)
-//   Backend::own  noise (pg_noise), progressive resolves (pg_out), pixel lists (fb)
+//   null stream   features, denoise (Post::io), denoise_var (PostVar::io), display (disp), queries (Query::io), rt_render (fb)
+//   Backend::own  noise and noise_sigma (pg_noise), progressive resolves (pg_out), pixel lists (fb)
 struct StagedCall {
     rt_context* c = nullptr;
     Backend* b = nullptr;

@@ -681,6 +681,57 @@ int rt_denoise_device(rt_context* c, int w, int h, const void* in, const void* a
     return rt_backend_denoise(c, w, h, in, alb, nd, p, blend, out, true, stream);
 }
 
+// ---- the variance-guided filter (rt_dnv.h)
+// Defaults from the quality sweep on Cornell 64x64, a uniform and an adaptive 64-sample frame
+// against 512 spp.
+void rt_denoise_var_default_params(rt_denoise_var_params* p)
+{
+    if (!p) return;
+    p->passes = 3;
+    p->sigma_color = 1.0f;
+    p->sigma_normal = 0.3f;
+    p->sigma_albedo = 0.1f;
+    p->sigma_depth = 0.1f;
+    p->var_floor = 0.01f;
+}
+
+static int denoise_var_ready(rt_context* c, int w, int h, const void* in, const void* sigma, const void* alb, const void* nd,
+                             const rt_denoise_var_params* params, float blend, const void* out, const void* sigma_out,
+                             bool device, rt_denoise_var_params& p)
+{
+    if (!c) return rt_fail(nullptr, RT_ERR_ARG, "rt_denoise_var: ctx is NULL");
+    if (params) p = *params;
+    else rt_denoise_var_default_params(&p);
+    // (rt_denoise's own checks, on its share of the arguments)
+    const rt_denoise_params q{p.passes, p.sigma_color, p.sigma_normal, p.sigma_albedo, p.sigma_depth};
+    rt_denoise_params unused;
+    if (int r = denoise_ready(c, w, h, in, alb, nd, &q, blend, out, unused)) return r;
+    if (!sigma) return rt_fail(c, RT_ERR_ARG, "rt_denoise_var: sigma is NULL");
+    if (!std::isfinite(p.var_floor) || !(p.var_floor > 0.0f))
+        return rt_fail(c, RT_ERR_ARG, "rt_denoise_var: var_floor is not finite and > 0");
+    if (device && ((uintptr_t)in % 16 != 0 || (uintptr_t)out % 16 != 0 || (uintptr_t)alb % 16 != 0 || (uintptr_t)nd % 16 != 0 ||
+                   (uintptr_t)sigma % 4 != 0 || (uintptr_t)sigma_out % 4 != 0))
+        return rt_fail(c, RT_ERR_ARG, "rt_denoise_var_device: the float4 buffers must be 16-byte aligned, sigma and "
+                                      "sigma_out 4-byte aligned");
+    return RT_OK;
+}
+
+int rt_denoise_var(rt_context* c, int w, int h, const float* in, const float* sigma, const float* alb, const float* nd,
+                   const rt_denoise_var_params* params, float blend, float* out, float* sigma_out)
+{
+    rt_denoise_var_params p;
+    if (int r = denoise_var_ready(c, w, h, in, sigma, alb, nd, params, blend, out, sigma_out, false, p)) return r;
+    return rt_backend_denoise_var(c, w, h, in, sigma, alb, nd, p, blend, out, sigma_out, false, nullptr);
+}
+
+int rt_denoise_var_device(rt_context* c, int w, int h, const void* in, const void* sigma, const void* alb, const void* nd,
+                          const rt_denoise_var_params* params, float blend, void* out, void* sigma_out, void* stream)
+{
+    rt_denoise_var_params p;
+    if (int r = denoise_var_ready(c, w, h, in, sigma, alb, nd, params, blend, out, sigma_out, true, p)) return r;
+    return rt_backend_denoise_var(c, w, h, in, sigma, alb, nd, p, blend, out, sigma_out, true, stream);
+}
+
 // ---------------------------------------------------------- display stage
 // The reference's literals (render_kernel.cpp:175, :178).
 void rt_display_default_params(rt_display_params* p)
@@ -1052,6 +1103,25 @@ int rt_progress_noise_device(rt_context* c, float threshold, void* d_stats, void
     if (c->prog.adaptive)  // (every tile with its own counts)
         return rt_backend_progress_adapt_noise(c, A, (int32_t*)d_stats, (float*)d_pixel_err, (float*)d_tile_err, true, stream);
     return rt_backend_progress_noise(c, A, (int32_t*)d_stats, (float*)d_pixel_err, (float*)d_tile_err, true, stream);
+}
+
+// ---- the estimate's numerator per pixel (rt_dnv.h): what rt_denoise_var takes as sigma
+int rt_progress_noise_sigma(rt_context* c, float* sigma)
+{
+    rtk::NoiseArgs A;
+    if (int r = noise_ready(c, "rt_progress_noise_sigma", 0.0f, A)) return r;
+    if (!sigma) return rt_fail(c, RT_ERR_ARG, "rt_progress_noise_sigma: sigma is NULL");
+    return rt_backend_progress_noise_sigma(c, A, sigma, false, nullptr);
+}
+
+int rt_progress_noise_sigma_device(rt_context* c, void* d_sigma, void* stream)
+{
+    rtk::NoiseArgs A;
+    if (int r = noise_ready(c, "rt_progress_noise_sigma_device", 0.0f, A)) return r;
+    if (!d_sigma) return rt_fail(c, RT_ERR_ARG, "rt_progress_noise_sigma_device: d_sigma is NULL");
+    if ((uintptr_t)d_sigma % 4 != 0)
+        return rt_fail(c, RT_ERR_ARG, "rt_progress_noise_sigma_device: the buffer must be 4-byte aligned");
+    return rt_backend_progress_noise_sigma(c, A, (float*)d_sigma, true, stream);
 }
 
 void rt_progress_end(rt_context* c) { progress_drop(c); }

@@ -150,6 +150,11 @@ int rt_backend_features(rt_context* ctx, int w, int h, void* albedo, void* norma
 // alb and nd both null: colour only. p is validated (rt_capi_host.cpp).
 int rt_backend_denoise(rt_context* ctx, int w, int h, const void* in, const void* alb, const void* nd,
                        const rt_denoise_params& p, float blend, void* out, bool device, void* stream);
+// The variance-guided filter (rt_dnv.h): rt_backend_denoise plus sigma (w*h floats) and the optional
+// sigma_out (w*h floats, or null). p is validated (rt_capi_host.cpp).
+int rt_backend_denoise_var(rt_context* ctx, int w, int h, const void* in, const void* sigma, const void* alb, const void* nd,
+                           const rt_denoise_var_params& p, float blend, void* out, void* sigma_out, bool device,
+                           void* stream);
 // The display stage (rt_display.h), on the root device like the post stage: in (w*h float4) ->
 // out (w*h float4, may be `in`, or null) and out8 (w*h RGBA bytes, rows reversed when flip, or
 // null). The arguments are validated and inv_gamma = 1.0f / gamma (rt_capi_host.cpp).
@@ -188,6 +193,9 @@ int rt_backend_progress_track(rt_context* ctx, const float* half);
 int rt_backend_progress_read_half(rt_context* ctx, float* half);
 int rt_backend_progress_noise(rt_context* ctx, const rtk::NoiseArgs& args, int32_t* stats, float* pixel_err,
                               float* tile_err, bool device, void* stream);
+// noise_sigma: the estimate's numerator k * d per pixel (rt_dnv.h; rows * w floats), with the tile's counts
+// when prog.adaptive; args: the frame's counts as for noise. Both forms as noise.
+int rt_backend_progress_noise_sigma(rt_context* ctx, const rtk::NoiseArgs& args, float* sigma, bool device, void* stream);
 // An adaptive progression (rt_adapt.h; ctx->prog.adaptive is set by the caller once adapt_begin succeeds).
 // adapt_begin: the two count arrays, tiles_h * tiles_w int32 each, from the host arrays or, for null,
 //   prog.done and prog.n_a in every tile. With prog.adaptive set, resolve divides by the pixel's tile count.

@@ -17,6 +17,7 @@
 #include "rt_adapt.h"
 #include "rt_context.h"
 #include "rt_denoise.h"
+#include "rt_dnv.h"
 #include "rt_display.h"
 #include "rt_noise.h"
 #include "rt_query.h"
@@ -709,6 +710,64 @@ int rt_backend_denoise(rt_context* c, int w, int h, const void* in, const void* 
                 dst[q] = last ? rtk::dn_blend(f, ((const float4_*)in)[q], blend) : f;
             }
         src = dst;
+    }
+    c->last_kernel_ms = (omp_get_wtime() - t0) * 1e3;
+    return RT_OK;
+}
+
+// The variance-guided filter on the host: the loops around rt_dnv.h's per-pixel functions that
+// k_dnv_prep and the two filter kernels (rt_dnv.hip) run one thread per pixel.
+int rt_backend_denoise_var(rt_context* c, int w, int h, const void* in, const void* sigma, const void* alb, const void* nd,
+                           const rt_denoise_var_params& p, float blend, void* out, void* sigma_out, bool, void*)
+{
+    const size_t n = (size_t)w * h;
+    std::vector<float4_> rec[2] = {std::vector<float4_>(n), std::vector<float4_>(p.passes > 1 ? n : 0)};
+    const float4_* orig = (const float4_*)in;
+    const double t0 = omp_get_wtime();
+#pragma omp parallel for schedule(static)
+    for (long i = 0; i < (long)n; i++) rec[0][i] = rtk::dnv_prep(orig[i], ((const float*)sigma)[i]);
+    for (int i = 0; i < p.passes; i++) {
+        const bool last = i + 1 == p.passes;
+        const rtk::DnvPass P{w,
+                             h,
+                             1 << i,
+                             rtk::dn_inv_sigma2(p.sigma_color),
+                             rtk::dn_inv_sigma2(p.sigma_normal),
+                             rtk::dn_inv_sigma2(p.sigma_albedo),
+                             rtk::dn_inv_sigma2(p.sigma_depth),
+                             p.var_floor,
+                             rec[i & 1].data(),
+                             (const float4_*)nd,
+                             (const float4_*)alb};
+        float4_* dst = last ? (float4_*)out : rec[(i + 1) & 1].data();
+        const rtk::DnvDirect F{P};
+#pragma omp parallel for schedule(static)
+        for (int y = 0; y < h; y++)
+            for (int x = 0; x < w; x++) {
+                const size_t q = (size_t)y * w + x;
+                const float4_ f = rtk::dnv_filter_pixel(P, x, y, F);
+                dst[q] = last ? rtk::dn_blend(f, orig[q], blend) : f;
+                if (last && sigma_out) ((float*)sigma_out)[q] = rt_sqrtf(f.w);
+            }
+    }
+    c->last_kernel_ms = (omp_get_wtime() - t0) * 1e3;
+    return RT_OK;
+}
+
+// The estimate's numerator per pixel (k_dnv_sigma of rt_dnv.hip): the tile's counts when adaptive.
+int rt_backend_progress_noise_sigma(rt_context* c, const rtk::NoiseArgs& F, float* sigma, bool, void*)
+{
+    const RtProgress& P = c->prog;
+    const double t0 = omp_get_wtime();
+    const int tw = P.tiles_w();
+    for (long i = 0; i < (long)P.npx(); i++) {
+        rtk::NoiseArgs A = F;
+        if (P.adaptive) {
+            const int t = rtk::adapt_tile_of((int)i, P.w, tw);
+            A = rtk::adapt_tile_args(P.tile_n[t], P.tile_nA[t], F);
+        }
+        const float s = rtk::dnv_noise_sigma(P.state[i], P.half[i], A);
+        std::memcpy((char*)sigma + 4 * i, &s, 4);
     }
     c->last_kernel_ms = (omp_get_wtime() - t0) * 1e3;
     return RT_OK;

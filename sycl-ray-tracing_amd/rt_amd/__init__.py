@@ -25,13 +25,14 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _capi
-from ._capi import DenoiseParams, DisplayParams, NoiseStats  # noqa: F401
+from ._capi import DenoiseParams, DenoiseVarParams, DisplayParams, NoiseStats  # noqa: F401
 from ._capi import (RT_ERR_ARG, RT_ERR_HIP, RT_ERR_IO, RT_ERR_NODEV, RT_ERR_STATE, RT_OK,  # noqa: F401
                     RtError, check, lib, ptr)
 
 __all__ = ["Camera", "Image", "ParsedOBJ", "parse_obj", "compute_env_map_cdf", "luminance_of_pixels", "BVH",
            "RenderKernel", "RtError", "octree_dump", "make_materials", "read_image_float", "write_image_png",
-           "image_to_rgba8", "DenoiseParams", "denoise_default_params", "DisplayParams", "write_image_hdr"]
+           "image_to_rgba8", "DenoiseParams", "denoise_default_params", "DisplayParams", "write_image_hdr", "DenoiseVarParams",
+           "denoise_var_default_params"]
 
 
 # ------------------------------------------------------------------ camera
@@ -153,6 +154,26 @@ def _denoise_params(L_, params) -> DenoiseParams:
     for k, v in (params or {}).items():
         if k not in dict(DenoiseParams._fields_):
             raise TypeError(f"unknown denoise parameter {k}")
+        setattr(p, k, v)
+    return p
+
+
+def denoise_var_default_params(hostsim: bool = False) -> DenoiseVarParams:
+    """rt_denoise_var_default_params: the variance-guided filter's defaults."""
+    p = DenoiseVarParams()
+    lib(hostsim).rt_denoise_var_default_params(ctypes.byref(p))
+    return p
+
+
+def _denoise_var_params(L_, params) -> DenoiseVarParams:
+    """params: None (defaults), a DenoiseVarParams, or a dict of its fields over the defaults."""
+    if isinstance(params, DenoiseVarParams):
+        return params
+    p = DenoiseVarParams()
+    L_.rt_denoise_var_default_params(ctypes.byref(p))
+    for k, v in (params or {}).items():
+        if k not in dict(DenoiseVarParams._fields_):
+            raise TypeError(f"unknown denoise_var parameter {k}")
         setattr(p, k, v)
     return p
 
@@ -531,6 +552,57 @@ class RenderKernel:
         check(self.L, self.L.rt_denoise_device(self.ctx, int(width or self.width), int(height or self.height), vp(d_in),
                                                vp(d_albedo), vp(d_normal_depth), ctypes.byref(p), float(blend_factor),
                                                vp(d_out), vp(stream)), self.ctx, "rt_denoise_device")
+
+    # ---- variance-guided denoise (rt_progress_noise_sigma, rt_denoise_var; include/rt_hip.h)
+    def progress_noise_sigma(self) -> np.ndarray:
+        """rt_progress_noise_sigma after at least two passes of a tracked progression: [rows_local, w]
+        float32, the noise estimate's numerator k * d per pixel, in the units of the linear frame."""
+        i = self.progress_info()
+        s = np.empty((i["rows_local"], self.width), np.float32)
+        check(self.L, self.L.rt_progress_noise_sigma(self.ctx, ptr(s)), self.ctx, "rt_progress_noise_sigma")
+        return s
+
+    def progress_noise_sigma_device(self, d_sigma: int, stream: int | None = None):
+        """rt_progress_noise_sigma_device: the same into a device buffer (rows_local*w floats); no wait."""
+        check(self.L, self.L.rt_progress_noise_sigma_device(self.ctx, ctypes.c_void_p(d_sigma),
+                                                            ctypes.c_void_p(stream) if stream else None), self.ctx,
+              "rt_progress_noise_sigma_device")
+
+    def denoise_var(self, image: Image | None = None, sigma=None, blend_factor: float = 1.0, guides=True, params=None,
+                    return_sigma: bool = False):
+        """denoise() with the colour edge-stop scaled per pixel by sigma ([h, w] float32, a standard
+        deviation of the image's colour; None: progress_noise_sigma() of the live progression, which
+        must cover the whole frame). params: None, a DenoiseVarParams or a dict of its fields.
+        return_sigma: (Image, sigma_out), the standard deviation left after the last pass."""
+        image = self.frame_buffer if image is None else image
+        src = np.ascontiguousarray(image.pixels, dtype=np.float32)
+        h, w = src.shape[:2]
+        sig = self.progress_noise_sigma() if sigma is None else sigma
+        sig = np.ascontiguousarray(sig, dtype=np.float32)
+        assert sig.shape == (h, w), "sigma is one float per pixel of the image"
+        alb = nd = None
+        if guides is True:
+            assert (w, h) == (self.width, self.height), "guides are rendered at the kernel's own size"
+            alb, nd = self.features()
+        elif guides:
+            alb, nd = (np.ascontiguousarray(g, dtype=np.float32).reshape(h, w, 4) for g in guides)
+        out = Image(w, h)
+        left = np.empty((h, w), np.float32) if return_sigma else None
+        p = _denoise_var_params(self.L, params)
+        check(self.L, self.L.rt_denoise_var(self.ctx, w, h, ptr(src), ptr(sig), ptr(alb), ptr(nd), ctypes.byref(p),
+                                            float(blend_factor), ptr(out.pixels), ptr(left)), self.ctx, "rt_denoise_var")
+        return (out, left) if return_sigma else out
+
+    def denoise_var_device(self, d_in: int, d_sigma: int, d_out: int, d_albedo: int | None = None,
+                           d_normal_depth: int | None = None, blend_factor: float = 1.0, params=None,
+                           d_sigma_out: int | None = None, stream: int | None = None, width=None, height=None):
+        """rt_denoise_var_device: device buffers (w*h*4 floats each, sigma and sigma_out w*h floats), no wait."""
+        p = _denoise_var_params(self.L, params)
+        vp = lambda a: ctypes.c_void_p(a) if a else None  # noqa: E731
+        check(self.L, self.L.rt_denoise_var_device(self.ctx, int(width or self.width), int(height or self.height), vp(d_in),
+                                                   vp(d_sigma), vp(d_albedo), vp(d_normal_depth), ctypes.byref(p),
+                                                   float(blend_factor), vp(d_out), vp(d_sigma_out), vp(stream)), self.ctx,
+              "rt_denoise_var_device")
 
     def render_variants(self, materials, frames=None, device_ptrs=None, row_offset: int = 0, row_stride: int = 1):
         """rt_render_variants: the material sweep as replicas. `materials` is

@@ -35,6 +35,8 @@ EXPORTS = [
     "rt_progress_resolve_linear_device", "rt_display", "rt_display_device", "rt_write_hdr",
     "rt_progress_noise_track", "rt_progress_noise", "rt_progress_noise_device",
     "rt_progress_advance_adaptive", "rt_progress_tile_counts",
+    "rt_progress_noise_sigma", "rt_progress_noise_sigma_device", "rt_denoise_var_default_params", "rt_denoise_var",
+    "rt_denoise_var_device",
 ]
 
 # return codes (include/rt_hip.h)
@@ -50,6 +52,12 @@ class DenoiseParams(ctypes.Structure):
     """struct rt_denoise_params (include/rt_hip.h)."""
     _fields_ = [("passes", ctypes.c_int), ("sigma_color", F), ("sigma_normal", F), ("sigma_albedo", F),
                 ("sigma_depth", F)]
+
+
+class DenoiseVarParams(ctypes.Structure):
+    """struct rt_denoise_var_params (include/rt_hip.h)."""
+    _fields_ = [("passes", ctypes.c_int), ("sigma_color", F), ("sigma_normal", F), ("sigma_albedo", F),
+                ("sigma_depth", F), ("var_floor", F)]
 
 
 class DisplayParams(ctypes.Structure):
@@ -136,6 +144,11 @@ _SIGS = {
     "rt_progress_noise_device": (I, [P, F, P, P, P, P]),
     "rt_progress_advance_adaptive": (I, [P, I, F, P, P]),
     "rt_progress_tile_counts": (I, [P, P, P]),
+    "rt_progress_noise_sigma": (I, [P, P]),
+    "rt_progress_noise_sigma_device": (I, [P, P, P]),
+    "rt_denoise_var_default_params": (None, [ctypes.POINTER(DenoiseVarParams)]),
+    "rt_denoise_var": (I, [P, I, I, P, P, P, P, ctypes.POINTER(DenoiseVarParams), F, P, P]),
+    "rt_denoise_var_device": (I, [P, I, I, P, P, P, P, ctypes.POINTER(DenoiseVarParams), F, P, P, P]),
     # product-only extras
     "rt_device_libm": (I, [I, I, P, P, P, I]),
     "rt_device_libm_digest": (I, [I, I, ctypes.c_uint32, I, P]),
@@ -150,6 +163,7 @@ _SIGS = {
     "rt_device_display_kernel_ms": (I, [P, I, I, P, P, P, P, I, P]),
     "rt_device_noise_kernel_ms": (I, [P, I, I, P, P, P, P, P, I, P]),
     "rt_device_adapt_kernel_ms": (I, [P, F, I, P, P]),
+    "rt_device_denoise_var_pass_ms": (I, [P, I, P, I]),
     # hostsim-only extra
     "rt_hostsim_heap_order": (I, [P, I, P, P]),
     "rt_hostsim_fast_queries": (I, [P, P, I, P, P]),

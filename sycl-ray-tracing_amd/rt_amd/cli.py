@@ -32,6 +32,12 @@ Adaptive sampling (RenderKernel.progress_advance_adaptive): --adaptive, with --n
 is still above T, until none is (or none fits under --samples any more: keep --samples a multiple of K).
 It also writes a fifth PNG, RT_samples.png: tile_n / samples in grey, so that one sees where the samples
 went. Without --adaptive nothing changes.
+
+Variance-guided denoise (RenderKernel.denoise_var): --denoise=var, with --noise-threshold=T. The frame is
+resolved linear, filtered with the progression's own per-pixel noise figure (progress_noise_sigma) as the
+colour edge-stop's scale, and then displayed; the three denoised PNGs are blends of that image with the
+render instead of the fixed-sigma filter's. It needs a tracked progression of at least two passes.
+--denoise=atrous (the default) is the run without the flag, byte for byte.
 """
 from __future__ import annotations
 
@@ -47,13 +53,13 @@ import rt_amd
 def parse(argv):
     a = dict(obj="data/OBJs/cornell_pbr.obj", sky="data/Skyspheres/evening_road_01_puresky_2k.hdr", w=512, h=512,
              samples=64, bounces=8, camera="dragon", out=".", hostsim=False, preview_every=0, checkpoint="",
-             exposure=None, gamma=None, hdr_out="", noise_threshold=None, adaptive=False)
+             exposure=None, gamma=None, hdr_out="", noise_threshold=None, adaptive=False, denoise="atrous")
     for s in argv:
         if s == "--hostsim":
             a["hostsim"] = True
         elif s == "--adaptive":
             a["adaptive"] = True
-        elif s.startswith(("--sky=", "--camera=", "--out=", "--checkpoint=", "--hdr-out=")):
+        elif s.startswith(("--sky=", "--camera=", "--out=", "--checkpoint=", "--hdr-out=", "--denoise=")):
             k, v = s[2:].split("=", 1)
             a[k.replace("-", "_")] = v
         elif s.startswith(("--exposure=", "--gamma=", "--noise-threshold=")):
@@ -81,13 +87,20 @@ def display_stage(a: dict) -> bool:
     return a["exposure"] is not None or a["gamma"] is not None or bool(a["hdr_out"])
 
 
+def linear_path(a: dict) -> bool:
+    """The frame is rendered or resolved linear and displayed afterwards: the display stage's flags, or
+    --denoise=var, which filters the linear frame."""
+    return display_stage(a) or a["denoise"] == "var"
+
+
 def display_args(a: dict) -> dict:
     return dict(exposure=1.5 if a["exposure"] is None else a["exposure"], gamma=2.2 if a["gamma"] is None else a["gamma"])
 
 
 def render_progressive(rk: rt_amd.RenderKernel, fb: rt_amd.Image, a: dict):
     """The frame in passes: previews and / or a checkpoint after each; fb ends as render() leaves it
-    (display stage: as render_linear() leaves it)."""
+    (display stage or --denoise=var: as render_linear() leaves it). Returns the linear frame filtered by
+    denoise_var under --denoise=var, else None."""
     step = a["preview_every"] if a["preview_every"] > 0 else a["samples"]
     ck = a["checkpoint"]
     if ck and os.path.exists(ck):
@@ -135,8 +148,12 @@ def render_progressive(rk: rt_amd.RenderKernel, fb: rt_amd.Image, a: dict):
             print(f"noise: done {done} max_tile {n['max_tile']:.6g} tiles_over {n['tiles_over']}")
             if n["tiles_over"] == 0:
                 break
-    if display_stage(a):
+    filtered = None
+    if linear_path(a):
         rk.progress_resolve_linear(fb)
+        if a["denoise"] == "var":  # (the sigma of the live progression, then the filter on the linear frame)
+            with np.errstate(all="ignore"):
+                filtered = rk.denoise_var(fb, None, 1.0)
     else:
         rk.progress_resolve(fb)
     if a["adaptive"]:  # where the samples went: tile_n / total in grey
@@ -147,6 +164,7 @@ def render_progressive(rk: rt_amd.RenderKernel, fb: rt_amd.Image, a: dict):
         counts.pixels[..., 3] = 1.0
         rt_amd.write_image_png(counts, os.path.join(a["out"], "RT_samples.png"))
     rk.progress_end()
+    return filtered
 
 
 def main(argv=None) -> int:
@@ -156,6 +174,13 @@ def main(argv=None) -> int:
         return 2
     if a["adaptive"] and a["noise_threshold"] is None:
         print("--adaptive needs --noise-threshold=T and --preview-every=K", file=sys.stderr)
+        return 2
+    if a["denoise"] not in ("atrous", "var"):
+        print("--denoise= takes atrous or var", file=sys.stderr)
+        return 2
+    if a["denoise"] == "var" and a["noise_threshold"] is None:
+        print("--denoise=var needs --noise-threshold=T and --preview-every=K (it filters with the progression's "
+              "noise estimate)", file=sys.stderr)
         return 2
     print(f"Reading OBJ {a['obj']} ...")
     P = rt_amd.parse_obj(a["obj"])
@@ -168,19 +193,29 @@ def main(argv=None) -> int:
                              P.emissive_triangle_indices, P.material_indices, None, rt_amd.BVH(P.triangles), sky,
                              rt_amd.compute_env_map_cdf(sky), hostsim=a["hostsim"])
     rk.set_camera(rt_amd.Camera.preset(a["camera"]))
+    filtered = None
     if a["preview_every"] > 0 or a["checkpoint"]:
-        render_progressive(rk, fb, a)
-    elif display_stage(a):
+        try:
+            filtered = render_progressive(rk, fb, a)
+        except rt_amd.RtError as e:
+            if a["denoise"] != "var" or "rt_progress_noise_sigma" not in str(e):
+                raise
+            print(f"--denoise=var: {e}", file=sys.stderr)
+            return 2
+    elif linear_path(a):
         rk.render_linear()
     else:
         rk.render()
-    if display_stage(a):  # fb holds the linear radiance: the .hdr file, then the displayed frame
+    if linear_path(a):  # fb holds the linear radiance: the .hdr file, then the displayed frame
         if a["hdr_out"]:
             rt_amd.write_image_hdr(fb, a["hdr_out"])
         fb = rk.display(fb, **display_args(a))
+        if filtered is not None:
+            filtered = rk.display(filtered, **display_args(a))
     print(f"{int((time.perf_counter() - t0) * 1e3)}ms")
     with np.errstate(all="ignore"):
-        filtered = rk.denoise(fb, 1.0)
+        if filtered is None:
+            filtered = rk.denoise(fb, 1.0)
         os.makedirs(a["out"], exist_ok=True)
         rt_amd.write_image_png(fb, os.path.join(a["out"], "RT_output.png"))
         for factor, name in ((1.0, "1"), (0.75, "0.75"), (0.5, "0.5")):

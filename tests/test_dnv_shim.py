@@ -1,0 +1,28 @@
+"""The C++ drop-in's RenderKernel::denoise_var and progress_noise_sigma (include/render_kernel_hip.h),
+compiled against the reference's own headers and objects and linked to the hostsim build of the C
+ABI: their outputs equal rt_progress_noise_sigma and rt_render_features + rt_denoise_var called
+directly, bit for bit. Container only: needs /root/reference (skipped elsewhere, as
+tests/test_denoise_shim.py)."""
+from __future__ import annotations
+
+import os
+import subprocess
+
+import pytest
+
+import golden_io as gio
+import scenes
+
+REF = "/root/reference/include"
+
+
+@pytest.mark.skipif(not os.path.isdir(REF), reason="needs the reference's headers (container only)")
+def test_cpp_shim_denoise_var_equals_c_abi(tmp_path):
+    subprocess.run(["make", "-C", gio.REPO, "-s", "ref", "build/dnv_shim_test"], check=True)
+    sky = tmp_path / "sky.raw"
+    scenes.write_sky_raw(str(sky), "S")
+    r = subprocess.run([os.path.join(gio.REPO, "build", "dnv_shim_test"), scenes.scene_path("cornell12"), str(sky),
+                        "33", "21", "3"], capture_output=True, text=True)
+    print(r.stdout, r.stderr)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "DNV_SHIM one_pass_throws 1 sigma 1 resolved 1 blend1 1 blend075 1 sigma_out 1 filtered 1 bad_size_throws 1" in r.stdout
