@@ -47,7 +47,8 @@ $(OBJ)/rt_hostsim.o: $(SRC)/rt_hostsim.cpp $(HDRS) $(ALL_SRC)
 #   rt_noise     a tracked progression's fold and noise estimate
 #   rt_adapt     an adaptive progression's selection, gather / scatter and resolves
 #   rt_dnv       the variance-guided filter and the absolute noise figure it takes
-HIP_UNITS := rt_render rt_wave_run rt_probe rt_denoise rt_query rt_display rt_noise rt_adapt rt_dnv
+#   rt_temporal  temporal accumulation: the previous frame reprojected into the new camera and blended in
+HIP_UNITS := rt_render rt_wave_run rt_probe rt_denoise rt_query rt_display rt_noise rt_adapt rt_dnv rt_temporal
 $(HIP_UNITS:%=$(OBJ)/%.o): $(OBJ)/%.o: $(SRC)/%.hip $(HDRS)
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
@@ -155,6 +156,7 @@ hostsim-variant: $(OBJ)/rt_imageio.host.o
 #   adaptive_shim_test  render_adaptive against the C ABI                   tests/test_adaptive_shim.py
 #                       (make sanitize-adaptive: the same program under ASan + UBSan over the hostsim sources)
 #   dnv_shim_test       denoise_var / progress_noise_sigma against the C ABI     tests/test_dnv_shim.py
+#   temporal_shim_test  temporal_accumulate against the C ABI                     tests/test_temporal_shim.py
 REFDIR ?= /root/reference
 REFOBJ := oracle/_ref/objO2
 REFOBJS := $(REFOBJ)/bvh.o $(REFOBJ)/flattened_bvh.o $(REFOBJ)/triangle.o $(REFOBJ)/vec.o $(REFOBJ)/color.o \

@@ -271,6 +271,39 @@ public:
         return out;
     }
 
+    // Temporal accumulation (rt_temporal_accumulate with its default parameters): the history of the
+    // previous frame, rendered under prev_camera, reprojected into the kernel's current camera and
+    // blended with `linear` (a linear frame, as render_linear leaves it) whose per-pixel standard
+    // deviation is sigma (progress_noise_sigma()). The feature pass runs under the current camera.
+    // history: the previous call's result, or null for the first frame. The result's rgba and sigma
+    // are what denoise_var takes; the whole result is the next call's history.
+    struct TemporalFrame {
+        Image rgba;
+        std::vector<float> sigma, length, normal_depth;
+    };
+    TemporalFrame temporal_accumulate(const Image& linear, const std::vector<float>& sigma, Camera prev_camera,
+                                      const TemporalFrame* history = nullptr) const
+    {
+        std::lock_guard<std::mutex> lk(m_mu);
+        const_cast<RenderKernel*>(this)->sync_materials();
+        const int w = linear.width(), h = linear.height();
+        const size_t n = (size_t)w * h;
+        if (sigma.size() != n) throw std::runtime_error("librt_hip: temporal_accumulate: sigma is not width * height floats");
+        if (history && (history->rgba.width() != w || history->rgba.height() != h || history->sigma.size() != n ||
+                        history->length.size() != n || history->normal_depth.size() != 4 * n))
+            throw std::runtime_error("librt_hip: temporal_accumulate: the history is not of the frame's size");
+        std::vector<float> albedo(n * 4);
+        TemporalFrame out{Image(w, h), std::vector<float>(n), std::vector<float>(n), std::vector<float>(n * 4)};
+        check(rt_render_features(m_ctx, w, h, albedo.data(), out.normal_depth.data()));
+        check(rt_temporal_accumulate(m_ctx, w, h, linear.data(), sigma.data(), out.normal_depth.data(),
+                                     &prev_camera.view_matrix.m[0][0], prev_camera.fov_dist,
+                                     history ? history->rgba.data() : nullptr, history ? history->sigma.data() : nullptr,
+                                     history ? history->length.data() : nullptr,
+                                     history ? history->normal_depth.data() : nullptr, nullptr, out.rgba.data(),
+                                     out.sigma.data(), out.length.data()));
+        return out;
+    }
+
     // INTERSECT_SCENE for a batch of rays through rt_query (the render's search-BVH walks, the
     // exact walk behind them): hits[i] as BVH::intersect + the sphere loop fill it (t = -1 and
     // primitive_index = -1 without a hit).

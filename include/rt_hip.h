@@ -557,6 +557,80 @@ int rt_denoise_var_device(rt_context* ctx, int w, int h, const void* d_rgba_in, 
                           const void* d_normal_depth, const rt_denoise_var_params* params, float blend, void* d_rgba_out,
                           void* d_sigma_out, void* stream);
 
+/* ---------------------------------------------- temporal accumulation
+ * The previous frame's accumulated colour, variance and history length reprojected into the
+ * current camera and blended with the new frame (the temporal half of SVGF, Schied et al. 2017):
+ * what rt_denoise_var then takes is an image of lower variance and a sigma map that says so.
+ * Stateless: the caller owns every buffer, and one call's rgba_out, sigma_out and len_out with
+ * the frame's normal_depth are the next call's history. Only the camera moves between frames.
+ * Float32 throughout, no contraction, IEEE division and square root, floorf; no expf.
+ *
+ * rt_temporal_accumulate / _device: rgba_in (float4[h][w], a linear frame such as
+ *   rt_progress_resolve_linear gives), sigma_in (float[h][w], its per-pixel standard deviation,
+ *   such as rt_progress_noise_sigma's) and normal_depth (float4[h][w], rt_render_features' buffer
+ *   under the context's current camera) describe this frame; prev_view (row-major 4x4) and
+ *   prev_fov_dist are the camera of the history; hist_rgba, hist_sigma, hist_len and
+ *   hist_normal_depth are the previous call's three outputs and the previous frame's
+ *   normal_depth, all four NULL for the first frame. Outputs, all required: rgba_out
+ *   (float4[h][w]), sigma_out and len_out (float[h][w]). For pixel p = (x, y), c = rgba_in[p],
+ *   {n_p, t} = normal_depth[p]:
+ *   1 v_c = sigma_in[p] * sigma_in[p]; a NaN v_c is 0, an infinite one the largest finite float.
+ *   2 The pixel is carried over, out = {c.rgb, 1}, sigma_out = sqrtf(v_c), len_out = 1, when
+ *     c.rgb is not finite, one of normal_depth[p]'s four floats is a NaN, the history is NULL,
+ *     or steps 4 and 5 find no history for it.
+ *   3 (o, d) = the feature pass's ray of the pixel (the context's camera, x_j = (float)x,
+ *     y_j = (float)y). A hit (t > 0): P = o + t d and t_exp = |P - o_prev|, the square root of
+ *     the squared distance, o_prev = the history camera's origin (its view matrix applied to 0,
+ *     in float, as the render computes its own). A miss: P = o_prev + d (the environment is at
+ *     infinity: only the rotation counts) and no depth or normal test below.
+ *   4 q = prev_inv applied to P as a point, prev_inv being the inverse of prev_view, computed
+ *     once per call in double by a general 4x4 inverse and rounded to float.
+ *     ratio = q.z / prev_fov_dist; unless ratio > 0 there is no history.
+ *       fx = (((q.x / ratio) / aspect + 1) * 0.5) * (float)w        aspect = (float)w / (float)h
+ *       fy = ((q.y / ratio + 1) * 0.5) * (float)h
+ *     the camera ray run backwards: with the same camera pixel x sits at fx = x. Unless
+ *     -1 < fx < w and -1 < fy < h there is no history (every tap would lie outside the image).
+ *     ix = floorf(fx), tx = fx - ix; iy and ty the same.
+ *   5 The four taps (ix + dx, iy + dy), dy outer, with the bilinear weight
+ *     b = (dy ? ty : 1 - ty) * (dx ? tx : 1 - tx). A tap q is skipped when b == 0, it lies
+ *     outside the image, hist_len[q] is not > 0, hist_rgba[q].rgb or hist_sigma[q] is not
+ *     finite, or its hit state (t_q > 0) differs from p's; for a hit p also unless
+ *     |t_q - t_exp| <= depth_tol * t_exp and dot(n_p, n_q) >= normal_cos (a NaN in the tap's
+ *     guide fails them). S = sum b; unless S > min_weight there is no history. Otherwise
+ *       c_h = sum b c_q / S     len_h = sum b len_q / S     v_h = sum b (sigma_q sigma_q) / S
+ *     v_h above the largest finite float is that float. An infinite hist_len counts.
+ *   6 len = min(len_h + 1, max_len); a = 1 / len; rgb = c_h + a (c - c_h), alpha 1;
+ *     v = ((1 - a) (1 - a)) v_h + a (a v_c), above the largest finite float that float;
+ *     sigma_out = sqrtf(v); len_out = len.
+ *   The alphas of rgba_in and hist_rgba play no part. The inputs are not written.
+ *   RT_ERR_STATE without a camera (no scene, BVH or environment map is needed). RT_ERR_ARG for a
+ *   NULL ctx, required buffer or prev_view; a parameter that is not finite, depth_tol < 0,
+ *   normal_cos outside [-1, 1], min_weight outside [0, 1), max_len < 1; a prev_fov_dist that is
+ *   zero or not finite; a prev_view that is singular or holds a non-finite entry; some but not
+ *   all of the four history buffers; an output whose bytes overlap an input's or another
+ *   output's; more than 262140 rows or 2^27 - 1 pixels (rt_denoise's limits). The device form
+ *   takes device pointers (the float4 buffers 16-byte aligned, the float buffers 4-byte aligned:
+ *   RT_ERR_ARG otherwise) and a stream (NULL: default) and returns without waiting. params NULL:
+ *   the defaults (rt_temporal_default_params). Runs on the root device of a multi-device
+ *   context; rt_last_kernel_ms as for rt_denoise. */
+typedef struct rt_temporal_params {
+    float depth_tol;   /* relative: |t_q - t_exp| <= depth_tol * t_exp             default 0.05 */
+    float normal_cos;  /* dot(n_p, n_q) >= normal_cos                              default 0.9  */
+    float min_weight;  /* the valid taps' bilinear weights must sum above this     default 0.1  */
+    float max_len;     /* history length cap, >= 1: alpha never below 1 / max_len  default 32   */
+} rt_temporal_params;
+void rt_temporal_default_params(rt_temporal_params* params);
+int rt_temporal_accumulate(rt_context* ctx, int w, int h, const float* rgba_in, const float* sigma_in,
+                           const float* normal_depth, const float prev_view[16], float prev_fov_dist,
+                           const float* hist_rgba, const float* hist_sigma, const float* hist_len,
+                           const float* hist_normal_depth, const rt_temporal_params* params, float* rgba_out,
+                           float* sigma_out, float* len_out);
+int rt_temporal_accumulate_device(rt_context* ctx, int w, int h, const void* d_rgba_in, const void* d_sigma_in,
+                                  const void* d_normal_depth, const float prev_view[16], float prev_fov_dist,
+                                  const void* d_hist_rgba, const void* d_hist_sigma, const void* d_hist_len,
+                                  const void* d_hist_normal_depth, const rt_temporal_params* params, void* d_rgba_out,
+                                  void* d_sigma_out, void* d_len_out, void* stream);
+
 /* Counters of the last render when enabled (RT_STAT_* order, rt_device.h);
  * with n up to 2 * RT_STAT_COUNT the second block is the share of the
  * gfx950 tail kernel (k_tail) in those totals. */

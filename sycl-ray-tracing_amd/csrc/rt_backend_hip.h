@@ -10,6 +10,7 @@
 //   rt_display.hip  the display stage and the linear resolve
 //   rt_noise.hip    a tracked progression's fold and noise estimate
 //   rt_dnv.hip      the variance-guided post stage and the absolute noise figure it takes
+//   rt_temporal.hip temporal accumulation: the previous frame reprojected and blended in
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -129,12 +130,16 @@ struct Marker {
 // created on first use and deleted with their Backend (its device current).
 struct Post;
 struct PostVar;  // (rt_dnv.hip: the variance-guided filter's buffers, Post's sibling)
+struct PostTemporal;  // (rt_temporal.hip: temporal accumulation's staging buffer, PostVar's sibling)
 struct Query;
 struct PostDelete {
     void operator()(Post* p) const;
 };
 struct PostVarDelete {
     void operator()(PostVar* p) const;
+};
+struct PostTemporalDelete {
+    void operator()(PostTemporal* p) const;
 };
 struct QueryDelete {
     void operator()(Query* q) const;
@@ -210,6 +215,7 @@ struct Backend {
     std::unique_ptr<PostVar, PostVarDelete> post_var;  // (rt_dnv.hip)
     std::unique_ptr<Query, QueryDelete> query;  // (rt_query.hip)
     std::unique_ptr<Adapt> adapt;               // (rt_adapt.hip)
+    std::unique_ptr<PostTemporal, PostTemporalDelete> post_temporal;  // (rt_temporal.hip)
 };
 
 Backend* rt_backend_dev0(rt_context* c);  // rt_backend.hip: the root device's Backend
@@ -221,7 +227,8 @@ Backend* rt_backend_dev0(rt_context* c);  // rt_backend.hip: the root device's B
 //   enter, [staging], in / out / inout per buffer, begin, the stage's launches, end
 // b's device is current until the StagedCall leaves scope, then the caller's again.
 // The host forms' streams are inherited from the stages as they were written, not chosen here:
-//   null stream   features, denoise (Post::io), denoise_var (PostVar::io), display (disp), queries (Query::io), rt_render (fb)
+//   null stream   features, denoise (Post::io), denoise_var (PostVar::io), temporal_accumulate
+//                 (PostTemporal::io), display (disp), queries (Query::io), rt_render (fb)
 //   Backend::own  noise and noise_sigma (pg_noise), progressive resolves (pg_out), pixel lists (fb)
 struct StagedCall {
     rt_context* c = nullptr;

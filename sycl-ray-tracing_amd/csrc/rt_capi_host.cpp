@@ -12,6 +12,7 @@
 #include "rt_context.h"
 #include "rt_denoise.h"
 #include "rt_noise.h"
+#include "rt_temporal.h"
 
 namespace {
 std::mutex g_err_mu;
@@ -730,6 +731,146 @@ int rt_denoise_var_device(rt_context* c, int w, int h, const void* in, const voi
     rt_denoise_var_params p;
     if (int r = denoise_var_ready(c, w, h, in, sigma, alb, nd, params, blend, out, sigma_out, true, p)) return r;
     return rt_backend_denoise_var(c, w, h, in, sigma, alb, nd, p, blend, out, sigma_out, true, stream);
+}
+
+// ---- temporal accumulation (rt_temporal.h)
+// Defaults: SVGF's depth and normal tests at the widths its authors' code uses for static scenes, a
+// history of 32 frames.
+void rt_temporal_default_params(rt_temporal_params* p)
+{
+    if (!p) return;
+    p->depth_tol = 0.05f;
+    p->normal_cos = 0.9f;
+    p->min_weight = 0.1f;
+    p->max_len = 32.0f;
+}
+
+// The inverse of a row-major 4x4 in double (Gauss-Jordan, partial pivoting), rounded to float.
+// false: a non-finite entry, a zero pivot (singular) or a non-finite result.
+static bool invert_view(const float m[16], float inv[16])
+{
+    double a[4][8];
+    for (int r = 0; r < 4; r++)
+        for (int k = 0; k < 4; k++) {
+            if (!std::isfinite(m[4 * r + k])) return false;
+            a[r][k] = m[4 * r + k];
+            a[r][4 + k] = r == k ? 1.0 : 0.0;
+        }
+    for (int col = 0; col < 4; col++) {
+        int piv = col;
+        for (int r = col + 1; r < 4; r++)
+            if (std::fabs(a[r][col]) > std::fabs(a[piv][col])) piv = r;
+        if (a[piv][col] == 0.0) return false;
+        if (piv != col)
+            for (int k = 0; k < 8; k++) std::swap(a[piv][k], a[col][k]);
+        const double d = a[col][col];
+        for (int k = 0; k < 8; k++) a[col][k] /= d;
+        for (int r = 0; r < 4; r++) {
+            if (r == col) continue;
+            const double f = a[r][col];
+            if (f == 0.0) continue;
+            for (int k = 0; k < 8; k++) a[r][k] -= f * a[col][k];
+        }
+    }
+    for (int r = 0; r < 4; r++)
+        for (int k = 0; k < 4; k++) {
+            inv[4 * r + k] = (float)a[r][4 + k];
+            if (!std::isfinite(inv[4 * r + k])) return false;
+        }
+    return true;
+}
+
+static bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb)
+{
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + nb && y < x + na;
+}
+
+static int temporal_ready(rt_context* c, const char* fn, int w, int h, const void* in, const void* sigma, const void* nd,
+                          const float* prev_view, float prev_fov, const void* h_rgba, const void* h_sigma,
+                          const void* h_len, const void* h_nd, const rt_temporal_params* params, const void* out,
+                          const void* sigma_out, const void* len_out, bool device, rtk::TemporalFrame& T)
+{
+    const std::string f = fn;
+    if (!c) return rt_fail(nullptr, RT_ERR_ARG, f + ": ctx is NULL");
+    if (!c->have_cam) return rt_fail(c, RT_ERR_STATE, f + ": camera not set");
+    if (w <= 0 || h <= 0 || !in || !sigma || !nd || !out || !sigma_out || !len_out || !prev_view)
+        return rt_fail(c, RT_ERR_ARG, f + ": bad buffers");
+    // (rt_denoise's frame-size limits: k_temporal tiles the frame 4 rows per block as its kernels do)
+    if ((double)w * (double)h > 134217727.0) return rt_fail(c, RT_ERR_ARG, f + ": too many pixels");
+    if (h > 4 * 65535) return rt_fail(c, RT_ERR_ARG, f + ": height above 262140 rows");
+    const int given = (h_rgba != nullptr) + (h_sigma != nullptr) + (h_len != nullptr) + (h_nd != nullptr);
+    if (given != 0 && given != 4)
+        return rt_fail(c, RT_ERR_ARG, f + ": the four history buffers must all be given or all be NULL");
+    rt_temporal_params p;
+    if (params) p = *params;
+    else rt_temporal_default_params(&p);
+    if (!std::isfinite(p.depth_tol) || !std::isfinite(p.normal_cos) || !std::isfinite(p.min_weight) || !std::isfinite(p.max_len))
+        return rt_fail(c, RT_ERR_ARG, f + ": a parameter is not finite");
+    if (p.depth_tol < 0.0f) return rt_fail(c, RT_ERR_ARG, f + ": depth_tol is negative");
+    if (p.normal_cos < -1.0f || p.normal_cos > 1.0f) return rt_fail(c, RT_ERR_ARG, f + ": normal_cos is outside [-1, 1]");
+    if (p.min_weight < 0.0f || !(p.min_weight < 1.0f)) return rt_fail(c, RT_ERR_ARG, f + ": min_weight is outside [0, 1)");
+    if (p.max_len < 1.0f) return rt_fail(c, RT_ERR_ARG, f + ": max_len is below 1");
+    if (!std::isfinite(prev_fov) || prev_fov == 0.0f) return rt_fail(c, RT_ERR_ARG, f + ": prev_fov_dist is zero or not finite");
+    const size_t n = (size_t)w * h;
+    const struct {
+        const void* p;
+        size_t bytes;
+    } ins[7] = {{in, 16 * n}, {sigma, 4 * n}, {nd, 16 * n}, {h_rgba, 16 * n}, {h_sigma, 4 * n}, {h_len, 4 * n}, {h_nd, 16 * n}},
+      outs[3] = {{out, 16 * n}, {sigma_out, 4 * n}, {len_out, 4 * n}};
+    for (int o = 0; o < 3; o++) {
+        for (int i = 0; i < 7; i++)
+            if (ins[i].p && ranges_overlap(outs[o].p, outs[o].bytes, ins[i].p, ins[i].bytes))
+                return rt_fail(c, RT_ERR_ARG, f + ": an output overlaps an input");
+        for (int k = o + 1; k < 3; k++)
+            if (ranges_overlap(outs[o].p, outs[o].bytes, outs[k].p, outs[k].bytes))
+                return rt_fail(c, RT_ERR_ARG, f + ": two outputs overlap");
+    }
+    if (device) {
+        const void* a16[5] = {in, nd, h_rgba, h_nd, out};
+        const void* a4[5] = {sigma, h_sigma, h_len, sigma_out, len_out};
+        for (int i = 0; i < 5; i++)
+            if ((uintptr_t)a16[i] % 16 != 0 || (uintptr_t)a4[i] % 4 != 0)
+                return rt_fail(c, RT_ERR_ARG, f + ": the float4 buffers must be 16-byte aligned, the float buffers 4-byte aligned");
+    }
+    T.cur = rtk::cam_view(c->cam, w, h);
+    if (!invert_view(prev_view, T.prev_inv.m))
+        return rt_fail(c, RT_ERR_ARG, f + ": prev_view is singular or not finite");
+    T.prev_inv.fov_dist = prev_fov;
+    RtCamera prev;
+    std::memcpy(prev.m, prev_view, 64);
+    prev.fov_dist = prev_fov;
+    const rtk::V3 op = rtk::xform_point(prev, rtk::v3(0.0f, 0.0f, 0.0f));
+    T.o_prev[0] = op.x, T.o_prev[1] = op.y, T.o_prev[2] = op.z;
+    T.depth_tol = p.depth_tol, T.normal_cos = p.normal_cos, T.min_weight = p.min_weight, T.max_len = p.max_len;
+    T.in = (const float4_*)in, T.sigma = (const float*)sigma, T.nd = (const float4_*)nd;
+    T.h_rgba = (const float4_*)h_rgba, T.h_sigma = (const float*)h_sigma, T.h_len = (const float*)h_len;
+    T.h_nd = (const float4_*)h_nd;
+    return RT_OK;
+}
+
+int rt_temporal_accumulate(rt_context* c, int w, int h, const float* in, const float* sigma, const float* nd,
+                           const float prev_view[16], float prev_fov_dist, const float* hist_rgba, const float* hist_sigma,
+                           const float* hist_len, const float* hist_nd, const rt_temporal_params* params, float* out,
+                           float* sigma_out, float* len_out)
+{
+    rtk::TemporalFrame T;
+    if (int r = temporal_ready(c, "rt_temporal_accumulate", w, h, in, sigma, nd, prev_view, prev_fov_dist, hist_rgba,
+                               hist_sigma, hist_len, hist_nd, params, out, sigma_out, len_out, false, T))
+        return r;
+    return rt_backend_temporal(c, T, out, sigma_out, len_out, false, nullptr);
+}
+
+int rt_temporal_accumulate_device(rt_context* c, int w, int h, const void* in, const void* sigma, const void* nd,
+                                  const float prev_view[16], float prev_fov_dist, const void* hist_rgba,
+                                  const void* hist_sigma, const void* hist_len, const void* hist_nd,
+                                  const rt_temporal_params* params, void* out, void* sigma_out, void* len_out, void* stream)
+{
+    rtk::TemporalFrame T;
+    if (int r = temporal_ready(c, "rt_temporal_accumulate_device", w, h, in, sigma, nd, prev_view, prev_fov_dist, hist_rgba,
+                               hist_sigma, hist_len, hist_nd, params, out, sigma_out, len_out, true, T))
+        return r;
+    return rt_backend_temporal(c, T, out, sigma_out, len_out, true, stream);
 }
 
 // ---------------------------------------------------------- display stage

@@ -155,6 +155,14 @@ int rt_backend_denoise(rt_context* ctx, int w, int h, const void* in, const void
 int rt_backend_denoise_var(rt_context* ctx, int w, int h, const void* in, const void* sigma, const void* alb, const void* nd,
                            const rt_denoise_var_params& p, float blend, void* out, void* sigma_out, bool device,
                            void* stream);
+// Temporal accumulation (rt_temporal.h), on the root device like the post stage: T holds the cameras, the
+// validated parameters and the caller's seven input buffers (the four of the history all null: the first
+// frame); rgba_out (w*h float4), sigma_out and len_out (w*h floats each) are required.
+namespace rtk {
+struct TemporalFrame;
+}
+int rt_backend_temporal(rt_context* ctx, rtk::TemporalFrame T, void* rgba_out, void* sigma_out, void* len_out, bool device,
+                        void* stream);
 // The display stage (rt_display.h), on the root device like the post stage: in (w*h float4) ->
 // out (w*h float4, may be `in`, or null) and out8 (w*h RGBA bytes, rows reversed when flip, or
 // null). The arguments are validated and inv_gamma = 1.0f / gamma (rt_capi_host.cpp).

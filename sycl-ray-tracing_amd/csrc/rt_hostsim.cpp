@@ -21,6 +21,7 @@
 #include "rt_display.h"
 #include "rt_noise.h"
 #include "rt_query.h"
+#include "rt_temporal.h"
 #include "rt_wave.h"
 
 // Stack window and step budget of the host build: smaller than the
@@ -769,6 +770,25 @@ int rt_backend_progress_noise_sigma(rt_context* c, const rtk::NoiseArgs& F, floa
         const float s = rtk::dnv_noise_sigma(P.state[i], P.half[i], A);
         std::memcpy((char*)sigma + 4 * i, &s, 4);
     }
+    c->last_kernel_ms = (omp_get_wtime() - t0) * 1e3;
+    return RT_OK;
+}
+
+// Temporal accumulation on the host: the loop around rt_temporal.h's temporal_pixel that k_temporal
+// (rt_temporal.hip) runs one thread per pixel.
+int rt_backend_temporal(rt_context* c, rtk::TemporalFrame T, void* rgba_out, void* sigma_out, void* len_out, bool, void*)
+{
+    const int w = T.cur.W, h = T.cur.H;
+    const double t0 = omp_get_wtime();
+#pragma omp parallel for schedule(static)
+    for (int y = 0; y < h; y++)
+        for (int x = 0; x < w; x++) {
+            const size_t p = (size_t)y * w + x;
+            const rtk::TemporalOut r = rtk::temporal_pixel(T, x, y);
+            ((float4_*)rgba_out)[p] = r.rgba;
+            ((float*)sigma_out)[p] = r.sigma;
+            ((float*)len_out)[p] = r.len;
+        }
     c->last_kernel_ms = (omp_get_wtime() - t0) * 1e3;
     return RT_OK;
 }

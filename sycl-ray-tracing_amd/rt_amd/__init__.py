@@ -25,14 +25,14 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _capi
-from ._capi import DenoiseParams, DenoiseVarParams, DisplayParams, NoiseStats  # noqa: F401
+from ._capi import DenoiseParams, DenoiseVarParams, DisplayParams, NoiseStats, TemporalParams  # noqa: F401
 from ._capi import (RT_ERR_ARG, RT_ERR_HIP, RT_ERR_IO, RT_ERR_NODEV, RT_ERR_STATE, RT_OK,  # noqa: F401
                     RtError, check, lib, ptr)
 
 __all__ = ["Camera", "Image", "ParsedOBJ", "parse_obj", "compute_env_map_cdf", "luminance_of_pixels", "BVH",
            "RenderKernel", "RtError", "octree_dump", "make_materials", "read_image_float", "write_image_png",
            "image_to_rgba8", "DenoiseParams", "denoise_default_params", "DisplayParams", "write_image_hdr", "DenoiseVarParams",
-           "denoise_var_default_params"]
+           "denoise_var_default_params", "TemporalParams", "temporal_default_params", "TemporalHistory"]
 
 
 # ------------------------------------------------------------------ camera
@@ -176,6 +176,62 @@ def _denoise_var_params(L_, params) -> DenoiseVarParams:
             raise TypeError(f"unknown denoise_var parameter {k}")
         setattr(p, k, v)
     return p
+
+
+def temporal_default_params(hostsim: bool = False) -> TemporalParams:
+    """rt_temporal_default_params: temporal accumulation's defaults."""
+    p = TemporalParams()
+    lib(hostsim).rt_temporal_default_params(ctypes.byref(p))
+    return p
+
+
+def _temporal_params(L_, params) -> TemporalParams:
+    """params: None (defaults), a TemporalParams, or a dict of its fields over the defaults."""
+    if isinstance(params, TemporalParams):
+        return params
+    p = TemporalParams()
+    L_.rt_temporal_default_params(ctypes.byref(p))
+    for k, v in (params or {}).items():
+        if k not in dict(TemporalParams._fields_):
+            raise TypeError(f"unknown temporal parameter {k}")
+        setattr(p, k, v)
+    return p
+
+
+class TemporalHistory:
+    """The state temporal accumulation carries from frame to frame: the accumulated colour, its standard
+    deviation, the history length, the previous frame's normal_depth and the previous camera.
+
+    push(kernel, linear, sigma) renders the features under the kernel's current camera, calls
+    RenderKernel.temporal_accumulate against what the last push kept (nothing on the first) and keeps the
+    result; it returns (rgba Image, sigma, length), which rt_denoise_var takes as its image and sigma.
+
+    Seeding across frames. A render seeds pixel (x, y) with 31 + x * y * N, N the declared sample total, so
+    two frames with the same total draw the same random numbers and their noise is correlated: accumulating
+    them averages nothing. Declare a different total per frame and stop early instead. Frame k:
+        kernel.set_camera(camera_k)
+        kernel.progress_begin(N0 + k); kernel.progress_track_noise()
+        kernel.progress_advance(s // 2); kernel.progress_advance(s // 2)
+        linear = kernel.progress_resolve_linear(Image(w, h)); sigma = kernel.progress_noise_sigma()
+        rgba, sigma_acc, length = history.push(kernel, linear, sigma)
+    and never finish the progression: a preview of the first s samples of the (N0 + k)-sample chain is a
+    supported state. Pixels with x * y == 0 (the first row and column) keep seed 31 in every frame."""
+
+    def __init__(self, params=None):
+        self.params = params
+        self.rgba = self.sigma = self.length = self.normal_depth = self.camera = None
+
+    def reset(self):
+        self.rgba = self.sigma = self.length = self.normal_depth = self.camera = None
+
+    def push(self, kernel: "RenderKernel", linear: Image, sigma):
+        _, nd = kernel.features()
+        hist = None if self.rgba is None else (self.rgba, self.sigma, self.length, self.normal_depth)
+        cam = kernel.camera if self.camera is None else self.camera
+        out, s_out, l_out = kernel.temporal_accumulate(linear, sigma, nd, cam, hist, self.params)
+        self.rgba, self.sigma, self.length, self.normal_depth = out, s_out, l_out, nd
+        self.camera = Camera(kernel.camera.view_matrix.copy(), kernel.camera.fov_dist)
+        return out, s_out, l_out
 
 
 # --------------------------------------------------------------------- OBJ
@@ -603,6 +659,47 @@ class RenderKernel:
                                                    vp(d_sigma), vp(d_albedo), vp(d_normal_depth), ctypes.byref(p),
                                                    float(blend_factor), vp(d_out), vp(d_sigma_out), vp(stream)), self.ctx,
               "rt_denoise_var_device")
+
+    # ---- temporal accumulation (rt_temporal_accumulate; include/rt_hip.h)
+    def temporal_accumulate(self, image: Image, sigma, normal_depth, prev_camera: Camera, history=None, params=None):
+        """rt_temporal_accumulate: the history reprojected from prev_camera into the kernel's current camera
+        and blended with this frame. image: a linear frame (progress_resolve_linear); sigma: [h, w] float32,
+        its standard deviation (progress_noise_sigma); normal_depth: features()[1] under the current camera;
+        history: None (the first frame) or (rgba, sigma, length, normal_depth), the previous call's result
+        and the previous frame's normal_depth. params: None, a TemporalParams or a dict of its fields.
+        Returns (rgba Image, sigma [h, w], length [h, w])."""
+        src = np.ascontiguousarray(image.pixels, dtype=np.float32)
+        h, w = src.shape[:2]
+        sig = np.ascontiguousarray(sigma, dtype=np.float32)
+        nd = np.ascontiguousarray(normal_depth, dtype=np.float32)
+        assert sig.shape == (h, w) and nd.shape == (h, w, 4), "sigma is one float per pixel, normal_depth four"
+        hist = [None] * 4
+        if history is not None:
+            shapes = ((h, w, 4), (h, w), (h, w), (h, w, 4))
+            hist = [np.ascontiguousarray(getattr(a, "pixels", a), dtype=np.float32).reshape(s)
+                    for a, s in zip(history, shapes)]
+        out, s_out, l_out = Image(w, h), np.empty((h, w), np.float32), np.empty((h, w), np.float32)
+        p = _temporal_params(self.L, params)
+        check(self.L, self.L.rt_temporal_accumulate(self.ctx, w, h, ptr(src), ptr(sig), ptr(nd), ptr(prev_camera.view_matrix),
+                                                    prev_camera.fov_dist, *(ptr(a) for a in hist), ctypes.byref(p),
+                                                    ptr(out.pixels), ptr(s_out), ptr(l_out)), self.ctx,
+              "rt_temporal_accumulate")
+        return out, s_out, l_out
+
+    def temporal_accumulate_device(self, d_in: int, d_sigma: int, d_normal_depth: int, prev_camera: Camera, d_out: int,
+                                   d_sigma_out: int, d_len_out: int, d_history=None, params=None,
+                                   stream: int | None = None, width=None, height=None):
+        """rt_temporal_accumulate_device: device buffers (w*h*4 floats for the float4 buffers, w*h floats for the
+        others), d_history None or (d_rgba, d_sigma, d_len, d_normal_depth); no wait."""
+        p = _temporal_params(self.L, params)
+        vp = lambda a: ctypes.c_void_p(a) if a else None  # noqa: E731
+        hist = d_history if d_history is not None else (None,) * 4
+        check(self.L, self.L.rt_temporal_accumulate_device(self.ctx, int(width or self.width), int(height or self.height),
+                                                           vp(d_in), vp(d_sigma), vp(d_normal_depth),
+                                                           ptr(prev_camera.view_matrix), prev_camera.fov_dist,
+                                                           *(vp(a) for a in hist), ctypes.byref(p), vp(d_out),
+                                                           vp(d_sigma_out), vp(d_len_out), vp(stream)), self.ctx,
+              "rt_temporal_accumulate_device")
 
     def render_variants(self, materials, frames=None, device_ptrs=None, row_offset: int = 0, row_stride: int = 1):
         """rt_render_variants: the material sweep as replicas. `materials` is

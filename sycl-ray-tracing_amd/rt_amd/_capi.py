@@ -37,6 +37,7 @@ EXPORTS = [
     "rt_progress_advance_adaptive", "rt_progress_tile_counts",
     "rt_progress_noise_sigma", "rt_progress_noise_sigma_device", "rt_denoise_var_default_params", "rt_denoise_var",
     "rt_denoise_var_device",
+    "rt_temporal_default_params", "rt_temporal_accumulate", "rt_temporal_accumulate_device",
 ]
 
 # return codes (include/rt_hip.h)
@@ -58,6 +59,11 @@ class DenoiseVarParams(ctypes.Structure):
     """struct rt_denoise_var_params (include/rt_hip.h)."""
     _fields_ = [("passes", ctypes.c_int), ("sigma_color", F), ("sigma_normal", F), ("sigma_albedo", F),
                 ("sigma_depth", F), ("var_floor", F)]
+
+
+class TemporalParams(ctypes.Structure):
+    """struct rt_temporal_params (include/rt_hip.h)."""
+    _fields_ = [("depth_tol", F), ("normal_cos", F), ("min_weight", F), ("max_len", F)]
 
 
 class DisplayParams(ctypes.Structure):
@@ -149,6 +155,9 @@ _SIGS = {
     "rt_denoise_var_default_params": (None, [ctypes.POINTER(DenoiseVarParams)]),
     "rt_denoise_var": (I, [P, I, I, P, P, P, P, ctypes.POINTER(DenoiseVarParams), F, P, P]),
     "rt_denoise_var_device": (I, [P, I, I, P, P, P, P, ctypes.POINTER(DenoiseVarParams), F, P, P, P]),
+    "rt_temporal_default_params": (None, [ctypes.POINTER(TemporalParams)]),
+    "rt_temporal_accumulate": (I, [P, I, I, P, P, P, P, F, P, P, P, P, ctypes.POINTER(TemporalParams), P, P, P]),
+    "rt_temporal_accumulate_device": (I, [P, I, I, P, P, P, P, F, P, P, P, P, ctypes.POINTER(TemporalParams), P, P, P, P]),
     # product-only extras
     "rt_device_libm": (I, [I, I, P, P, P, I]),
     "rt_device_libm_digest": (I, [I, I, ctypes.c_uint32, I, P]),
