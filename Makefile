@@ -48,7 +48,8 @@ $(OBJ)/rt_hostsim.o: $(SRC)/rt_hostsim.cpp $(HDRS) $(ALL_SRC)
 #   rt_adapt     an adaptive progression's selection, gather / scatter and resolves
 #   rt_dnv       the variance-guided filter and the absolute noise figure it takes
 #   rt_temporal  temporal accumulation: the previous frame reprojected into the new camera and blended in
-HIP_UNITS := rt_render rt_wave_run rt_probe rt_denoise rt_query rt_display rt_noise rt_adapt rt_dnv rt_temporal
+#   rt_firefly   firefly rejection: a pixel's luminance limited by a rank of its neighbours'
+HIP_UNITS := rt_render rt_wave_run rt_probe rt_denoise rt_query rt_display rt_noise rt_adapt rt_dnv rt_temporal rt_firefly
 $(HIP_UNITS:%=$(OBJ)/%.o): $(OBJ)/%.o: $(SRC)/%.hip $(HDRS)
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
@@ -157,6 +158,8 @@ hostsim-variant: $(OBJ)/rt_imageio.host.o
 #                       (make sanitize-adaptive: the same program under ASan + UBSan over the hostsim sources)
 #   dnv_shim_test       denoise_var / progress_noise_sigma against the C ABI     tests/test_dnv_shim.py
 #   temporal_shim_test  temporal_accumulate against the C ABI                     tests/test_temporal_shim.py
+#   firefly_shim_test   firefly_clamp against the C ABI                           tests/test_firefly_shim.py
+#                       (make sanitize-firefly: the same program under ASan + UBSan over the hostsim sources)
 REFDIR ?= /root/reference
 REFOBJ := oracle/_ref/objO2
 REFOBJS := $(REFOBJ)/bvh.o $(REFOBJ)/flattened_bvh.o $(REFOBJ)/triangle.o $(REFOBJ)/vec.o $(REFOBJ)/color.o \
@@ -206,3 +209,10 @@ build/san_asan/adaptive_shim_test: tests/native/adaptive_shim_test.cpp include/r
 	  $(filter-out build/san_asan/cpu_oracle.o,$(wildcard build/san_asan/*.o)) $(REFOBJS) -Wl,--gc-sections -o $@
 sanitize-adaptive: build/san_asan/adaptive_shim_test
 .PHONY: sanitize-adaptive
+
+# firefly_clamp and the firefly C calls under ASan + UBSan, in the same way.
+build/san_asan/firefly_shim_test: tests/native/firefly_shim_test.cpp include/render_kernel_hip.h build/san_asan/driver
+	$(CXX) -std=gnu++20 $(SAN_NUM) $(ASAN) -Iinclude -I$(REFDIR)/include -I$(REFDIR)/rapidobj -I$(REFDIR) $< \
+	  $(filter-out build/san_asan/cpu_oracle.o,$(wildcard build/san_asan/*.o)) $(REFOBJS) -Wl,--gc-sections -o $@
+sanitize-firefly: build/san_asan/firefly_shim_test
+.PHONY: sanitize-firefly

@@ -304,6 +304,29 @@ public:
         return out;
     }
 
+    // Firefly rejection (rt_firefly): every pixel of `image` (a linear frame) whose luminance is above
+    // gain * M + floor, M the rank-th largest luminance among its neighbours, scaled down to that limit.
+    // sigma: the frame's per-pixel standard deviation (progress_noise_sigma()), scaled with the colour
+    // into *sigma_out, or empty for none (sigma_out must then be null). scale_out, when given, receives
+    // the factor per pixel: below 1 where clamped. The result and *sigma_out are what temporal_accumulate
+    // and denoise_var take. It needs no scene state and does not render.
+    Image firefly_clamp(const Image& image, const std::vector<float>& sigma, const rt_firefly_params& params,
+                        std::vector<float>* sigma_out = nullptr, std::vector<float>* scale_out = nullptr) const
+    {
+        std::lock_guard<std::mutex> lk(m_mu);
+        const int w = image.width(), h = image.height();
+        const size_t n = (size_t)w * h;
+        if (!sigma.empty() && sigma.size() != n)
+            throw std::runtime_error("librt_hip: firefly_clamp: sigma is not width * height floats");
+        if (sigma.empty() && sigma_out) throw std::runtime_error("librt_hip: firefly_clamp: sigma_out without a sigma");
+        if (sigma_out) sigma_out->assign(n, 0.0f);
+        if (scale_out) scale_out->assign(n, 0.0f);
+        Image out(w, h);
+        check(rt_firefly(m_ctx, w, h, image.data(), sigma.empty() ? nullptr : sigma.data(), &params, out.data(),
+                         sigma_out ? sigma_out->data() : nullptr, scale_out ? scale_out->data() : nullptr));
+        return out;
+    }
+
     // INTERSECT_SCENE for a batch of rays through rt_query (the render's search-BVH walks, the
     // exact walk behind them): hits[i] as BVH::intersect + the sphere loop fill it (t = -1 and
     // primitive_index = -1 without a hit).

@@ -105,7 +105,8 @@ int rt_test_fail_device(rt_context* ctx, int device);
  * fast_spp x spp on), "near_scale" (the near box, scene box widened by this x its
  * largest extent: queries from outside it take the exact octree walk), "dn_variant"
  * (rt_denoise's and rt_denoise_var's filter kernel: 0 the product's choice per step, 1 direct
- * loads, 2 the LDS-halo tile at every step that has one), "rq_variant" (rt_query's search-BVH kernel:
+ * loads, 2 the LDS-halo tile at every step that has one), "ff_variant" (rt_firefly's kernel: 0 the
+ * product's choice, 1 direct loads, 2 the LDS tile of luminances), "rq_variant" (rt_query's search-BVH kernel:
  * 0 the product's choice, 1 plain rounds of one query per quad, 2 per-quad refill),
  * "chain_full" (1: the scene view reports an unmonotone tree, so the leaf verification
  * walks the whole ancestor chain instead of one slab test), the
@@ -630,6 +631,47 @@ int rt_temporal_accumulate_device(rt_context* ctx, int w, int h, const void* d_r
                                   const void* d_hist_rgba, const void* d_hist_sigma, const void* d_hist_len,
                                   const void* d_hist_normal_depth, const rt_temporal_params* params, void* d_rgba_out,
                                   void* d_sigma_out, void* d_len_out, void* stream);
+
+/* ---------------------------------------------- firefly rejection
+ * A linear frame of few samples carries its error in a few very bright pixels. This stage limits
+ * a pixel's luminance to a multiple of a high rank of its neighbours' luminances and scales the
+ * colour and the noise figure together; it goes between the linear resolve (with its
+ * rt_progress_noise_sigma) and rt_temporal_accumulate / rt_denoise_var. Stateless, no scene or
+ * camera needed. Float32 throughout, no contraction, IEEE division; no expf, no square root.
+ *
+ * rt_firefly / _device: rgba_in (float4[h][w]) and sigma_in (float[h][w], or NULL) in; rgba_out
+ *   (float4[h][w], required), sigma_out (float[h][w], NULL allowed; needs a sigma_in) and
+ *   scale_out (float[h][w], NULL allowed) out. For pixel p, c = rgba_in[p], s = sigma_in[p]:
+ *   1 L(c) = (0.2126f * c.r + 0.7152f * c.g) + 0.0722f * c.b.
+ *   2 The neighbours are the (2 radius + 1)^2 - 1 pixels around p. One outside the image, or whose
+ *     rgb is not all finite, is dropped. Every neighbour is read from rgba_in.
+ *   3 M = the rank-th largest L over the neighbours kept, each L taken as at least -FLT_MAX. With
+ *     fewer than `rank` neighbours kept the pixel is untouched.
+ *   4 limit = gain * M + floor.
+ *   5 When c.rgb is all finite, limit > 0 and L(c) > limit: f = limit / L(c), rgba_out = {f c.rgb,
+ *     c.a}, sigma_out = f s (a NaN or infinite s is copied instead), scale_out = f, which lies in
+ *     (0, 1) (0 only where the division underflows). Otherwise rgba_out = c and sigma_out = s bit
+ *     for bit and scale_out = 1: a centre that is not finite (rt_denoise_var's rule for it), a
+ *     limit that is zero, negative or a NaN, a centre luminance that is negative or not above it.
+ *   gain = +inf is the identity. The caller counts the clamped pixels as scale_out < 1.
+ *   RT_ERR_ARG for a NULL ctx, rgba_in or rgba_out; sigma_out without sigma_in; w or h below 1;
+ *   radius outside {1, 2}; rank outside 1..8; a NaN or negative gain; a NaN floor; an output whose
+ *   bytes overlap an input's or another output's; more than 262140 rows or 2^27 - 1 pixels
+ *   (rt_denoise's limits). The device form takes device pointers (the float4 buffers 16-byte
+ *   aligned, the float buffers 4-byte aligned: RT_ERR_ARG otherwise) and a stream (NULL: default)
+ *   and returns without waiting. params NULL: the defaults (rt_firefly_default_params). Runs on
+ *   the root device of a multi-device context; rt_last_kernel_ms as for rt_denoise. */
+typedef struct rt_firefly_params {
+    int radius;   /* neighbourhood half-width, 1 (3x3) or 2 (5x5)                            default 1 */
+    int rank;     /* M is the rank-th largest neighbour luminance, 1..8                      default 2 */
+    float gain;   /* limit = gain * M + floor; >= 0, +inf: the identity                      default 2 */
+    float floor;  /* added to the limit: the luminance below which nothing is ever clamped   default 0 */
+} rt_firefly_params;
+void rt_firefly_default_params(rt_firefly_params* params);
+int rt_firefly(rt_context* ctx, int w, int h, const float* rgba_in, const float* sigma_in, const rt_firefly_params* params,
+               float* rgba_out, float* sigma_out, float* scale_out);
+int rt_firefly_device(rt_context* ctx, int w, int h, const void* d_rgba_in, const void* d_sigma_in,
+                      const rt_firefly_params* params, void* d_rgba_out, void* d_sigma_out, void* d_scale_out, void* stream);
 
 /* Counters of the last render when enabled (RT_STAT_* order, rt_device.h);
  * with n up to 2 * RT_STAT_COUNT the second block is the share of the

@@ -13,6 +13,7 @@
 #include "rt_denoise.h"
 #include "rt_noise.h"
 #include "rt_temporal.h"
+#include "rt_firefly.h"
 
 namespace {
 std::mutex g_err_mu;
@@ -253,6 +254,7 @@ int rt_test_schedule(rt_context* c, const char* key, double value)
     else if (k == "fast_spp") s.fast_spp = value;
     else if (k == "near_scale") s.near_scale = value;
     else if (k == "dn_variant") s.dn_variant = std::max(0, std::min(2, v));
+    else if (k == "ff_variant") s.ff_variant = std::max(0, std::min(2, v));
     else if (k == "rq_variant") s.rq_variant = std::max(0, std::min(2, v));
     else if (k == "chain_full") {
         // the devices' views carry the flag: the next call uploads them again
@@ -871,6 +873,73 @@ int rt_temporal_accumulate_device(rt_context* c, int w, int h, const void* in, c
                                hist_sigma, hist_len, hist_nd, params, out, sigma_out, len_out, true, T))
         return r;
     return rt_backend_temporal(c, T, out, sigma_out, len_out, true, stream);
+}
+
+// ---- firefly rejection (rt_firefly.h)
+// Defaults from the sweep on Cornell 64x64, a 4-sample frame against 256 spp.
+void rt_firefly_default_params(rt_firefly_params* p)
+{
+    if (!p) return;
+    p->radius = 1;
+    p->rank = 2;
+    p->gain = 2.0f;
+    p->floor = 0.0f;
+}
+
+static int firefly_ready(rt_context* c, const char* fn, int w, int h, const void* in, const void* sigma,
+                         const rt_firefly_params* params, const void* out, const void* sigma_out, const void* scale_out,
+                         bool device, rtk::FireflyArgs& A)
+{
+    const std::string f = fn;
+    if (!c) return rt_fail(nullptr, RT_ERR_ARG, f + ": ctx is NULL");
+    if (w <= 0 || h <= 0) return rt_fail(c, RT_ERR_ARG, f + ": w and h must be at least 1");
+    if (!in || !out) return rt_fail(c, RT_ERR_ARG, f + ": rgba_in or rgba_out is NULL");
+    if (sigma_out && !sigma) return rt_fail(c, RT_ERR_ARG, f + ": sigma_out without a sigma_in");
+    // (rt_denoise's frame-size limits: the kernels tile the frame 4 rows per block as its kernels do)
+    if ((double)w * (double)h > 134217727.0) return rt_fail(c, RT_ERR_ARG, f + ": too many pixels");
+    if (h > 4 * 65535) return rt_fail(c, RT_ERR_ARG, f + ": height above 262140 rows");
+    rt_firefly_params p;
+    if (params) p = *params;
+    else rt_firefly_default_params(&p);
+    if (p.radius < 1 || p.radius > 2) return rt_fail(c, RT_ERR_ARG, f + ": radius must be 1 or 2");
+    if (p.rank < 1 || p.rank > rtk::FF_MAX_RANK) return rt_fail(c, RT_ERR_ARG, f + ": rank must be 1..8");
+    if (!(p.gain >= 0.0f)) return rt_fail(c, RT_ERR_ARG, f + ": gain is negative or a NaN");
+    if (p.floor != p.floor) return rt_fail(c, RT_ERR_ARG, f + ": floor is a NaN");
+    const size_t n = (size_t)w * h;
+    const struct {
+        const void* p;
+        size_t bytes;
+    } ins[2] = {{in, 16 * n}, {sigma, 4 * n}}, outs[3] = {{out, 16 * n}, {sigma_out, 4 * n}, {scale_out, 4 * n}};
+    for (int o = 0; o < 3; o++) {
+        if (!outs[o].p) continue;
+        for (int i = 0; i < 2; i++)
+            if (ins[i].p && ranges_overlap(outs[o].p, outs[o].bytes, ins[i].p, ins[i].bytes))
+                return rt_fail(c, RT_ERR_ARG, f + ": an output overlaps an input");
+        for (int k = o + 1; k < 3; k++)
+            if (outs[k].p && ranges_overlap(outs[o].p, outs[o].bytes, outs[k].p, outs[k].bytes))
+                return rt_fail(c, RT_ERR_ARG, f + ": two outputs overlap");
+    }
+    if (device && ((uintptr_t)in % 16 != 0 || (uintptr_t)out % 16 != 0 || (uintptr_t)sigma % 4 != 0 ||
+                   (uintptr_t)sigma_out % 4 != 0 || (uintptr_t)scale_out % 4 != 0))
+        return rt_fail(c, RT_ERR_ARG, f + ": the float4 buffers must be 16-byte aligned, the float buffers 4-byte aligned");
+    A = rtk::FireflyArgs{w, h, p.radius, p.rank, p.gain, p.floor, (const float4_*)in, (const float*)sigma};
+    return RT_OK;
+}
+
+int rt_firefly(rt_context* c, int w, int h, const float* in, const float* sigma, const rt_firefly_params* params, float* out,
+               float* sigma_out, float* scale_out)
+{
+    rtk::FireflyArgs A;
+    if (int r = firefly_ready(c, "rt_firefly", w, h, in, sigma, params, out, sigma_out, scale_out, false, A)) return r;
+    return rt_backend_firefly(c, A, out, sigma_out, scale_out, false, nullptr);
+}
+
+int rt_firefly_device(rt_context* c, int w, int h, const void* in, const void* sigma, const rt_firefly_params* params,
+                      void* out, void* sigma_out, void* scale_out, void* stream)
+{
+    rtk::FireflyArgs A;
+    if (int r = firefly_ready(c, "rt_firefly_device", w, h, in, sigma, params, out, sigma_out, scale_out, true, A)) return r;
+    return rt_backend_firefly(c, A, out, sigma_out, scale_out, true, stream);
 }
 
 // ---------------------------------------------------------- display stage

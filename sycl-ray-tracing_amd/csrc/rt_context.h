@@ -35,6 +35,7 @@ struct RtSchedule {
     double near_scale = -1.0;  // near box: the scene's box widened by this x its largest extent (rt_view_near;
                                // study probes only: answers never depend on it, only which walk gives them)
     int dn_variant = 0;        // rt_denoise's filter kernel: 0 per step as measured, 1 direct, 2 LDS tile where built
+    int ff_variant = 0;        // rt_firefly's kernel: 0 as measured, 1 direct loads, 2 the LDS tile of luminances
     int rq_variant = 0;        // rt_query's fast kernel: 0 as measured, 1 plain grid-stride rounds, 2 per-quad refill
     bool chain_full = false;   // the scene view reports chain_monotone = 0: chain_ok / quad_chain_ok run their full
                                // ancestor-chain loop (rt_fast.h), which no tree the host builds reaches otherwise
@@ -163,6 +164,14 @@ struct TemporalFrame;
 }
 int rt_backend_temporal(rt_context* ctx, rtk::TemporalFrame T, void* rgba_out, void* sigma_out, void* len_out, bool device,
                         void* stream);
+// Firefly rejection (rt_firefly.h), on the root device like the post stage: A holds the validated parameters,
+// the frame (w*h float4) and its sigma (w*h floats, or null); rgba_out (w*h float4) is required, sigma_out
+// (null when A.sigma is) and scale_out (w*h floats each) may be null.
+namespace rtk {
+struct FireflyArgs;
+}
+int rt_backend_firefly(rt_context* ctx, rtk::FireflyArgs A, void* rgba_out, void* sigma_out, void* scale_out, bool device,
+                       void* stream);
 // The display stage (rt_display.h), on the root device like the post stage: in (w*h float4) ->
 // out (w*h float4, may be `in`, or null) and out8 (w*h RGBA bytes, rows reversed when flip, or
 // null). The arguments are validated and inv_gamma = 1.0f / gamma (rt_capi_host.cpp).

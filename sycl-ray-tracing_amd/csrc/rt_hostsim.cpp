@@ -22,6 +22,7 @@
 #include "rt_noise.h"
 #include "rt_query.h"
 #include "rt_temporal.h"
+#include "rt_firefly.h"
 #include "rt_wave.h"
 
 // Stack window and step budget of the host build: smaller than the
@@ -789,6 +790,32 @@ int rt_backend_temporal(rt_context* c, rtk::TemporalFrame T, void* rgba_out, voi
             ((float*)sigma_out)[p] = r.sigma;
             ((float*)len_out)[p] = r.len;
         }
+    c->last_kernel_ms = (omp_get_wtime() - t0) * 1e3;
+    return RT_OK;
+}
+
+// Firefly rejection on the host: the loop around rt_firefly.h's firefly_pixel that the kernels of
+// rt_firefly.hip run one thread per pixel, the neighbours read straight from the frame (FfDirect).
+template <int R>
+static void firefly_rows(const rtk::FireflyArgs& A, float4_* rgba_out, float* sigma_out, float* scale_out)
+{
+    const rtk::FfDirect F{A};
+#pragma omp parallel for schedule(static)
+    for (int y = 0; y < A.h; y++)
+        for (int x = 0; x < A.w; x++) {
+            const size_t p = (size_t)y * A.w + x;
+            const rtk::FireflyOut r = rtk::firefly_pixel<R>(A, x, y, A.in[p], A.sigma ? A.sigma[p] : 0.0f, F);
+            rgba_out[p] = r.rgba;
+            if (sigma_out) sigma_out[p] = r.sigma;
+            if (scale_out) scale_out[p] = r.scale;
+        }
+}
+
+int rt_backend_firefly(rt_context* c, rtk::FireflyArgs A, void* rgba_out, void* sigma_out, void* scale_out, bool, void*)
+{
+    const double t0 = omp_get_wtime();
+    if (A.radius == 1) firefly_rows<1>(A, (float4_*)rgba_out, (float*)sigma_out, (float*)scale_out);
+    else firefly_rows<2>(A, (float4_*)rgba_out, (float*)sigma_out, (float*)scale_out);
     c->last_kernel_ms = (omp_get_wtime() - t0) * 1e3;
     return RT_OK;
 }

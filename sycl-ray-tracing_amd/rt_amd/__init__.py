@@ -25,14 +25,16 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _capi
-from ._capi import DenoiseParams, DenoiseVarParams, DisplayParams, NoiseStats, TemporalParams  # noqa: F401
+from ._capi import (DenoiseParams, DenoiseVarParams, DisplayParams, FireflyParams, NoiseStats,  # noqa: F401
+                    TemporalParams)
 from ._capi import (RT_ERR_ARG, RT_ERR_HIP, RT_ERR_IO, RT_ERR_NODEV, RT_ERR_STATE, RT_OK,  # noqa: F401
                     RtError, check, lib, ptr)
 
 __all__ = ["Camera", "Image", "ParsedOBJ", "parse_obj", "compute_env_map_cdf", "luminance_of_pixels", "BVH",
            "RenderKernel", "RtError", "octree_dump", "make_materials", "read_image_float", "write_image_png",
            "image_to_rgba8", "DenoiseParams", "denoise_default_params", "DisplayParams", "write_image_hdr", "DenoiseVarParams",
-           "denoise_var_default_params", "TemporalParams", "temporal_default_params", "TemporalHistory"]
+           "denoise_var_default_params", "TemporalParams", "temporal_default_params", "TemporalHistory",
+           "FireflyParams", "firefly_default_params"]
 
 
 # ------------------------------------------------------------------ camera
@@ -198,13 +200,35 @@ def _temporal_params(L_, params) -> TemporalParams:
     return p
 
 
+def firefly_default_params(hostsim: bool = False) -> FireflyParams:
+    """rt_firefly_default_params: the firefly rejection stage's defaults."""
+    p = FireflyParams()
+    lib(hostsim).rt_firefly_default_params(ctypes.byref(p))
+    return p
+
+
+def _firefly_params(L_, params) -> FireflyParams:
+    """params: None (defaults), a FireflyParams, or a dict of its fields over the defaults."""
+    if isinstance(params, FireflyParams):
+        return params
+    p = FireflyParams()
+    L_.rt_firefly_default_params(ctypes.byref(p))
+    for k, v in (params or {}).items():
+        if k not in dict(FireflyParams._fields_):
+            raise TypeError(f"unknown firefly parameter {k}")
+        setattr(p, k, v)
+    return p
+
+
 class TemporalHistory:
     """The state temporal accumulation carries from frame to frame: the accumulated colour, its standard
     deviation, the history length, the previous frame's normal_depth and the previous camera.
 
-    push(kernel, linear, sigma) renders the features under the kernel's current camera, calls
+    push(kernel, linear, sigma, firefly=None) renders the features under the kernel's current camera, calls
     RenderKernel.temporal_accumulate against what the last push kept (nothing on the first) and keeps the
     result; it returns (rgba Image, sigma, length), which rt_denoise_var takes as its image and sigma.
+    firefly: a FireflyParams or a dict of its fields ({}: the defaults) puts RenderKernel.firefly_clamp in front,
+    so that a spike is limited before the history keeps it; None: the frame is accumulated as it is.
 
     Seeding across frames. A render seeds pixel (x, y) with 31 + x * y * N, N the declared sample total, so
     two frames with the same total draw the same random numbers and their noise is correlated: accumulating
@@ -224,7 +248,9 @@ class TemporalHistory:
     def reset(self):
         self.rgba = self.sigma = self.length = self.normal_depth = self.camera = None
 
-    def push(self, kernel: "RenderKernel", linear: Image, sigma):
+    def push(self, kernel: "RenderKernel", linear: Image, sigma, firefly=None):
+        if firefly is not None:
+            linear, sigma = kernel.firefly_clamp(linear, sigma, firefly)
         _, nd = kernel.features()
         hist = None if self.rgba is None else (self.rgba, self.sigma, self.length, self.normal_depth)
         cam = kernel.camera if self.camera is None else self.camera
@@ -700,6 +726,36 @@ class RenderKernel:
                                                            *(vp(a) for a in hist), ctypes.byref(p), vp(d_out),
                                                            vp(d_sigma_out), vp(d_len_out), vp(stream)), self.ctx,
               "rt_temporal_accumulate_device")
+
+    # ---- firefly rejection (rt_firefly; include/rt_hip.h)
+    def firefly_clamp(self, image: Image, sigma=None, params=None, return_scale: bool = False):
+        """rt_firefly: every pixel of a linear frame whose luminance is above gain * M + floor, M the rank-th
+        largest luminance among its neighbours, scaled down to that limit, and its sigma ([h, w] float32, or None)
+        with it. params: None, a FireflyParams or a dict of its fields. Returns (Image, sigma_out), sigma_out None
+        without a sigma; return_scale: (Image, sigma_out, scale), scale [h, w] float32, below 1 where clamped."""
+        src = np.ascontiguousarray(image.pixels, dtype=np.float32)
+        h, w = src.shape[:2]
+        sig = s_out = None
+        if sigma is not None:
+            sig = np.ascontiguousarray(sigma, dtype=np.float32)
+            assert sig.shape == (h, w), "sigma is one float per pixel of the image"
+            s_out = np.empty((h, w), np.float32)
+        out = Image(w, h)
+        scale = np.empty((h, w), np.float32) if return_scale else None
+        p = _firefly_params(self.L, params)
+        check(self.L, self.L.rt_firefly(self.ctx, w, h, ptr(src), ptr(sig), ctypes.byref(p), ptr(out.pixels), ptr(s_out),
+                                        ptr(scale)), self.ctx, "rt_firefly")
+        return (out, s_out, scale) if return_scale else (out, s_out)
+
+    def firefly_clamp_device(self, d_in: int, d_out: int, d_sigma: int | None = None, d_sigma_out: int | None = None,
+                             d_scale_out: int | None = None, params=None, stream: int | None = None, width=None,
+                             height=None):
+        """rt_firefly_device: device buffers (w*h*4 floats for the frames, w*h floats for the others), no wait."""
+        p = _firefly_params(self.L, params)
+        vp = lambda a: ctypes.c_void_p(a) if a else None  # noqa: E731
+        check(self.L, self.L.rt_firefly_device(self.ctx, int(width or self.width), int(height or self.height), vp(d_in),
+                                               vp(d_sigma), ctypes.byref(p), vp(d_out), vp(d_sigma_out), vp(d_scale_out),
+                                               vp(stream)), self.ctx, "rt_firefly_device")
 
     def render_variants(self, materials, frames=None, device_ptrs=None, row_offset: int = 0, row_stride: int = 1):
         """rt_render_variants: the material sweep as replicas. `materials` is

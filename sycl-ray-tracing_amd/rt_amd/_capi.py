@@ -38,6 +38,7 @@ EXPORTS = [
     "rt_progress_noise_sigma", "rt_progress_noise_sigma_device", "rt_denoise_var_default_params", "rt_denoise_var",
     "rt_denoise_var_device",
     "rt_temporal_default_params", "rt_temporal_accumulate", "rt_temporal_accumulate_device",
+    "rt_firefly_default_params", "rt_firefly", "rt_firefly_device",
 ]
 
 # return codes (include/rt_hip.h)
@@ -64,6 +65,11 @@ class DenoiseVarParams(ctypes.Structure):
 class TemporalParams(ctypes.Structure):
     """struct rt_temporal_params (include/rt_hip.h)."""
     _fields_ = [("depth_tol", F), ("normal_cos", F), ("min_weight", F), ("max_len", F)]
+
+
+class FireflyParams(ctypes.Structure):
+    """struct rt_firefly_params (include/rt_hip.h)."""
+    _fields_ = [("radius", I), ("rank", I), ("gain", F), ("floor", F)]
 
 
 class DisplayParams(ctypes.Structure):
@@ -158,6 +164,9 @@ _SIGS = {
     "rt_temporal_default_params": (None, [ctypes.POINTER(TemporalParams)]),
     "rt_temporal_accumulate": (I, [P, I, I, P, P, P, P, F, P, P, P, P, ctypes.POINTER(TemporalParams), P, P, P]),
     "rt_temporal_accumulate_device": (I, [P, I, I, P, P, P, P, F, P, P, P, P, ctypes.POINTER(TemporalParams), P, P, P, P]),
+    "rt_firefly_default_params": (None, [ctypes.POINTER(FireflyParams)]),
+    "rt_firefly": (I, [P, I, I, P, P, ctypes.POINTER(FireflyParams), P, P, P]),
+    "rt_firefly_device": (I, [P, I, I, P, P, ctypes.POINTER(FireflyParams), P, P, P, P]),
     # product-only extras
     "rt_device_libm": (I, [I, I, P, P, P, I]),
     "rt_device_libm_digest": (I, [I, I, ctypes.c_uint32, I, P]),

@@ -38,6 +38,12 @@ resolved linear, filtered with the progression's own per-pixel noise figure (pro
 colour edge-stop's scale, and then displayed; the three denoised PNGs are blends of that image with the
 render instead of the fixed-sigma filter's. It needs a tracked progression of at least two passes.
 --denoise=atrous (the default) is the run without the flag, byte for byte.
+
+Firefly rejection (RenderKernel.firefly_clamp): --firefly or --firefly=GAIN, with --denoise=var only. The linear
+frame and its noise figure pass through rt_firefly (its defaults, or GAIN in the place of the default gain) between
+the resolve and the filter, and the line "firefly: clamped N of M pixels" is printed. RT_output.png and --hdr-out
+stay the unclamped render; the three denoised PNGs come from the clamped frame. Without the flag a run writes the
+bytes it writes today.
 """
 from __future__ import annotations
 
@@ -53,12 +59,16 @@ import rt_amd
 def parse(argv):
     a = dict(obj="data/OBJs/cornell_pbr.obj", sky="data/Skyspheres/evening_road_01_puresky_2k.hdr", w=512, h=512,
              samples=64, bounces=8, camera="dragon", out=".", hostsim=False, preview_every=0, checkpoint="",
-             exposure=None, gamma=None, hdr_out="", noise_threshold=None, adaptive=False, denoise="atrous")
+             exposure=None, gamma=None, hdr_out="", noise_threshold=None, adaptive=False, denoise="atrous", firefly=None)
     for s in argv:
         if s == "--hostsim":
             a["hostsim"] = True
         elif s == "--adaptive":
             a["adaptive"] = True
+        elif s == "--firefly":  # (the stage's default gain)
+            a["firefly"] = {}
+        elif s.startswith("--firefly="):
+            a["firefly"] = {"gain": float(s.split("=", 1)[1])}
         elif s.startswith(("--sky=", "--camera=", "--out=", "--checkpoint=", "--hdr-out=", "--denoise=")):
             k, v = s[2:].split("=", 1)
             a[k.replace("-", "_")] = v
@@ -153,7 +163,12 @@ def render_progressive(rk: rt_amd.RenderKernel, fb: rt_amd.Image, a: dict):
         rk.progress_resolve_linear(fb)
         if a["denoise"] == "var":  # (the sigma of the live progression, then the filter on the linear frame)
             with np.errstate(all="ignore"):
-                filtered = rk.denoise_var(fb, None, 1.0)
+                if a["firefly"] is None:
+                    filtered = rk.denoise_var(fb, None, 1.0)
+                else:  # (the clamp scales the noise figure with the colour: the filter takes both)
+                    clamped, sigma, scale = rk.firefly_clamp(fb, rk.progress_noise_sigma(), a["firefly"], return_scale=True)
+                    print(f"firefly: clamped {int((scale < 1).sum())} of {scale.size} pixels")
+                    filtered = rk.denoise_var(clamped, sigma, 1.0)
     else:
         rk.progress_resolve(fb)
     if a["adaptive"]:  # where the samples went: tile_n / total in grey
@@ -181,6 +196,12 @@ def main(argv=None) -> int:
     if a["denoise"] == "var" and a["noise_threshold"] is None:
         print("--denoise=var needs --noise-threshold=T and --preview-every=K (it filters with the progression's "
               "noise estimate)", file=sys.stderr)
+        return 2
+    if a["firefly"] is not None and a["denoise"] != "var":
+        print("--firefly needs --denoise=var (it clamps the linear frame the variance-guided filter takes)", file=sys.stderr)
+        return 2
+    if a["firefly"] and not a["firefly"]["gain"] >= 0.0:
+        print("--firefly=GAIN takes a gain of at least 0", file=sys.stderr)
         return 2
     print(f"Reading OBJ {a['obj']} ...")
     P = rt_amd.parse_obj(a["obj"])
