@@ -118,6 +118,29 @@ public:
         return out;
     }
 
+    // Exposure metering (rt_meter): the log-luminance histogram of a linear frame of any size, 256
+    // bins of an eighth of an octave and the stat words. It needs no scene state and does not render.
+    rt_meter_hist meter(const Image& linear) const
+    {
+        std::lock_guard<std::mutex> lk(m_mu);
+        rt_meter_hist hist;
+        check(rt_meter(m_ctx, linear.width(), linear.height(), linear.data(), &hist));
+        return hist;
+    }
+
+    // meter(), then rt_meter_solve: the exposure display() should take for this frame. prev: the
+    // last frame's exposure (<= 0: none) and dt the seconds since, for params' tau_up / tau_down
+    // (null: the defaults, which jump to the target). result, when given, receives the whole answer.
+    float auto_exposure(const Image& linear, float prev = 0.0f, float dt = 0.0f, const rt_meter_params* params = nullptr,
+                        rt_meter_result* result = nullptr) const
+    {
+        const rt_meter_hist hist = meter(linear);
+        rt_meter_result r;
+        check(rt_meter_solve(&hist, params, prev, dt, &r));
+        if (result) *result = r;
+        return r.exposure;
+    }
+
     // write_image_hdr (image_io.h:20, image_io.cpp:208-214) through rt_write_hdr: the rgb channels
     // as a Radiance RGBE file. A member, so that it does not collide with the reference's own
     // function when image_io.h is included too.

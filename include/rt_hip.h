@@ -106,7 +106,9 @@ int rt_test_fail_device(rt_context* ctx, int device);
  * largest extent: queries from outside it take the exact octree walk), "dn_variant"
  * (rt_denoise's and rt_denoise_var's filter kernel: 0 the product's choice per step, 1 direct
  * loads, 2 the LDS-halo tile at every step that has one), "ff_variant" (rt_firefly's kernel: 0 the
- * product's choice, 1 direct loads, 2 the LDS tile of luminances), "rq_variant" (rt_query's search-BVH kernel:
+ * product's choice, 1 direct loads, 2 the LDS tile of luminances), "mt_variant" (rt_meter's kernel: 0 the
+ * product's choice, 1 global atomics per pixel, 2 per-wave bins in LDS), "mt_blocks" (rt_meter's grid: 0 the
+ * product's cap, n > 0 that many blocks, at most 65536), "rq_variant" (rt_query's search-BVH kernel:
  * 0 the product's choice, 1 plain rounds of one query per quad, 2 per-quad refill),
  * "chain_full" (1: the scene view reports an unmonotone tree, so the leaf verification
  * walks the whole ancestor chain instead of one slab test), the
@@ -672,6 +674,76 @@ int rt_firefly(rt_context* ctx, int w, int h, const float* rgba_in, const float*
                float* rgba_out, float* sigma_out, float* scale_out);
 int rt_firefly_device(rt_context* ctx, int w, int h, const void* d_rgba_in, const void* d_sigma_in,
                       const rt_firefly_params* params, void* d_rgba_out, void* d_sigma_out, void* d_scale_out, void* stream);
+
+/* ---------------------------------------------- exposure metering
+ * What exposure rt_display should take for a linear frame: a log-luminance histogram of the frame
+ * (a gfx950 kernel, integer counts: the same words as the CPU build in any execution order) and a
+ * host-only solve that turns the histogram into the exposure of rt_display's curve 1 - exp(-x e).
+ * It goes behind the last stage that changes the linear frame and in front of rt_display.
+ *
+ * rt_meter / _device: every pixel of a w x h float4 linear frame is classified; alpha is ignored.
+ *   1 L = (0.2126f * r + 0.7152f * g) + 0.0722f * b (rt_firefly's luminance, no contraction).
+ *   2 r, g, b or L not finite: nonfinite. Else L <= 0 (-0 too): nonpositive. Neither is binned.
+ *   3 Else k = bits(L) >> 20 (exponent and top 3 mantissa bits), bin = clamp(k - 856, 0, 255):
+ *     256 bins, eight per octave, over [2^-20, 2^12); bin b starts at asfloat((b + 856) << 20).
+ *     k < 856 (denormals too) counts `under` and lands in bin 0; k > 1111 counts `over` and lands
+ *     in bin 255. `counted` goes up; bits(L) is folded into max_bits and min_bits (0 and
+ *     0xFFFFFFFF when nothing was counted). No libm call.
+ *   The bins sum to counted, and counted + nonpositive + nonfinite = w h. No scene has to be bound.
+ *   RT_ERR_ARG: a NULL ctx, frame or histogram, non-positive sizes, more than 2^27 - 1 pixels
+ *   (rt_display's limit: no word can overflow). The device form takes device pointers (d_linear
+ *   16-byte aligned, d_hist 4-byte aligned with room for 264 words: RT_ERR_ARG otherwise) and a
+ *   stream (NULL: default), clears d_hist on that stream itself and returns without waiting; the
+ *   host form takes any alignment. The input is not written. Runs on the root device of a
+ *   multi-device context and restores the caller's current device; rt_last_kernel_ms as for
+ *   rt_display.
+ * rt_meter_solve (host only, no context, double arithmetic): n = counted, lo = floor(low n),
+ *   hi = floor((1 - high) n); with lo + hi >= n nothing is trimmed.
+ *   1 lo samples are removed from the lowest bins upward and hi from the highest downward: c'_b,
+ *     N' = sum c'_b.
+ *   2 Bin b stands for the log2 luminance (2 b - 319) / 16, its middle. S = sum c'_b (2 b - 319),
+ *     an exact integer; log2_mean = S / (16 N'), L_m = exp2(log2_mean).
+ *   3 target = clamp(-log1p(-key) / L_m, min_exposure, max_exposure): the exposure at which L_m
+ *     displays as `key` before the gamma.
+ *   4 tau = tau_up if target > prev_exposure, else tau_down. With prev_exposure > 0, tau > 0 and
+ *     dt_seconds >= 0: log2 e = log2 prev + (log2 target - log2 prev) (1 - exp(-dt / tau)).
+ *     Otherwise e = target.
+ *   5 N' = 0: exposure = target = prev_exposure when that is > 0, else 1.5; log2_mean = 0, valid = 0.
+ *   params NULL: the defaults. RT_ERR_ARG: a NULL histogram or result; low or high outside [0, 1]
+ *   or low > high; key outside (0, 1); bounds that are not finite, not positive or inverted; a
+ *   negative or NaN tau_up or tau_down. The message is rt_last_error(NULL)'s. */
+typedef struct rt_meter_hist {
+    unsigned int bins[256];
+    unsigned int counted;      /* pixels binned: finite, luminance > 0 */
+    unsigned int under;        /* of those, below 2^-20 (in bin 0) */
+    unsigned int over;         /* of those, at or above 2^12 (in bin 255) */
+    unsigned int nonpositive;  /* finite pixels of luminance <= 0, not binned */
+    unsigned int nonfinite;    /* pixels with a NaN or an infinity in r, g, b or the luminance, not binned */
+    unsigned int max_bits;     /* the largest and ... */
+    unsigned int min_bits;     /* ... smallest binned luminance, as the float's bits */
+    unsigned int reserved;     /* 0 */
+} rt_meter_hist;
+typedef struct rt_meter_params {
+    float low;           /* share of the counted pixels trimmed from the dark end     default 0.10 */
+    float high;          /* ... 1 - the share trimmed from the bright end             default 0.95 */
+    float key;           /* the display value, before the gamma, the log-average luminance maps to; the
+                            photographic convention, not a measured optimum            default 0.18 */
+    float min_exposure;  /* the target is clamped to [min_exposure, ...               default 2^-8 */
+    float max_exposure;  /* ... max_exposure]                                          default 2^12 */
+    float tau_up;        /* time constant in seconds while the exposure rises; 0: at once   default 0 */
+    float tau_down;      /* ... and while it falls                                     default 0 */
+} rt_meter_params;
+typedef struct rt_meter_result {
+    float exposure;      /* what rt_display_params.exposure takes */
+    float target;        /* the exposure before the adaptation */
+    float log2_mean;     /* log2 of the trimmed log-average luminance */
+    int valid;           /* 0: no pixel was left to average */
+} rt_meter_result;
+void rt_meter_default_params(rt_meter_params* params);
+int rt_meter(rt_context* ctx, int w, int h, const float* linear_rgba, rt_meter_hist* out);
+int rt_meter_device(rt_context* ctx, int w, int h, const void* d_linear, void* d_hist, void* stream);
+int rt_meter_solve(const rt_meter_hist* hist, const rt_meter_params* params, float prev_exposure, float dt_seconds,
+                   rt_meter_result* out);
 
 /* Counters of the last render when enabled (RT_STAT_* order, rt_device.h);
  * with n up to 2 * RT_STAT_COUNT the second block is the share of the

@@ -14,6 +14,7 @@
 #include "rt_noise.h"
 #include "rt_temporal.h"
 #include "rt_firefly.h"
+#include "rt_meter.h"
 
 namespace {
 std::mutex g_err_mu;
@@ -255,6 +256,8 @@ int rt_test_schedule(rt_context* c, const char* key, double value)
     else if (k == "near_scale") s.near_scale = value;
     else if (k == "dn_variant") s.dn_variant = std::max(0, std::min(2, v));
     else if (k == "ff_variant") s.ff_variant = std::max(0, std::min(2, v));
+    else if (k == "mt_variant") s.mt_variant = std::max(0, std::min(2, v));
+    else if (k == "mt_blocks") s.mt_blocks = std::max(0, std::min(65536, v));
     else if (k == "rq_variant") s.rq_variant = std::max(0, std::min(2, v));
     else if (k == "chain_full") {
         // the devices' views carry the flag: the next call uploads them again
@@ -940,6 +943,100 @@ int rt_firefly_device(rt_context* c, int w, int h, const void* in, const void* s
     rtk::FireflyArgs A;
     if (int r = firefly_ready(c, "rt_firefly_device", w, h, in, sigma, params, out, sigma_out, scale_out, true, A)) return r;
     return rt_backend_firefly(c, A, out, sigma_out, scale_out, true, stream);
+}
+
+// ---- exposure metering (rt_meter.h)
+// The photographic convention (a log-average that displays as middle grey, 0.18), not a measured optimum;
+// the trims keep a dark corner and the light source out of the average.
+void rt_meter_default_params(rt_meter_params* p)
+{
+    if (!p) return;
+    p->low = 0.10f;
+    p->high = 0.95f;
+    p->key = 0.18f;
+    p->min_exposure = 0x1p-8f;
+    p->max_exposure = 0x1p12f;
+    p->tau_up = 0.0f;
+    p->tau_down = 0.0f;
+}
+
+static int meter_ready(rt_context* c, const char* fn, int w, int h, const void* in, const void* hist, bool device)
+{
+    const std::string f = fn;
+    if (!c) return rt_fail(nullptr, RT_ERR_ARG, f + ": ctx is NULL");
+    if (w <= 0 || h <= 0) return rt_fail(c, RT_ERR_ARG, f + ": w and h must be at least 1");
+    if (!in || !hist) return rt_fail(c, RT_ERR_ARG, f + ": the frame or the histogram is NULL");
+    // (rt_display's limit; with it no word of the histogram can overflow)
+    if ((double)w * (double)h > 134217727.0) return rt_fail(c, RT_ERR_ARG, f + ": too many pixels");
+    if (device && ((uintptr_t)in % 16 != 0 || (uintptr_t)hist % 4 != 0))
+        return rt_fail(c, RT_ERR_ARG, f + ": d_linear must be 16-byte aligned, d_hist 4-byte aligned");
+    return RT_OK;
+}
+
+int rt_meter(rt_context* c, int w, int h, const float* linear, rt_meter_hist* out)
+{
+    static_assert(sizeof(rt_meter_hist) == rtk::MT_WORDS * sizeof(uint32_t), "rt_meter_hist is MT_WORDS words");
+    if (int r = meter_ready(c, "rt_meter", w, h, linear, out, false)) return r;
+    return rt_backend_meter(c, w, h, linear, out, false, nullptr);
+}
+
+int rt_meter_device(rt_context* c, int w, int h, const void* d_linear, void* d_hist, void* stream)
+{
+    if (int r = meter_ready(c, "rt_meter_device", w, h, d_linear, d_hist, true)) return r;
+    return rt_backend_meter(c, w, h, d_linear, d_hist, true, stream);
+}
+
+// Host only, in double: the formulas of include/rt_hip.h, in their order.
+int rt_meter_solve(const rt_meter_hist* hist, const rt_meter_params* params, float prev_exposure, float dt_seconds,
+                   rt_meter_result* out)
+{
+    const std::string f = "rt_meter_solve";
+    if (!hist || !out) return rt_fail(nullptr, RT_ERR_ARG, f + ": the histogram or the result is NULL");
+    rt_meter_params p;
+    if (params) p = *params;
+    else rt_meter_default_params(&p);
+    if (!(p.low >= 0.0f && p.low <= 1.0f) || !(p.high >= 0.0f && p.high <= 1.0f) || p.low > p.high)
+        return rt_fail(nullptr, RT_ERR_ARG, f + ": low and high must lie in [0, 1] with low <= high");
+    if (!(p.key > 0.0f && p.key < 1.0f)) return rt_fail(nullptr, RT_ERR_ARG, f + ": key must lie in (0, 1)");
+    if (!std::isfinite(p.min_exposure) || !std::isfinite(p.max_exposure) || !(p.min_exposure > 0.0f) ||
+        p.min_exposure > p.max_exposure)
+        return rt_fail(nullptr, RT_ERR_ARG, f + ": the exposure bounds must be finite, positive and ordered");
+    if (!(p.tau_up >= 0.0f) || !(p.tau_down >= 0.0f))
+        return rt_fail(nullptr, RT_ERR_ARG, f + ": tau_up or tau_down is negative or a NaN");
+    const double n = (double)hist->counted, prev = (double)prev_exposure, dt = (double)dt_seconds;
+    double lo = std::floor((double)p.low * n), hi = std::floor((1.0 - (double)p.high) * n);
+    if (lo + hi >= n) lo = hi = 0.0;
+    uint64_t c[256];
+    for (int b = 0; b < 256; b++) c[b] = hist->bins[b];
+    uint64_t cut = (uint64_t)lo;
+    for (int b = 0; b < 256 && cut; b++) {
+        const uint64_t d = std::min(cut, c[b]);
+        c[b] -= d, cut -= d;
+    }
+    cut = (uint64_t)hi;
+    for (int b = 255; b >= 0 && cut; b--) {
+        const uint64_t d = std::min(cut, c[b]);
+        c[b] -= d, cut -= d;
+    }
+    uint64_t N = 0;
+    int64_t S = 0;
+    for (int b = 0; b < 256; b++) N += c[b], S += (int64_t)c[b] * (2 * b - 319);
+    if (N == 0) {
+        const float e = prev_exposure > 0.0f ? prev_exposure : 1.5f;
+        *out = rt_meter_result{e, e, 0.0f, 0};
+        return RT_OK;
+    }
+    const double log2_mean = (double)S / (16.0 * (double)N);
+    const double Lm = std::exp2(log2_mean);
+    const double target = std::min(std::max(-std::log1p(-(double)p.key) / Lm, (double)p.min_exposure), (double)p.max_exposure);
+    const double tau = (double)(target > prev ? p.tau_up : p.tau_down);
+    double e = target;
+    if (prev > 0.0 && tau > 0.0 && dt >= 0.0) {
+        const double l0 = std::log2(prev);
+        e = std::exp2(l0 + (std::log2(target) - l0) * (1.0 - std::exp(-dt / tau)));
+    }
+    *out = rt_meter_result{(float)e, (float)target, (float)log2_mean, 1};
+    return RT_OK;
 }
 
 // ---------------------------------------------------------- display stage

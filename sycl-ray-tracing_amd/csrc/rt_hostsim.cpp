@@ -23,6 +23,7 @@
 #include "rt_query.h"
 #include "rt_temporal.h"
 #include "rt_firefly.h"
+#include "rt_meter.h"
 #include "rt_wave.h"
 
 // Stack window and step budget of the host build: smaller than the
@@ -816,6 +817,37 @@ int rt_backend_firefly(rt_context* c, rtk::FireflyArgs A, void* rgba_out, void* 
     const double t0 = omp_get_wtime();
     if (A.radius == 1) firefly_rows<1>(A, (float4_*)rgba_out, (float*)sigma_out, (float*)scale_out);
     else firefly_rows<2>(A, (float4_*)rgba_out, (float*)sigma_out, (float*)scale_out);
+    c->last_kernel_ms = (omp_get_wtime() - t0) * 1e3;
+    return RT_OK;
+}
+
+// Exposure metering on the host: the loop around rt_meter.h's meter_pixel that the kernels of
+// rt_meter.hip walk grid-stride. Each thread counts its rows into a histogram of its own; the
+// histograms are integers, so the merge gives the same words in any order.
+int rt_backend_meter(rt_context* c, int w, int h, const void* in, void* hist, bool, void*)
+{
+    const double t0 = omp_get_wtime();
+    uint32_t total[rtk::MT_WORDS] = {};
+    total[rtk::MT_MIN_BITS] = 0xffffffffu;
+#pragma omp parallel
+    {
+        uint32_t own[rtk::MT_WORDS] = {};
+        own[rtk::MT_MIN_BITS] = 0xffffffffu;
+#pragma omp for schedule(static) nowait
+        for (long i = 0; i < (long)w * h; i++) {
+            float4_ px;
+            std::memcpy(&px, (const char*)in + 16 * i, 16);
+            rtk::meter_count(own, px);
+        }
+#pragma omp critical(rt_meter_merge)
+        {
+            for (int k = 0; k < rtk::MT_WORDS; k++)
+                if (k == rtk::MT_MAX_BITS) total[k] = std::max(total[k], own[k]);
+                else if (k == rtk::MT_MIN_BITS) total[k] = std::min(total[k], own[k]);
+                else total[k] += own[k];
+        }
+    }
+    std::memcpy(hist, total, sizeof(total));
     c->last_kernel_ms = (omp_get_wtime() - t0) * 1e3;
     return RT_OK;
 }

@@ -25,8 +25,8 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _capi
-from ._capi import (DenoiseParams, DenoiseVarParams, DisplayParams, FireflyParams, NoiseStats,  # noqa: F401
-                    TemporalParams)
+from ._capi import (METER_STATS, METER_WORDS, DenoiseParams, DenoiseVarParams, DisplayParams, FireflyParams,  # noqa: F401
+                    MeterParams, MeterResult, NoiseStats, TemporalParams)
 from ._capi import (RT_ERR_ARG, RT_ERR_HIP, RT_ERR_IO, RT_ERR_NODEV, RT_ERR_STATE, RT_OK,  # noqa: F401
                     RtError, check, lib, ptr)
 
@@ -34,7 +34,8 @@ __all__ = ["Camera", "Image", "ParsedOBJ", "parse_obj", "compute_env_map_cdf", "
            "RenderKernel", "RtError", "octree_dump", "make_materials", "read_image_float", "write_image_png",
            "image_to_rgba8", "DenoiseParams", "denoise_default_params", "DisplayParams", "write_image_hdr", "DenoiseVarParams",
            "denoise_var_default_params", "TemporalParams", "temporal_default_params", "TemporalHistory",
-           "FireflyParams", "firefly_default_params"]
+           "FireflyParams", "firefly_default_params", "MeterParams", "meter_default_params", "meter_stats", "meter_solve",
+           "ExposureAdapter", "METER_WORDS", "METER_STATS"]
 
 
 # ------------------------------------------------------------------ camera
@@ -218,6 +219,74 @@ def _firefly_params(L_, params) -> FireflyParams:
             raise TypeError(f"unknown firefly parameter {k}")
         setattr(p, k, v)
     return p
+
+
+def meter_default_params(hostsim: bool = False) -> MeterParams:
+    """rt_meter_default_params: the defaults of rt_meter_solve."""
+    p = MeterParams()
+    lib(hostsim).rt_meter_default_params(ctypes.byref(p))
+    return p
+
+
+def _meter_params(L_, params) -> MeterParams:
+    """params: None (defaults), a MeterParams, or a dict of its fields over the defaults."""
+    if isinstance(params, MeterParams):
+        return params
+    p = MeterParams()
+    L_.rt_meter_default_params(ctypes.byref(p))
+    for k, v in (params or {}).items():
+        if k not in dict(MeterParams._fields_):
+            raise TypeError(f"unknown meter parameter {k}")
+        setattr(p, k, v)
+    return p
+
+
+def meter_stats(hist) -> dict:
+    """The words of an rt_meter_hist by name: "bins" (a view of the 256 counts) and the stat words as ints."""
+    h = np.asarray(hist, dtype=np.uint32).reshape(METER_WORDS)
+    return {"bins": h[:256], **{k: int(h[256 + i]) for i, k in enumerate(METER_STATS)}}
+
+
+def meter_solve(hist, prev: float = 0.0, dt: float = 0.0, hostsim: bool = False, **params) -> dict:
+    """rt_meter_solve: a histogram of RenderKernel.meter (264 uint32 words) to the exposure display() takes.
+    prev: the last frame's exposure (<= 0: none) and dt the seconds since, for the adaptation with tau_up /
+    tau_down; params: fields of MeterParams over the defaults, or params=MeterParams. Host code only (no
+    context); hostsim picks the library that is asked. Returns {"exposure", "target", "log2_mean", "valid"}."""
+    return _meter_solve(lib(hostsim), hist, prev, dt, params)
+
+
+def _meter_solve(L_, hist, prev, dt, params) -> dict:
+    p = _meter_params(L_, params.pop("params") if "params" in params else params)
+    h = np.ascontiguousarray(hist, dtype=np.uint32).reshape(METER_WORDS)
+    r = MeterResult()
+    check(L_, L_.rt_meter_solve(ptr(h), ctypes.byref(p), float(prev), float(dt), ctypes.byref(r)), None, "rt_meter_solve")
+    return {"exposure": float(r.exposure), "target": float(r.target), "log2_mean": float(r.log2_mean), "valid": bool(r.valid)}
+
+
+class ExposureAdapter:
+    """The exposure carried from frame to frame, TemporalHistory's sibling for the display stage:
+    update(linear, dt) meters the frame (RenderKernel.meter), solves with the exposure of the last update as
+    prev and dt seconds since, keeps the result and returns it. The first update, or one after reset(), jumps
+    to the target. tau_up / tau_down: the time constants in seconds while the exposure rises and falls (0: at
+    once); kernel: the RenderKernel whose context meters (or pass one to update); params: further fields of
+    MeterParams."""
+
+    def __init__(self, tau_up: float = 0.0, tau_down: float = 0.0, kernel: "RenderKernel | None" = None, **params):
+        self.params = dict(params, tau_up=tau_up, tau_down=tau_down)
+        self.kernel = kernel
+        self.exposure = 0.0
+        self.last = None  # (the last update's whole result)
+
+    def reset(self):
+        self.exposure, self.last = 0.0, None
+
+    def update(self, linear, dt: float, kernel: "RenderKernel | None" = None) -> float:
+        kernel = kernel or self.kernel
+        if kernel is None:
+            raise ValueError("ExposureAdapter.update: no RenderKernel given here or to the constructor")
+        self.last = kernel.auto_exposure(linear, prev=self.exposure, dt=dt, full=True, **self.params)
+        self.exposure = self.last["exposure"]
+        return self.exposure
 
 
 class TemporalHistory:
@@ -457,6 +526,33 @@ class RenderKernel:
         check(self.L, self.L.rt_display_device(self.ctx, int(width or self.width), int(height or self.height),
                                                vp(d_linear), ctypes.byref(p), vp(d_rgba), vp(d_rgba8), vp(stream)),
               self.ctx, "rt_display_device")
+
+    # ---- exposure metering (rt_meter, rt_meter_solve; include/rt_hip.h)
+    def meter(self, linear=None) -> np.ndarray:
+        """rt_meter: the luminance histogram of a linear frame (an Image or a [h, w, 4] float32 array; default:
+        the bound Image, after render_linear()): the 264 uint32 words of rt_meter_hist, 256 bins of an eighth
+        of an octave over [2^-20, 2^12) and the stat words (meter_stats names them). It needs no scene."""
+        linear = self.frame_buffer if linear is None else linear
+        src = np.ascontiguousarray(getattr(linear, "pixels", linear), dtype=np.float32)
+        assert src.ndim == 3 and src.shape[2] == 4, "a linear frame is [h, w, 4] float32"
+        h, w = src.shape[:2]
+        hist = np.empty(METER_WORDS, np.uint32)
+        check(self.L, self.L.rt_meter(self.ctx, w, h, ptr(src), ptr(hist)), self.ctx, "rt_meter")
+        return hist
+
+    def meter_device(self, d_linear: int, d_hist: int, stream: int | None = None, width=None, height=None):
+        """rt_meter_device: device buffers (w*h*4 floats in, 264 words out, cleared by the call), no wait."""
+        vp = lambda a: ctypes.c_void_p(a) if a else None  # noqa: E731
+        check(self.L, self.L.rt_meter_device(self.ctx, int(width or self.width), int(height or self.height), vp(d_linear),
+                                             vp(d_hist), vp(stream)), self.ctx, "rt_meter_device")
+
+    def auto_exposure(self, linear=None, prev: float = 0.0, dt: float = 0.0, full: bool = False, **params):
+        """meter(), then meter_solve: the exposure display() should take for this linear frame. prev / dt and
+        params as meter_solve's. Returns the exposure, or with full the whole result and the histogram
+        ({"exposure", "target", "log2_mean", "valid", "hist"})."""
+        hist = self.meter(linear)
+        r = _meter_solve(self.L, hist, prev, dt, params)
+        return dict(r, hist=hist) if full else r["exposure"]
 
     # ---- progressive rendering (rt_progress_*, include/rt_hip.h)
     def progress_begin(self, samples_total: int | None = None, row_offset: int = 0, row_stride: int = 1):

@@ -39,6 +39,7 @@ EXPORTS = [
     "rt_denoise_var_device",
     "rt_temporal_default_params", "rt_temporal_accumulate", "rt_temporal_accumulate_device",
     "rt_firefly_default_params", "rt_firefly", "rt_firefly_device",
+    "rt_meter_default_params", "rt_meter", "rt_meter_device", "rt_meter_solve",
 ]
 
 # return codes (include/rt_hip.h)
@@ -70,6 +71,21 @@ class TemporalParams(ctypes.Structure):
 class FireflyParams(ctypes.Structure):
     """struct rt_firefly_params (include/rt_hip.h)."""
     _fields_ = [("radius", I), ("rank", I), ("gain", F), ("floor", F)]
+
+
+METER_WORDS = 264  # struct rt_meter_hist: 256 bins, then the words named below
+METER_STATS = ("counted", "under", "over", "nonpositive", "nonfinite", "max_bits", "min_bits", "reserved")
+
+
+class MeterParams(ctypes.Structure):
+    """struct rt_meter_params (include/rt_hip.h)."""
+    _fields_ = [("low", F), ("high", F), ("key", F), ("min_exposure", F), ("max_exposure", F), ("tau_up", F),
+                ("tau_down", F)]
+
+
+class MeterResult(ctypes.Structure):
+    """struct rt_meter_result (include/rt_hip.h)."""
+    _fields_ = [("exposure", F), ("target", F), ("log2_mean", F), ("valid", I)]
 
 
 class DisplayParams(ctypes.Structure):
@@ -167,7 +183,12 @@ _SIGS = {
     "rt_firefly_default_params": (None, [ctypes.POINTER(FireflyParams)]),
     "rt_firefly": (I, [P, I, I, P, P, ctypes.POINTER(FireflyParams), P, P, P]),
     "rt_firefly_device": (I, [P, I, I, P, P, ctypes.POINTER(FireflyParams), P, P, P, P]),
+    "rt_meter_default_params": (None, [ctypes.POINTER(MeterParams)]),
+    "rt_meter": (I, [P, I, I, P, P]),
+    "rt_meter_device": (I, [P, I, I, P, P, P]),
+    "rt_meter_solve": (I, [P, ctypes.POINTER(MeterParams), F, F, ctypes.POINTER(MeterResult)]),
     # product-only extras
+    "rt_device_meter_kernel_ms": (I, [P, I, I, P, P, I, I, P]),
     "rt_device_libm": (I, [I, I, P, P, P, I]),
     "rt_device_libm_digest": (I, [I, I, ctypes.c_uint32, I, P]),
     "rt_device_last_kernel_ms": (ctypes.c_double, [P]),

@@ -44,6 +44,12 @@ frame and its noise figure pass through rt_firefly (its defaults, or GAIN in the
 the resolve and the filter, and the line "firefly: clamped N of M pixels" is printed. RT_output.png and --hdr-out
 stay the unclamped render; the three denoised PNGs come from the clamped frame. Without the flag a run writes the
 bytes it writes today.
+
+Exposure metering (RenderKernel.auto_exposure): --auto-exposure or --auto-exposure=KEY, not with --exposure=. The
+run goes through render_linear and display as with --gamma=; the final linear frame (under --denoise=var the
+filtered one) is metered, the line "auto-exposure: E" is printed and the frame is displayed with E instead of 1.5.
+KEY replaces the default key of 0.18. Each preview is metered on its own. Without the flag a run writes the bytes
+it writes today.
 """
 from __future__ import annotations
 
@@ -59,7 +65,8 @@ import rt_amd
 def parse(argv):
     a = dict(obj="data/OBJs/cornell_pbr.obj", sky="data/Skyspheres/evening_road_01_puresky_2k.hdr", w=512, h=512,
              samples=64, bounces=8, camera="dragon", out=".", hostsim=False, preview_every=0, checkpoint="",
-             exposure=None, gamma=None, hdr_out="", noise_threshold=None, adaptive=False, denoise="atrous", firefly=None)
+             exposure=None, gamma=None, hdr_out="", noise_threshold=None, adaptive=False, denoise="atrous", firefly=None,
+             auto_exposure=None)
     for s in argv:
         if s == "--hostsim":
             a["hostsim"] = True
@@ -69,6 +76,10 @@ def parse(argv):
             a["firefly"] = {}
         elif s.startswith("--firefly="):
             a["firefly"] = {"gain": float(s.split("=", 1)[1])}
+        elif s == "--auto-exposure":  # (the solve's default key)
+            a["auto_exposure"] = {}
+        elif s.startswith("--auto-exposure="):
+            a["auto_exposure"] = {"key": float(s.split("=", 1)[1])}
         elif s.startswith(("--sky=", "--camera=", "--out=", "--checkpoint=", "--hdr-out=", "--denoise=")):
             k, v = s[2:].split("=", 1)
             a[k.replace("-", "_")] = v
@@ -93,8 +104,8 @@ def blend(filtered: rt_amd.Image, image: rt_amd.Image, factor: float) -> rt_amd.
 
 
 def display_stage(a: dict) -> bool:
-    """Any of --exposure, --gamma, --hdr-out: the run goes through render_linear and display."""
-    return a["exposure"] is not None or a["gamma"] is not None or bool(a["hdr_out"])
+    """Any of --exposure, --gamma, --hdr-out, --auto-exposure: the run goes through render_linear and display."""
+    return a["exposure"] is not None or a["gamma"] is not None or bool(a["hdr_out"]) or a["auto_exposure"] is not None
 
 
 def linear_path(a: dict) -> bool:
@@ -103,8 +114,20 @@ def linear_path(a: dict) -> bool:
     return display_stage(a) or a["denoise"] == "var"
 
 
-def display_args(a: dict) -> dict:
-    return dict(exposure=1.5 if a["exposure"] is None else a["exposure"], gamma=2.2 if a["gamma"] is None else a["gamma"])
+def display_args(a: dict, exposure=None) -> dict:
+    """exposure: the metered one of --auto-exposure, in the place of --exposure= or 1.5."""
+    if exposure is None:
+        exposure = 1.5 if a["exposure"] is None else a["exposure"]
+    return dict(exposure=exposure, gamma=2.2 if a["gamma"] is None else a["gamma"])
+
+
+def metered(rk: rt_amd.RenderKernel, linear: rt_amd.Image, a: dict, what: str = ""):
+    """--auto-exposure: the exposure RenderKernel.auto_exposure gives for this frame, printed; else None."""
+    if a["auto_exposure"] is None:
+        return None
+    e = rk.auto_exposure(linear, **a["auto_exposure"])
+    print(f"auto-exposure{what}: {e:.9g}")
+    return e
 
 
 def render_progressive(rk: rt_amd.RenderKernel, fb: rt_amd.Image, a: dict):
@@ -143,7 +166,8 @@ def render_progressive(rk: rt_amd.RenderKernel, fb: rt_amd.Image, a: dict):
             os.replace(ck + ".tmp", ck)
         if a["preview_every"] > 0:
             if display_stage(a):
-                shown = rk.display(rk.progress_resolve_linear(preview), **display_args(a))
+                rk.progress_resolve_linear(preview)
+                shown = rk.display(preview, **display_args(a, metered(rk, preview, a, f" (preview {done})")))
             else:
                 shown = rk.progress_resolve(preview)
             rt_amd.write_image_png(shown, os.path.join(a["out"], f"RT_preview_{done}.png"))
@@ -203,6 +227,12 @@ def main(argv=None) -> int:
     if a["firefly"] and not a["firefly"]["gain"] >= 0.0:
         print("--firefly=GAIN takes a gain of at least 0", file=sys.stderr)
         return 2
+    if a["auto_exposure"] is not None and a["exposure"] is not None:
+        print("--auto-exposure meters the exposure: it does not go with --exposure=", file=sys.stderr)
+        return 2
+    if a["auto_exposure"] and not 0.0 < a["auto_exposure"]["key"] < 1.0:
+        print("--auto-exposure=KEY takes a key inside (0, 1)", file=sys.stderr)
+        return 2
     print(f"Reading OBJ {a['obj']} ...")
     P = rt_amd.parse_obj(a["obj"])
     print(f"Reading Environment Map {a['sky']} ...")
@@ -230,9 +260,10 @@ def main(argv=None) -> int:
     if linear_path(a):  # fb holds the linear radiance: the .hdr file, then the displayed frame
         if a["hdr_out"]:
             rt_amd.write_image_hdr(fb, a["hdr_out"])
-        fb = rk.display(fb, **display_args(a))
+        args = display_args(a, metered(rk, fb if filtered is None else filtered, a))
+        fb = rk.display(fb, **args)
         if filtered is not None:
-            filtered = rk.display(filtered, **display_args(a))
+            filtered = rk.display(filtered, **args)
     print(f"{int((time.perf_counter() - t0) * 1e3)}ms")
     with np.errstate(all="ignore"):
         if filtered is None:
