@@ -50,8 +50,9 @@ $(OBJ)/rt_hostsim.o: $(SRC)/rt_hostsim.cpp $(HDRS) $(ALL_SRC)
 #   rt_temporal  temporal accumulation: the previous frame reprojected into the new camera and blended in
 #   rt_firefly   firefly rejection: a pixel's luminance limited by a rank of its neighbours'
 #   rt_meter     exposure metering: the luminance histogram of a linear frame
+#   rt_upscale   guided upscale: a low-resolution frame taken to the output size along the full-size guides
 HIP_UNITS := rt_render rt_wave_run rt_probe rt_denoise rt_query rt_display rt_noise rt_adapt rt_dnv rt_temporal rt_firefly \
-             rt_meter
+             rt_meter rt_upscale
 $(HIP_UNITS:%=$(OBJ)/%.o): $(OBJ)/%.o: $(SRC)/%.hip $(HDRS)
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
@@ -164,6 +165,8 @@ hostsim-variant: $(OBJ)/rt_imageio.host.o
 #                       (make sanitize-firefly: the same program under ASan + UBSan over the hostsim sources)
 #   meter_shim_test     meter / auto_exposure against the C ABI                   tests/test_meter_shim.py
 #                       (make sanitize-meter: the same program under ASan + UBSan over the hostsim sources)
+#   upscale_shim_test   upscale against the C ABI                                 tests/test_upscale_shim.py
+#                       (make sanitize-upscale: the same program under ASan + UBSan over the hostsim sources)
 REFDIR ?= /root/reference
 REFOBJ := oracle/_ref/objO2
 REFOBJS := $(REFOBJ)/bvh.o $(REFOBJ)/flattened_bvh.o $(REFOBJ)/triangle.o $(REFOBJ)/vec.o $(REFOBJ)/color.o \
@@ -230,3 +233,13 @@ sanitize-meter: build/san_asan/meter_shim_test
 	ASAN_OPTIONS=halt_on_error=1:detect_leaks=1 UBSAN_OPTIONS=print_stacktrace=1:halt_on_error=1 OMP_NUM_THREADS=4 \
 	  build/san_asan/meter_shim_test scenes/cornell_pbr.obj - 33 21 3
 .PHONY: sanitize-meter
+
+# upscale and the upscale C calls under ASan + UBSan, in the same way; the target runs the program (a host
+# program with its own main) on the small Cornell scene.
+build/san_asan/upscale_shim_test: tests/native/upscale_shim_test.cpp include/render_kernel_hip.h build/san_asan/driver
+	$(CXX) -std=gnu++20 $(SAN_NUM) $(ASAN) -Iinclude -I$(REFDIR)/include -I$(REFDIR)/rapidobj -I$(REFDIR) $< \
+	  $(filter-out build/san_asan/cpu_oracle.o,$(wildcard build/san_asan/*.o)) $(REFOBJS) -Wl,--gc-sections -o $@
+sanitize-upscale: build/san_asan/upscale_shim_test
+	ASAN_OPTIONS=halt_on_error=1:detect_leaks=1 UBSAN_OPTIONS=print_stacktrace=1:halt_on_error=1 OMP_NUM_THREADS=4 \
+	  build/san_asan/upscale_shim_test scenes/cornell_pbr.obj - 33 21 3
+.PHONY: sanitize-upscale

@@ -327,6 +327,40 @@ public:
         return out;
     }
 
+    // Guided upscale (rt_upscale): `low`, a linear frame rendered by a kernel of low.width() x low.height()
+    // under this kernel's camera, taken to width x height along the first-hit guides, which this call
+    // renders at both sizes (as denoise() renders its own). sigma: the low frame's per-pixel standard
+    // deviation (progress_noise_sigma() of the low-resolution kernel), carried into *sigma_out at the
+    // output size, or empty for none (sigma_out must then be null). params: null for the defaults.
+    Image upscale(const Image& low, int width, int height, const std::vector<float>& sigma,
+                  const rt_upscale_params* params = nullptr, std::vector<float>* sigma_out = nullptr) const
+    {
+        std::lock_guard<std::mutex> lk(m_mu);
+        const_cast<RenderKernel*>(this)->sync_materials();
+        const int wl = low.width(), hl = low.height();
+        if (width < wl || height < hl) throw std::runtime_error("librt_hip: upscale: the output is smaller than the low frame");
+        const size_t n_lo = (size_t)wl * hl, n = (size_t)width * height;
+        if (!sigma.empty() && sigma.size() != n_lo)
+            throw std::runtime_error("librt_hip: upscale: sigma is not low.width() * low.height() floats");
+        if (sigma.empty() != (sigma_out == nullptr))
+            throw std::runtime_error("librt_hip: upscale: sigma and sigma_out go together");
+        std::vector<float> alb_lo(n_lo * 4), nd_lo(n_lo * 4), alb_hi(n * 4), nd_hi(n * 4);
+        check(rt_render_features(m_ctx, wl, hl, alb_lo.data(), nd_lo.data()));
+        check(rt_render_features(m_ctx, width, height, alb_hi.data(), nd_hi.data()));
+        if (sigma_out) sigma_out->assign(n, 0.0f);
+        Image out(width, height);
+        check(rt_upscale(m_ctx, wl, hl, width, height, low.data(), sigma.empty() ? nullptr : sigma.data(), alb_lo.data(),
+                         nd_lo.data(), alb_hi.data(), nd_hi.data(), params, out.data(),
+                         sigma_out ? sigma_out->data() : nullptr));
+        return out;
+    }
+
+    // upscale() without a noise figure.
+    Image upscale(const Image& low, int width, int height, const rt_upscale_params* params = nullptr) const
+    {
+        return upscale(low, width, height, std::vector<float>(), params, nullptr);
+    }
+
     // Firefly rejection (rt_firefly): every pixel of `image` (a linear frame) whose luminance is above
     // gain * M + floor, M the rank-th largest luminance among its neighbours, scaled down to that limit.
     // sigma: the frame's per-pixel standard deviation (progress_noise_sigma()), scaled with the colour

@@ -108,7 +108,8 @@ int rt_test_fail_device(rt_context* ctx, int device);
  * loads, 2 the LDS-halo tile at every step that has one), "ff_variant" (rt_firefly's kernel: 0 the
  * product's choice, 1 direct loads, 2 the LDS tile of luminances), "mt_variant" (rt_meter's kernel: 0 the
  * product's choice, 1 global atomics per pixel, 2 per-wave bins in LDS), "mt_blocks" (rt_meter's grid: 0 the
- * product's cap, n > 0 that many blocks, at most 65536), "rq_variant" (rt_query's search-BVH kernel:
+ * product's cap, n > 0 that many blocks, at most 65536), "up_variant" (rt_upscale's kernel: 0 the product's
+ * choice, 1 direct loads, 2 the low-resolution footprint staged in LDS), "rq_variant" (rt_query's search-BVH kernel:
  * 0 the product's choice, 1 plain rounds of one query per quad, 2 per-quad refill),
  * "chain_full" (1: the scene view reports an unmonotone tree, so the leaf verification
  * walks the whole ancestor chain instead of one slab test), the
@@ -744,6 +745,65 @@ int rt_meter(rt_context* ctx, int w, int h, const float* linear_rgba, rt_meter_h
 int rt_meter_device(rt_context* ctx, int w, int h, const void* d_linear, void* d_hist, void* stream);
 int rt_meter_solve(const rt_meter_hist* hist, const rt_meter_params* params, float prev_exposure, float dt_seconds,
                    rt_meter_result* out);
+
+/* ---------------------------------------------- guided upscale
+ * Render small, reconstruct at full size: a frame of w_lo x h_lo pixels (rt_render_linear or a
+ * progression's linear resolve, optionally with its rt_progress_noise_sigma) is taken to w x h by
+ * joint-bilateral upsampling. Each low-resolution tap is weighted by how well its first-hit guides
+ * (rt_render_features at w_lo x h_lo) agree with the output pixel's (rt_render_features at w x h),
+ * so geometry, material and silhouette edges come out at output resolution; the colour itself is
+ * never compared. The camera maps a pixel through x / w, so the two sizes see the same field of
+ * view when their aspects agree. Stateless, no scene or camera needed. Float32 throughout, no
+ * contraction, IEEE division and square root, rt_libm's expf.
+ *
+ * rt_upscale / _device: rgba_lo, albedo_lo, normal_depth_lo (float4[h_lo][w_lo]), sigma_lo
+ *   (float[h_lo][w_lo], or NULL), albedo_hi, normal_depth_hi (float4[h][w]) in; rgba_out
+ *   (float4[h][w], alpha 1) and sigma_out (float[h][w]; required exactly when sigma_lo is given) out.
+ *   With sx = (float)w_lo / (float)w, sy = (float)h_lo / (float)h, for output pixel (X, Y):
+ *   fx = (float)X * sx, x0 = (int)fx, tx = fx - (float)x0, the same in y (no half-pixel term: the
+ *   feature rays aim at x_j = x).
+ *   Guide weight of low tap q against output pixel p: skipped when their hit states (t > 0) differ;
+ *   e = |n_p - n_q|^2 / sigma_normal^2 + |a_p - a_q|^2 / sigma_albedo^2, plus ((t_p - t_q) /
+ *   max(t_p, t_q))^2 / sigma_depth^2 when both hit; skipped when !(e >= 0); g = expf(-e). A tap
+ *   outside the low frame, with a colour that is not finite, with a sigma that is not finite (when
+ *   given) or with a spatial weight of exactly 0 is skipped too.
+ *   1 The taps (x0 + dx, y0 + dy), dx, dy in {0, 1}, dy outer, spatial weight b = (1 - ty, ty)[dy] *
+ *     (1 - tx, tx)[dx], wgt = b g; sums of wgt c, S = sum wgt, V = sum wgt (wgt v_q) in tap order,
+ *     v_q = sigma_q^2, at most the largest float. Taken when S > min_weight.
+ *   2 Otherwise dx, dy in {-1, 0, 1, 2}, dy outer, b = k(y) k(x), k(d) = 1 - |d| / 2 at d =
+ *     (float)(x0 + dx) - fx; the same guide weight and sums. Taken when S > 0.
+ *   3 Otherwise the taps and weights of 1 with g = 1: plain bilinear over the finite taps inside the
+ *     frame. Taken when S > 0. Otherwise rgba_out = {0, 0, 0, 1} and sigma_out = +inf.
+ *   rgb = sums / S; sigma_out = sqrtf(min(V, largest float)) / S. Neighbouring outputs share taps:
+ *   sigma_out is each pixel's marginal figure, not that of an independent sample. Where step 2 is
+ *   taken with no agreeing tap (every weight below about 1e-19, S of that order) V is a denormal
+ *   float and sigma_out is unreliable, off by up to sqrt(2^-144) / S: a caller that feeds sigma_out
+ *   to rt_denoise_var or a history should not trust it at such pixels. rgba_out is not affected.
+ *   A NaN or infinite output guide, or an output pixel whose hit state no tap shares, therefore gets
+ *   the bilinear value. With w_lo == w, h_lo == h (at most 2^24 a side) and the same guides on both
+ *   sides rgba_out equals rgba_lo's rgb bit for bit wherever colour and sigma are finite, and
+ *   sigma_out equals a sigma_lo >= 0 whose square is a normal float.
+ *   RT_ERR_ARG for a NULL ctx or required buffer; a size below 1; w_lo > w or h_lo > h; sigma_out
+ *   without sigma_lo or the reverse; a sigma that is not positive and finite; min_weight outside
+ *   [0, 1); an output whose bytes overlap an input's or the other output's; more than 262140 output
+ *   rows or 2^27 - 1 output pixels (rt_denoise's limits). The device form takes device pointers (the
+ *   float4 buffers 16-byte aligned, the float buffers 4-byte aligned: RT_ERR_ARG otherwise) and a
+ *   stream (NULL: default) and returns without waiting. params NULL: the defaults. Runs on the
+ *   root device of a multi-device context; rt_last_kernel_ms as for rt_denoise. */
+typedef struct rt_upscale_params {
+    float sigma_normal; /* guide edge-stops, as rt_denoise_params'             defaults: rt_denoise's */
+    float sigma_albedo;
+    float sigma_depth;
+    float min_weight;   /* tier 1 is taken when its weight sum is above this, [0, 1)      default 0.1 */
+} rt_upscale_params;
+void rt_upscale_default_params(rt_upscale_params* params);
+int rt_upscale(rt_context* ctx, int w_lo, int h_lo, int w, int h, const float* rgba_lo, const float* sigma_lo,
+               const float* albedo_lo, const float* normal_depth_lo, const float* albedo_hi, const float* normal_depth_hi,
+               const rt_upscale_params* params, float* rgba_out, float* sigma_out);
+int rt_upscale_device(rt_context* ctx, int w_lo, int h_lo, int w, int h, const void* d_rgba_lo, const void* d_sigma_lo,
+                      const void* d_albedo_lo, const void* d_normal_depth_lo, const void* d_albedo_hi,
+                      const void* d_normal_depth_hi, const rt_upscale_params* params, void* d_rgba_out, void* d_sigma_out,
+                      void* stream);
 
 /* Counters of the last render when enabled (RT_STAT_* order, rt_device.h);
  * with n up to 2 * RT_STAT_COUNT the second block is the share of the

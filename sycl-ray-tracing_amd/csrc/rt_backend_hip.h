@@ -12,6 +12,7 @@
 //   rt_dnv.hip      the variance-guided post stage and the absolute noise figure it takes
 //   rt_temporal.hip temporal accumulation: the previous frame reprojected and blended in
 //   rt_firefly.hip  firefly rejection: a pixel's luminance limited by a rank of its neighbours'
+//   rt_upscale.hip  guided upscale: a low-resolution frame taken to the output size along the full-size guides
 //   rt_meter.hip    exposure metering: the luminance histogram of a linear frame
 #pragma once
 
@@ -135,6 +136,7 @@ struct PostVar;  // (rt_dnv.hip: the variance-guided filter's buffers, Post's si
 struct PostTemporal;  // (rt_temporal.hip: temporal accumulation's staging buffer, PostVar's sibling)
 struct PostFirefly;  // (rt_firefly.hip: the firefly stage's staging buffer, PostTemporal's sibling)
 struct PostMeter;  // (rt_meter.hip: the metering stage's staging buffer, PostFirefly's sibling)
+struct PostUpscale;  // (rt_upscale.hip: the upscale stage's staging buffer, PostMeter's sibling)
 struct Query;
 struct PostDelete {
     void operator()(Post* p) const;
@@ -150,6 +152,9 @@ struct PostFireflyDelete {
 };
 struct PostMeterDelete {
     void operator()(PostMeter* p) const;
+};
+struct PostUpscaleDelete {
+    void operator()(PostUpscale* p) const;
 };
 struct QueryDelete {
     void operator()(Query* q) const;
@@ -228,6 +233,7 @@ struct Backend {
     std::unique_ptr<PostTemporal, PostTemporalDelete> post_temporal;  // (rt_temporal.hip)
     std::unique_ptr<PostFirefly, PostFireflyDelete> post_firefly;     // (rt_firefly.hip)
     std::unique_ptr<PostMeter, PostMeterDelete> post_meter;           // (rt_meter.hip)
+    std::unique_ptr<PostUpscale, PostUpscaleDelete> post_upscale;     // (rt_upscale.hip)
 };
 
 Backend* rt_backend_dev0(rt_context* c);  // rt_backend.hip: the root device's Backend
@@ -240,8 +246,8 @@ Backend* rt_backend_dev0(rt_context* c);  // rt_backend.hip: the root device's B
 // b's device is current until the StagedCall leaves scope, then the caller's again.
 // The host forms' streams are inherited from the stages as they were written, not chosen here:
 //   null stream   features, denoise (Post::io), denoise_var (PostVar::io), temporal_accumulate
-//                 (PostTemporal::io), firefly (PostFirefly::io), meter (PostMeter::io), display (disp),
-//                 queries (Query::io), rt_render (fb)
+//                 (PostTemporal::io), firefly (PostFirefly::io), meter (PostMeter::io), upscale (PostUpscale::io),
+//                 display (disp), queries (Query::io), rt_render (fb)
 //   Backend::own  noise and noise_sigma (pg_noise), progressive resolves (pg_out), pixel lists (fb)
 struct StagedCall {
     rt_context* c = nullptr;

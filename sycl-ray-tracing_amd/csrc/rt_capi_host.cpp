@@ -14,6 +14,7 @@
 #include "rt_noise.h"
 #include "rt_temporal.h"
 #include "rt_firefly.h"
+#include "rt_upscale.h"
 #include "rt_meter.h"
 
 namespace {
@@ -257,6 +258,7 @@ int rt_test_schedule(rt_context* c, const char* key, double value)
     else if (k == "dn_variant") s.dn_variant = std::max(0, std::min(2, v));
     else if (k == "ff_variant") s.ff_variant = std::max(0, std::min(2, v));
     else if (k == "mt_variant") s.mt_variant = std::max(0, std::min(2, v));
+    else if (k == "up_variant") s.up_variant = std::max(0, std::min(2, v));
     else if (k == "mt_blocks") s.mt_blocks = std::max(0, std::min(65536, v));
     else if (k == "rq_variant") s.rq_variant = std::max(0, std::min(2, v));
     else if (k == "chain_full") {
@@ -943,6 +945,93 @@ int rt_firefly_device(rt_context* c, int w, int h, const void* in, const void* s
     rtk::FireflyArgs A;
     if (int r = firefly_ready(c, "rt_firefly_device", w, h, in, sigma, params, out, sigma_out, scale_out, true, A)) return r;
     return rt_backend_firefly(c, A, out, sigma_out, scale_out, true, stream);
+}
+
+// ---- guided upscale (rt_upscale.h)
+// The guide sigmas are rt_denoise's; min_weight is the share of a pixel's bilinear weight below which
+// the four taps are taken as not seeing its surface.
+void rt_upscale_default_params(rt_upscale_params* p)
+{
+    if (!p) return;
+    rt_denoise_params d;
+    rt_denoise_default_params(&d);
+    p->sigma_normal = d.sigma_normal;
+    p->sigma_albedo = d.sigma_albedo;
+    p->sigma_depth = d.sigma_depth;
+    p->min_weight = 0.1f;
+}
+
+static int upscale_ready(rt_context* c, const char* fn, int w_lo, int h_lo, int w, int h, const void* rgba_lo,
+                         const void* sigma_lo, const void* alb_lo, const void* nd_lo, const void* alb_hi, const void* nd_hi,
+                         const rt_upscale_params* params, const void* out, const void* sigma_out, bool device, rtk::UpArgs& A)
+{
+    const std::string f = fn;
+    if (!c) return rt_fail(nullptr, RT_ERR_ARG, f + ": ctx is NULL");
+    if (w_lo <= 0 || h_lo <= 0 || w <= 0 || h <= 0) return rt_fail(c, RT_ERR_ARG, f + ": every size must be at least 1");
+    if (w_lo > w || h_lo > h) return rt_fail(c, RT_ERR_ARG, f + ": the low frame is larger than the output (w_lo > w or h_lo > h)");
+    if (!rgba_lo || !alb_lo || !nd_lo || !alb_hi || !nd_hi || !out)
+        return rt_fail(c, RT_ERR_ARG, f + ": a frame, a guide buffer or rgba_out is NULL");
+    if (sigma_out && !sigma_lo) return rt_fail(c, RT_ERR_ARG, f + ": sigma_out without a sigma_lo");
+    if (sigma_lo && !sigma_out) return rt_fail(c, RT_ERR_ARG, f + ": sigma_lo without a sigma_out");
+    // (rt_denoise's frame-size limits, on the output: the kernels tile it 4 rows per block as its kernels do)
+    if ((double)w * (double)h > 134217727.0) return rt_fail(c, RT_ERR_ARG, f + ": too many pixels");
+    if (h > 4 * 65535) return rt_fail(c, RT_ERR_ARG, f + ": height above 262140 rows");
+    rt_upscale_params p;
+    if (params) p = *params;
+    else rt_upscale_default_params(&p);
+    const float sig[3] = {p.sigma_normal, p.sigma_albedo, p.sigma_depth};
+    for (float s : sig)
+        if (!(s > 0.0f) || !std::isfinite(s))
+            return rt_fail(c, RT_ERR_ARG, f + ": sigma_normal, sigma_albedo and sigma_depth must be positive and finite");
+    if (!(p.min_weight >= 0.0f && p.min_weight < 1.0f)) return rt_fail(c, RT_ERR_ARG, f + ": min_weight must lie in [0, 1)");
+    const size_t n_lo = (size_t)w_lo * h_lo, n = (size_t)w * h;
+    const struct {
+        const void* p;
+        size_t bytes;
+    } ins[6] = {{rgba_lo, 16 * n_lo}, {sigma_lo, 4 * n_lo}, {alb_lo, 16 * n_lo}, {nd_lo, 16 * n_lo}, {alb_hi, 16 * n}, {nd_hi, 16 * n}},
+      outs[2] = {{out, 16 * n}, {sigma_out, 4 * n}};
+    for (int o = 0; o < 2; o++) {
+        if (!outs[o].p) continue;
+        for (int i = 0; i < 6; i++)
+            if (ins[i].p && ranges_overlap(outs[o].p, outs[o].bytes, ins[i].p, ins[i].bytes))
+                return rt_fail(c, RT_ERR_ARG, f + ": an output overlaps an input");
+    }
+    if (sigma_out && ranges_overlap(out, 16 * n, sigma_out, 4 * n)) return rt_fail(c, RT_ERR_ARG, f + ": two outputs overlap");
+    if (device) {
+        const void* p16[6] = {rgba_lo, alb_lo, nd_lo, alb_hi, nd_hi, out};
+        for (const void* q : p16)
+            if ((uintptr_t)q % 16 != 0)
+                return rt_fail(c, RT_ERR_ARG, f + ": the float4 buffers must be 16-byte aligned, the float buffers 4-byte aligned");
+        if ((uintptr_t)sigma_lo % 4 != 0 || (uintptr_t)sigma_out % 4 != 0)
+            return rt_fail(c, RT_ERR_ARG, f + ": the float4 buffers must be 16-byte aligned, the float buffers 4-byte aligned");
+    }
+    A = rtk::UpArgs{w_lo, h_lo, w, h, (float)w_lo / (float)w, (float)h_lo / (float)h, rtk::dn_inv_sigma2(p.sigma_normal),
+                    rtk::dn_inv_sigma2(p.sigma_albedo), rtk::dn_inv_sigma2(p.sigma_depth), p.min_weight,
+                    (const float4_*)rgba_lo, (const float*)sigma_lo, (const float4_*)alb_lo, (const float4_*)nd_lo,
+                    (const float4_*)alb_hi, (const float4_*)nd_hi};
+    return RT_OK;
+}
+
+int rt_upscale(rt_context* c, int w_lo, int h_lo, int w, int h, const float* rgba_lo, const float* sigma_lo,
+               const float* albedo_lo, const float* normal_depth_lo, const float* albedo_hi, const float* normal_depth_hi,
+               const rt_upscale_params* params, float* rgba_out, float* sigma_out)
+{
+    rtk::UpArgs A;
+    if (int r = upscale_ready(c, "rt_upscale", w_lo, h_lo, w, h, rgba_lo, sigma_lo, albedo_lo, normal_depth_lo, albedo_hi,
+                              normal_depth_hi, params, rgba_out, sigma_out, false, A))
+        return r;
+    return rt_backend_upscale(c, A, rgba_out, sigma_out, false, nullptr);
+}
+
+int rt_upscale_device(rt_context* c, int w_lo, int h_lo, int w, int h, const void* rgba_lo, const void* sigma_lo,
+                      const void* albedo_lo, const void* normal_depth_lo, const void* albedo_hi, const void* normal_depth_hi,
+                      const rt_upscale_params* params, void* rgba_out, void* sigma_out, void* stream)
+{
+    rtk::UpArgs A;
+    if (int r = upscale_ready(c, "rt_upscale_device", w_lo, h_lo, w, h, rgba_lo, sigma_lo, albedo_lo, normal_depth_lo,
+                              albedo_hi, normal_depth_hi, params, rgba_out, sigma_out, true, A))
+        return r;
+    return rt_backend_upscale(c, A, rgba_out, sigma_out, true, stream);
 }
 
 // ---- exposure metering (rt_meter.h)

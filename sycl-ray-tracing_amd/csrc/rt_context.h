@@ -37,6 +37,7 @@ struct RtSchedule {
     int dn_variant = 0;        // rt_denoise's filter kernel: 0 per step as measured, 1 direct, 2 LDS tile where built
     int ff_variant = 0;        // rt_firefly's kernel: 0 as measured, 1 direct loads, 2 the LDS tile of luminances
     int mt_variant = 0;        // rt_meter's kernel: 0 as measured, 1 the direct kernel, 2 the LDS kernel
+    int up_variant = 0;        // rt_upscale's kernel: 0 as measured, 1 direct loads, 2 the LDS footprint
     int mt_blocks = 0;         // rt_meter's grid: 0 the product's cap, n > 0 that many blocks (many grid-stride rounds)
     int rq_variant = 0;        // rt_query's fast kernel: 0 as measured, 1 plain grid-stride rounds, 2 per-quad refill
     bool chain_full = false;   // the scene view reports chain_monotone = 0: chain_ok / quad_chain_ok run their full
@@ -177,6 +178,13 @@ int rt_backend_firefly(rt_context* ctx, rtk::FireflyArgs A, void* rgba_out, void
 // Exposure metering (rt_meter.h), on the root device like the post stage: in (w*h float4) -> hist
 // (rtk::MT_WORDS uint32 words, cleared by the call). The arguments are validated (rt_capi_host.cpp).
 int rt_backend_meter(rt_context* ctx, int w, int h, const void* in, void* hist, bool device, void* stream);
+// The guided upscale (rt_upscale.h), on the root device like the post stage: A holds the validated sizes and
+// parameters, the low frame (w_lo*h_lo float4), its sigma (floats, or null) and guides, and the full-size guides
+// (w*h float4); rgba_out (w*h float4) is required, sigma_out (w*h floats) is null exactly when A.sigma_lo is.
+namespace rtk {
+struct UpArgs;
+}
+int rt_backend_upscale(rt_context* ctx, rtk::UpArgs A, void* rgba_out, void* sigma_out, bool device, void* stream);
 // The display stage (rt_display.h), on the root device like the post stage: in (w*h float4) ->
 // out (w*h float4, may be `in`, or null) and out8 (w*h RGBA bytes, rows reversed when flip, or
 // null). The arguments are validated and inv_gamma = 1.0f / gamma (rt_capi_host.cpp).

@@ -23,6 +23,7 @@
 #include "rt_query.h"
 #include "rt_temporal.h"
 #include "rt_firefly.h"
+#include "rt_upscale.h"
 #include "rt_meter.h"
 #include "rt_wave.h"
 
@@ -817,6 +818,26 @@ int rt_backend_firefly(rt_context* c, rtk::FireflyArgs A, void* rgba_out, void* 
     const double t0 = omp_get_wtime();
     if (A.radius == 1) firefly_rows<1>(A, (float4_*)rgba_out, (float*)sigma_out, (float*)scale_out);
     else firefly_rows<2>(A, (float4_*)rgba_out, (float*)sigma_out, (float*)scale_out);
+    c->last_kernel_ms = (omp_get_wtime() - t0) * 1e3;
+    return RT_OK;
+}
+
+// The guided upscale on the host: the loop around rt_upscale.h's up_pixel that the kernels of
+// rt_upscale.hip run one thread per output pixel, the taps read straight from the low frame (UpDirect).
+int rt_backend_upscale(rt_context* c, rtk::UpArgs A, void* rgba_out, void* sigma_out, bool, void*)
+{
+    const double t0 = omp_get_wtime();
+    const rtk::UpDirect F{A};
+    float4_* out = (float4_*)rgba_out;
+    float* sout = (float*)sigma_out;
+#pragma omp parallel for schedule(static)
+    for (int y = 0; y < A.h; y++)
+        for (int x = 0; x < A.w; x++) {
+            const size_t p = (size_t)y * A.w + x;
+            const rtk::UpOut r = rtk::up_pixel(A, x, y, A.nd_hi[p], A.alb_hi[p], F);
+            out[p] = r.rgba;
+            if (sout) sout[p] = r.sigma;
+        }
     c->last_kernel_ms = (omp_get_wtime() - t0) * 1e3;
     return RT_OK;
 }

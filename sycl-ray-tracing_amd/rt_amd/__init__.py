@@ -26,7 +26,7 @@ import numpy as np
 
 from . import _capi
 from ._capi import (METER_STATS, METER_WORDS, DenoiseParams, DenoiseVarParams, DisplayParams, FireflyParams,  # noqa: F401
-                    MeterParams, MeterResult, NoiseStats, TemporalParams)
+                    MeterParams, MeterResult, NoiseStats, TemporalParams, UpscaleParams)
 from ._capi import (RT_ERR_ARG, RT_ERR_HIP, RT_ERR_IO, RT_ERR_NODEV, RT_ERR_STATE, RT_OK,  # noqa: F401
                     RtError, check, lib, ptr)
 
@@ -35,7 +35,7 @@ __all__ = ["Camera", "Image", "ParsedOBJ", "parse_obj", "compute_env_map_cdf", "
            "image_to_rgba8", "DenoiseParams", "denoise_default_params", "DisplayParams", "write_image_hdr", "DenoiseVarParams",
            "denoise_var_default_params", "TemporalParams", "temporal_default_params", "TemporalHistory",
            "FireflyParams", "firefly_default_params", "MeterParams", "meter_default_params", "meter_stats", "meter_solve",
-           "ExposureAdapter", "METER_WORDS", "METER_STATS"]
+           "ExposureAdapter", "METER_WORDS", "METER_STATS", "UpscaleParams", "upscale_default_params"]
 
 
 # ------------------------------------------------------------------ camera
@@ -217,6 +217,26 @@ def _firefly_params(L_, params) -> FireflyParams:
     for k, v in (params or {}).items():
         if k not in dict(FireflyParams._fields_):
             raise TypeError(f"unknown firefly parameter {k}")
+        setattr(p, k, v)
+    return p
+
+
+def upscale_default_params(hostsim: bool = False) -> UpscaleParams:
+    """rt_upscale_default_params: the guided upscale stage's defaults."""
+    p = UpscaleParams()
+    lib(hostsim).rt_upscale_default_params(ctypes.byref(p))
+    return p
+
+
+def _upscale_params(L_, params) -> UpscaleParams:
+    """params: None (defaults), an UpscaleParams, or a dict of its fields over the defaults."""
+    if isinstance(params, UpscaleParams):
+        return params
+    p = UpscaleParams()
+    L_.rt_upscale_default_params(ctypes.byref(p))
+    for k, v in (params or {}).items():
+        if k not in dict(UpscaleParams._fields_):
+            raise TypeError(f"unknown upscale parameter {k}")
         setattr(p, k, v)
     return p
 
@@ -683,14 +703,15 @@ class RenderKernel:
         check(self.L, self.L.rt_camera_rays(self.ctx, self.width, self.height, ptr(rays)), self.ctx, "rt_camera_rays")
         return rays
 
-    def features(self):
+    def features(self, size=None):
         """rt_render_features: (albedo, normal_depth), each [h, w, 4] float32: the first hit of
-        every pixel's centre ray, {diffuse rgb, 0} and {n.xyz, t} (miss: zeros and t = -1)."""
+        every pixel's centre ray, {diffuse rgb, 0} and {n.xyz, t} (miss: zeros and t = -1).
+        size: (w, h) of the guides, default the kernel's own (upscale() takes them at both sizes)."""
         self._sync_materials()
-        alb = np.empty((self.height, self.width, 4), np.float32)
+        w, h = size if size is not None else (self.width, self.height)
+        alb = np.empty((h, w, 4), np.float32)
         nd = np.empty_like(alb)
-        check(self.L, self.L.rt_render_features(self.ctx, self.width, self.height, ptr(alb), ptr(nd)), self.ctx,
-              "rt_render_features")
+        check(self.L, self.L.rt_render_features(self.ctx, w, h, ptr(alb), ptr(nd)), self.ctx, "rt_render_features")
         return alb, nd
 
     def features_device(self, d_albedo: int, d_normal_depth: int, stream: int | None = None):
@@ -852,6 +873,41 @@ class RenderKernel:
         check(self.L, self.L.rt_firefly_device(self.ctx, int(width or self.width), int(height or self.height), vp(d_in),
                                                vp(d_sigma), ctypes.byref(p), vp(d_out), vp(d_sigma_out), vp(d_scale_out),
                                                vp(stream)), self.ctx, "rt_firefly_device")
+
+    # ---- guided upscale (rt_upscale; include/rt_hip.h)
+    def upscale(self, low_rgba, low_albedo, low_nd, hi_albedo, hi_nd, sigma=None, params=None):
+        """rt_upscale: a low-resolution linear frame (an Image or [h_lo, w_lo, 4] float32) taken to the size of the
+        full-size guides by joint-bilateral upsampling along them. low_albedo / low_nd and hi_albedo / hi_nd:
+        features() at the two sizes. sigma: the low frame's [h_lo, w_lo] noise figure, or None. params: None, an
+        UpscaleParams or a dict of its fields. Returns the Image, or (Image, sigma_out [h, w]) with a sigma."""
+        f4 = lambda a: np.ascontiguousarray(a.pixels if isinstance(a, Image) else a, dtype=np.float32)  # noqa: E731
+        lo, la, ln, ha, hn = f4(low_rgba), f4(low_albedo), f4(low_nd), f4(hi_albedo), f4(hi_nd)
+        h_lo, w_lo = lo.shape[:2]
+        h, w = hn.shape[:2]
+        assert la.shape == ln.shape == (h_lo, w_lo, 4) and lo.shape == la.shape, "the low frame and its guides: one size"
+        assert ha.shape == (h, w, 4) and hn.shape == ha.shape, "the full-size guides: one size"
+        sig = s_out = None
+        if sigma is not None:
+            sig = np.ascontiguousarray(sigma, dtype=np.float32)
+            assert sig.shape == (h_lo, w_lo), "sigma is one float per pixel of the low frame"
+            s_out = np.empty((h, w), np.float32)
+        out = Image(w, h)
+        p = _upscale_params(self.L, params)
+        check(self.L, self.L.rt_upscale(self.ctx, w_lo, h_lo, w, h, ptr(lo), ptr(sig), ptr(la), ptr(ln), ptr(ha), ptr(hn),
+                                        ctypes.byref(p), ptr(out.pixels), ptr(s_out)), self.ctx, "rt_upscale")
+        return out if sigma is None else (out, s_out)
+
+    def upscale_device(self, size_lo, size, d_low_rgba: int, d_low_albedo: int, d_low_nd: int, d_hi_albedo: int,
+                       d_hi_nd: int, d_out: int, d_sigma: int | None = None, d_sigma_out: int | None = None, params=None,
+                       stream: int | None = None):
+        """rt_upscale_device: device buffers (4 floats per pixel for the frames and guides, 1 for the sigmas) at
+        size_lo = (w_lo, h_lo) and size = (w, h); no wait."""
+        p = _upscale_params(self.L, params)
+        vp = lambda a: ctypes.c_void_p(a) if a else None  # noqa: E731
+        check(self.L, self.L.rt_upscale_device(self.ctx, int(size_lo[0]), int(size_lo[1]), int(size[0]), int(size[1]),
+                                               vp(d_low_rgba), vp(d_sigma), vp(d_low_albedo), vp(d_low_nd), vp(d_hi_albedo),
+                                               vp(d_hi_nd), ctypes.byref(p), vp(d_out), vp(d_sigma_out), vp(stream)),
+              self.ctx, "rt_upscale_device")
 
     def render_variants(self, materials, frames=None, device_ptrs=None, row_offset: int = 0, row_stride: int = 1):
         """rt_render_variants: the material sweep as replicas. `materials` is

@@ -39,6 +39,7 @@ EXPORTS = [
     "rt_denoise_var_device",
     "rt_temporal_default_params", "rt_temporal_accumulate", "rt_temporal_accumulate_device",
     "rt_firefly_default_params", "rt_firefly", "rt_firefly_device",
+    "rt_upscale_default_params", "rt_upscale", "rt_upscale_device",
     "rt_meter_default_params", "rt_meter", "rt_meter_device", "rt_meter_solve",
 ]
 
@@ -86,6 +87,11 @@ class MeterParams(ctypes.Structure):
 class MeterResult(ctypes.Structure):
     """struct rt_meter_result (include/rt_hip.h)."""
     _fields_ = [("exposure", F), ("target", F), ("log2_mean", F), ("valid", I)]
+
+
+class UpscaleParams(ctypes.Structure):
+    """struct rt_upscale_params (include/rt_hip.h)."""
+    _fields_ = [("sigma_normal", F), ("sigma_albedo", F), ("sigma_depth", F), ("min_weight", F)]
 
 
 class DisplayParams(ctypes.Structure):
@@ -187,8 +193,12 @@ _SIGS = {
     "rt_meter": (I, [P, I, I, P, P]),
     "rt_meter_device": (I, [P, I, I, P, P, P]),
     "rt_meter_solve": (I, [P, ctypes.POINTER(MeterParams), F, F, ctypes.POINTER(MeterResult)]),
+    "rt_upscale_default_params": (None, [ctypes.POINTER(UpscaleParams)]),
+    "rt_upscale": (I, [P, I, I, I, I, P, P, P, P, P, P, ctypes.POINTER(UpscaleParams), P, P]),
+    "rt_upscale_device": (I, [P, I, I, I, I, P, P, P, P, P, P, ctypes.POINTER(UpscaleParams), P, P, P]),
     # product-only extras
     "rt_device_meter_kernel_ms": (I, [P, I, I, P, P, I, I, P]),
+    "rt_device_upscale_kernel_ms": (I, [P, I, I, I, I, P, P, P, P, P, P, P, P, I, I, P]),
     "rt_device_libm": (I, [I, I, P, P, P, I]),
     "rt_device_libm_digest": (I, [I, I, ctypes.c_uint32, I, P]),
     "rt_device_last_kernel_ms": (ctypes.c_double, [P]),

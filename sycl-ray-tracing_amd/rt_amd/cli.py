@@ -50,6 +50,13 @@ run goes through render_linear and display as with --gamma=; the final linear fr
 filtered one) is metered, the line "auto-exposure: E" is printed and the frame is displayed with E instead of 1.5.
 KEY replaces the default key of 0.18. Each preview is metered on its own. Without the flag a run writes the bytes
 it writes today.
+
+Guided upscale (RenderKernel.upscale): --upscale=F, 1 < F <= 4. The scene is rendered, and under --denoise=var
+filtered, at max(1, round(w / F)) x max(1, round(h / F)); the first-hit guides are rendered at that size and at
+w x h, the linear frame (and the filtered one) is upscaled along them, and metering, display, --hdr-out, the
+fixed-sigma filter and the four PNGs follow at w x h. The run goes through render_linear and display as with
+--gamma=. Previews, checkpoints and RT_samples.png have the low size. The line "upscale: WLxHL -> WxH" is printed.
+Without the flag a run writes the bytes it writes today.
 """
 from __future__ import annotations
 
@@ -66,7 +73,7 @@ def parse(argv):
     a = dict(obj="data/OBJs/cornell_pbr.obj", sky="data/Skyspheres/evening_road_01_puresky_2k.hdr", w=512, h=512,
              samples=64, bounces=8, camera="dragon", out=".", hostsim=False, preview_every=0, checkpoint="",
              exposure=None, gamma=None, hdr_out="", noise_threshold=None, adaptive=False, denoise="atrous", firefly=None,
-             auto_exposure=None)
+             auto_exposure=None, upscale=None)
     for s in argv:
         if s == "--hostsim":
             a["hostsim"] = True
@@ -83,7 +90,7 @@ def parse(argv):
         elif s.startswith(("--sky=", "--camera=", "--out=", "--checkpoint=", "--hdr-out=", "--denoise=")):
             k, v = s[2:].split("=", 1)
             a[k.replace("-", "_")] = v
-        elif s.startswith(("--exposure=", "--gamma=", "--noise-threshold=")):
+        elif s.startswith(("--exposure=", "--gamma=", "--noise-threshold=", "--upscale=")):
             k, v = s[2:].split("=", 1)
             a[k.replace("-", "_")] = float(v)
         elif s.startswith(("--w=", "--h=", "--samples=", "--bounces=", "--preview-every=")):
@@ -109,9 +116,14 @@ def display_stage(a: dict) -> bool:
 
 
 def linear_path(a: dict) -> bool:
-    """The frame is rendered or resolved linear and displayed afterwards: the display stage's flags, or
-    --denoise=var, which filters the linear frame."""
-    return display_stage(a) or a["denoise"] == "var"
+    """The frame is rendered or resolved linear and displayed afterwards: the display stage's flags,
+    --denoise=var, which filters the linear frame, or --upscale=, which upscales it."""
+    return display_stage(a) or a["denoise"] == "var" or a["upscale"] is not None
+
+
+def low_size(a: dict):
+    """--upscale=F: the size the scene is rendered at."""
+    return max(1, int(round(a["w"] / a["upscale"]))), max(1, int(round(a["h"] / a["upscale"])))
 
 
 def display_args(a: dict, exposure=None) -> dict:
@@ -233,12 +245,18 @@ def main(argv=None) -> int:
     if a["auto_exposure"] and not 0.0 < a["auto_exposure"]["key"] < 1.0:
         print("--auto-exposure=KEY takes a key inside (0, 1)", file=sys.stderr)
         return 2
+    if a["upscale"] is not None and not 1.0 < a["upscale"] <= 4.0:
+        print("--upscale=F takes a factor with 1 < F <= 4", file=sys.stderr)
+        return 2
     print(f"Reading OBJ {a['obj']} ...")
     P = rt_amd.parse_obj(a["obj"])
     print(f"Reading Environment Map {a['sky']} ...")
     sky = rt_amd.read_image_float(a["sky"])
     print(f"[{a['w']}x{a['h']}]: {a['samples']} samples\n")
     t0 = time.perf_counter()
+    full = (a["w"], a["h"])
+    if a["upscale"] is not None:  # (everything up to the upscale runs at the low size)
+        a = dict(a, w=low_size(a)[0], h=low_size(a)[1])
     fb = rt_amd.Image(a["w"], a["h"])
     rk = rt_amd.RenderKernel(a["w"], a["h"], a["samples"], a["bounces"], fb, P.triangles, P.materials,
                              P.emissive_triangle_indices, P.material_indices, None, rt_amd.BVH(P.triangles), sky,
@@ -257,6 +275,13 @@ def main(argv=None) -> int:
         rk.render_linear()
     else:
         rk.render()
+    guides = True
+    if a["upscale"] is not None:  # (the linear frame, and the filtered one, to the full size along the guides)
+        print(f"upscale: {a['w']}x{a['h']} -> {full[0]}x{full[1]}")
+        low_guides, guides = rk.features(), rk.features(size=full)
+        fb = rk.upscale(fb, *low_guides, *guides)
+        if filtered is not None:
+            filtered = rk.upscale(filtered, *low_guides, *guides)
     if linear_path(a):  # fb holds the linear radiance: the .hdr file, then the displayed frame
         if a["hdr_out"]:
             rt_amd.write_image_hdr(fb, a["hdr_out"])
@@ -267,7 +292,7 @@ def main(argv=None) -> int:
     print(f"{int((time.perf_counter() - t0) * 1e3)}ms")
     with np.errstate(all="ignore"):
         if filtered is None:
-            filtered = rk.denoise(fb, 1.0)
+            filtered = rk.denoise(fb, 1.0, guides)
         os.makedirs(a["out"], exist_ok=True)
         rt_amd.write_image_png(fb, os.path.join(a["out"], "RT_output.png"))
         for factor, name in ((1.0, "1"), (0.75, "0.75"), (0.5, "0.5")):
