@@ -51,6 +51,10 @@ $(OBJ)/rt_hostsim.o: $(SRC)/rt_hostsim.cpp $(HDRS) $(ALL_SRC)
 #   rt_firefly   firefly rejection: a pixel's luminance limited by a rank of its neighbours'
 #   rt_meter     exposure metering: the luminance histogram of a linear frame
 #   rt_upscale   guided upscale: a low-resolution frame taken to the output size along the full-size guides
+# (the host forms of the last four stage through a DevBuf of Backend each, rt_backend_hip.h, as rt_display does)
+# the backend-independent C ABI, in both libraries: contexts, scene, renders, queries, progressions
+# (rt_capi_host) and the frame stages with their shared argument rules (rt_capi_stages, rt_stage_args.h)
+CAPI_OBJS := $(OBJ)/rt_capi_host.host.o $(OBJ)/rt_capi_stages.host.o
 HIP_UNITS := rt_render rt_wave_run rt_probe rt_denoise rt_query rt_display rt_noise rt_adapt rt_dnv rt_temporal rt_firefly \
              rt_meter rt_upscale
 $(HIP_UNITS:%=$(OBJ)/%.o): $(OBJ)/%.o: $(SRC)/%.hip $(HDRS)
@@ -62,7 +66,7 @@ $(OBJ)/rt_backend.o: $(SRC)/rt_backend.hip $(HDRS) $(ALL_SRC)
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -DRT_BUILD_SRC='"$(SRC_HASH)"' -c $< -o $@
 
-$(LIB)/librt_hip.so: $(HIP_UNITS:%=$(OBJ)/%.o) $(OBJ)/rt_backend.o $(OBJ)/rt_scene.host.o $(OBJ)/rt_imageio.host.o $(OBJ)/rt_capi_host.host.o
+$(LIB)/librt_hip.so: $(HIP_UNITS:%=$(OBJ)/%.o) $(OBJ)/rt_backend.o $(OBJ)/rt_scene.host.o $(OBJ)/rt_imageio.host.o $(CAPI_OBJS)
 	@mkdir -p $(LIB)
 	$(HIPCC) -shared --offload-arch=$(ARCH) -fPIC $^ -o $@
 
@@ -73,7 +77,7 @@ stamp: $(LIB)/librt_hip.so
 	  git diff --quiet HEAD -- $(SRC) include 2>/dev/null || c="$$c-dirty"; \
 	  h=$$(cat $(SRC)/* include/*.h | sha256sum | cut -c1-12); echo "$$c src=$$h" > BUILD_COMMIT
 
-$(LIB)/librt_hostsim.so: $(OBJ)/rt_hostsim.o $(OBJ)/rt_scene.host.o $(OBJ)/rt_imageio.host.o $(OBJ)/rt_capi_host.host.o
+$(LIB)/librt_hostsim.so: $(OBJ)/rt_hostsim.o $(OBJ)/rt_scene.host.o $(OBJ)/rt_imageio.host.o $(CAPI_OBJS)
 	@mkdir -p $(LIB)
 	$(CXX) -shared -fopenmp $^ -o $@
 
@@ -132,7 +136,7 @@ clean:
 .PHONY: all ref clean stamp
 
 # experiment builds: make variant V=name DEFS="-DRT_TAIL_OCC=2" -> lib/librt_hip_name.so (RT_HIP_LIB=...)
-variant: $(OBJ)/rt_scene.host.o $(OBJ)/rt_imageio.host.o $(OBJ)/rt_capi_host.host.o
+variant: $(OBJ)/rt_scene.host.o $(OBJ)/rt_imageio.host.o $(CAPI_OBJS)
 	@mkdir -p $(LIB)
 	for u in $(HIP_UNITS); do $(HIPCC) $(HIPFLAGS) $(DEFS) -c $(SRC)/$$u.hip -o $(OBJ)/$${u}_$(V).o || exit 1; done
 	$(HIPCC) $(HIPFLAGS) $(DEFS) -DRT_BUILD_SRC='"$(SRC_HASH)"' -DRT_BUILD_DEFS='"$(DEFS)"' -c $(SRC)/rt_backend.hip -o $(OBJ)/rt_backend_$(V).o
@@ -145,7 +149,8 @@ hostsim-variant: $(OBJ)/rt_imageio.host.o
 	$(CXX) $(CXXFLAGS) -fopenmp $(DEFS) -DRT_BUILD_SRC='"$(SRC_HASH)"' -DRT_BUILD_DEFS='"$(DEFS)"' -c $(SRC)/rt_hostsim.cpp -o $(OBJ)/rt_hostsim_$(V).o
 	$(CXX) $(CXXFLAGS) $(DEFS) -c $(SRC)/rt_scene.cpp -o $(OBJ)/rt_scene_$(V).o
 	$(CXX) $(CXXFLAGS) $(DEFS) -c $(SRC)/rt_capi_host.cpp -o $(OBJ)/rt_capi_host_$(V).o
-	$(CXX) -shared -fopenmp $(OBJ)/rt_hostsim_$(V).o $(OBJ)/rt_scene_$(V).o $(OBJ)/rt_capi_host_$(V).o $(OBJ)/rt_imageio.host.o -o $(LIB)/librt_hostsim_$(V).so
+	$(CXX) $(CXXFLAGS) $(DEFS) -c $(SRC)/rt_capi_stages.cpp -o $(OBJ)/rt_capi_stages_$(V).o
+	$(CXX) -shared -fopenmp $(OBJ)/rt_hostsim_$(V).o $(OBJ)/rt_scene_$(V).o $(OBJ)/rt_capi_host_$(V).o $(OBJ)/rt_capi_stages_$(V).o $(OBJ)/rt_imageio.host.o -o $(LIB)/librt_hostsim_$(V).so
 
 # C++ drop-in check (container only): include/render_kernel_hip.h against the
 # reference's headers and objects (oracle/_ref, `make ref`), linked to the hostsim
@@ -190,7 +195,7 @@ build/%_test_hip: tests/native/%_test.cpp include/render_kernel_hip.h include/rt
 # TSan: libgomp is not TSan-instrumented (its barriers would be reported as races), so the
 # TSan run uses one OpenMP thread per region; what it checks is the std::thread layer of the
 # multi-device driver (rt_for_devices, rt_render_variants) and the shared context state.
-SAN_SRCS := $(SRC)/rt_hostsim.cpp $(SRC)/rt_scene.cpp $(SRC)/rt_imageio.cpp $(SRC)/rt_capi_host.cpp
+SAN_SRCS := $(SRC)/rt_hostsim.cpp $(SRC)/rt_scene.cpp $(SRC)/rt_imageio.cpp $(SRC)/rt_capi_host.cpp $(SRC)/rt_capi_stages.cpp
 SAN_NUM := -ffp-contract=off -fno-fast-math -fno-omit-frame-pointer -g -O1 -fopenmp
 ASAN := -fsanitize=address,undefined -fno-sanitize-recover=undefined
 TSAN := -fsanitize=thread
@@ -209,37 +214,17 @@ sanitize: build/san_asan/driver build/san_tsan/driver
 
 .PHONY: sanitize
 
-# render_adaptive and the adaptive C calls under ASan + UBSan: tests/native/adaptive_shim_test.cpp with the
-# hostsim sources of build/san_asan in one stand-alone executable (container only: the reference's objects).
-build/san_asan/adaptive_shim_test: tests/native/adaptive_shim_test.cpp include/render_kernel_hip.h build/san_asan/driver
+# A drop-in's program under ASan + UBSan: tests/native/X_shim_test.cpp with the hostsim sources of build/san_asan
+# in one stand-alone executable, a host program with its own main (container only: the reference's objects).
+#   sanitize-adaptive  render_adaptive and the adaptive C calls   (builds)
+#   sanitize-firefly   firefly_clamp and the firefly C calls      (builds)
+#   sanitize-meter     meter / auto_exposure and the metering C calls   (builds, then runs on the small Cornell scene)
+#   sanitize-upscale   upscale and the upscale C calls                  (builds, then runs on the small Cornell scene)
+build/san_asan/%_shim_test: tests/native/%_shim_test.cpp include/render_kernel_hip.h build/san_asan/driver
 	$(CXX) -std=gnu++20 $(SAN_NUM) $(ASAN) -Iinclude -I$(REFDIR)/include -I$(REFDIR)/rapidobj -I$(REFDIR) $< \
 	  $(filter-out build/san_asan/cpu_oracle.o,$(wildcard build/san_asan/*.o)) $(REFOBJS) -Wl,--gc-sections -o $@
-sanitize-adaptive: build/san_asan/adaptive_shim_test
-.PHONY: sanitize-adaptive
-
-# firefly_clamp and the firefly C calls under ASan + UBSan, in the same way.
-build/san_asan/firefly_shim_test: tests/native/firefly_shim_test.cpp include/render_kernel_hip.h build/san_asan/driver
-	$(CXX) -std=gnu++20 $(SAN_NUM) $(ASAN) -Iinclude -I$(REFDIR)/include -I$(REFDIR)/rapidobj -I$(REFDIR) $< \
-	  $(filter-out build/san_asan/cpu_oracle.o,$(wildcard build/san_asan/*.o)) $(REFOBJS) -Wl,--gc-sections -o $@
-sanitize-firefly: build/san_asan/firefly_shim_test
-.PHONY: sanitize-firefly
-
-# meter / auto_exposure and the metering C calls under ASan + UBSan, in the same way; the target runs the
-# program (a host program with its own main) on the small Cornell scene.
-build/san_asan/meter_shim_test: tests/native/meter_shim_test.cpp include/render_kernel_hip.h build/san_asan/driver
-	$(CXX) -std=gnu++20 $(SAN_NUM) $(ASAN) -Iinclude -I$(REFDIR)/include -I$(REFDIR)/rapidobj -I$(REFDIR) $< \
-	  $(filter-out build/san_asan/cpu_oracle.o,$(wildcard build/san_asan/*.o)) $(REFOBJS) -Wl,--gc-sections -o $@
-sanitize-meter: build/san_asan/meter_shim_test
+sanitize-adaptive sanitize-firefly: sanitize-%: build/san_asan/%_shim_test
+sanitize-meter sanitize-upscale: sanitize-%: build/san_asan/%_shim_test
 	ASAN_OPTIONS=halt_on_error=1:detect_leaks=1 UBSAN_OPTIONS=print_stacktrace=1:halt_on_error=1 OMP_NUM_THREADS=4 \
-	  build/san_asan/meter_shim_test scenes/cornell_pbr.obj - 33 21 3
-.PHONY: sanitize-meter
-
-# upscale and the upscale C calls under ASan + UBSan, in the same way; the target runs the program (a host
-# program with its own main) on the small Cornell scene.
-build/san_asan/upscale_shim_test: tests/native/upscale_shim_test.cpp include/render_kernel_hip.h build/san_asan/driver
-	$(CXX) -std=gnu++20 $(SAN_NUM) $(ASAN) -Iinclude -I$(REFDIR)/include -I$(REFDIR)/rapidobj -I$(REFDIR) $< \
-	  $(filter-out build/san_asan/cpu_oracle.o,$(wildcard build/san_asan/*.o)) $(REFOBJS) -Wl,--gc-sections -o $@
-sanitize-upscale: build/san_asan/upscale_shim_test
-	ASAN_OPTIONS=halt_on_error=1:detect_leaks=1 UBSAN_OPTIONS=print_stacktrace=1:halt_on_error=1 OMP_NUM_THREADS=4 \
-	  build/san_asan/upscale_shim_test scenes/cornell_pbr.obj - 33 21 3
-.PHONY: sanitize-upscale
+	  $< scenes/cornell_pbr.obj - 33 21 3
+.PHONY: sanitize-adaptive sanitize-firefly sanitize-meter sanitize-upscale

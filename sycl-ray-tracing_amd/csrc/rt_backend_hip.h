@@ -133,28 +133,12 @@ struct Marker {
 // created on first use and deleted with their Backend (its device current).
 struct Post;
 struct PostVar;  // (rt_dnv.hip: the variance-guided filter's buffers, Post's sibling)
-struct PostTemporal;  // (rt_temporal.hip: temporal accumulation's staging buffer, PostVar's sibling)
-struct PostFirefly;  // (rt_firefly.hip: the firefly stage's staging buffer, PostTemporal's sibling)
-struct PostMeter;  // (rt_meter.hip: the metering stage's staging buffer, PostFirefly's sibling)
-struct PostUpscale;  // (rt_upscale.hip: the upscale stage's staging buffer, PostMeter's sibling)
 struct Query;
 struct PostDelete {
     void operator()(Post* p) const;
 };
 struct PostVarDelete {
     void operator()(PostVar* p) const;
-};
-struct PostTemporalDelete {
-    void operator()(PostTemporal* p) const;
-};
-struct PostFireflyDelete {
-    void operator()(PostFirefly* p) const;
-};
-struct PostMeterDelete {
-    void operator()(PostMeter* p) const;
-};
-struct PostUpscaleDelete {
-    void operator()(PostUpscale* p) const;
 };
 struct QueryDelete {
     void operator()(Query* q) const;
@@ -204,6 +188,12 @@ struct Backend {
     DevBuf pg_base, pg_state, pg_out;  // a progression (rt_progress_*): base values, paused state, host-resolve staging
     DevBuf pg_half, pg_noise;          // a tracked one: the A passes' sum; the host noise query's stat words and maps
     DevBuf disp;      // rt_display with host pointers: the frame (in, float out in place), then the 8-bit output
+    // the other stages' host-pointer calls, each its own staging buffer, grown on first use and kept across calls:
+    DevBuf temporal_io;  // rt_temporal_accumulate: the three inputs of this frame, the four of the history, the three outputs
+    DevBuf firefly_io;   // rt_firefly: the frame and its sigma, then the three outputs
+    DevBuf meter_io;     // rt_meter: the frame, then the histogram
+    DevBuf upscale_io;   // rt_upscale: the low frame, its sigma and guides, the full-size guides, then the two outputs
+    int cus = 0;         // the device's compute units, asked by the first rt_meter (rt_meter.hip; 0: not yet)
     DevBuf shard;     // multi-device renders: the root's N blocks of rows_max rows (scatter source /
                       // gather target); device d >= 1: its block
     Pinned<int32_t> h_act[RT_MAX_LANES];  // per lane: live-slot counters (sharded) + 8 fallback counters
@@ -230,10 +220,6 @@ struct Backend {
     std::unique_ptr<PostVar, PostVarDelete> post_var;  // (rt_dnv.hip)
     std::unique_ptr<Query, QueryDelete> query;  // (rt_query.hip)
     std::unique_ptr<Adapt> adapt;               // (rt_adapt.hip)
-    std::unique_ptr<PostTemporal, PostTemporalDelete> post_temporal;  // (rt_temporal.hip)
-    std::unique_ptr<PostFirefly, PostFireflyDelete> post_firefly;     // (rt_firefly.hip)
-    std::unique_ptr<PostMeter, PostMeterDelete> post_meter;           // (rt_meter.hip)
-    std::unique_ptr<PostUpscale, PostUpscaleDelete> post_upscale;     // (rt_upscale.hip)
 };
 
 Backend* rt_backend_dev0(rt_context* c);  // rt_backend.hip: the root device's Backend
@@ -246,7 +232,7 @@ Backend* rt_backend_dev0(rt_context* c);  // rt_backend.hip: the root device's B
 // b's device is current until the StagedCall leaves scope, then the caller's again.
 // The host forms' streams are inherited from the stages as they were written, not chosen here:
 //   null stream   features, denoise (Post::io), denoise_var (PostVar::io), temporal_accumulate
-//                 (PostTemporal::io), firefly (PostFirefly::io), meter (PostMeter::io), upscale (PostUpscale::io),
+//                 (temporal_io), firefly (firefly_io), meter (meter_io), upscale (upscale_io),
 //                 display (disp), queries (Query::io), rt_render (fb)
 //   Backend::own  noise and noise_sigma (pg_noise), progressive resolves (pg_out), pixel lists (fb)
 struct StagedCall {

@@ -1,6 +1,8 @@
 // rt_capi_host.cpp — the backend-independent half of the C ABI
 // (include/rt_hip.h): argument checking, host scene preparation, host
-// helpers. The compute half lives in rt_render.hip (gfx950).
+// helpers: contexts, scene / BVH / env / camera, renders, queries, progressions,
+// stats, mesh and image helpers. The frame stages are rt_capi_stages.cpp. The
+// compute half lives in rt_render.hip (gfx950).
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -10,12 +12,7 @@
 
 #include "rt_adapt.h"
 #include "rt_context.h"
-#include "rt_denoise.h"
 #include "rt_noise.h"
-#include "rt_temporal.h"
-#include "rt_firefly.h"
-#include "rt_upscale.h"
-#include "rt_meter.h"
 
 namespace {
 std::mutex g_err_mu;
@@ -77,10 +74,9 @@ static int create_finish(rt_context* c, rt_context** out)
     return RT_OK;
 }
 
-// The device tables made current. mats_too: a changed material table alone (rt_set_materials,
-// rt_render_variants) is a reason too; env_stub: bind the placeholder env first (the calls that need no env).
+// (rt_context.h) mats_too: rt_set_materials, rt_render_variants
 static void placeholder_env(rt_context* c);
-static int tables_current(rt_context* c, bool mats_too, bool env_stub)
+int rt_tables_current(rt_context* c, bool mats_too, bool env_stub)
 {
     if (!c->dirty && !(mats_too && c->mats_dirty_only)) return RT_OK;
     if (env_stub) placeholder_env(c);
@@ -479,7 +475,7 @@ static int check_ready(rt_context* c, int w, int h, int spp, int bounces)
     // the reference seeds with the int 31 + x*y*spp (render_kernel.cpp:77)
     if ((double)(w - 1) * (double)(h - 1) * (double)spp + 31.0 > 2147483647.0)
         return rt_fail(c, RT_ERR_ARG, "31 + x*y*spp overflows int (reference seed)");
-    return tables_current(c, true, false);
+    return rt_tables_current(c, true, false);
 }
 
 int rt_render(rt_context* c, int w, int h, int spp, int bounces, float* fb)
@@ -551,7 +547,7 @@ int rt_intersect(rt_context* c, const float* rays, int n, void* out)
     if (!c || !c->have_scene || !c->have_bvh) return rt_fail(c, RT_ERR_STATE, "rt_intersect: scene/BVH not set");
     if (n < 0 || (n > 0 && (!rays || !out))) return rt_fail(c, RT_ERR_ARG, "rt_intersect: bad buffers");
     if (n == 0) return RT_OK;
-    if (int r = tables_current(c, false, true)) return r;
+    if (int r = rt_tables_current(c, false, true)) return r;
     return rt_backend_intersect(c, rays, n, out);
 }
 
@@ -571,7 +567,7 @@ static int query_ready(rt_context* c, const char* fn, int mode, const void* rays
         c->query_on_device = false;
         return RT_OK;
     }
-    return tables_current(c, false, true);
+    return rt_tables_current(c, false, true);
 }
 
 // Spheres and the brute-force mode take k_intersect's path for every query (rt_query.h).
@@ -600,587 +596,6 @@ long rt_query_last_exact(rt_context* c)
 {
     if (!c) return rt_fail(nullptr, RT_ERR_ARG, "rt_query_last_exact: ctx is NULL");
     return rt_backend_query_last_exact(c);
-}
-
-// ------------------------------------------------------------- post stage
-int rt_camera_rays(rt_context* c, int w, int h, float* rays)
-{
-    if (!c) return rt_fail(nullptr, RT_ERR_ARG, "rt_camera_rays: ctx is NULL");
-    if (!c->have_cam) return rt_fail(c, RT_ERR_STATE, "rt_camera_rays: camera not set");
-    if (w <= 0 || h <= 0 || !rays) return rt_fail(c, RT_ERR_ARG, "rt_camera_rays: bad arguments");
-    const rtk::CamView V = rtk::cam_view(c->cam, w, h);
-    for (int y = 0; y < h; y++)
-        for (int x = 0; x < w; x++) {
-            rtk::V3 o, d;
-            rtk::feature_ray(V, x, y, o, d);
-            float* r = rays + 6 * ((size_t)y * w + x);
-            r[0] = o.x, r[1] = o.y, r[2] = o.z, r[3] = d.x, r[4] = d.y, r[5] = d.z;
-        }
-    return RT_OK;
-}
-
-static int features_ready(rt_context* c, int w, int h, const void* alb, const void* nd)
-{
-    if (!c) return rt_fail(nullptr, RT_ERR_ARG, "rt_render_features: ctx is NULL");
-    if (!c->have_scene || !c->have_bvh) return rt_fail(c, RT_ERR_STATE, "rt_render_features: scene/BVH not set");
-    if (!c->have_cam) return rt_fail(c, RT_ERR_STATE, "rt_render_features: camera not set");
-    if (w <= 0 || h <= 0 || !alb || !nd || alb == nd) return rt_fail(c, RT_ERR_ARG, "rt_render_features: bad buffers");
-    if ((double)w * (double)h > 268435455.0) return rt_fail(c, RT_ERR_ARG, "rt_render_features: too many pixels");
-    return tables_current(c, true, true);
-}
-
-int rt_render_features(rt_context* c, int w, int h, float* albedo, float* normal_depth)
-{
-    if (int r = features_ready(c, w, h, albedo, normal_depth)) return r;
-    return rt_backend_features(c, w, h, albedo, normal_depth, false, nullptr);
-}
-
-int rt_render_features_device(rt_context* c, int w, int h, void* d_albedo, void* d_normal_depth, void* stream)
-{
-    if (int r = features_ready(c, w, h, d_albedo, d_normal_depth)) return r;
-    return rt_backend_features(c, w, h, d_albedo, d_normal_depth, true, stream);
-}
-
-// Defaults from the quality sweep on Cornell 64x64, 16 spp against 512 spp.
-void rt_denoise_default_params(rt_denoise_params* p)
-{
-    if (!p) return;
-    p->passes = 5;
-    p->sigma_color = 1.0f;
-    p->sigma_normal = 0.3f;
-    p->sigma_albedo = 0.1f;
-    p->sigma_depth = 0.1f;
-}
-
-static int denoise_ready(rt_context* c, int w, int h, const void* in, const void* alb, const void* nd,
-                         const rt_denoise_params* params, float blend, const void* out, rt_denoise_params& p)
-{
-    if (!c) return rt_fail(nullptr, RT_ERR_ARG, "rt_denoise: ctx is NULL");
-    if (w <= 0 || h <= 0 || !in || !out) return rt_fail(c, RT_ERR_ARG, "rt_denoise: bad buffers");
-    if ((double)w * (double)h > 134217727.0) return rt_fail(c, RT_ERR_ARG, "rt_denoise: too many pixels");
-    // (the filter kernels tile the frame 4 rows per block: 65535 blocks in y at most)
-    if (h > 4 * 65535) return rt_fail(c, RT_ERR_ARG, "rt_denoise: height above 262140 rows");
-    if (in == out) return rt_fail(c, RT_ERR_ARG, "rt_denoise: rgba_in and rgba_out are the same buffer");
-    if ((alb == nullptr) != (nd == nullptr))
-        return rt_fail(c, RT_ERR_ARG, "rt_denoise: albedo and normal_depth must both be given or both be NULL");
-    if (params) p = *params;
-    else rt_denoise_default_params(&p);
-    if (p.passes < 1 || p.passes > 10) return rt_fail(c, RT_ERR_ARG, "rt_denoise: passes must be 1..10");
-    const float sig[4] = {p.sigma_color, p.sigma_normal, p.sigma_albedo, p.sigma_depth};
-    for (float s : sig)
-        if (!std::isfinite(s) || !(s > 0.0f)) return rt_fail(c, RT_ERR_ARG, "rt_denoise: a sigma is not finite and > 0");
-    if (!std::isfinite(blend)) return rt_fail(c, RT_ERR_ARG, "rt_denoise: blend is not finite");
-    return RT_OK;
-}
-
-int rt_denoise(rt_context* c, int w, int h, const float* in, const float* alb, const float* nd,
-               const rt_denoise_params* params, float blend, float* out)
-{
-    rt_denoise_params p;
-    if (int r = denoise_ready(c, w, h, in, alb, nd, params, blend, out, p)) return r;
-    return rt_backend_denoise(c, w, h, in, alb, nd, p, blend, out, false, nullptr);
-}
-
-int rt_denoise_device(rt_context* c, int w, int h, const void* in, const void* alb, const void* nd,
-                      const rt_denoise_params* params, float blend, void* out, void* stream)
-{
-    rt_denoise_params p;
-    if (int r = denoise_ready(c, w, h, in, alb, nd, params, blend, out, p)) return r;
-    return rt_backend_denoise(c, w, h, in, alb, nd, p, blend, out, true, stream);
-}
-
-// ---- the variance-guided filter (rt_dnv.h)
-// Defaults from the quality sweep on Cornell 64x64, a uniform and an adaptive 64-sample frame
-// against 512 spp.
-void rt_denoise_var_default_params(rt_denoise_var_params* p)
-{
-    if (!p) return;
-    p->passes = 3;
-    p->sigma_color = 1.0f;
-    p->sigma_normal = 0.3f;
-    p->sigma_albedo = 0.1f;
-    p->sigma_depth = 0.1f;
-    p->var_floor = 0.01f;
-}
-
-static int denoise_var_ready(rt_context* c, int w, int h, const void* in, const void* sigma, const void* alb, const void* nd,
-                             const rt_denoise_var_params* params, float blend, const void* out, const void* sigma_out,
-                             bool device, rt_denoise_var_params& p)
-{
-    if (!c) return rt_fail(nullptr, RT_ERR_ARG, "rt_denoise_var: ctx is NULL");
-    if (params) p = *params;
-    else rt_denoise_var_default_params(&p);
-    // (rt_denoise's own checks, on its share of the arguments)
-    const rt_denoise_params q{p.passes, p.sigma_color, p.sigma_normal, p.sigma_albedo, p.sigma_depth};
-    rt_denoise_params unused;
-    if (int r = denoise_ready(c, w, h, in, alb, nd, &q, blend, out, unused)) return r;
-    if (!sigma) return rt_fail(c, RT_ERR_ARG, "rt_denoise_var: sigma is NULL");
-    if (!std::isfinite(p.var_floor) || !(p.var_floor > 0.0f))
-        return rt_fail(c, RT_ERR_ARG, "rt_denoise_var: var_floor is not finite and > 0");
-    if (device && ((uintptr_t)in % 16 != 0 || (uintptr_t)out % 16 != 0 || (uintptr_t)alb % 16 != 0 || (uintptr_t)nd % 16 != 0 ||
-                   (uintptr_t)sigma % 4 != 0 || (uintptr_t)sigma_out % 4 != 0))
-        return rt_fail(c, RT_ERR_ARG, "rt_denoise_var_device: the float4 buffers must be 16-byte aligned, sigma and "
-                                      "sigma_out 4-byte aligned");
-    return RT_OK;
-}
-
-int rt_denoise_var(rt_context* c, int w, int h, const float* in, const float* sigma, const float* alb, const float* nd,
-                   const rt_denoise_var_params* params, float blend, float* out, float* sigma_out)
-{
-    rt_denoise_var_params p;
-    if (int r = denoise_var_ready(c, w, h, in, sigma, alb, nd, params, blend, out, sigma_out, false, p)) return r;
-    return rt_backend_denoise_var(c, w, h, in, sigma, alb, nd, p, blend, out, sigma_out, false, nullptr);
-}
-
-int rt_denoise_var_device(rt_context* c, int w, int h, const void* in, const void* sigma, const void* alb, const void* nd,
-                          const rt_denoise_var_params* params, float blend, void* out, void* sigma_out, void* stream)
-{
-    rt_denoise_var_params p;
-    if (int r = denoise_var_ready(c, w, h, in, sigma, alb, nd, params, blend, out, sigma_out, true, p)) return r;
-    return rt_backend_denoise_var(c, w, h, in, sigma, alb, nd, p, blend, out, sigma_out, true, stream);
-}
-
-// ---- temporal accumulation (rt_temporal.h)
-// Defaults: SVGF's depth and normal tests at the widths its authors' code uses for static scenes, a
-// history of 32 frames.
-void rt_temporal_default_params(rt_temporal_params* p)
-{
-    if (!p) return;
-    p->depth_tol = 0.05f;
-    p->normal_cos = 0.9f;
-    p->min_weight = 0.1f;
-    p->max_len = 32.0f;
-}
-
-// The inverse of a row-major 4x4 in double (Gauss-Jordan, partial pivoting), rounded to float.
-// false: a non-finite entry, a zero pivot (singular) or a non-finite result.
-static bool invert_view(const float m[16], float inv[16])
-{
-    double a[4][8];
-    for (int r = 0; r < 4; r++)
-        for (int k = 0; k < 4; k++) {
-            if (!std::isfinite(m[4 * r + k])) return false;
-            a[r][k] = m[4 * r + k];
-            a[r][4 + k] = r == k ? 1.0 : 0.0;
-        }
-    for (int col = 0; col < 4; col++) {
-        int piv = col;
-        for (int r = col + 1; r < 4; r++)
-            if (std::fabs(a[r][col]) > std::fabs(a[piv][col])) piv = r;
-        if (a[piv][col] == 0.0) return false;
-        if (piv != col)
-            for (int k = 0; k < 8; k++) std::swap(a[piv][k], a[col][k]);
-        const double d = a[col][col];
-        for (int k = 0; k < 8; k++) a[col][k] /= d;
-        for (int r = 0; r < 4; r++) {
-            if (r == col) continue;
-            const double f = a[r][col];
-            if (f == 0.0) continue;
-            for (int k = 0; k < 8; k++) a[r][k] -= f * a[col][k];
-        }
-    }
-    for (int r = 0; r < 4; r++)
-        for (int k = 0; k < 4; k++) {
-            inv[4 * r + k] = (float)a[r][4 + k];
-            if (!std::isfinite(inv[4 * r + k])) return false;
-        }
-    return true;
-}
-
-static bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb)
-{
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + nb && y < x + na;
-}
-
-static int temporal_ready(rt_context* c, const char* fn, int w, int h, const void* in, const void* sigma, const void* nd,
-                          const float* prev_view, float prev_fov, const void* h_rgba, const void* h_sigma,
-                          const void* h_len, const void* h_nd, const rt_temporal_params* params, const void* out,
-                          const void* sigma_out, const void* len_out, bool device, rtk::TemporalFrame& T)
-{
-    const std::string f = fn;
-    if (!c) return rt_fail(nullptr, RT_ERR_ARG, f + ": ctx is NULL");
-    if (!c->have_cam) return rt_fail(c, RT_ERR_STATE, f + ": camera not set");
-    if (w <= 0 || h <= 0 || !in || !sigma || !nd || !out || !sigma_out || !len_out || !prev_view)
-        return rt_fail(c, RT_ERR_ARG, f + ": bad buffers");
-    // (rt_denoise's frame-size limits: k_temporal tiles the frame 4 rows per block as its kernels do)
-    if ((double)w * (double)h > 134217727.0) return rt_fail(c, RT_ERR_ARG, f + ": too many pixels");
-    if (h > 4 * 65535) return rt_fail(c, RT_ERR_ARG, f + ": height above 262140 rows");
-    const int given = (h_rgba != nullptr) + (h_sigma != nullptr) + (h_len != nullptr) + (h_nd != nullptr);
-    if (given != 0 && given != 4)
-        return rt_fail(c, RT_ERR_ARG, f + ": the four history buffers must all be given or all be NULL");
-    rt_temporal_params p;
-    if (params) p = *params;
-    else rt_temporal_default_params(&p);
-    if (!std::isfinite(p.depth_tol) || !std::isfinite(p.normal_cos) || !std::isfinite(p.min_weight) || !std::isfinite(p.max_len))
-        return rt_fail(c, RT_ERR_ARG, f + ": a parameter is not finite");
-    if (p.depth_tol < 0.0f) return rt_fail(c, RT_ERR_ARG, f + ": depth_tol is negative");
-    if (p.normal_cos < -1.0f || p.normal_cos > 1.0f) return rt_fail(c, RT_ERR_ARG, f + ": normal_cos is outside [-1, 1]");
-    if (p.min_weight < 0.0f || !(p.min_weight < 1.0f)) return rt_fail(c, RT_ERR_ARG, f + ": min_weight is outside [0, 1)");
-    if (p.max_len < 1.0f) return rt_fail(c, RT_ERR_ARG, f + ": max_len is below 1");
-    if (!std::isfinite(prev_fov) || prev_fov == 0.0f) return rt_fail(c, RT_ERR_ARG, f + ": prev_fov_dist is zero or not finite");
-    const size_t n = (size_t)w * h;
-    const struct {
-        const void* p;
-        size_t bytes;
-    } ins[7] = {{in, 16 * n}, {sigma, 4 * n}, {nd, 16 * n}, {h_rgba, 16 * n}, {h_sigma, 4 * n}, {h_len, 4 * n}, {h_nd, 16 * n}},
-      outs[3] = {{out, 16 * n}, {sigma_out, 4 * n}, {len_out, 4 * n}};
-    for (int o = 0; o < 3; o++) {
-        for (int i = 0; i < 7; i++)
-            if (ins[i].p && ranges_overlap(outs[o].p, outs[o].bytes, ins[i].p, ins[i].bytes))
-                return rt_fail(c, RT_ERR_ARG, f + ": an output overlaps an input");
-        for (int k = o + 1; k < 3; k++)
-            if (ranges_overlap(outs[o].p, outs[o].bytes, outs[k].p, outs[k].bytes))
-                return rt_fail(c, RT_ERR_ARG, f + ": two outputs overlap");
-    }
-    if (device) {
-        const void* a16[5] = {in, nd, h_rgba, h_nd, out};
-        const void* a4[5] = {sigma, h_sigma, h_len, sigma_out, len_out};
-        for (int i = 0; i < 5; i++)
-            if ((uintptr_t)a16[i] % 16 != 0 || (uintptr_t)a4[i] % 4 != 0)
-                return rt_fail(c, RT_ERR_ARG, f + ": the float4 buffers must be 16-byte aligned, the float buffers 4-byte aligned");
-    }
-    T.cur = rtk::cam_view(c->cam, w, h);
-    if (!invert_view(prev_view, T.prev_inv.m))
-        return rt_fail(c, RT_ERR_ARG, f + ": prev_view is singular or not finite");
-    T.prev_inv.fov_dist = prev_fov;
-    RtCamera prev;
-    std::memcpy(prev.m, prev_view, 64);
-    prev.fov_dist = prev_fov;
-    const rtk::V3 op = rtk::xform_point(prev, rtk::v3(0.0f, 0.0f, 0.0f));
-    T.o_prev[0] = op.x, T.o_prev[1] = op.y, T.o_prev[2] = op.z;
-    T.depth_tol = p.depth_tol, T.normal_cos = p.normal_cos, T.min_weight = p.min_weight, T.max_len = p.max_len;
-    T.in = (const float4_*)in, T.sigma = (const float*)sigma, T.nd = (const float4_*)nd;
-    T.h_rgba = (const float4_*)h_rgba, T.h_sigma = (const float*)h_sigma, T.h_len = (const float*)h_len;
-    T.h_nd = (const float4_*)h_nd;
-    return RT_OK;
-}
-
-int rt_temporal_accumulate(rt_context* c, int w, int h, const float* in, const float* sigma, const float* nd,
-                           const float prev_view[16], float prev_fov_dist, const float* hist_rgba, const float* hist_sigma,
-                           const float* hist_len, const float* hist_nd, const rt_temporal_params* params, float* out,
-                           float* sigma_out, float* len_out)
-{
-    rtk::TemporalFrame T;
-    if (int r = temporal_ready(c, "rt_temporal_accumulate", w, h, in, sigma, nd, prev_view, prev_fov_dist, hist_rgba,
-                               hist_sigma, hist_len, hist_nd, params, out, sigma_out, len_out, false, T))
-        return r;
-    return rt_backend_temporal(c, T, out, sigma_out, len_out, false, nullptr);
-}
-
-int rt_temporal_accumulate_device(rt_context* c, int w, int h, const void* in, const void* sigma, const void* nd,
-                                  const float prev_view[16], float prev_fov_dist, const void* hist_rgba,
-                                  const void* hist_sigma, const void* hist_len, const void* hist_nd,
-                                  const rt_temporal_params* params, void* out, void* sigma_out, void* len_out, void* stream)
-{
-    rtk::TemporalFrame T;
-    if (int r = temporal_ready(c, "rt_temporal_accumulate_device", w, h, in, sigma, nd, prev_view, prev_fov_dist, hist_rgba,
-                               hist_sigma, hist_len, hist_nd, params, out, sigma_out, len_out, true, T))
-        return r;
-    return rt_backend_temporal(c, T, out, sigma_out, len_out, true, stream);
-}
-
-// ---- firefly rejection (rt_firefly.h)
-// Defaults from the sweep on Cornell 64x64, a 4-sample frame against 256 spp.
-void rt_firefly_default_params(rt_firefly_params* p)
-{
-    if (!p) return;
-    p->radius = 1;
-    p->rank = 2;
-    p->gain = 2.0f;
-    p->floor = 0.0f;
-}
-
-static int firefly_ready(rt_context* c, const char* fn, int w, int h, const void* in, const void* sigma,
-                         const rt_firefly_params* params, const void* out, const void* sigma_out, const void* scale_out,
-                         bool device, rtk::FireflyArgs& A)
-{
-    const std::string f = fn;
-    if (!c) return rt_fail(nullptr, RT_ERR_ARG, f + ": ctx is NULL");
-    if (w <= 0 || h <= 0) return rt_fail(c, RT_ERR_ARG, f + ": w and h must be at least 1");
-    if (!in || !out) return rt_fail(c, RT_ERR_ARG, f + ": rgba_in or rgba_out is NULL");
-    if (sigma_out && !sigma) return rt_fail(c, RT_ERR_ARG, f + ": sigma_out without a sigma_in");
-    // (rt_denoise's frame-size limits: the kernels tile the frame 4 rows per block as its kernels do)
-    if ((double)w * (double)h > 134217727.0) return rt_fail(c, RT_ERR_ARG, f + ": too many pixels");
-    if (h > 4 * 65535) return rt_fail(c, RT_ERR_ARG, f + ": height above 262140 rows");
-    rt_firefly_params p;
-    if (params) p = *params;
-    else rt_firefly_default_params(&p);
-    if (p.radius < 1 || p.radius > 2) return rt_fail(c, RT_ERR_ARG, f + ": radius must be 1 or 2");
-    if (p.rank < 1 || p.rank > rtk::FF_MAX_RANK) return rt_fail(c, RT_ERR_ARG, f + ": rank must be 1..8");
-    if (!(p.gain >= 0.0f)) return rt_fail(c, RT_ERR_ARG, f + ": gain is negative or a NaN");
-    if (p.floor != p.floor) return rt_fail(c, RT_ERR_ARG, f + ": floor is a NaN");
-    const size_t n = (size_t)w * h;
-    const struct {
-        const void* p;
-        size_t bytes;
-    } ins[2] = {{in, 16 * n}, {sigma, 4 * n}}, outs[3] = {{out, 16 * n}, {sigma_out, 4 * n}, {scale_out, 4 * n}};
-    for (int o = 0; o < 3; o++) {
-        if (!outs[o].p) continue;
-        for (int i = 0; i < 2; i++)
-            if (ins[i].p && ranges_overlap(outs[o].p, outs[o].bytes, ins[i].p, ins[i].bytes))
-                return rt_fail(c, RT_ERR_ARG, f + ": an output overlaps an input");
-        for (int k = o + 1; k < 3; k++)
-            if (outs[k].p && ranges_overlap(outs[o].p, outs[o].bytes, outs[k].p, outs[k].bytes))
-                return rt_fail(c, RT_ERR_ARG, f + ": two outputs overlap");
-    }
-    if (device && ((uintptr_t)in % 16 != 0 || (uintptr_t)out % 16 != 0 || (uintptr_t)sigma % 4 != 0 ||
-                   (uintptr_t)sigma_out % 4 != 0 || (uintptr_t)scale_out % 4 != 0))
-        return rt_fail(c, RT_ERR_ARG, f + ": the float4 buffers must be 16-byte aligned, the float buffers 4-byte aligned");
-    A = rtk::FireflyArgs{w, h, p.radius, p.rank, p.gain, p.floor, (const float4_*)in, (const float*)sigma};
-    return RT_OK;
-}
-
-int rt_firefly(rt_context* c, int w, int h, const float* in, const float* sigma, const rt_firefly_params* params, float* out,
-               float* sigma_out, float* scale_out)
-{
-    rtk::FireflyArgs A;
-    if (int r = firefly_ready(c, "rt_firefly", w, h, in, sigma, params, out, sigma_out, scale_out, false, A)) return r;
-    return rt_backend_firefly(c, A, out, sigma_out, scale_out, false, nullptr);
-}
-
-int rt_firefly_device(rt_context* c, int w, int h, const void* in, const void* sigma, const rt_firefly_params* params,
-                      void* out, void* sigma_out, void* scale_out, void* stream)
-{
-    rtk::FireflyArgs A;
-    if (int r = firefly_ready(c, "rt_firefly_device", w, h, in, sigma, params, out, sigma_out, scale_out, true, A)) return r;
-    return rt_backend_firefly(c, A, out, sigma_out, scale_out, true, stream);
-}
-
-// ---- guided upscale (rt_upscale.h)
-// The guide sigmas are rt_denoise's; min_weight is the share of a pixel's bilinear weight below which
-// the four taps are taken as not seeing its surface.
-void rt_upscale_default_params(rt_upscale_params* p)
-{
-    if (!p) return;
-    rt_denoise_params d;
-    rt_denoise_default_params(&d);
-    p->sigma_normal = d.sigma_normal;
-    p->sigma_albedo = d.sigma_albedo;
-    p->sigma_depth = d.sigma_depth;
-    p->min_weight = 0.1f;
-}
-
-static int upscale_ready(rt_context* c, const char* fn, int w_lo, int h_lo, int w, int h, const void* rgba_lo,
-                         const void* sigma_lo, const void* alb_lo, const void* nd_lo, const void* alb_hi, const void* nd_hi,
-                         const rt_upscale_params* params, const void* out, const void* sigma_out, bool device, rtk::UpArgs& A)
-{
-    const std::string f = fn;
-    if (!c) return rt_fail(nullptr, RT_ERR_ARG, f + ": ctx is NULL");
-    if (w_lo <= 0 || h_lo <= 0 || w <= 0 || h <= 0) return rt_fail(c, RT_ERR_ARG, f + ": every size must be at least 1");
-    if (w_lo > w || h_lo > h) return rt_fail(c, RT_ERR_ARG, f + ": the low frame is larger than the output (w_lo > w or h_lo > h)");
-    if (!rgba_lo || !alb_lo || !nd_lo || !alb_hi || !nd_hi || !out)
-        return rt_fail(c, RT_ERR_ARG, f + ": a frame, a guide buffer or rgba_out is NULL");
-    if (sigma_out && !sigma_lo) return rt_fail(c, RT_ERR_ARG, f + ": sigma_out without a sigma_lo");
-    if (sigma_lo && !sigma_out) return rt_fail(c, RT_ERR_ARG, f + ": sigma_lo without a sigma_out");
-    // (rt_denoise's frame-size limits, on the output: the kernels tile it 4 rows per block as its kernels do)
-    if ((double)w * (double)h > 134217727.0) return rt_fail(c, RT_ERR_ARG, f + ": too many pixels");
-    if (h > 4 * 65535) return rt_fail(c, RT_ERR_ARG, f + ": height above 262140 rows");
-    rt_upscale_params p;
-    if (params) p = *params;
-    else rt_upscale_default_params(&p);
-    const float sig[3] = {p.sigma_normal, p.sigma_albedo, p.sigma_depth};
-    for (float s : sig)
-        if (!(s > 0.0f) || !std::isfinite(s))
-            return rt_fail(c, RT_ERR_ARG, f + ": sigma_normal, sigma_albedo and sigma_depth must be positive and finite");
-    if (!(p.min_weight >= 0.0f && p.min_weight < 1.0f)) return rt_fail(c, RT_ERR_ARG, f + ": min_weight must lie in [0, 1)");
-    const size_t n_lo = (size_t)w_lo * h_lo, n = (size_t)w * h;
-    const struct {
-        const void* p;
-        size_t bytes;
-    } ins[6] = {{rgba_lo, 16 * n_lo}, {sigma_lo, 4 * n_lo}, {alb_lo, 16 * n_lo}, {nd_lo, 16 * n_lo}, {alb_hi, 16 * n}, {nd_hi, 16 * n}},
-      outs[2] = {{out, 16 * n}, {sigma_out, 4 * n}};
-    for (int o = 0; o < 2; o++) {
-        if (!outs[o].p) continue;
-        for (int i = 0; i < 6; i++)
-            if (ins[i].p && ranges_overlap(outs[o].p, outs[o].bytes, ins[i].p, ins[i].bytes))
-                return rt_fail(c, RT_ERR_ARG, f + ": an output overlaps an input");
-    }
-    if (sigma_out && ranges_overlap(out, 16 * n, sigma_out, 4 * n)) return rt_fail(c, RT_ERR_ARG, f + ": two outputs overlap");
-    if (device) {
-        const void* p16[6] = {rgba_lo, alb_lo, nd_lo, alb_hi, nd_hi, out};
-        for (const void* q : p16)
-            if ((uintptr_t)q % 16 != 0)
-                return rt_fail(c, RT_ERR_ARG, f + ": the float4 buffers must be 16-byte aligned, the float buffers 4-byte aligned");
-        if ((uintptr_t)sigma_lo % 4 != 0 || (uintptr_t)sigma_out % 4 != 0)
-            return rt_fail(c, RT_ERR_ARG, f + ": the float4 buffers must be 16-byte aligned, the float buffers 4-byte aligned");
-    }
-    A = rtk::UpArgs{w_lo, h_lo, w, h, (float)w_lo / (float)w, (float)h_lo / (float)h, rtk::dn_inv_sigma2(p.sigma_normal),
-                    rtk::dn_inv_sigma2(p.sigma_albedo), rtk::dn_inv_sigma2(p.sigma_depth), p.min_weight,
-                    (const float4_*)rgba_lo, (const float*)sigma_lo, (const float4_*)alb_lo, (const float4_*)nd_lo,
-                    (const float4_*)alb_hi, (const float4_*)nd_hi};
-    return RT_OK;
-}
-
-int rt_upscale(rt_context* c, int w_lo, int h_lo, int w, int h, const float* rgba_lo, const float* sigma_lo,
-               const float* albedo_lo, const float* normal_depth_lo, const float* albedo_hi, const float* normal_depth_hi,
-               const rt_upscale_params* params, float* rgba_out, float* sigma_out)
-{
-    rtk::UpArgs A;
-    if (int r = upscale_ready(c, "rt_upscale", w_lo, h_lo, w, h, rgba_lo, sigma_lo, albedo_lo, normal_depth_lo, albedo_hi,
-                              normal_depth_hi, params, rgba_out, sigma_out, false, A))
-        return r;
-    return rt_backend_upscale(c, A, rgba_out, sigma_out, false, nullptr);
-}
-
-int rt_upscale_device(rt_context* c, int w_lo, int h_lo, int w, int h, const void* rgba_lo, const void* sigma_lo,
-                      const void* albedo_lo, const void* normal_depth_lo, const void* albedo_hi, const void* normal_depth_hi,
-                      const rt_upscale_params* params, void* rgba_out, void* sigma_out, void* stream)
-{
-    rtk::UpArgs A;
-    if (int r = upscale_ready(c, "rt_upscale_device", w_lo, h_lo, w, h, rgba_lo, sigma_lo, albedo_lo, normal_depth_lo,
-                              albedo_hi, normal_depth_hi, params, rgba_out, sigma_out, true, A))
-        return r;
-    return rt_backend_upscale(c, A, rgba_out, sigma_out, true, stream);
-}
-
-// ---- exposure metering (rt_meter.h)
-// The photographic convention (a log-average that displays as middle grey, 0.18), not a measured optimum;
-// the trims keep a dark corner and the light source out of the average.
-void rt_meter_default_params(rt_meter_params* p)
-{
-    if (!p) return;
-    p->low = 0.10f;
-    p->high = 0.95f;
-    p->key = 0.18f;
-    p->min_exposure = 0x1p-8f;
-    p->max_exposure = 0x1p12f;
-    p->tau_up = 0.0f;
-    p->tau_down = 0.0f;
-}
-
-static int meter_ready(rt_context* c, const char* fn, int w, int h, const void* in, const void* hist, bool device)
-{
-    const std::string f = fn;
-    if (!c) return rt_fail(nullptr, RT_ERR_ARG, f + ": ctx is NULL");
-    if (w <= 0 || h <= 0) return rt_fail(c, RT_ERR_ARG, f + ": w and h must be at least 1");
-    if (!in || !hist) return rt_fail(c, RT_ERR_ARG, f + ": the frame or the histogram is NULL");
-    // (rt_display's limit; with it no word of the histogram can overflow)
-    if ((double)w * (double)h > 134217727.0) return rt_fail(c, RT_ERR_ARG, f + ": too many pixels");
-    if (device && ((uintptr_t)in % 16 != 0 || (uintptr_t)hist % 4 != 0))
-        return rt_fail(c, RT_ERR_ARG, f + ": d_linear must be 16-byte aligned, d_hist 4-byte aligned");
-    return RT_OK;
-}
-
-int rt_meter(rt_context* c, int w, int h, const float* linear, rt_meter_hist* out)
-{
-    static_assert(sizeof(rt_meter_hist) == rtk::MT_WORDS * sizeof(uint32_t), "rt_meter_hist is MT_WORDS words");
-    if (int r = meter_ready(c, "rt_meter", w, h, linear, out, false)) return r;
-    return rt_backend_meter(c, w, h, linear, out, false, nullptr);
-}
-
-int rt_meter_device(rt_context* c, int w, int h, const void* d_linear, void* d_hist, void* stream)
-{
-    if (int r = meter_ready(c, "rt_meter_device", w, h, d_linear, d_hist, true)) return r;
-    return rt_backend_meter(c, w, h, d_linear, d_hist, true, stream);
-}
-
-// Host only, in double: the formulas of include/rt_hip.h, in their order.
-int rt_meter_solve(const rt_meter_hist* hist, const rt_meter_params* params, float prev_exposure, float dt_seconds,
-                   rt_meter_result* out)
-{
-    const std::string f = "rt_meter_solve";
-    if (!hist || !out) return rt_fail(nullptr, RT_ERR_ARG, f + ": the histogram or the result is NULL");
-    rt_meter_params p;
-    if (params) p = *params;
-    else rt_meter_default_params(&p);
-    if (!(p.low >= 0.0f && p.low <= 1.0f) || !(p.high >= 0.0f && p.high <= 1.0f) || p.low > p.high)
-        return rt_fail(nullptr, RT_ERR_ARG, f + ": low and high must lie in [0, 1] with low <= high");
-    if (!(p.key > 0.0f && p.key < 1.0f)) return rt_fail(nullptr, RT_ERR_ARG, f + ": key must lie in (0, 1)");
-    if (!std::isfinite(p.min_exposure) || !std::isfinite(p.max_exposure) || !(p.min_exposure > 0.0f) ||
-        p.min_exposure > p.max_exposure)
-        return rt_fail(nullptr, RT_ERR_ARG, f + ": the exposure bounds must be finite, positive and ordered");
-    if (!(p.tau_up >= 0.0f) || !(p.tau_down >= 0.0f))
-        return rt_fail(nullptr, RT_ERR_ARG, f + ": tau_up or tau_down is negative or a NaN");
-    const double n = (double)hist->counted, prev = (double)prev_exposure, dt = (double)dt_seconds;
-    double lo = std::floor((double)p.low * n), hi = std::floor((1.0 - (double)p.high) * n);
-    if (lo + hi >= n) lo = hi = 0.0;
-    uint64_t c[256];
-    for (int b = 0; b < 256; b++) c[b] = hist->bins[b];
-    uint64_t cut = (uint64_t)lo;
-    for (int b = 0; b < 256 && cut; b++) {
-        const uint64_t d = std::min(cut, c[b]);
-        c[b] -= d, cut -= d;
-    }
-    cut = (uint64_t)hi;
-    for (int b = 255; b >= 0 && cut; b--) {
-        const uint64_t d = std::min(cut, c[b]);
-        c[b] -= d, cut -= d;
-    }
-    uint64_t N = 0;
-    int64_t S = 0;
-    for (int b = 0; b < 256; b++) N += c[b], S += (int64_t)c[b] * (2 * b - 319);
-    if (N == 0) {
-        const float e = prev_exposure > 0.0f ? prev_exposure : 1.5f;
-        *out = rt_meter_result{e, e, 0.0f, 0};
-        return RT_OK;
-    }
-    const double log2_mean = (double)S / (16.0 * (double)N);
-    const double Lm = std::exp2(log2_mean);
-    const double target = std::min(std::max(-std::log1p(-(double)p.key) / Lm, (double)p.min_exposure), (double)p.max_exposure);
-    const double tau = (double)(target > prev ? p.tau_up : p.tau_down);
-    double e = target;
-    if (prev > 0.0 && tau > 0.0 && dt >= 0.0) {
-        const double l0 = std::log2(prev);
-        e = std::exp2(l0 + (std::log2(target) - l0) * (1.0 - std::exp(-dt / tau)));
-    }
-    *out = rt_meter_result{(float)e, (float)target, (float)log2_mean, 1};
-    return RT_OK;
-}
-
-// ---------------------------------------------------------- display stage
-// The reference's literals (render_kernel.cpp:175, :178).
-void rt_display_default_params(rt_display_params* p)
-{
-    if (!p) return;
-    p->exposure = 1.5f;
-    p->gamma = 2.2f;
-    p->flip_y = 0;
-}
-
-static int display_ready(rt_context* c, const char* fn, int w, int h, const void* in, const rt_display_params* params,
-                         const void* out, const void* out8, bool device, rt_display_params& p)
-{
-    const std::string f = fn;
-    if (!c) return rt_fail(nullptr, RT_ERR_ARG, f + ": ctx is NULL");
-    if (w <= 0 || h <= 0 || !in) return rt_fail(c, RT_ERR_ARG, f + ": bad buffers");
-    if ((double)w * (double)h > 134217727.0) return rt_fail(c, RT_ERR_ARG, f + ": too many pixels");
-    if (!out && !out8) return rt_fail(c, RT_ERR_ARG, f + ": rgba_out and rgba8_out are both NULL");
-    // (the float output may be the input, pixel for pixel; a pixel's bytes land at another pixel's place)
-    const size_t n = (size_t)w * h;
-    const char *i0 = (const char*)in, *b0 = (const char*)out8;
-    if (out8 && b0 < i0 + 16 * n && i0 < b0 + 4 * n) return rt_fail(c, RT_ERR_ARG, f + ": rgba8_out overlaps the input");
-    const char* o0 = (const char*)out;
-    if (out8 && out && b0 < o0 + 16 * n && o0 < b0 + 4 * n) return rt_fail(c, RT_ERR_ARG, f + ": rgba8_out overlaps rgba_out");
-    // (the float output is the input or apart from it: a partial overlap would read pixels already written)
-    if (out && o0 != i0 && o0 < i0 + 16 * n && i0 < o0 + 16 * n)
-        return rt_fail(c, RT_ERR_ARG, f + ": rgba_out overlaps the input without being it");
-    // (k_display moves a pixel with one 16-byte load / store and its bytes with one 4-byte store;
-    // the host form copies through buffers of its own and takes any alignment)
-    if (device && ((uintptr_t)in % 16 != 0 || (uintptr_t)out % 16 != 0 || (uintptr_t)out8 % 4 != 0))
-        return rt_fail(c, RT_ERR_ARG, f + ": d_linear and d_rgba_out must be 16-byte aligned, d_rgba8_out 4-byte aligned");
-    if (params) p = *params;
-    else rt_display_default_params(&p);
-    if (!std::isfinite(p.exposure)) return rt_fail(c, RT_ERR_ARG, f + ": the exposure is not finite");
-    if (!std::isfinite(p.gamma) || !(p.gamma > 0.0f)) return rt_fail(c, RT_ERR_ARG, f + ": the gamma is not finite and > 0");
-    return RT_OK;
-}
-
-int rt_display(rt_context* c, int w, int h, const float* linear, const rt_display_params* params, float* out,
-               unsigned char* out8)
-{
-    rt_display_params p;
-    if (int r = display_ready(c, "rt_display", w, h, linear, params, out, out8, false, p)) return r;
-    // (an IEEE division at run time: at 2.2f it is the float the literal 1.0f / 2.2f of tonemap_pixel is)
-    return rt_backend_display(c, w, h, linear, p.exposure, 1.0f / p.gamma, p.flip_y != 0, out, out8, false, nullptr);
-}
-
-int rt_display_device(rt_context* c, int w, int h, const void* d_linear, const rt_display_params* params, void* d_out,
-                      void* d_out8, void* stream)
-{
-    rt_display_params p;
-    if (int r = display_ready(c, "rt_display_device", w, h, d_linear, params, d_out, d_out8, true, p)) return r;
-    return rt_backend_display(c, w, h, d_linear, p.exposure, 1.0f / p.gamma, p.flip_y != 0, d_out, d_out8, true, stream);
 }
 
 int rt_set_intersect_mode(rt_context* c, int use_bvh)

@@ -151,11 +151,11 @@ int rt_backend_intersect(rt_context* ctx, const float* rays, int n, void* out);
 // The post stage (rt_denoise.h), on the context's root device. device = false: host buffers,
 // synchronous; true: device buffers on `stream`, no wait (hostsim: host pointers, stream unused).
 int rt_backend_features(rt_context* ctx, int w, int h, void* albedo, void* normal_depth, bool device, void* stream);
-// alb and nd both null: colour only. p is validated (rt_capi_host.cpp).
+// alb and nd both null: colour only. p is validated (rt_capi_stages.cpp).
 int rt_backend_denoise(rt_context* ctx, int w, int h, const void* in, const void* alb, const void* nd,
                        const rt_denoise_params& p, float blend, void* out, bool device, void* stream);
 // The variance-guided filter (rt_dnv.h): rt_backend_denoise plus sigma (w*h floats) and the optional
-// sigma_out (w*h floats, or null). p is validated (rt_capi_host.cpp).
+// sigma_out (w*h floats, or null). p is validated (rt_capi_stages.cpp).
 int rt_backend_denoise_var(rt_context* ctx, int w, int h, const void* in, const void* sigma, const void* alb, const void* nd,
                            const rt_denoise_var_params& p, float blend, void* out, void* sigma_out, bool device,
                            void* stream);
@@ -176,7 +176,7 @@ struct FireflyArgs;
 int rt_backend_firefly(rt_context* ctx, rtk::FireflyArgs A, void* rgba_out, void* sigma_out, void* scale_out, bool device,
                        void* stream);
 // Exposure metering (rt_meter.h), on the root device like the post stage: in (w*h float4) -> hist
-// (rtk::MT_WORDS uint32 words, cleared by the call). The arguments are validated (rt_capi_host.cpp).
+// (rtk::MT_WORDS uint32 words, cleared by the call). The arguments are validated (rt_capi_stages.cpp).
 int rt_backend_meter(rt_context* ctx, int w, int h, const void* in, void* hist, bool device, void* stream);
 // The guided upscale (rt_upscale.h), on the root device like the post stage: A holds the validated sizes and
 // parameters, the low frame (w_lo*h_lo float4), its sigma (floats, or null) and guides, and the full-size guides
@@ -187,7 +187,7 @@ struct UpArgs;
 int rt_backend_upscale(rt_context* ctx, rtk::UpArgs A, void* rgba_out, void* sigma_out, bool device, void* stream);
 // The display stage (rt_display.h), on the root device like the post stage: in (w*h float4) ->
 // out (w*h float4, may be `in`, or null) and out8 (w*h RGBA bytes, rows reversed when flip, or
-// null). The arguments are validated and inv_gamma = 1.0f / gamma (rt_capi_host.cpp).
+// null). The arguments are validated and inv_gamma = 1.0f / gamma (rt_capi_stages.cpp).
 int rt_backend_display(rt_context* ctx, int w, int h, const void* in, float exposure, float inv_gamma, bool flip,
                        void* out, void* out8, bool device, void* stream);
 
@@ -244,6 +244,10 @@ int rt_backend_progress_adapt_noise(rt_context* ctx, const rtk::NoiseArgs& args,
                                     float* tile_err, bool device, void* stream);
 
 int rt_fail(rt_context* ctx, int code, const std::string& msg);
+// The device tables made current before a call that reads them (rt_capi_host.cpp; rt_capi_stages.cpp for the
+// feature buffers). mats_too: a changed material table alone is a reason too; env_stub: bind the placeholder
+// env first (the calls that need no env).
+int rt_tables_current(rt_context* ctx, bool mats_too, bool env_stub);
 // RtDiag from the environment (rt_create*)
 void rt_read_diag(rt_context* ctx);
 // While set (per host thread), rt_fail writes its message to *sink instead of the

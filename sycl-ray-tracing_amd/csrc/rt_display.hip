@@ -23,7 +23,7 @@ namespace {
 
 constexpr int threads = 256;
 
-// n = w * h pixels (at most 2^27 - 1: rt_capi_host.cpp); in and out may be one buffer
+// n = w * h pixels (at most 2^27 - 1: rt_capi_stages.cpp); in and out may be one buffer
 template <bool FLOAT_OUT, bool BYTE_OUT>
 __global__ __launch_bounds__(256) void k_display(const float4_* in, float4_* out, uint32_t* out8, int n,
                                                  int w, int h, int flip, float exposure, float inv_gamma)

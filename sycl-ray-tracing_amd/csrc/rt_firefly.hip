@@ -109,28 +109,14 @@ bool ff_use_lds(int variant) { return variant != 1; }
 
 }  // namespace
 
-// This stage's staging buffer on the root device, a sibling of rt_temporal.hip's PostTemporal, cached across calls.
-struct PostFirefly {
-    DevBuf io;  // host-pointer calls: the frame and its sigma, then the three outputs
-};
-
-void PostFireflyDelete::operator()(PostFirefly* p) const { delete p; }
-
-static PostFirefly* post_firefly_of(Backend* b)  // (created on first use)
-{
-    if (!b->post_firefly) b->post_firefly.reset(new PostFirefly());
-    return b->post_firefly.get();
-}
-
 int rt_backend_firefly(rt_context* c, rtk::FireflyArgs A, void* rgba_out, void* sigma_out, void* scale_out, bool device,
                        void* stream)
 {
     Backend* b = rt_backend_dev0(c);
     StagedCall st;
     if (int r = st.enter(c, b, device, stream, nullptr)) return r;
-    PostFirefly* post = post_firefly_of(b);
     const size_t n = (size_t)A.w * A.h, bytes = n * sizeof(float4_), fbytes = st.pad(n * sizeof(float));
-    if (int r = st.staging(post->io, 2 * bytes + 3 * fbytes)) return r;
+    if (int r = st.staging(b->firefly_io, 2 * bytes + 3 * fbytes)) return r;
     A.in = (const float4_*)st.in(A.in, bytes);
     A.sigma = (const float*)st.in(A.sigma, n * sizeof(float));  // (null: no sigma_in)
     float4_* d_out = (float4_*)st.out(rgba_out, bytes);

@@ -41,7 +41,7 @@ constexpr int threads = 256, waves = threads / 64;
 #define MT_BLOCKS_PER_CU 2  // the grid cap (the flush against the walk)
 #endif
 
-// n = w * h pixels (at most 2^27 - 1: rt_capi_host.cpp) and at most 65536 blocks (mt_grid), so
+// n = w * h pixels (at most 2^27 - 1: rt_capi_stages.cpp) and at most 65536 blocks (mt_grid), so
 // base + gridDim.x * 256 stays below 2^28.
 __global__ __launch_bounds__(256) void k_meter_direct(const float4_* __restrict__ in, unsigned n, uint32_t* __restrict__ hist)
 {
@@ -158,22 +158,10 @@ unsigned mt_grid(size_t n, int cus, int forced)
 
 }  // namespace
 
-// This stage's staging buffer on the root device, a sibling of rt_firefly.hip's PostFirefly, cached across calls.
-struct PostMeter {
-    DevBuf io;    // host-pointer calls: the frame, then the histogram
-    int cus = 0;  // the device's compute units
-};
-
-void PostMeterDelete::operator()(PostMeter* p) const { delete p; }
-
-static int post_meter_of(rt_context* c, Backend* b, PostMeter** out)  // (created on first use)
+// The device's compute units (Backend::cus), asked on first use.
+static int meter_cus(rt_context* c, Backend* b)
 {
-    if (!b->post_meter) {
-        std::unique_ptr<PostMeter, PostMeterDelete> p(new PostMeter());
-        HIPCHK(c, hipDeviceGetAttribute(&p->cus, hipDeviceAttributeMultiprocessorCount, b->device));
-        b->post_meter = std::move(p);
-    }
-    *out = b->post_meter.get();
+    if (!b->cus) HIPCHK(c, hipDeviceGetAttribute(&b->cus, hipDeviceAttributeMultiprocessorCount, b->device));
     return RT_OK;
 }
 
@@ -182,17 +170,16 @@ int rt_backend_meter(rt_context* c, int w, int h, const void* in, void* hist, bo
     Backend* b = rt_backend_dev0(c);
     StagedCall st;
     if (int r = st.enter(c, b, device, stream, nullptr)) return r;
-    PostMeter* post = nullptr;
-    if (int r = post_meter_of(c, b, &post)) return r;
+    if (int r = meter_cus(c, b)) return r;
     const size_t n = (size_t)w * h, bytes = n * sizeof(float4_), hbytes = rtk::MT_WORDS * sizeof(uint32_t);
-    if (int r = st.staging(post->io, bytes + st.pad(hbytes))) return r;
+    if (int r = st.staging(b->meter_io, bytes + st.pad(hbytes))) return r;
     const float4_* d_in = (const float4_*)st.in(in, bytes);
     uint32_t* d_hist = (uint32_t*)st.out(hist, hbytes);
     if (int r = st.begin()) return r;
     // the histogram starts at zero, min_bits at all ones: the caller need not clear it
     HIPCHK(c, hipMemsetAsync(d_hist, 0, hbytes, st.s));
     HIPCHK(c, hipMemsetAsync(d_hist + rtk::MT_MIN_BITS, 0xff, sizeof(uint32_t), st.s));
-    const dim3 grid(mt_grid(n, post->cus, c->sched.mt_blocks));
+    const dim3 grid(mt_grid(n, b->cus, c->sched.mt_blocks));
     if (mt_use_lds(c->sched.mt_variant))
         hipLaunchKernelGGL(k_meter_lds, grid, dim3(threads), 0, st.s, d_in, (unsigned)n, d_hist);
     else
@@ -216,13 +203,12 @@ extern "C" int rt_device_meter_kernel_ms(rt_context* c, int w, int h, const void
     Backend* b = rt_backend_dev0(c);
     DeviceScope sc;
     if (int r = sc.enter(c, b->device)) return r;
-    PostMeter* post = nullptr;
-    if (int r = post_meter_of(c, b, &post)) return r;
+    if (int r = meter_cus(c, b)) return r;
     Event e0, e1;
     HIPCHK(c, hipEventCreate(&e0.h));
     HIPCHK(c, hipEventCreate(&e1.h));
     const size_t n = (size_t)w * h;
-    const dim3 grid(mt_grid(n, post->cus, blocks));
+    const dim3 grid(mt_grid(n, b->cus, blocks));
     uint32_t* hist = (uint32_t*)d_hist;
     for (int r = 0; r < reps; r++)
         for (int k = 0; k < 2; k++) {

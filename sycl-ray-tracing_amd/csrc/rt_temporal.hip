@@ -40,29 +40,15 @@ __global__ __launch_bounds__(256) void k_temporal(rtk::TemporalFrame T, float4_*
 
 }  // namespace
 
-// This stage's staging buffer on the root device, a sibling of rt_dnv.hip's PostVar, cached across calls.
-struct PostTemporal {
-    DevBuf io;  // host-pointer calls: the three inputs of this frame, the four of the history, the three outputs
-};
-
-void PostTemporalDelete::operator()(PostTemporal* p) const { delete p; }
-
-static PostTemporal* post_temporal_of(Backend* b)  // (created on first use)
-{
-    if (!b->post_temporal) b->post_temporal.reset(new PostTemporal());
-    return b->post_temporal.get();
-}
-
 int rt_backend_temporal(rt_context* c, rtk::TemporalFrame T, void* rgba_out, void* sigma_out, void* len_out, bool device,
                         void* stream)
 {
     Backend* b = rt_backend_dev0(c);
     StagedCall st;
     if (int r = st.enter(c, b, device, stream, nullptr)) return r;
-    PostTemporal* post = post_temporal_of(b);
     const int w = T.cur.W, h = T.cur.H;
     const size_t n = (size_t)w * h, bytes = n * sizeof(float4_), fbytes = st.pad(n * sizeof(float));
-    if (int r = st.staging(post->io, 5 * bytes + 5 * fbytes)) return r;
+    if (int r = st.staging(b->temporal_io, 5 * bytes + 5 * fbytes)) return r;
     T.in = (const float4_*)st.in(T.in, bytes);
     T.sigma = (const float*)st.in(T.sigma, n * sizeof(float));
     T.nd = (const float4_*)st.in(T.nd, bytes);

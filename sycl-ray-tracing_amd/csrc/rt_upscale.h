@@ -51,7 +51,7 @@
 //                               falls below the normal range. A pixel whose colour or sigma is not
 //                               finite is rebuilt from its neighbours by tier 2.
 //   overlapping buffers         an output whose bytes overlap an input's or the other output's is
-//                               RT_ERR_ARG (rt_capi_host.cpp): a block reads low pixels other blocks write
+//                               RT_ERR_ARG (rt_capi_stages.cpp): a block reads low pixels other blocks write
 #pragma once
 
 #include "rt_dnv.h"

@@ -119,28 +119,14 @@ void up_launch(const rtk::UpArgs& A, bool lds, float4_* d_out, float* d_sout, hi
 
 }  // namespace
 
-// This stage's staging buffer on the root device, a sibling of rt_meter.hip's PostMeter, cached across calls.
-struct PostUpscale {
-    DevBuf io;  // host-pointer calls: the low frame, its sigma and guides, the full-size guides, then the two outputs
-};
-
-void PostUpscaleDelete::operator()(PostUpscale* p) const { delete p; }
-
-static PostUpscale* post_upscale_of(Backend* b)  // (created on first use)
-{
-    if (!b->post_upscale) b->post_upscale.reset(new PostUpscale());
-    return b->post_upscale.get();
-}
-
 int rt_backend_upscale(rt_context* c, rtk::UpArgs A, void* rgba_out, void* sigma_out, bool device, void* stream)
 {
     Backend* b = rt_backend_dev0(c);
     StagedCall st;
     if (int r = st.enter(c, b, device, stream, nullptr)) return r;
-    PostUpscale* post = post_upscale_of(b);
     const size_t n_lo = (size_t)A.w_lo * A.h_lo, n = (size_t)A.w * A.h;
     const size_t b_lo = n_lo * sizeof(float4_), b_hi = n * sizeof(float4_);
-    if (int r = st.staging(post->io, 3 * b_lo + st.pad(n_lo * sizeof(float)) + 3 * b_hi + st.pad(n * sizeof(float)))) return r;
+    if (int r = st.staging(b->upscale_io, 3 * b_lo + st.pad(n_lo * sizeof(float)) + 3 * b_hi + st.pad(n * sizeof(float)))) return r;
     A.rgba_lo = (const float4_*)st.in(A.rgba_lo, b_lo);
     A.sigma_lo = (const float*)st.in(A.sigma_lo, n_lo * sizeof(float));  // (null: no sigma)
     A.alb_lo = (const float4_*)st.in(A.alb_lo, b_lo);

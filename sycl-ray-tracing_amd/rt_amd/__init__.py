@@ -141,124 +141,53 @@ def write_image_hdr(image: Image, filename: str, flipY: bool = True) -> bool:
     return True
 
 
-def denoise_default_params(hostsim: bool = False) -> DenoiseParams:
-    """rt_denoise_default_params: the à-trous filter's defaults (passes and the four sigmas)."""
-    p = DenoiseParams()
-    lib(hostsim).rt_denoise_default_params(ctypes.byref(p))
-    return p
+def _vp(a):
+    """A device address (an int, or None / 0 for "not given") as the void* argument of a *_device call."""
+    return ctypes.c_void_p(a) if a else None
 
 
-def _denoise_params(L_, params) -> DenoiseParams:
-    """params: None (defaults), a DenoiseParams, or a dict of its fields over the defaults."""
-    if isinstance(params, DenoiseParams):
+def _params(L_, cls, stage: str, params):
+    """A stage's parameter struct. params: None (rt_<stage>_default_params), a cls, or a dict of its fields
+    over the defaults."""
+    if isinstance(params, cls):
         return params
-    p = DenoiseParams()
-    L_.rt_denoise_default_params(ctypes.byref(p))
+    p = cls()
+    getattr(L_, f"rt_{stage}_default_params")(ctypes.byref(p))
     for k, v in (params or {}).items():
-        if k not in dict(DenoiseParams._fields_):
-            raise TypeError(f"unknown denoise parameter {k}")
+        if k not in dict(cls._fields_):
+            raise TypeError(f"unknown {stage} parameter {k}")
         setattr(p, k, v)
     return p
+
+
+def denoise_default_params(hostsim: bool = False) -> DenoiseParams:
+    """rt_denoise_default_params: the à-trous filter's defaults (passes and the four sigmas)."""
+    return _params(lib(hostsim), DenoiseParams, "denoise", None)
 
 
 def denoise_var_default_params(hostsim: bool = False) -> DenoiseVarParams:
     """rt_denoise_var_default_params: the variance-guided filter's defaults."""
-    p = DenoiseVarParams()
-    lib(hostsim).rt_denoise_var_default_params(ctypes.byref(p))
-    return p
-
-
-def _denoise_var_params(L_, params) -> DenoiseVarParams:
-    """params: None (defaults), a DenoiseVarParams, or a dict of its fields over the defaults."""
-    if isinstance(params, DenoiseVarParams):
-        return params
-    p = DenoiseVarParams()
-    L_.rt_denoise_var_default_params(ctypes.byref(p))
-    for k, v in (params or {}).items():
-        if k not in dict(DenoiseVarParams._fields_):
-            raise TypeError(f"unknown denoise_var parameter {k}")
-        setattr(p, k, v)
-    return p
+    return _params(lib(hostsim), DenoiseVarParams, "denoise_var", None)
 
 
 def temporal_default_params(hostsim: bool = False) -> TemporalParams:
     """rt_temporal_default_params: temporal accumulation's defaults."""
-    p = TemporalParams()
-    lib(hostsim).rt_temporal_default_params(ctypes.byref(p))
-    return p
-
-
-def _temporal_params(L_, params) -> TemporalParams:
-    """params: None (defaults), a TemporalParams, or a dict of its fields over the defaults."""
-    if isinstance(params, TemporalParams):
-        return params
-    p = TemporalParams()
-    L_.rt_temporal_default_params(ctypes.byref(p))
-    for k, v in (params or {}).items():
-        if k not in dict(TemporalParams._fields_):
-            raise TypeError(f"unknown temporal parameter {k}")
-        setattr(p, k, v)
-    return p
+    return _params(lib(hostsim), TemporalParams, "temporal", None)
 
 
 def firefly_default_params(hostsim: bool = False) -> FireflyParams:
     """rt_firefly_default_params: the firefly rejection stage's defaults."""
-    p = FireflyParams()
-    lib(hostsim).rt_firefly_default_params(ctypes.byref(p))
-    return p
-
-
-def _firefly_params(L_, params) -> FireflyParams:
-    """params: None (defaults), a FireflyParams, or a dict of its fields over the defaults."""
-    if isinstance(params, FireflyParams):
-        return params
-    p = FireflyParams()
-    L_.rt_firefly_default_params(ctypes.byref(p))
-    for k, v in (params or {}).items():
-        if k not in dict(FireflyParams._fields_):
-            raise TypeError(f"unknown firefly parameter {k}")
-        setattr(p, k, v)
-    return p
+    return _params(lib(hostsim), FireflyParams, "firefly", None)
 
 
 def upscale_default_params(hostsim: bool = False) -> UpscaleParams:
     """rt_upscale_default_params: the guided upscale stage's defaults."""
-    p = UpscaleParams()
-    lib(hostsim).rt_upscale_default_params(ctypes.byref(p))
-    return p
-
-
-def _upscale_params(L_, params) -> UpscaleParams:
-    """params: None (defaults), an UpscaleParams, or a dict of its fields over the defaults."""
-    if isinstance(params, UpscaleParams):
-        return params
-    p = UpscaleParams()
-    L_.rt_upscale_default_params(ctypes.byref(p))
-    for k, v in (params or {}).items():
-        if k not in dict(UpscaleParams._fields_):
-            raise TypeError(f"unknown upscale parameter {k}")
-        setattr(p, k, v)
-    return p
+    return _params(lib(hostsim), UpscaleParams, "upscale", None)
 
 
 def meter_default_params(hostsim: bool = False) -> MeterParams:
     """rt_meter_default_params: the defaults of rt_meter_solve."""
-    p = MeterParams()
-    lib(hostsim).rt_meter_default_params(ctypes.byref(p))
-    return p
-
-
-def _meter_params(L_, params) -> MeterParams:
-    """params: None (defaults), a MeterParams, or a dict of its fields over the defaults."""
-    if isinstance(params, MeterParams):
-        return params
-    p = MeterParams()
-    L_.rt_meter_default_params(ctypes.byref(p))
-    for k, v in (params or {}).items():
-        if k not in dict(MeterParams._fields_):
-            raise TypeError(f"unknown meter parameter {k}")
-        setattr(p, k, v)
-    return p
+    return _params(lib(hostsim), MeterParams, "meter", None)
 
 
 def meter_stats(hist) -> dict:
@@ -276,7 +205,7 @@ def meter_solve(hist, prev: float = 0.0, dt: float = 0.0, hostsim: bool = False,
 
 
 def _meter_solve(L_, hist, prev, dt, params) -> dict:
-    p = _meter_params(L_, params.pop("params") if "params" in params else params)
+    p = _params(L_, MeterParams, "meter", params.pop("params") if "params" in params else params)
     h = np.ascontiguousarray(hist, dtype=np.uint32).reshape(METER_WORDS)
     r = MeterResult()
     check(L_, L_.rt_meter_solve(ptr(h), ctypes.byref(p), float(prev), float(dt), ctypes.byref(r)), None, "rt_meter_solve")
@@ -542,9 +471,8 @@ class RenderKernel:
         """rt_display_device: device buffers (w*h*4 floats in and out, w*h*4 bytes), no wait; d_rgba may be
         d_linear (in place)."""
         p = DisplayParams(float(exposure), float(gamma), int(bool(flip_y)))
-        vp = lambda a: ctypes.c_void_p(a) if a else None  # noqa: E731
         check(self.L, self.L.rt_display_device(self.ctx, int(width or self.width), int(height or self.height),
-                                               vp(d_linear), ctypes.byref(p), vp(d_rgba), vp(d_rgba8), vp(stream)),
+                                               _vp(d_linear), ctypes.byref(p), _vp(d_rgba), _vp(d_rgba8), _vp(stream)),
               self.ctx, "rt_display_device")
 
     # ---- exposure metering (rt_meter, rt_meter_solve; include/rt_hip.h)
@@ -562,9 +490,8 @@ class RenderKernel:
 
     def meter_device(self, d_linear: int, d_hist: int, stream: int | None = None, width=None, height=None):
         """rt_meter_device: device buffers (w*h*4 floats in, 264 words out, cleared by the call), no wait."""
-        vp = lambda a: ctypes.c_void_p(a) if a else None  # noqa: E731
-        check(self.L, self.L.rt_meter_device(self.ctx, int(width or self.width), int(height or self.height), vp(d_linear),
-                                             vp(d_hist), vp(stream)), self.ctx, "rt_meter_device")
+        check(self.L, self.L.rt_meter_device(self.ctx, int(width or self.width), int(height or self.height), _vp(d_linear),
+                                             _vp(d_hist), _vp(stream)), self.ctx, "rt_meter_device")
 
     def auto_exposure(self, linear=None, prev: float = 0.0, dt: float = 0.0, full: bool = False, **params):
         """meter(), then meter_solve: the exposure display() should take for this linear frame. prev / dt and
@@ -738,7 +665,7 @@ class RenderKernel:
         elif guides:
             alb, nd = (np.ascontiguousarray(g, dtype=np.float32).reshape(h, w, 4) for g in guides)
         out = Image(w, h)
-        p = _denoise_params(self.L, params)
+        p = _params(self.L, DenoiseParams, "denoise", params)
         check(self.L, self.L.rt_denoise(self.ctx, w, h, ptr(src), ptr(alb), ptr(nd), ctypes.byref(p),
                                         float(blend_factor), ptr(out.pixels)), self.ctx, "rt_denoise")
         return out
@@ -746,11 +673,10 @@ class RenderKernel:
     def denoise_device(self, d_in: int, d_out: int, d_albedo: int | None = None, d_normal_depth: int | None = None,
                        blend_factor: float = 1.0, params=None, stream: int | None = None, width=None, height=None):
         """rt_denoise_device: device buffers (w*h*4 floats each), no wait."""
-        p = _denoise_params(self.L, params)
-        vp = lambda a: ctypes.c_void_p(a) if a else None  # noqa: E731
-        check(self.L, self.L.rt_denoise_device(self.ctx, int(width or self.width), int(height or self.height), vp(d_in),
-                                               vp(d_albedo), vp(d_normal_depth), ctypes.byref(p), float(blend_factor),
-                                               vp(d_out), vp(stream)), self.ctx, "rt_denoise_device")
+        p = _params(self.L, DenoiseParams, "denoise", params)
+        check(self.L, self.L.rt_denoise_device(self.ctx, int(width or self.width), int(height or self.height), _vp(d_in),
+                                               _vp(d_albedo), _vp(d_normal_depth), ctypes.byref(p), float(blend_factor),
+                                               _vp(d_out), _vp(stream)), self.ctx, "rt_denoise_device")
 
     # ---- variance-guided denoise (rt_progress_noise_sigma, rt_denoise_var; include/rt_hip.h)
     def progress_noise_sigma(self) -> np.ndarray:
@@ -787,7 +713,7 @@ class RenderKernel:
             alb, nd = (np.ascontiguousarray(g, dtype=np.float32).reshape(h, w, 4) for g in guides)
         out = Image(w, h)
         left = np.empty((h, w), np.float32) if return_sigma else None
-        p = _denoise_var_params(self.L, params)
+        p = _params(self.L, DenoiseVarParams, "denoise_var", params)
         check(self.L, self.L.rt_denoise_var(self.ctx, w, h, ptr(src), ptr(sig), ptr(alb), ptr(nd), ctypes.byref(p),
                                             float(blend_factor), ptr(out.pixels), ptr(left)), self.ctx, "rt_denoise_var")
         return (out, left) if return_sigma else out
@@ -796,11 +722,10 @@ class RenderKernel:
                            d_normal_depth: int | None = None, blend_factor: float = 1.0, params=None,
                            d_sigma_out: int | None = None, stream: int | None = None, width=None, height=None):
         """rt_denoise_var_device: device buffers (w*h*4 floats each, sigma and sigma_out w*h floats), no wait."""
-        p = _denoise_var_params(self.L, params)
-        vp = lambda a: ctypes.c_void_p(a) if a else None  # noqa: E731
-        check(self.L, self.L.rt_denoise_var_device(self.ctx, int(width or self.width), int(height or self.height), vp(d_in),
-                                                   vp(d_sigma), vp(d_albedo), vp(d_normal_depth), ctypes.byref(p),
-                                                   float(blend_factor), vp(d_out), vp(d_sigma_out), vp(stream)), self.ctx,
+        p = _params(self.L, DenoiseVarParams, "denoise_var", params)
+        check(self.L, self.L.rt_denoise_var_device(self.ctx, int(width or self.width), int(height or self.height), _vp(d_in),
+                                                   _vp(d_sigma), _vp(d_albedo), _vp(d_normal_depth), ctypes.byref(p),
+                                                   float(blend_factor), _vp(d_out), _vp(d_sigma_out), _vp(stream)), self.ctx,
               "rt_denoise_var_device")
 
     # ---- temporal accumulation (rt_temporal_accumulate; include/rt_hip.h)
@@ -822,7 +747,7 @@ class RenderKernel:
             hist = [np.ascontiguousarray(getattr(a, "pixels", a), dtype=np.float32).reshape(s)
                     for a, s in zip(history, shapes)]
         out, s_out, l_out = Image(w, h), np.empty((h, w), np.float32), np.empty((h, w), np.float32)
-        p = _temporal_params(self.L, params)
+        p = _params(self.L, TemporalParams, "temporal", params)
         check(self.L, self.L.rt_temporal_accumulate(self.ctx, w, h, ptr(src), ptr(sig), ptr(nd), ptr(prev_camera.view_matrix),
                                                     prev_camera.fov_dist, *(ptr(a) for a in hist), ctypes.byref(p),
                                                     ptr(out.pixels), ptr(s_out), ptr(l_out)), self.ctx,
@@ -834,14 +759,13 @@ class RenderKernel:
                                    stream: int | None = None, width=None, height=None):
         """rt_temporal_accumulate_device: device buffers (w*h*4 floats for the float4 buffers, w*h floats for the
         others), d_history None or (d_rgba, d_sigma, d_len, d_normal_depth); no wait."""
-        p = _temporal_params(self.L, params)
-        vp = lambda a: ctypes.c_void_p(a) if a else None  # noqa: E731
+        p = _params(self.L, TemporalParams, "temporal", params)
         hist = d_history if d_history is not None else (None,) * 4
         check(self.L, self.L.rt_temporal_accumulate_device(self.ctx, int(width or self.width), int(height or self.height),
-                                                           vp(d_in), vp(d_sigma), vp(d_normal_depth),
+                                                           _vp(d_in), _vp(d_sigma), _vp(d_normal_depth),
                                                            ptr(prev_camera.view_matrix), prev_camera.fov_dist,
-                                                           *(vp(a) for a in hist), ctypes.byref(p), vp(d_out),
-                                                           vp(d_sigma_out), vp(d_len_out), vp(stream)), self.ctx,
+                                                           *(_vp(a) for a in hist), ctypes.byref(p), _vp(d_out),
+                                                           _vp(d_sigma_out), _vp(d_len_out), _vp(stream)), self.ctx,
               "rt_temporal_accumulate_device")
 
     # ---- firefly rejection (rt_firefly; include/rt_hip.h)
@@ -859,7 +783,7 @@ class RenderKernel:
             s_out = np.empty((h, w), np.float32)
         out = Image(w, h)
         scale = np.empty((h, w), np.float32) if return_scale else None
-        p = _firefly_params(self.L, params)
+        p = _params(self.L, FireflyParams, "firefly", params)
         check(self.L, self.L.rt_firefly(self.ctx, w, h, ptr(src), ptr(sig), ctypes.byref(p), ptr(out.pixels), ptr(s_out),
                                         ptr(scale)), self.ctx, "rt_firefly")
         return (out, s_out, scale) if return_scale else (out, s_out)
@@ -868,11 +792,10 @@ class RenderKernel:
                              d_scale_out: int | None = None, params=None, stream: int | None = None, width=None,
                              height=None):
         """rt_firefly_device: device buffers (w*h*4 floats for the frames, w*h floats for the others), no wait."""
-        p = _firefly_params(self.L, params)
-        vp = lambda a: ctypes.c_void_p(a) if a else None  # noqa: E731
-        check(self.L, self.L.rt_firefly_device(self.ctx, int(width or self.width), int(height or self.height), vp(d_in),
-                                               vp(d_sigma), ctypes.byref(p), vp(d_out), vp(d_sigma_out), vp(d_scale_out),
-                                               vp(stream)), self.ctx, "rt_firefly_device")
+        p = _params(self.L, FireflyParams, "firefly", params)
+        check(self.L, self.L.rt_firefly_device(self.ctx, int(width or self.width), int(height or self.height), _vp(d_in),
+                                               _vp(d_sigma), ctypes.byref(p), _vp(d_out), _vp(d_sigma_out), _vp(d_scale_out),
+                                               _vp(stream)), self.ctx, "rt_firefly_device")
 
     # ---- guided upscale (rt_upscale; include/rt_hip.h)
     def upscale(self, low_rgba, low_albedo, low_nd, hi_albedo, hi_nd, sigma=None, params=None):
@@ -892,7 +815,7 @@ class RenderKernel:
             assert sig.shape == (h_lo, w_lo), "sigma is one float per pixel of the low frame"
             s_out = np.empty((h, w), np.float32)
         out = Image(w, h)
-        p = _upscale_params(self.L, params)
+        p = _params(self.L, UpscaleParams, "upscale", params)
         check(self.L, self.L.rt_upscale(self.ctx, w_lo, h_lo, w, h, ptr(lo), ptr(sig), ptr(la), ptr(ln), ptr(ha), ptr(hn),
                                         ctypes.byref(p), ptr(out.pixels), ptr(s_out)), self.ctx, "rt_upscale")
         return out if sigma is None else (out, s_out)
@@ -902,12 +825,11 @@ class RenderKernel:
                        stream: int | None = None):
         """rt_upscale_device: device buffers (4 floats per pixel for the frames and guides, 1 for the sigmas) at
         size_lo = (w_lo, h_lo) and size = (w, h); no wait."""
-        p = _upscale_params(self.L, params)
-        vp = lambda a: ctypes.c_void_p(a) if a else None  # noqa: E731
+        p = _params(self.L, UpscaleParams, "upscale", params)
         check(self.L, self.L.rt_upscale_device(self.ctx, int(size_lo[0]), int(size_lo[1]), int(size[0]), int(size[1]),
-                                               vp(d_low_rgba), vp(d_sigma), vp(d_low_albedo), vp(d_low_nd), vp(d_hi_albedo),
-                                               vp(d_hi_nd), ctypes.byref(p), vp(d_out), vp(d_sigma_out), vp(stream)),
-              self.ctx, "rt_upscale_device")
+                                               _vp(d_low_rgba), _vp(d_sigma), _vp(d_low_albedo), _vp(d_low_nd),
+                                               _vp(d_hi_albedo), _vp(d_hi_nd), ctypes.byref(p), _vp(d_out), _vp(d_sigma_out),
+                                               _vp(stream)), self.ctx, "rt_upscale_device")
 
     def render_variants(self, materials, frames=None, device_ptrs=None, row_offset: int = 0, row_stride: int = 1):
         """rt_render_variants: the material sweep as replicas. `materials` is
@@ -979,9 +901,8 @@ class RenderKernel:
     def query_device(self, d_rays: int, n: int, d_out: int, mode: str = "closest", exact: bool = False,
                      stream: int | None = None):
         """rt_query_device: device buffers (n*6 floats in, n*11 or n int32 out) on `stream`; no wait."""
-        vp = lambda a: ctypes.c_void_p(a) if a else None  # noqa: E731
-        check(self.L, self.L.rt_query_device(self.ctx, self._query_mode(mode, exact), vp(d_rays), int(n), vp(d_out),
-                                             vp(stream)), self.ctx, "rt_query_device")
+        check(self.L, self.L.rt_query_device(self.ctx, self._query_mode(mode, exact), _vp(d_rays), int(n), _vp(d_out),
+                                             _vp(stream)), self.ctx, "rt_query_device")
 
     def query_last_exact(self) -> int:
         """rt_query_last_exact: queries of the last query call that took the exact walk (waits)."""
