@@ -152,37 +152,26 @@ hostsim-variant: $(OBJ)/rt_imageio.host.o
 	$(CXX) $(CXXFLAGS) $(DEFS) -c $(SRC)/rt_capi_stages.cpp -o $(OBJ)/rt_capi_stages_$(V).o
 	$(CXX) -shared -fopenmp $(OBJ)/rt_hostsim_$(V).o $(OBJ)/rt_scene_$(V).o $(OBJ)/rt_capi_host_$(V).o $(OBJ)/rt_capi_stages_$(V).o $(OBJ)/rt_imageio.host.o -o $(LIB)/librt_hostsim_$(V).so
 
-# C++ drop-in check (container only): include/render_kernel_hip.h against the
-# reference's headers and objects (oracle/_ref, `make ref`), linked to the hostsim
-# build of the C ABI (build/X_test), and to the product library (build/X_test_hip: built here,
-# run on the GPU box, which has no reference tree; the binary carries what it needs).
-#   shim_test           render()                         tests/test_shim.py
-#   denoise_shim_test   denoise() against rt_render_features + rt_denoise   tests/test_denoise_shim.py
-#   query_shim_test     query_closest / query_any against rt_intersect      tests/test_query_shim.py
-#   progress_shim_test  render_progressive against render()                 tests/test_progress_shim.py
-#   display_shim_test   display(render_linear()) against render()           tests/test_display_shim.py
-#   noise_test          progress_track_noise / progress_noise against the C ABI tests/test_noise_shim.py
-#   adaptive_shim_test  render_adaptive against the C ABI                   tests/test_adaptive_shim.py
-#                       (make sanitize-adaptive: the same program under ASan + UBSan over the hostsim sources)
-#   dnv_shim_test       denoise_var / progress_noise_sigma against the C ABI     tests/test_dnv_shim.py
-#   temporal_shim_test  temporal_accumulate against the C ABI                     tests/test_temporal_shim.py
-#   firefly_shim_test   firefly_clamp against the C ABI                           tests/test_firefly_shim.py
-#                       (make sanitize-firefly: the same program under ASan + UBSan over the hostsim sources)
-#   meter_shim_test     meter / auto_exposure against the C ABI                   tests/test_meter_shim.py
-#                       (make sanitize-meter: the same program under ASan + UBSan over the hostsim sources)
-#   upscale_shim_test   upscale against the C ABI                                 tests/test_upscale_shim.py
-#                       (make sanitize-upscale: the same program under ASan + UBSan over the hostsim sources)
+# C++ drop-in checks (container only): include/render_kernel_hip.h against the reference's headers and objects
+# (oracle/_ref, `make ref`). Every program in SHIM_PROGS is tests/native/<p>.cpp over tests/native/shim_common.h,
+# linked to the hostsim build of the C ABI (build/<p>) and to the product library (build/<p>_hip: built here by
+# `make shims-hip`, run on the GPU box, which has no reference tree; the binary carries what it needs).
+# tests/test_shims.py holds the invocations and runs both forms; each program's head says what it checks.
+SHIM_PROGS := shim_test $(addsuffix _shim_test,denoise query progress display noise adaptive dnv temporal firefly meter upscale)
+shims: $(SHIM_PROGS:%=build/%)
+shims-hip: $(SHIM_PROGS:%=build/%_hip)
+.PHONY: shims shims-hip
 REFDIR ?= /root/reference
 REFOBJ := oracle/_ref/objO2
 REFOBJS := $(REFOBJ)/bvh.o $(REFOBJ)/flattened_bvh.o $(REFOBJ)/triangle.o $(REFOBJ)/vec.o $(REFOBJ)/color.o \
   $(REFOBJ)/mat.o $(REFOBJ)/camera.o $(REFOBJ)/ray.o $(REFOBJ)/utils.o
-build/%_test: tests/native/%_test.cpp include/render_kernel_hip.h include/rt_hip.h $(LIB)/librt_hostsim.so
+build/%_test: tests/native/%_test.cpp tests/native/shim_common.h include/render_kernel_hip.h include/rt_hip.h $(LIB)/librt_hostsim.so
 	@mkdir -p build
 	$(CXX) -std=gnu++20 -O2 -fopenmp -Iinclude -I$(REFDIR)/include -I$(REFDIR)/rapidobj -I$(REFDIR) $< \
 	  $(REFOBJS) -Wl,--gc-sections \
 	  -L$(LIB) -lrt_hostsim -Wl,-rpath,'$$ORIGIN/../$(LIB)' -o $@
 
-build/%_test_hip: tests/native/%_test.cpp include/render_kernel_hip.h include/rt_hip.h $(LIB)/librt_hip.so
+build/%_test_hip: tests/native/%_test.cpp tests/native/shim_common.h include/render_kernel_hip.h include/rt_hip.h $(LIB)/librt_hip.so
 	@mkdir -p build
 	$(CXX) -std=gnu++20 -O2 -fopenmp -Iinclude -I$(REFDIR)/include -I$(REFDIR)/rapidobj -I$(REFDIR) $< \
 	  $(REFOBJS) -Wl,--gc-sections \
@@ -214,17 +203,19 @@ sanitize: build/san_asan/driver build/san_tsan/driver
 
 .PHONY: sanitize
 
-# A drop-in's program under ASan + UBSan: tests/native/X_shim_test.cpp with the hostsim sources of build/san_asan
-# in one stand-alone executable, a host program with its own main (container only: the reference's objects).
-#   sanitize-adaptive  render_adaptive and the adaptive C calls   (builds)
-#   sanitize-firefly   firefly_clamp and the firefly C calls      (builds)
-#   sanitize-meter     meter / auto_exposure and the metering C calls   (builds, then runs on the small Cornell scene)
-#   sanitize-upscale   upscale and the upscale C calls                  (builds, then runs on the small Cornell scene)
-build/san_asan/%_shim_test: tests/native/%_shim_test.cpp include/render_kernel_hip.h build/san_asan/driver
+# A drop-in's program under ASan + UBSan: make sanitize-X builds tests/native/X_shim_test.cpp with the hostsim
+# sources of build/san_asan in one stand-alone executable, a host program with its own main (container only: the
+# reference's objects), and runs it on the small Cornell scene under the flat sky: at 33 x 21, but for the layouts
+# that differ and for adaptive, whose every-tile-takes-every-pass check does not hold at that size under that sky.
+SAN_ARGS = - 33 21 3
+sanitize-adaptive: SAN_ARGS = - 40 30 4
+sanitize-denoise: SAN_ARGS = - 33 21 2 3
+sanitize-query: SAN_ARGS = 33 21
+sanitize-display: SAN_ARGS = - 33 21 3 build/san_asan/display.hdr
+build/san_asan/%_shim_test: tests/native/%_shim_test.cpp tests/native/shim_common.h include/render_kernel_hip.h build/san_asan/driver
 	$(CXX) -std=gnu++20 $(SAN_NUM) $(ASAN) -Iinclude -I$(REFDIR)/include -I$(REFDIR)/rapidobj -I$(REFDIR) $< \
-	  $(filter-out build/san_asan/cpu_oracle.o,$(wildcard build/san_asan/*.o)) $(REFOBJS) -Wl,--gc-sections -o $@
-sanitize-adaptive sanitize-firefly: sanitize-%: build/san_asan/%_shim_test
-sanitize-meter sanitize-upscale: sanitize-%: build/san_asan/%_shim_test
+	  $(SAN_SRCS:$(SRC)/%.cpp=build/san_asan/%.o) $(REFOBJS) -Wl,--gc-sections -o $@
+.PRECIOUS: build/san_asan/%_shim_test
+sanitize-%: build/san_asan/%_shim_test
 	ASAN_OPTIONS=halt_on_error=1:detect_leaks=1 UBSAN_OPTIONS=print_stacktrace=1:halt_on_error=1 OMP_NUM_THREADS=4 \
-	  $< scenes/cornell_pbr.obj - 33 21 3
-.PHONY: sanitize-adaptive sanitize-firefly sanitize-meter sanitize-upscale
+	  $< scenes/cornell_pbr.obj $(SAN_ARGS)

@@ -17,7 +17,7 @@ repeated when the frame is longer than the list:
   constant   every pixel (0.25, 0.5, 0.125): one bin
   black      every pixel 0: nothing is counted
 
-Shared by tests/test_meter.py (hostsim), tests/test_meter_gpu.py (gfx950) and tests/test_meter_shim.py.
+Shared by tests/test_meter.py (hostsim) and tests/test_meter_gpu.py (gfx950).
 Helpers only: no tests here."""
 from __future__ import annotations
 

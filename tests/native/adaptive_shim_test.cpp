@@ -4,51 +4,23 @@
 // passes made through the C calls on that context give the Image and the tile counts that
 // render_adaptive returns, bit for bit, with both active and inactive tiles among them. At threshold 0
 // every tile takes every pass: the counts are all 8 and the Image is render()'s. max_passes = 1 stops
-// after one adaptive pass (counts 4 and 6). Built like shim_test (the reference's headers and objects;
-// linked to the hostsim build, and to the product library for the GPU run);
-// tests/test_adaptive_shim.py runs it.
-//   adaptive_shim_test <obj> <sky.raw> W H bounces
+// after one adaptive pass (counts 4 and 6).
+//   adaptive_shim_test <obj> <sky.raw | -> W H bounces
 #include <algorithm>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
 
-#include "image.h"
-#include "utils.h"
-#include "render_kernel_hip.h"
-
-static Image read_sky_raw(const char* path)  // int w, h; float rgb[h][w][3]
-{
-    FILE* f = std::fopen(path, "rb");
-    if (!f) std::exit(3);
-    int wh[2];
-    if (std::fread(wh, 4, 2, f) != 2) std::exit(3);
-    std::vector<float> rgb((size_t)wh[0] * wh[1] * 3);
-    if (std::fread(rgb.data(), 4, rgb.size(), f) != rgb.size()) std::exit(3);
-    std::fclose(f);
-    Image out(wh[0], wh[1]);
-    for (int i = 0; i < wh[0] * wh[1]; i++) out[i] = Color(rgb[3 * i], rgb[3 * i + 1], rgb[3 * i + 2], 0.0f);
-    return out;
-}
+#include "shim_common.h"
 
 int main(int argc, char** argv)
 {
     if (argc < 6) return 2;
     const int W = std::atoi(argv[3]), H = std::atoi(argv[4]), nb = std::atoi(argv[5]), spp = 8, step = 2;
-    ParsedOBJ obj = Utils::parse_obj(argv[1]);
-    BVH bvh(&obj.triangles);
-    Image sky = read_sky_raw(argv[2]);
-    std::vector<float> cdf = Utils::compute_env_map_cdf(sky);
-    std::vector<Sphere> spheres;
+    shim::Scene scene(argv[1], argv[2]);
     Camera cam = Camera::CORNELL_BOX_CAMERA;
-    const size_t bytes = (size_t)W * H * 4 * sizeof(float);
     const int n_tiles = ((W + 7) / 8) * ((H + 7) / 8);
 
     // the C calls, on the context of a kernel that has rendered (scene, BVH, env and camera bound)
     Image whole(W, H), blank(W, H);
-    RenderKernel rc(W, H, spp, nb, whole, obj.triangles, obj.materials, obj.emissive_triangle_indices,
-                    obj.material_indices, spheres, bvh, sky, cdf);
+    RenderKernel rc = scene.kernel(W, H, spp, nb, whole);
     rc.set_camera(cam);
     rc.render();
     rt_context* ctx = rc.context();
@@ -73,36 +45,27 @@ int main(int argc, char** argv)
     rt_progress_end(ctx);
 
     Image adaptive(W, H), full(W, H), one(W, H);
-    RenderKernel ra(W, H, spp, nb, adaptive, obj.triangles, obj.materials, obj.emissive_triangle_indices,
-                    obj.material_indices, spheres, bvh, sky, cdf);
+    RenderKernel ra = scene.kernel(W, H, spp, nb, adaptive);
     ra.set_camera(cam);
     const std::vector<int> got_n = ra.render_adaptive(threshold, step);
-    const bool frame = c_ok && std::memcmp(adaptive.data(), want_fb.data(), bytes) == 0;
+    const bool frame = c_ok && shim::same_bits(adaptive, want_fb);
     const bool counts = c_ok && got_n == want_n;
     const int lo = *std::min_element(got_n.begin(), got_n.end()), hi = *std::max_element(got_n.begin(), got_n.end());
     const bool mixed = c_passes >= 1 && lo == 2 * step && hi > lo && hi <= spp;
 
-    RenderKernel rf(W, H, spp, nb, full, obj.triangles, obj.materials, obj.emissive_triangle_indices,
-                    obj.material_indices, spheres, bvh, sky, cdf);
+    RenderKernel rf = scene.kernel(W, H, spp, nb, full);
     rf.set_camera(cam);
     const std::vector<int> full_n = rf.render_adaptive(0.0f, step);
-    const bool all = std::count(full_n.begin(), full_n.end(), spp) == n_tiles && std::memcmp(full.data(), whole.data(), bytes) == 0;
+    const bool all = std::count(full_n.begin(), full_n.end(), spp) == n_tiles && shim::same_bits(full, whole);
 
-    RenderKernel ro(W, H, spp, nb, one, obj.triangles, obj.materials, obj.emissive_triangle_indices,
-                    obj.material_indices, spheres, bvh, sky, cdf);
+    RenderKernel ro = scene.kernel(W, H, spp, nb, one);
     ro.set_camera(cam);
     const std::vector<int> one_n = ro.render_adaptive(threshold, step, 1);
     bool capped = (int)one_n.size() == n_tiles;
     for (size_t t = 0; capped && t < one_n.size(); t++) capped = one_n[t] == std::min(want_n[t], 3 * step);
 
-    bool throws = false;  // (a threshold the C ABI refuses)
-    try {
-        ro.render_adaptive(-1.0f, step);
-    } catch (const std::runtime_error&) {
-        throws = true;
-    }
+    const bool throws = shim::throws([&] { ro.render_adaptive(-1.0f, step); });  // (a threshold the C ABI refuses)
 
-    std::printf("ADAPTIVE_SHIM frame %d counts %d mixed %d all %d max_passes %d throws %d\n", frame ? 1 : 0, counts ? 1 : 0,
-                mixed ? 1 : 0, all ? 1 : 0, capped ? 1 : 0, throws ? 1 : 0);
-    return frame && counts && mixed && all && capped && throws ? 0 : 1;
+    return shim::verdict("ADAPTIVE_SHIM", {{"frame", frame}, {"counts", counts}, {"mixed", mixed}, {"all", all},
+                                           {"max_passes", capped}, {"throws", throws}});
 }

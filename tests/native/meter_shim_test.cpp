@@ -3,60 +3,26 @@
 // samples with a NaN, a negative and a very bright pixel planted; the drop-in's histogram equals
 // rt_meter's on a bare context (the stage needs no scene) word for word, and its exposure equals
 // rt_meter_solve's on that histogram, at the defaults and with parameters, a previous exposure
-// and a time step. Built like shim_test (the reference's headers and objects, linked to the
-// hostsim build of the C ABI); tests/test_meter_shim.py runs it, and make sanitize-meter builds it
-// with ASan and UBSan over the hostsim sources and runs it.
-//   meter_shim_test <obj> <sky.raw | -> W H bounces      (-: a flat grey sky of 8 x 4 texels)
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
+// and a time step.
+//   meter_shim_test <obj> <sky.raw | -> W H bounces
 #include <limits>
-#include <vector>
 
-#include "image.h"
-#include "utils.h"
-#include "render_kernel_hip.h"
-
-static Image read_sky_raw(const char* path)  // int w, h; float rgb[h][w][3]
-{
-    if (std::strcmp(path, "-") == 0) {
-        Image flat(8, 4);
-        for (int i = 0; i < 32; i++) flat[i] = Color(0.5f, 0.5f, 0.5f, 0.0f);
-        return flat;
-    }
-    FILE* f = std::fopen(path, "rb");
-    if (!f) std::exit(3);
-    int wh[2];
-    if (std::fread(wh, 4, 2, f) != 2) std::exit(3);
-    std::vector<float> rgb((size_t)wh[0] * wh[1] * 3);
-    if (std::fread(rgb.data(), 4, rgb.size(), f) != rgb.size()) std::exit(3);
-    std::fclose(f);
-    Image out(wh[0], wh[1]);
-    for (int i = 0; i < wh[0] * wh[1]; i++) out[i] = Color(rgb[3 * i], rgb[3 * i + 1], rgb[3 * i + 2], 0.0f);
-    return out;
-}
+#include "shim_common.h"
 
 int main(int argc, char** argv)
 {
     if (argc < 6) return 2;
     const int W = std::atoi(argv[3]), H = std::atoi(argv[4]), nb = std::atoi(argv[5]);
-    ParsedOBJ obj = Utils::parse_obj(argv[1]);
-    BVH bvh(&obj.triangles);
-    Image sky = read_sky_raw(argv[2]);
-    std::vector<float> cdf = Utils::compute_env_map_cdf(sky);
-    std::vector<Sphere> spheres;
+    shim::Scene scene(argv[1], argv[2]);
 
     Image frame(W, H);
-    RenderKernel rk(W, H, 2, nb, frame, obj.triangles, obj.materials, obj.emissive_triangle_indices, obj.material_indices,
-                    spheres, bvh, sky, cdf);
+    RenderKernel rk = scene.kernel(W, H, 2, nb, frame);
     rk.set_camera(Camera::CORNELL_BOX_CAMERA);
     rk.render_linear();
     frame[0] = Color(std::numeric_limits<float>::quiet_NaN(), 0.5f, 0.5f, 1.0f);
     frame[1] = Color(-1.0f, -2.0f, -0.5f, 1.0f);
     frame[(size_t)(H / 2) * W + W / 2] = Color(9000.0f, 8000.0f, 7000.0f, 1.0f);
-    Image black(5, 3);
-    for (int i = 0; i < 15; i++) black[i] = Color(0.0f, 0.0f, 0.0f, 1.0f);
+    Image black(5, 3, Color(0.0f, 0.0f, 0.0f, 1.0f));
 
     rt_meter_params slow;
     rt_meter_default_params(&slow);
@@ -76,10 +42,7 @@ int main(int argc, char** argv)
     rc = rc ? rc : rt_meter_solve(&h0, nullptr, 0.0f, 0.0f, &s_def);
     rc = rc ? rc : rt_meter_solve(&h0, &slow, 40.0f, 0.25f, &s_slow);
     rc = rc ? rc : rt_meter_solve(&h1, nullptr, 0.75f, 0.25f, &s_black);
-    if (rc) {
-        std::printf("C ABI failed: %d %s\n", rc, rt_last_error(nullptr));
-        return 1;
-    }
+    if (shim::c_abi_failed(rc)) return 1;
     rt_destroy(c);
     auto same = [](const rt_meter_result& a, const rt_meter_result& b) { return std::memcmp(&a, &b, sizeof a) == 0; };
     const bool hist = std::memcmp(&h_shim, &h0, sizeof h0) == 0 && std::memcmp(&h_black, &h1, sizeof h1) == 0;
@@ -88,14 +51,11 @@ int main(int argc, char** argv)
     const bool defaults = same(r_def, s_def) && e_def == s_def.exposure && s_def.valid == 1 && e_def == s_def.target;
     const bool params = same(r_slow, s_slow) && e_slow == s_slow.exposure && e_slow != s_slow.target && e_slow != e_def;
     const bool empty = same(r_black, s_black) && e_black == 0.75f && s_black.valid == 0;
-    bool bad_params = false;
-    try {
+    const bool bad_params = shim::throws([&] {
         rt_meter_params bad = slow;
         bad.key = 1.5f;
         rk.auto_exposure(frame, 0.0f, 0.0f, &bad);
-    } catch (const std::runtime_error&) {
-        bad_params = true;
-    }
+    });
     std::printf("METER_SHIM hist %d counts %d defaults %d params %d empty %d bad_params_throw %d exposure %.9g\n", hist ? 1 : 0,
                 counts ? 1 : 0, defaults ? 1 : 0, params ? 1 : 0, empty ? 1 : 0, bad_params ? 1 : 0, (double)e_def);
     return hist && counts && defaults && params && empty && bad_params ? 0 : 1;

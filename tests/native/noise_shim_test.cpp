@@ -1,34 +1,11 @@
-// noise_test.cpp — the drop-in's RenderKernel::progress_track_noise / progress_noise and
+// noise_shim_test.cpp — the drop-in's RenderKernel::progress_track_noise / progress_noise and
 // render_progressive_tracked (include/render_kernel_hip.h) against the C ABI: Cornell, 6 samples in
 // passes of 2. The callback queries the noise from the second pass on and the struct equals what
 // rt_progress_noise reports on the kernel's context at that point, whose tile map's largest value is
 // the struct's max_tile; a query after one pass throws; the tracked frame is render()'s Image bit for
-// bit; a threshold above the first max_tile stops the passes after the second. Built like shim_test (the reference's headers and objects;
-// linked to the hostsim build, and to the product library for the GPU run); tests/test_noise_shim.py
-// runs it.
-//   noise_test <obj> <sky.raw> W H bounces
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
-
-#include "image.h"
-#include "utils.h"
-#include "render_kernel_hip.h"
-
-static Image read_sky_raw(const char* path)  // int w, h; float rgb[h][w][3]
-{
-    FILE* f = std::fopen(path, "rb");
-    if (!f) std::exit(3);
-    int wh[2];
-    if (std::fread(wh, 4, 2, f) != 2) std::exit(3);
-    std::vector<float> rgb((size_t)wh[0] * wh[1] * 3);
-    if (std::fread(rgb.data(), 4, rgb.size(), f) != rgb.size()) std::exit(3);
-    std::fclose(f);
-    Image out(wh[0], wh[1]);
-    for (int i = 0; i < wh[0] * wh[1]; i++) out[i] = Color(rgb[3 * i], rgb[3 * i + 1], rgb[3 * i + 2], 0.0f);
-    return out;
-}
+// bit; a threshold above the first max_tile stops the passes after the second.
+//   noise_shim_test <obj> <sky.raw | -> W H bounces
+#include "shim_common.h"
 
 static bool same(const rt_noise_stats& a, const rt_noise_stats& b)
 {
@@ -41,22 +18,15 @@ int main(int argc, char** argv)
     if (argc < 6) return 2;
     const int W = std::atoi(argv[3]), H = std::atoi(argv[4]), nb = std::atoi(argv[5]), spp = 6;
     const float threshold = 0.05f;
-    ParsedOBJ obj = Utils::parse_obj(argv[1]);
-    BVH bvh(&obj.triangles);
-    Image sky = read_sky_raw(argv[2]);
-    std::vector<float> cdf = Utils::compute_env_map_cdf(sky);
-    std::vector<Sphere> spheres;
+    shim::Scene scene(argv[1], argv[2]);
     Camera cam = Camera::CORNELL_BOX_CAMERA;
-    const size_t bytes = (size_t)W * H * 4 * sizeof(float);
 
     Image whole(W, H), tracked(W, H), early(W, H);
-    RenderKernel rk(W, H, spp, nb, whole, obj.triangles, obj.materials, obj.emissive_triangle_indices,
-                    obj.material_indices, spheres, bvh, sky, cdf);
+    RenderKernel rk = scene.kernel(W, H, spp, nb, whole);
     rk.set_camera(cam);
     rk.render();
 
-    RenderKernel rt(W, H, spp, nb, tracked, obj.triangles, obj.materials, obj.emissive_triangle_indices,
-                    obj.material_indices, spheres, bvh, sky, cdf);
+    RenderKernel rt = scene.kernel(W, H, spp, nb, tracked);
     rt.set_camera(cam);
     std::vector<rt_noise_stats> got, want;
     bool threw = false, max_ok = true;
@@ -65,11 +35,7 @@ int main(int argc, char** argv)
     rt.render_progressive_tracked(2, [&](const Image&, int done, int) {
         rt_noise_stats st;
         if (done == 2) {
-            try {
-                rt.progress_noise(threshold, st);
-            } catch (const std::runtime_error&) {
-                threw = true;  // (one pass only)
-            }
+            threw = shim::throws([&] { rt.progress_noise(threshold, st); });  // (one pass only)
             return true;
         }
         rt.progress_noise(threshold, st);
@@ -82,7 +48,7 @@ int main(int argc, char** argv)
         max_ok = max_ok && top == c_st.max_tile;
         return true;
     });
-    const bool frame = std::memcmp(tracked.data(), whole.data(), bytes) == 0;
+    const bool frame = shim::same_bits(tracked, whole);
 
     bool agree = got.size() == 2 && want.size() == 2;
     for (size_t i = 0; agree && i < got.size(); i++) agree = same(got[i], want[i]);
@@ -91,8 +57,7 @@ int main(int argc, char** argv)
                       got[1].passes == 3 && got[0].nonfinite == 0 && got[0].max_tile > 0.0f;
 
     // a threshold above the first max_tile: the callback stops after the second pass
-    RenderKernel re(W, H, spp, nb, early, obj.triangles, obj.materials, obj.emissive_triangle_indices,
-                    obj.material_indices, spheres, bvh, sky, cdf);
+    RenderKernel re = scene.kernel(W, H, spp, nb, early);
     re.set_camera(cam);
     int calls = 0, stopped_at = 0;
     re.render_progressive_tracked(2, [&](const Image&, int done, int) {
@@ -108,18 +73,11 @@ int main(int argc, char** argv)
     // an untracked render_progressive leaves the progression untracked: the query throws
     bool untracked = false;
     re.render_progressive(3, [&](const Image&, int done, int) {
-        if (done == 6) {
-            rt_noise_stats st;
-            try {
-                re.progress_noise(threshold, st);
-            } catch (const std::runtime_error&) {
-                untracked = true;
-            }
-        }
+        rt_noise_stats st;
+        if (done == 6) untracked = shim::throws([&] { re.progress_noise(threshold, st); });
         return true;
     });
 
-    std::printf("NOISE_SHIM frame %d one_pass_throws %d agree %d sane %d stops %d untracked_throws %d\n", frame ? 1 : 0,
-                threw ? 1 : 0, agree ? 1 : 0, sane ? 1 : 0, stops ? 1 : 0, untracked ? 1 : 0);
-    return frame && threw && agree && sane && stops && untracked ? 0 : 1;
+    return shim::verdict("NOISE_SHIM", {{"frame", frame}, {"one_pass_throws", threw}, {"agree", agree}, {"sane", sane},
+                                        {"stops", stops}, {"untracked_throws", untracked}});
 }

@@ -1,52 +1,30 @@
 // query_shim_test.cpp — the drop-in's RenderKernel::query_closest / query_any
 // (include/render_kernel_hip.h, over rt_query) against rt_intersect called directly on a
 // second context bound to the same scene: the Cornell camera rays of a W x H frame
-// (rt_camera_rays), every HitInfo field and every occlusion flag. Built like shim_test (the
-// reference's headers and objects; build/query_shim_test links the hostsim build of the C
-// ABI, build/query_shim_test_hip the product library); tests/test_query_shim.py runs both.
+// (rt_camera_rays), every HitInfo field and every occlusion flag.
 //   query_shim_test <obj> W H
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
-
-#include "image.h"
 #include "ray.h"
-#include "utils.h"
-#include "render_kernel_hip.h"
+#include "shim_common.h"
 
 int main(int argc, char** argv)
 {
     if (argc < 4) return 2;
     const int W = std::atoi(argv[2]), H = std::atoi(argv[3]);
-    ParsedOBJ obj = Utils::parse_obj(argv[1]);
-    BVH bvh(&obj.triangles);
-    Image sky(1, 1), fb(W, H);
-    std::vector<float> cdf;
-    std::vector<Sphere> spheres;
+    shim::Scene scene(argv[1]);  // (no sky: the queries need none)
+    Image fb(W, H);
     Camera cam = Camera::CORNELL_BOX_CAMERA;
-    RenderKernel rk(W, H, 1, 1, fb, obj.triangles, obj.materials, obj.emissive_triangle_indices, obj.material_indices,
-                    spheres, bvh, sky, cdf);
+    RenderKernel rk = scene.kernel(W, H, 1, 1, fb);
     rk.set_camera(cam);
 
-    rt_context* c = nullptr;
-    int rc = rt_create(0, &c);
-    rc = rc ? rc : rt_set_scene(c, reinterpret_cast<const float*>(obj.triangles.data()), (int)obj.triangles.size(),
-                                obj.material_indices.data(), (int)obj.material_indices.size(),
-                                reinterpret_cast<const float*>(obj.materials.data()), (int)obj.materials.size(),
-                                obj.emissive_triangle_indices.data(), (int)obj.emissive_triangle_indices.size(),
-                                nullptr, 0);
-    rc = rc ? rc : rt_build_bvh(c, 32, 8);
+    int rc = 0;
+    rt_context* c = scene.c_context(rc);
     rc = rc ? rc : rt_set_camera(c, &cam.view_matrix.m[0][0], cam.fov_dist);
     const size_t n = (size_t)W * H;
     std::vector<float> r(n * 6);
     std::vector<int> want(n * 11);
     rc = rc ? rc : rt_camera_rays(c, W, H, r.data());
     rc = rc ? rc : rt_intersect(c, r.data(), (int)n, want.data());
-    if (rc) {
-        std::printf("C ABI failed: %d %s\n", rc, rt_last_error(nullptr));
-        return 1;
-    }
+    if (shim::c_abi_failed(rc)) return 1;
     rt_destroy(c);
 
     std::vector<Ray> rays;
@@ -76,6 +54,5 @@ int main(int argc, char** argv)
         closest = closest && hits[i].primitive_index == w[1] && std::memcmp(f, w + 2, sizeof f) == 0;
     }
     const bool some = found > n / 2;  // (the Cornell camera looks into the box)
-    std::printf("QUERY_SHIM closest %d any %d hits %d\n", closest ? 1 : 0, any ? 1 : 0, some ? 1 : 0);
-    return closest && any && some ? 0 : 1;
+    return shim::verdict("QUERY_SHIM", {{"closest", closest}, {"any", any}, {"hits", some}});
 }

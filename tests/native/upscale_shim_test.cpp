@@ -3,54 +3,21 @@
 // pixel planted, and a synthetic sigma map; the drop-in's frame and sigma equal rt_upscale's on a
 // bare context (the stage needs no scene) fed with rt_render_features' guides at both sizes, bit
 // for bit, at the defaults with a sigma and with parameters without one; the wrong sizes throw.
-// Built like shim_test (the reference's headers and objects, linked to the hostsim build of the C
-// ABI); tests/test_upscale_shim.py runs it, and make sanitize-upscale builds it with ASan and UBSan
-// over the hostsim sources and runs it.
-//   upscale_shim_test <obj> <sky.raw | -> W H bounces      (-: a flat grey sky of 8 x 4 texels)
+//   upscale_shim_test <obj> <sky.raw | -> W H bounces
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <limits>
-#include <vector>
 
-#include "image.h"
-#include "utils.h"
-#include "render_kernel_hip.h"
-
-static Image read_sky_raw(const char* path)  // int w, h; float rgb[h][w][3]
-{
-    if (std::strcmp(path, "-") == 0) {
-        Image flat(8, 4);
-        for (int i = 0; i < 32; i++) flat[i] = Color(0.5f, 0.5f, 0.5f, 0.0f);
-        return flat;
-    }
-    FILE* f = std::fopen(path, "rb");
-    if (!f) std::exit(3);
-    int wh[2];
-    if (std::fread(wh, 4, 2, f) != 2) std::exit(3);
-    std::vector<float> rgb((size_t)wh[0] * wh[1] * 3);
-    if (std::fread(rgb.data(), 4, rgb.size(), f) != rgb.size()) std::exit(3);
-    std::fclose(f);
-    Image out(wh[0], wh[1]);
-    for (int i = 0; i < wh[0] * wh[1]; i++) out[i] = Color(rgb[3 * i], rgb[3 * i + 1], rgb[3 * i + 2], 0.0f);
-    return out;
-}
+#include "shim_common.h"
 
 int main(int argc, char** argv)
 {
     if (argc < 6) return 2;
     const int W = std::atoi(argv[3]), H = std::atoi(argv[4]), nb = std::atoi(argv[5]);
     const int WL = (W + 1) / 2, HL = (H + 1) / 2;
-    ParsedOBJ obj = Utils::parse_obj(argv[1]);
-    BVH bvh(&obj.triangles);
-    Image sky = read_sky_raw(argv[2]);
-    std::vector<float> cdf = Utils::compute_env_map_cdf(sky);
-    std::vector<Sphere> spheres;
+    shim::Scene scene(argv[1], argv[2]);
 
     Image low(WL, HL);
-    RenderKernel rk(WL, HL, 2, nb, low, obj.triangles, obj.materials, obj.emissive_triangle_indices, obj.material_indices,
-                    spheres, bvh, sky, cdf);
+    RenderKernel rk = scene.kernel(WL, HL, 2, nb, low);
     rk.set_camera(Camera::CORNELL_BOX_CAMERA);
     rk.render_linear();
     low[1] = Color(std::numeric_limits<float>::quiet_NaN(), 0.5f, 0.5f, 1.0f);
@@ -75,39 +42,19 @@ int main(int argc, char** argv)
                               nullptr, c_def.data(), s_c.data());
     rc = rc ? rc : rt_upscale(c, WL, HL, W, H, low.data(), nullptr, alb_lo.data(), nd_lo.data(), alb_hi.data(), nd_hi.data(),
                               &tight, c_par.data(), nullptr);
-    if (rc) {
-        std::printf("C ABI failed: %d %s\n", rc, rt_last_error(nullptr));
-        return 1;
-    }
+    if (shim::c_abi_failed(rc)) return 1;
     rt_destroy(c);
-    const bool frame = std::memcmp(up_def.data(), c_def.data(), n * 16) == 0 && up_def.width() == W && up_def.height() == H;
-    const bool sig = s_shim.size() == n && std::memcmp(s_shim.data(), s_c.data(), n * 4) == 0;
-    const bool params = std::memcmp(up_par.data(), c_par.data(), n * 16) == 0 && std::memcmp(up_par.data(), up_def.data(), n * 16) != 0;
+    const bool frame = up_def.width() == W && up_def.height() == H && shim::same_bits(up_def, c_def);
+    const bool sig = shim::same_bits(s_shim, s_c);
+    const bool params = shim::same_bits(up_par, c_par) && !shim::same_bits(up_par, up_def);
     bool finite = true;  // (the NaN pixel and the infinite sigma are rebuilt from their neighbours)
     for (size_t i = 0; i < n; i++) finite = finite && std::isfinite(up_def[i].r) && std::isfinite(s_shim[i]) && up_def[i].a == 1.0f;
-    int thrown = 0;
-    try {
-        rk.upscale(low, WL - 1, H);
-    } catch (const std::runtime_error&) {
-        thrown++;
-    }
-    try {
-        rk.upscale(low, W, H, std::vector<float>(3, 0.1f), nullptr, &s_shim);
-    } catch (const std::runtime_error&) {
-        thrown++;
-    }
-    try {
-        rk.upscale(low, W, H, sigma);
-    } catch (const std::runtime_error&) {
-        thrown++;
-    }
-    try {
-        rt_upscale_params bad = tight;
-        bad.min_weight = 1.0f;
-        rk.upscale(low, W, H, &bad);
-    } catch (const std::runtime_error&) {
-        thrown++;
-    }
+    rt_upscale_params bad = tight;
+    bad.min_weight = 1.0f;
+    int thrown = shim::throws([&] { rk.upscale(low, WL - 1, H); });
+    thrown += shim::throws([&] { rk.upscale(low, W, H, std::vector<float>(3, 0.1f), nullptr, &s_shim); });
+    thrown += shim::throws([&] { rk.upscale(low, W, H, sigma); });
+    thrown += shim::throws([&] { rk.upscale(low, W, H, &bad); });
     std::printf("UPSCALE_SHIM frame %d sigma %d params %d finite %d bad_arguments_throw %d\n", frame ? 1 : 0, sig ? 1 : 0,
                 params ? 1 : 0, finite ? 1 : 0, thrown);
     return frame && sig && params && finite && thrown == 4 ? 0 : 1;

@@ -1,38 +1,18 @@
 """The bindings of the firefly rejection stage against the C calls, on the hostsim build: RenderKernel.firefly_clamp
-and TemporalHistory.push(firefly=...) of rt_amd, the C++ drop-in's RenderKernel::firefly_clamp
-(include/render_kernel_hip.h; container only: it needs /root/reference, skipped elsewhere as
-tests/test_temporal_shim.py), and the command line's --firefly."""
+and TemporalHistory.push(firefly=...) of rt_amd, and the command line's --firefly. (The C++ drop-in's
+RenderKernel::firefly_clamp is a row of tests/test_shims.py.)"""
 from __future__ import annotations
-
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import dnv_cases as dv
 import firefly_cases as fc
-import golden_io as gio
 import noise_cases as nc
 import rt_amd
 import scenes
 import temporal_cases as tc
 from rt_amd import cli
-
-REF = "/root/reference/include"
-
-
-@pytest.mark.skipif(not os.path.isdir(REF), reason="needs the reference's headers (container only)")
-def test_cpp_shim_firefly_clamp_equals_c_abi(tmp_path):
-    subprocess.run(["make", "-C", gio.REPO, "-s", "ref", "build/firefly_shim_test"], check=True)
-    sky = tmp_path / "sky.raw"
-    scenes.write_sky_raw(str(sky), "S")
-    r = subprocess.run([os.path.join(gio.REPO, "build", "firefly_shim_test"), scenes.scene_path("cornell12"), str(sky),
-                        "33", "21", "3"], capture_output=True, text=True)
-    print(r.stdout, r.stderr)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert ("FIREFLY_SHIM defaults 1 params 1 no_sigma 1 clamped 1 bad_size_throws 1 sigma_out_without_sigma_throws 1"
-            in r.stdout)
 
 
 def test_python_firefly_clamp_equals_the_c_abi(cameras, manifest):

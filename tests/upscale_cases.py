@@ -13,7 +13,7 @@ Planted faults, by flat index i of the low frame (j of the output guides), in fr
 and, in low frames of at least 37 x 29, a 4 x 4 block of NaN colours at x 20..23, y 10..13: the output pixels whose
 sixteen taps all fall in it are the empty case.
 
-Shared by tests/test_upscale.py (hostsim), tests/test_upscale_gpu.py (gfx950) and tests/test_upscale_shim.py.
+Shared by tests/test_upscale.py (hostsim) and tests/test_upscale_gpu.py (gfx950).
 Helpers only: no tests here."""
 from __future__ import annotations
 
