@@ -41,12 +41,13 @@ $(OBJ)/rt_hostsim.o: $(SRC)/rt_hostsim.cpp $(HDRS) $(ALL_SRC)
 # translation unit of its own so that the render kernels' code generation does not depend on it:
 #   rt_wave_run  the host loop that launches them (run_wave; no device code)
 #   rt_probe     the kernels no render calls (rt_intersect's walk, query benchmark, self-tests)
-#   rt_denoise   the post stage (feature pass + filter)
+#   rt_denoise   the post stage (feature pass + rt_denoise's entry points to the à-trous filter)
 #   rt_query     the ray queries (rt_query / rt_query_device)
 #   rt_display   the display stage (tone-map + 8-bit conversion, linear resolve)
 #   rt_noise     a tracked progression's fold and noise estimate
 #   rt_adapt     an adaptive progression's selection, gather / scatter and resolves
-#   rt_dnv       the variance-guided filter and the absolute noise figure it takes
+#   rt_dnv       the absolute noise figure and rt_denoise_var's entry points to the same filter
+#                (rt_atrous_hip.h holds the filter's device side once; each of the two units compiles its own mode of it)
 #   rt_temporal  temporal accumulation: the previous frame reprojected into the new camera and blended in
 #   rt_firefly   firefly rejection: a pixel's luminance limited by a rank of its neighbours'
 #   rt_meter     exposure metering: the luminance histogram of a linear frame

@@ -129,17 +129,9 @@ struct Marker {
     }
 };
 
-// The post stage's buffers (rt_denoise.hip) and the ray queries' workspace (rt_query.hip),
-// created on first use and deleted with their Backend (its device current).
-struct Post;
-struct PostVar;  // (rt_dnv.hip: the variance-guided filter's buffers, Post's sibling)
+// The ray queries' workspace (rt_query.hip), created on first use and deleted with its Backend
+// (its device current).
 struct Query;
-struct PostDelete {
-    void operator()(Post* p) const;
-};
-struct PostVarDelete {
-    void operator()(PostVar* p) const;
-};
 struct QueryDelete {
     void operator()(Query* q) const;
 };
@@ -148,6 +140,17 @@ namespace rtk {
 struct WaveView;
 struct PixSrc;
 }
+
+// The buffers of an à-trous stage on the root device (rt_atrous_hip.h: rt_denoise's and rt_denoise_var's,
+// one each), created on first use and cached across calls like the render's.
+struct Post {
+    DevBuf io;  // host-pointer calls: the stage's inputs and outputs
+    DevBuf pp;  // the two buffers the passes alternate between
+    // optional timing (dn_pass_ms): an event before each launch (rt_denoise_var's prep, each pass) and after the last
+    bool timing = false;
+    Event pev[12];
+    int timed_passes = 0;
+};
 
 // An adaptive progression's buffers (rt_adapt.hip), created by its first adaptive pass or a
 // version-3 load and dropped with the progression.
@@ -216,8 +219,7 @@ struct Backend {
     Event tev[RT_MAX_LANES][3][RT_MAX_TIMED_ITERS];
     double kms[3] = {0, 0, 0};      // k_trace, k_step, k_tail
     long klaunch[3] = {0, 0, 0};
-    std::unique_ptr<Post, PostDelete> post;     // (rt_denoise.hip)
-    std::unique_ptr<PostVar, PostVarDelete> post_var;  // (rt_dnv.hip)
+    std::unique_ptr<Post> post, post_var;       // (rt_denoise.hip, rt_dnv.hip)
     std::unique_ptr<Query, QueryDelete> query;  // (rt_query.hip)
     std::unique_ptr<Adapt> adapt;               // (rt_adapt.hip)
 };
@@ -231,7 +233,7 @@ Backend* rt_backend_dev0(rt_context* c);  // rt_backend.hip: the root device's B
 //   enter, [staging], in / out / inout per buffer, begin, the stage's launches, end
 // b's device is current until the StagedCall leaves scope, then the caller's again.
 // The host forms' streams are inherited from the stages as they were written, not chosen here:
-//   null stream   features, denoise (Post::io), denoise_var (PostVar::io), temporal_accumulate
+//   null stream   features, denoise and denoise_var (a Post::io each), temporal_accumulate
 //                 (temporal_io), firefly (firefly_io), meter (meter_io), upscale (upscale_io),
 //                 display (disp), queries (Query::io), rt_render (fb)
 //   Backend::own  noise and noise_sigma (pg_noise), progressive resolves (pg_out), pixel lists (fb)

@@ -17,7 +17,7 @@
 //        f = limit / L(c), out = {f c.r, f c.g, f c.b, c.a}, sigma_out = f s, scale_out = f
 //      untouched otherwise: out = c and sigma_out = s bit for bit, scale_out = 1
 // A centre whose rgb is not finite is kept as it is, with scale 1: rt_denoise_var's rule for such a
-// centre (dnv_filter_pixel returns it unfiltered), so the chain hands it on unchanged.
+// centre (dn_filter_pixel returns it unfiltered), so the chain hands it on unchanged.
 // Decisions the list above leaves open, made here:
 //   a limit not > 0    leaves p untouched: f would be zero or negative, and a scale is in (0, 1]. Neighbours
 //                      of zero or negative luminance therefore limit nothing at floor 0; a spike over black

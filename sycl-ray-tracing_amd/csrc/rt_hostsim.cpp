@@ -685,75 +685,48 @@ int rt_backend_features(rt_context* c, int w, int h, void* albedo, void* normal_
     return RT_OK;
 }
 
+// One pass of the à-trous filter in mode M: the loop the filter kernels (rt_atrous_hip.h) run one thread per pixel.
+template <class M>
+static int host_filter_pass(const rtk::DnPass& P, float4_* dst, const float4_* orig, float blend, float* sigma_out)
+{
+    const rtk::DnDirect F{P};
+#pragma omp parallel for schedule(static)
+    for (int y = 0; y < P.h; y++)
+        for (int x = 0; x < P.w; x++)
+            rtk::dn_store(rtk::dn_filter_pixel<M>(P, x, y, F), (size_t)y * P.w + x, dst, orig, blend, sigma_out);
+    return RT_OK;
+}
+
 int rt_backend_denoise(rt_context* c, int w, int h, const void* in, const void* alb, const void* nd,
                        const rt_denoise_params& p, float blend, void* out, bool, void*)
 {
     const size_t n = (size_t)w * h;
     std::vector<float4_> ping(p.passes > 1 ? n : 0), pong(p.passes > 2 ? n : 0);
-    const float4_* src = (const float4_*)in;
+    const float4_* orig = (const float4_*)in;
     const double t0 = omp_get_wtime();
-    for (int i = 0; i < p.passes; i++) {
-        const bool last = i + 1 == p.passes;
-        rtk::DnPass P{w,
-                      h,
-                      1 << i,
-                      rtk::dn_inv_sigma2(std::ldexp((double)p.sigma_color, -i)),
-                      rtk::dn_inv_sigma2(p.sigma_normal),
-                      rtk::dn_inv_sigma2(p.sigma_albedo),
-                      rtk::dn_inv_sigma2(p.sigma_depth),
-                      src,
-                      (const float4_*)nd,
-                      (const float4_*)alb};
-        float4_* dst = last ? (float4_*)out : (i & 1) ? pong.data() : ping.data();
-        const rtk::DnDirect F{P};
-#pragma omp parallel for schedule(static)
-        for (int y = 0; y < h; y++)
-            for (int x = 0; x < w; x++) {
-                const size_t q = (size_t)y * w + x;
-                const float4_ f = rtk::dn_filter_pixel(P, x, y, F);
-                dst[q] = last ? rtk::dn_blend(f, ((const float4_*)in)[q], blend) : f;
-            }
-        src = dst;
-    }
+    rtk::dn_run_passes(w, h, p, orig, {ping.data(), pong.data()}, 0, (float4_*)out, (const float4_*)nd, (const float4_*)alb,
+                       [&](const rtk::DnPass& P, float4_* dst, bool last) {
+                           return host_filter_pass<rtk::DnFixed>(P, dst, last ? orig : nullptr, blend, nullptr);
+                       });
     c->last_kernel_ms = (omp_get_wtime() - t0) * 1e3;
     return RT_OK;
 }
 
-// The variance-guided filter on the host: the loops around rt_dnv.h's per-pixel functions that
-// k_dnv_prep and the two filter kernels (rt_dnv.hip) run one thread per pixel.
+// The variance-guided filter on the host: k_dnv_prep's loop (rt_dnv.hip), then the passes over its records.
 int rt_backend_denoise_var(rt_context* c, int w, int h, const void* in, const void* sigma, const void* alb, const void* nd,
                            const rt_denoise_var_params& p, float blend, void* out, void* sigma_out, bool, void*)
 {
     const size_t n = (size_t)w * h;
-    std::vector<float4_> rec[2] = {std::vector<float4_>(n), std::vector<float4_>(p.passes > 1 ? n : 0)};
+    std::vector<float4_> rec0(n), rec1(p.passes > 1 ? n : 0);
     const float4_* orig = (const float4_*)in;
     const double t0 = omp_get_wtime();
 #pragma omp parallel for schedule(static)
-    for (long i = 0; i < (long)n; i++) rec[0][i] = rtk::dnv_prep(orig[i], ((const float*)sigma)[i]);
-    for (int i = 0; i < p.passes; i++) {
-        const bool last = i + 1 == p.passes;
-        const rtk::DnvPass P{w,
-                             h,
-                             1 << i,
-                             rtk::dn_inv_sigma2(p.sigma_color),
-                             rtk::dn_inv_sigma2(p.sigma_normal),
-                             rtk::dn_inv_sigma2(p.sigma_albedo),
-                             rtk::dn_inv_sigma2(p.sigma_depth),
-                             p.var_floor,
-                             rec[i & 1].data(),
-                             (const float4_*)nd,
-                             (const float4_*)alb};
-        float4_* dst = last ? (float4_*)out : rec[(i + 1) & 1].data();
-        const rtk::DnvDirect F{P};
-#pragma omp parallel for schedule(static)
-        for (int y = 0; y < h; y++)
-            for (int x = 0; x < w; x++) {
-                const size_t q = (size_t)y * w + x;
-                const float4_ f = rtk::dnv_filter_pixel(P, x, y, F);
-                dst[q] = last ? rtk::dn_blend(f, orig[q], blend) : f;
-                if (last && sigma_out) ((float*)sigma_out)[q] = rt_sqrtf(f.w);
-            }
-    }
+    for (long i = 0; i < (long)n; i++) rec0[i] = rtk::dnv_prep(orig[i], ((const float*)sigma)[i]);
+    rtk::dn_run_passes(w, h, p, rec0.data(), {rec0.data(), rec1.data()}, 1, (float4_*)out, (const float4_*)nd,
+                       (const float4_*)alb, [&](const rtk::DnPass& P, float4_* dst, bool last) {
+                           return host_filter_pass<rtk::DnVar>(P, dst, last ? orig : nullptr, blend,
+                                                               last ? (float*)sigma_out : nullptr);
+                       });
     c->last_kernel_ms = (omp_get_wtime() - t0) * 1e3;
     return RT_OK;
 }
