@@ -416,6 +416,21 @@ public:
         hit.assign(found.begin(), found.end());
     }
 
+    // The first-hit guides of the camera's frame from the render's own walks (rt_render_gbuffer): albedo =
+    // {diffuse rgb, 0} and normal_depth = {n.xyz, t} (a miss: zeros and t = -1), each resized to the kernel's
+    // width x height; ids, when given, 2 ints per pixel = {primitive, material index}, {-1, -1} for a miss.
+    // exact: every pixel takes the exact walk (RT_GBUFFER_EXACT), rt_render_features' bits with no exception.
+    void gbuffer(Image& albedo, Image& normal_depth, std::vector<int>* ids = nullptr, bool exact = false) const
+    {
+        std::lock_guard<std::mutex> lk(m_mu);
+        const_cast<RenderKernel*>(this)->sync_materials();
+        albedo = Image(m_width, m_height);
+        normal_depth = Image(m_width, m_height);
+        if (ids) ids->assign((size_t)m_width * m_height * 2, 0);
+        check(rt_render_gbuffer(m_ctx, m_width, m_height, exact ? RT_GBUFFER_EXACT : 0, albedo.data(), normal_depth.data(),
+                                ids ? ids->data() : nullptr));
+    }
+
     int device_count() const { return rt_device_count(m_ctx); }
 
 private:

@@ -110,7 +110,9 @@ int rt_test_fail_device(rt_context* ctx, int device);
  * product's choice, 1 global atomics per pixel, 2 per-wave bins in LDS), "mt_blocks" (rt_meter's grid: 0 the
  * product's cap, n > 0 that many blocks, at most 65536), "up_variant" (rt_upscale's kernel: 0 the product's
  * choice, 1 direct loads, 2 the low-resolution footprint staged in LDS), "rq_variant" (rt_query's search-BVH kernel:
- * 0 the product's choice, 1 plain rounds of one query per quad, 2 per-quad refill),
+ * 0 the product's choice, 1 plain rounds of one query per quad, 2 per-quad refill), "gb_variant" (the same three
+ * for rt_render_gbuffer's search-BVH kernel), the stressor "gb_force_every" (N > 0: G-buffer pixels with
+ * i mod N == 0 go to the exact walk's list instead of the search-BVH walk; 0: off),
  * "chain_full" (1: the scene view reports an unmonotone tree, so the leaf verification
  * walks the whole ancestor chain instead of one slab test), the
  * stressor "force_fallback" (every k-th query by a ray hash skips to the exact
@@ -309,6 +311,48 @@ int rt_denoise(rt_context* ctx, int w, int h, const float* rgba_in, const float*
 int rt_denoise_device(rt_context* ctx, int w, int h, const void* d_rgba_in, const void* d_albedo,
                       const void* d_normal_depth, const rt_denoise_params* params, float blend, void* d_rgba_out,
                       void* stream);
+
+/* ------------------------------------------- first-hit G-buffer on the walks
+ * rt_render_features' two buffers, and the optional primitive and material ids, from the
+ * walks the render uses instead of one exact octree walk per lane: the guide pass for
+ * scenes where that walk's chain of dependent loads sets the pass's time.
+ *
+ * albedo and normal_depth are rt_render_features' records for the same ray (the centre of
+ * the pixel's jitter window); ids, when given, is int32[h][w][2] = {primitive,
+ * material_indices[primitive]}, {-1, -1} for a miss. The output is what
+ * rt_query(RT_QUERY_CLOSEST) answers for rt_camera_rays(w, h), bit for bit, turned into
+ * records by rt_render_features' rule: a hit where word 0 says so, t word 2, the normal
+ * words 6..8, the primitive word 1.
+ *
+ * Routing is rt_query's: a pixel whose origin lies inside the near box takes the
+ * search-BVH walk, four lanes per pixel; a walk that does not settle hands its pixel to
+ * the exact octree walk, eight lanes per walk, as do all pixels of a camera outside the
+ * near box. A context with spheres, or in rt_set_intersect_mode(0), has no octree answer
+ * to share: every pixel takes rt_render_features' own one-lane walk there. The flag
+ * RT_GBUFFER_EXACT sends every pixel to the exact walk, and the output then equals
+ * rt_render_features bit for bit, with no exception. Without the flag the shell limit of
+ * DESIGN.md §4 applies as it does to the render and to rt_query: from a camera inside the
+ * near box but far outside the scene's box, the search-BVH walk can miss a grazing hit that
+ * the exact walk finds. A guide taken from the walks is the first hit the render saw.
+ *
+ * rt_render_gbuffer: host buffers; runs, waits, downloads; rt_last_kernel_ms is the
+ * kernels' time. rt_render_gbuffer_device: device buffers on `stream` (NULL: default),
+ * returns without waiting; rt_last_kernel_ms is -1 and rt_device_last_kernel_ms reads the
+ * events once the stream is synchronized. The workspace (the fallback list, the octets'
+ * spill areas) belongs to the context and grows with the frame; calls on one context must
+ * not overlap in time on different streams. A multi-device context runs the stage on its
+ * root device and restores the caller's current device. rt_gbuffer_last_exact: how many
+ * pixels of the last call took the exact walk; waits for that call.
+ * RT_ERR_STATE without scene, BVH or camera; RT_ERR_ARG for w or h <= 0, more than
+ * 2^27 - 1 pixels, unknown flag bits, a NULL albedo or normal_depth, any two buffers that
+ * overlap by range, or (device form) a float4 buffer not 16-byte aligned or ids not 8-byte
+ * aligned. */
+#define RT_GBUFFER_EXACT 0x100 /* flag: every pixel takes the exact walk */
+int rt_render_gbuffer(rt_context* ctx, int w, int h, int flags, float* albedo, float* normal_depth,
+                      int* ids /*optional*/);
+int rt_render_gbuffer_device(rt_context* ctx, int w, int h, int flags, void* d_albedo, void* d_normal_depth, void* d_ids,
+                             void* stream);
+long rt_gbuffer_last_exact(rt_context* ctx); /* pixels of the last call that took the exact walk; waits */
 
 /* ---------------------------------------------------- progressive rendering
  * A frame of samples_total samples rendered in passes: previews after the first few

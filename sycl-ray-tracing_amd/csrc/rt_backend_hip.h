@@ -14,6 +14,7 @@
 //   rt_firefly.hip  firefly rejection: a pixel's luminance limited by a rank of its neighbours'
 //   rt_upscale.hip  guided upscale: a low-resolution frame taken to the output size along the full-size guides
 //   rt_meter.hip    exposure metering: the luminance histogram of a linear frame
+//   rt_gbuffer.hip  the first-hit G-buffer on the render's walks (quads in front, octets behind)
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -136,6 +137,12 @@ struct QueryDelete {
     void operator()(Query* q) const;
 };
 
+// The G-buffer stage's workspace (rt_gbuffer.hip), owned the same way.
+struct Gbuf;
+struct GbufDelete {
+    void operator()(Gbuf* g) const;
+};
+
 namespace rtk {
 struct WaveView;
 struct PixSrc;
@@ -222,6 +229,7 @@ struct Backend {
     std::unique_ptr<Post> post, post_var;       // (rt_denoise.hip, rt_dnv.hip)
     std::unique_ptr<Query, QueryDelete> query;  // (rt_query.hip)
     std::unique_ptr<Adapt> adapt;               // (rt_adapt.hip)
+    std::unique_ptr<Gbuf, GbufDelete> gbuf;     // (rt_gbuffer.hip)
 };
 
 Backend* rt_backend_dev0(rt_context* c);  // rt_backend.hip: the root device's Backend

@@ -257,6 +257,8 @@ int rt_test_schedule(rt_context* c, const char* key, double value)
     else if (k == "up_variant") s.up_variant = std::max(0, std::min(2, v));
     else if (k == "mt_blocks") s.mt_blocks = std::max(0, std::min(65536, v));
     else if (k == "rq_variant") s.rq_variant = std::max(0, std::min(2, v));
+    else if (k == "gb_variant") s.gb_variant = std::max(0, std::min(2, v));
+    else if (k == "gb_force_every") s.gb_force_every = std::max(0, v);
     else if (k == "chain_full") {
         // the devices' views carry the flag: the next call uploads them again
         if (s.chain_full != (v != 0)) c->dirty = true;

@@ -55,6 +55,49 @@ int rt_render_features_device(rt_context* c, int w, int h, void* d_albedo, void*
     return rt_backend_features(c, w, h, d_albedo, d_normal_depth, true, stream);
 }
 
+// ---- the first-hit G-buffer on the render's walks (rt_gbuffer.h)
+static int gbuffer_ready(rt_context* c, const char* fn, int w, int h, int flags, const void* alb, const void* nd,
+                         const void* ids, bool device)
+{
+    const size_t n = w > 0 && h > 0 ? (size_t)w * h : 0;
+    const StageArgs a{c, fn, device, {{alb, 16 * n, SA_OUT, SA_REQ, 16}, {nd, 16 * n, SA_OUT, SA_REQ, 16}, {ids, 8 * n, SA_OUT, SA_OPT, 8}}};
+    if (!c) return a.fail(": ctx is NULL");
+    if (!c->have_scene || !c->have_bvh) return a.fail(": scene/BVH not set", RT_ERR_STATE);
+    if (!c->have_cam) return a.fail(": camera not set", RT_ERR_STATE);
+    if (w <= 0 || h <= 0) return a.fail(": w and h must be at least 1");
+    if (int r = a.frame_limits(w, h, false)) return r;
+    if (flags & ~RT_GBUFFER_EXACT) return a.fail(": unknown flag bits");
+    if (a.missing()) return a.fail(": albedo or normal_depth is NULL");
+    if (int r = a.overlap()) return r;
+    if (int r = a.aligned(": the float4 buffers must be 16-byte aligned, ids 8-byte aligned")) return r;
+    return rt_tables_current(c, true, true);
+}
+
+// Spheres and the brute-force mode have no search-BVH walk and no octree answer to share (rt_query.h).
+static bool gbuffer_all_exact(const rt_context* c, int flags)
+{
+    return (flags & RT_GBUFFER_EXACT) != 0 || !c->spheres.empty() || c->brute;
+}
+
+int rt_render_gbuffer(rt_context* c, int w, int h, int flags, float* albedo, float* normal_depth, int* ids)
+{
+    if (int r = gbuffer_ready(c, "rt_render_gbuffer", w, h, flags, albedo, normal_depth, ids, false)) return r;
+    return rt_backend_gbuffer(c, w, h, gbuffer_all_exact(c, flags), albedo, normal_depth, ids, false, nullptr);
+}
+
+int rt_render_gbuffer_device(rt_context* c, int w, int h, int flags, void* d_albedo, void* d_normal_depth, void* d_ids,
+                             void* stream)
+{
+    if (int r = gbuffer_ready(c, "rt_render_gbuffer_device", w, h, flags, d_albedo, d_normal_depth, d_ids, true)) return r;
+    return rt_backend_gbuffer(c, w, h, gbuffer_all_exact(c, flags), d_albedo, d_normal_depth, d_ids, true, stream);
+}
+
+long rt_gbuffer_last_exact(rt_context* c)
+{
+    if (!c) return rt_fail(nullptr, RT_ERR_ARG, "rt_gbuffer_last_exact: ctx is NULL");
+    return rt_backend_gbuffer_last_exact(c);
+}
+
 // Defaults from the quality sweep on Cornell 64x64, 16 spp against 512 spp.
 void rt_denoise_default_params(rt_denoise_params* p)
 {

@@ -40,6 +40,8 @@ struct RtSchedule {
     int up_variant = 0;        // rt_upscale's kernel: 0 as measured, 1 direct loads, 2 the LDS footprint
     int mt_blocks = 0;         // rt_meter's grid: 0 the product's cap, n > 0 that many blocks (many grid-stride rounds)
     int rq_variant = 0;        // rt_query's fast kernel: 0 as measured, 1 plain grid-stride rounds, 2 per-quad refill
+    int gb_variant = 0;        // rt_render_gbuffer's fast kernel: 0 as measured, 1 plain 16-pixel rounds, 2 per-quad refill
+    int gb_force_every = 0;    // stressor: G-buffer pixels with i % N == 0 skip to the exact walk's list (0: off)
     bool chain_full = false;   // the scene view reports chain_monotone = 0: chain_ok / quad_chain_ok run their full
                                // ancestor-chain loop (rt_fast.h), which no tree the host builds reaches otherwise
 };
@@ -126,6 +128,8 @@ struct rt_context {
     double last_kernel_ms = 0.0;
     long query_exact = 0;         // rt_query_last_exact: the last call's exact-walk count where the host knows it,
     bool query_on_device = false; // ... else (gfx950, a routed call) it is read from the device's fallback counter
+    long gbuffer_exact = 0;         // rt_gbuffer_last_exact: the same pair for the last rt_render_gbuffer call
+    bool gbuffer_on_device = false;
 
     bool dirty = true;            // host state changed since the last upload
     bool mats_dirty_only = false; // only the material table changed (rt_set_materials)
@@ -198,6 +202,14 @@ int rt_backend_query(rt_context* ctx, bool any, bool all_exact, const void* rays
                      void* stream);
 // Queries of the last rt_backend_query that took the exact walk (waits for them); < 0: an error.
 long rt_backend_query_last_exact(rt_context* ctx);
+
+// The first-hit G-buffer (rt_gbuffer.h), on the root device like the post stage: albedo and normal_depth
+// (w*h float4 each) and the optional ids (w*h int32 pairs, or null); all_exact: every pixel takes the
+// exact walk. The arguments are validated (rt_capi_stages.cpp). Both forms as rt_backend_query.
+int rt_backend_gbuffer(rt_context* ctx, int w, int h, bool all_exact, void* albedo, void* normal_depth, void* ids,
+                       bool device, void* stream);
+// Pixels of the last rt_backend_gbuffer that took the exact walk (waits for them); < 0: an error.
+long rt_backend_gbuffer_last_exact(rt_context* ctx);
 
 // Progressions (ctx->prog describes the frame; single-device contexts only, arguments validated).
 // begin: the backend's buffers for prog.npx() pixels; base / state: host float4 per pixel, or

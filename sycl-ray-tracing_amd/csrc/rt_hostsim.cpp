@@ -21,6 +21,7 @@
 #include "rt_display.h"
 #include "rt_noise.h"
 #include "rt_query.h"
+#include "rt_gbuffer.h"
 #include "rt_temporal.h"
 #include "rt_firefly.h"
 #include "rt_upscale.h"
@@ -890,6 +891,41 @@ int rt_backend_query(rt_context* c, bool any, bool all_exact, const void* rays_v
 }
 
 long rt_backend_query_last_exact(rt_context* c) { return c->query_exact; }
+
+// The first-hit G-buffer on the host (rt_gbuffer.h): gb_pixel per pixel, the routing above with the
+// gb_force_every stressor in front of it.
+int rt_backend_gbuffer(rt_context* c, int w, int h, bool all_exact, void* albedo, void* normal_depth, void* ids_v, bool,
+                       void*)
+{
+    const RtSceneView S = rt_host_view(c);
+    const rtk::CamView V = rtk::cam_view(c->cam, w, h);
+    float4_* alb = (float4_*)albedo;
+    float4_* nd = (float4_*)normal_depth;
+    int32_t* ids = (int32_t*)ids_v;
+    const int force = c->sched.gb_force_every;
+    long exact = 0;
+    const double t0 = omp_get_wtime();
+#pragma omp parallel reduction(+ : exact)
+    {
+        std::vector<rtk::StackEnt> stack(RT_STACK_CAP);
+        rtk::IdxStack<RT_HOSTSIM_FAST_CAP> fst;
+#pragma omp for schedule(dynamic, 64)
+        for (long i = 0; i < (long)w * h; i++) {
+            bool ex;
+            const rtk::GbRecord r = rtk::gb_pixel(S, V, (int)i, all_exact, force, stack.data(), fst, &ex);
+            nd[i] = r.nd;
+            alb[i] = r.alb;
+            if (ids) ids[2 * i] = r.prim, ids[2 * i + 1] = r.mat;
+            exact += ex ? 1 : 0;
+        }
+    }
+    c->last_kernel_ms = (omp_get_wtime() - t0) * 1e3;
+    c->gbuffer_exact = exact;
+    c->gbuffer_on_device = false;
+    return RT_OK;
+}
+
+long rt_backend_gbuffer_last_exact(rt_context* c) { return c->gbuffer_exact; }
 
 // The search-BVH closest-hit query the render's k_trace stage runs (rt_fast.h
 // fast_query_closest, with its verification), for tests/test_hostsim.py: out_t = the

@@ -269,7 +269,7 @@ class TemporalHistory:
     def push(self, kernel: "RenderKernel", linear: Image, sigma, firefly=None):
         if firefly is not None:
             linear, sigma = kernel.firefly_clamp(linear, sigma, firefly)
-        _, nd = kernel.features()
+        _, nd = kernel.guides()
         hist = None if self.rgba is None else (self.rgba, self.sigma, self.length, self.normal_depth)
         cam = kernel.camera if self.camera is None else self.camera
         out, s_out, l_out = kernel.temporal_accumulate(linear, sigma, nd, cam, hist, self.params)
@@ -649,6 +649,45 @@ class RenderKernel:
                                                        ctypes.c_void_p(stream) if stream else None), self.ctx,
               "rt_render_features_device")
 
+    # ---- first-hit G-buffer on the render's walks (rt_render_gbuffer; include/rt_hip.h)
+    def gbuffer(self, size=None, exact: bool = False, ids: bool = False):
+        """rt_render_gbuffer: features()' (albedo, normal_depth) from the search-BVH walks with the
+        8-lane exact walk behind them; ids=True adds [h, w, 2] int32 = {primitive, material index},
+        {-1, -1} for a miss. exact=True sends every pixel down the exact walk (RT_GBUFFER_EXACT):
+        features()' bits with no exception. size: (w, h), default the kernel's own."""
+        self._sync_materials()
+        w, h = size if size is not None else (self.width, self.height)
+        alb = np.empty((h, w, 4), np.float32)
+        nd = np.empty_like(alb)
+        pid = np.empty((h, w, 2), np.int32) if ids else None
+        check(self.L, self.L.rt_render_gbuffer(self.ctx, w, h, _capi.GBUFFER_EXACT if exact else 0, ptr(alb), ptr(nd),
+                                               ptr(pid)), self.ctx, "rt_render_gbuffer")
+        return (alb, nd, pid) if ids else (alb, nd)
+
+    def gbuffer_device(self, d_albedo: int, d_normal_depth: int, d_ids: int | None = None, exact: bool = False,
+                       stream: int | None = None, size=None):
+        """rt_render_gbuffer_device: the same into device buffers (w*h*4 floats each, ids w*h*2 int32 or
+        None); no wait."""
+        self._sync_materials()
+        w, h = size if size is not None else (self.width, self.height)
+        check(self.L, self.L.rt_render_gbuffer_device(self.ctx, w, h, _capi.GBUFFER_EXACT if exact else 0, _vp(d_albedo),
+                                                      _vp(d_normal_depth), _vp(d_ids), _vp(stream)), self.ctx,
+              "rt_render_gbuffer_device")
+
+    def gbuffer_last_exact(self) -> int:
+        """rt_gbuffer_last_exact: pixels of the last gbuffer call that took the exact walk (waits)."""
+        r = int(self.L.rt_gbuffer_last_exact(self.ctx))
+        if r < 0:
+            check(self.L, r, self.ctx, "rt_gbuffer_last_exact")
+        return r
+
+    # guides of the stages below: features() or, with guide_source = "walks" (the CLI's --guides=walks), gbuffer()
+    guide_source = "exact"
+
+    def guides(self, size=None):
+        """The (albedo, normal_depth) pair the stages below are guided by, from guide_source."""
+        return self.gbuffer(size) if self.guide_source == "walks" else self.features(size)
+
     def denoise(self, image: Image | None = None, blend_factor: float = 1.0, guides=True, params=None) -> Image:
         """The call shape of Utils::OIDN_denoise(image, blend_factor): a new Image,
         blend_factor * filtered + (1 - blend_factor) * image, alpha 1. image: default the frame
@@ -661,7 +700,7 @@ class RenderKernel:
         alb = nd = None
         if guides is True:
             assert (w, h) == (self.width, self.height), "guides are rendered at the kernel's own size"
-            alb, nd = self.features()
+            alb, nd = self.guides()
         elif guides:
             alb, nd = (np.ascontiguousarray(g, dtype=np.float32).reshape(h, w, 4) for g in guides)
         out = Image(w, h)
@@ -708,7 +747,7 @@ class RenderKernel:
         alb = nd = None
         if guides is True:
             assert (w, h) == (self.width, self.height), "guides are rendered at the kernel's own size"
-            alb, nd = self.features()
+            alb, nd = self.guides()
         elif guides:
             alb, nd = (np.ascontiguousarray(g, dtype=np.float32).reshape(h, w, 4) for g in guides)
         out = Image(w, h)

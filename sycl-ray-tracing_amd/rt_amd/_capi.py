@@ -29,6 +29,7 @@ EXPORTS = [
     "rt_camera_rays", "rt_render_features", "rt_render_features_device", "rt_denoise_default_params", "rt_denoise",
     "rt_denoise_device",
     "rt_query", "rt_query_device", "rt_query_last_exact",
+    "rt_render_gbuffer", "rt_render_gbuffer_device", "rt_gbuffer_last_exact",
     "rt_progress_begin", "rt_progress_advance", "rt_progress_resolve", "rt_progress_resolve_device",
     "rt_progress_info", "rt_progress_save", "rt_progress_load", "rt_progress_end",
     "rt_display_default_params", "rt_render_linear", "rt_render_linear_device", "rt_progress_resolve_linear",
@@ -154,6 +155,9 @@ _SIGS = {
     "rt_camera_rays": (I, [P, I, I, P]),
     "rt_render_features": (I, [P, I, I, P, P]),
     "rt_render_features_device": (I, [P, I, I, P, P, P]),
+    "rt_render_gbuffer": (I, [P, I, I, I, P, P, P]),
+    "rt_render_gbuffer_device": (I, [P, I, I, I, P, P, P, P]),
+    "rt_gbuffer_last_exact": (L, [P]),
     "rt_denoise_default_params": (None, [ctypes.POINTER(DenoiseParams)]),
     "rt_denoise": (I, [P, I, I, P, P, P, ctypes.POINTER(DenoiseParams), F, P]),
     "rt_denoise_device": (I, [P, I, I, P, P, P, ctypes.POINTER(DenoiseParams), F, P, P]),
@@ -222,6 +226,8 @@ _SIGS = {
 
 # rt_query modes (include/rt_hip.h)
 QUERY_CLOSEST, QUERY_ANY, QUERY_EXACT = 0, 1, 0x100
+# rt_render_gbuffer flags (include/rt_hip.h)
+GBUFFER_EXACT = 0x100
 
 STAT_NAMES = ["rays", "vol", "tri", "leaf", "mat", "env", "cdf", "heap_slow", "any_rays", "any_vol", "any_tri",
               "any_leaf", "verify", "fallback", "quad_visits", "wave_slots", "refills", "drain_slots", "drain_visits",

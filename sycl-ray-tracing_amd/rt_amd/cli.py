@@ -57,6 +57,10 @@ w x h, the linear frame (and the filtered one) is upscaled along them, and meter
 fixed-sigma filter and the four PNGs follow at w x h. The run goes through render_linear and display as with
 --gamma=. Previews, checkpoints and RT_samples.png have the low size. The line "upscale: WLxHL -> WxH" is printed.
 Without the flag a run writes the bytes it writes today.
+
+Guide source (RenderKernel.guide_source): --guides=walks|exact, default exact. exact takes the first-hit guides of the
+filters and of --upscale= from features(), as a run without the flag does, byte for byte; walks takes them from
+gbuffer(), the render's own search-BVH walks with the 8-lane exact walk behind them.
 """
 from __future__ import annotations
 
@@ -73,7 +77,7 @@ def parse(argv):
     a = dict(obj="data/OBJs/cornell_pbr.obj", sky="data/Skyspheres/evening_road_01_puresky_2k.hdr", w=512, h=512,
              samples=64, bounces=8, camera="dragon", out=".", hostsim=False, preview_every=0, checkpoint="",
              exposure=None, gamma=None, hdr_out="", noise_threshold=None, adaptive=False, denoise="atrous", firefly=None,
-             auto_exposure=None, upscale=None)
+             auto_exposure=None, upscale=None, guides="exact")
     for s in argv:
         if s == "--hostsim":
             a["hostsim"] = True
@@ -87,7 +91,7 @@ def parse(argv):
             a["auto_exposure"] = {}
         elif s.startswith("--auto-exposure="):
             a["auto_exposure"] = {"key": float(s.split("=", 1)[1])}
-        elif s.startswith(("--sky=", "--camera=", "--out=", "--checkpoint=", "--hdr-out=", "--denoise=")):
+        elif s.startswith(("--sky=", "--camera=", "--out=", "--checkpoint=", "--hdr-out=", "--denoise=", "--guides=")):
             k, v = s[2:].split("=", 1)
             a[k.replace("-", "_")] = v
         elif s.startswith(("--exposure=", "--gamma=", "--noise-threshold=", "--upscale=")):
@@ -229,6 +233,9 @@ def main(argv=None) -> int:
     if a["denoise"] not in ("atrous", "var"):
         print("--denoise= takes atrous or var", file=sys.stderr)
         return 2
+    if a["guides"] not in ("walks", "exact"):
+        print("--guides= takes walks or exact", file=sys.stderr)
+        return 2
     if a["denoise"] == "var" and a["noise_threshold"] is None:
         print("--denoise=var needs --noise-threshold=T and --preview-every=K (it filters with the progression's "
               "noise estimate)", file=sys.stderr)
@@ -262,6 +269,7 @@ def main(argv=None) -> int:
                              P.emissive_triangle_indices, P.material_indices, None, rt_amd.BVH(P.triangles), sky,
                              rt_amd.compute_env_map_cdf(sky), hostsim=a["hostsim"])
     rk.set_camera(rt_amd.Camera.preset(a["camera"]))
+    rk.guide_source = a["guides"]
     filtered = None
     if a["preview_every"] > 0 or a["checkpoint"]:
         try:
@@ -278,7 +286,7 @@ def main(argv=None) -> int:
     guides = True
     if a["upscale"] is not None:  # (the linear frame, and the filtered one, to the full size along the guides)
         print(f"upscale: {a['w']}x{a['h']} -> {full[0]}x{full[1]}")
-        low_guides, guides = rk.features(), rk.features(size=full)
+        low_guides, guides = rk.guides(), rk.guides(size=full)
         fb = rk.upscale(fb, *low_guides, *guides)
         if filtered is not None:
             filtered = rk.upscale(filtered, *low_guides, *guides)
