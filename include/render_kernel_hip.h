@@ -384,6 +384,20 @@ public:
         return out;
     }
 
+    // Bloom (rt_bloom): the energy of `linear` above params' luminance threshold spread by a Gaussian pyramid
+    // and added back; it goes between render_linear() or the last filter and display(). params: null for
+    // the defaults. layer_out, when given, receives what was added, 4 floats per pixel {rgb, 0}. It needs
+    // no scene state and does not render.
+    Image bloom(const Image& linear, const rt_bloom_params* params = nullptr, std::vector<float>* layer_out = nullptr) const
+    {
+        std::lock_guard<std::mutex> lk(m_mu);
+        const int w = linear.width(), h = linear.height();
+        if (layer_out) layer_out->assign((size_t)w * h * 4, 0.0f);
+        Image out(w, h);
+        check(rt_bloom(m_ctx, w, h, linear.data(), params, out.data(), layer_out ? layer_out->data() : nullptr));
+        return out;
+    }
+
     // INTERSECT_SCENE for a batch of rays through rt_query (the render's search-BVH walks, the
     // exact walk behind them): hits[i] as BVH::intersect + the sphere loop fill it (t = -1 and
     // primitive_index = -1 without a hit).

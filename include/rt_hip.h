@@ -109,7 +109,8 @@ int rt_test_fail_device(rt_context* ctx, int device);
  * product's choice, 1 direct loads, 2 the LDS tile of luminances), "mt_variant" (rt_meter's kernel: 0 the
  * product's choice, 1 global atomics per pixel, 2 per-wave bins in LDS), "mt_blocks" (rt_meter's grid: 0 the
  * product's cap, n > 0 that many blocks, at most 65536), "up_variant" (rt_upscale's kernel: 0 the product's
- * choice, 1 direct loads, 2 the low-resolution footprint staged in LDS), "rq_variant" (rt_query's search-BVH kernel:
+ * choice, 1 direct loads, 2 the low-resolution footprint staged in LDS), "bloom_variant" (rt_bloom's reduce kernel:
+ * 0 the product's choice, 1 direct loads, 2 the source footprint staged in LDS), "rq_variant" (rt_query's search-BVH kernel:
  * 0 the product's choice, 1 plain rounds of one query per quad, 2 per-quad refill), "gb_variant" (the same three
  * for rt_render_gbuffer's search-BVH kernel), the stressor "gb_force_every" (N > 0: G-buffer pixels with
  * i mod N == 0 go to the exact walk's list instead of the search-BVH walk; 0: off),
@@ -848,6 +849,55 @@ int rt_upscale_device(rt_context* ctx, int w_lo, int h_lo, int w, int h, const v
                       const void* d_albedo_lo, const void* d_normal_depth_lo, const void* d_albedo_hi,
                       const void* d_normal_depth_hi, const rt_upscale_params* params, void* d_rgba_out, void* d_sigma_out,
                       void* stream);
+
+/* ---------------------------------------------- bloom
+ * A light many times brighter than what rt_display maps to white clips to a flat, hard-edged patch.
+ * This stage spreads the energy above a luminance threshold with a Gaussian pyramid and adds it back;
+ * it goes behind the last stage that changes the linear frame and in front of rt_display (meter the
+ * frame before it, so that the exposure does not chase the glow). Stateless, no scene or camera
+ * needed. Float32 throughout, no contraction, IEEE division; no expf, no square root.
+ *
+ * rt_bloom / _device: linear_rgba (float4[h][w]) in; rgba_out (float4[h][w], required) and layer_out
+ *   (float4[h][w], NULL allowed) out. For pixel p, c = linear_rgba[p]:
+ *   1 Bright pass. L = (0.2126f * c.r + 0.7152f * c.g) + 0.0722f * c.b (rt_firefly's luminance);
+ *     s = min(max((L - threshold) + knee, 0), 2 knee); q = knee > 0 ? s s / (4 knee) : 0;
+ *     e = max(q, L - threshold); b = e > 0 ? c.rgb (e / L) : 0. A pixel whose rgb is not all finite,
+ *     or whose L is not finite, gives b = 0.
+ *   2 Reduce, k = 1..levels: level k has (w_{k-1} + 1) / 2 x (h_{k-1} + 1) / 2 texels (level 0: b at
+ *     w x h); g_k(x, y) = sum over m, n = -2..2 of W[m] W[n] g_{k-1}(2x + m, 2y + n), W = {1, 4, 6,
+ *     4, 1} / 16, coordinates clamped to the edge of level k-1; the five row sums first, each in
+ *     ascending m, then the column sum in ascending n, every addition left to right.
+ *   3 Expand and accumulate: u_levels = g_levels; k = levels-1 .. 1: u_k = g_k + expand(u_{k+1}).
+ *     expand at (x, y) from a w' x h' level: xs = x >> 1, xn = clamp(xs + (x odd ? 1 : -1), 0, w' - 1),
+ *     ys, yn likewise; row(yy) = 0.75 g(xs, yy) + 0.25 g(xn, yy); value = 0.75 row(ys) + 0.25 row(yn).
+ *   4 B = expand(u_1) at w x h; scale = intensity / levels (one float division); rgba_out = {c.rgb +
+ *     scale B, c.a}. A centre whose rgb is not all finite is copied bit for bit and, its b being 0,
+ *     does not leak into its neighbours.
+ *   5 layer_out = {scale B, 0}.
+ *   A frame with nothing above threshold - knee, or intensity 0, comes back equal to its input as
+ *   values (a -0 channel as +0; alpha bit for bit), with a layer of zeroes. Nothing is clamped: a
+ *   negative channel of a bright pixel spreads as negative glow, and a sum that passes the largest
+ *   float is an infinity. The input is not written.
+ *   RT_ERR_ARG for a NULL ctx, linear_rgba or rgba_out; w or h below 1; levels outside 1..8; a
+ *   threshold, knee or intensity that is negative, a NaN or an infinity; knee > threshold; an output
+ *   whose bytes overlap the input's or the other output's; more than 262140 rows or 2^27 - 1 pixels
+ *   (rt_denoise's limits). The device form takes device pointers (16-byte aligned: RT_ERR_ARG
+ *   otherwise) and a stream (NULL: default) and returns without waiting; the pyramid, about a third of
+ *   the frame's bytes, is a buffer of the context reused across calls and sizes, so two device-form
+ *   calls of one context must not run at the same time on different streams. params NULL: the
+ *   defaults (rt_bloom_default_params). Runs on the root device of a multi-device context;
+ *   rt_last_kernel_ms as for rt_denoise. */
+typedef struct rt_bloom_params {
+    float threshold;  /* luminance above which a pixel glows; >= 0                              default 1   */
+    float knee;       /* half-width of the soft transition below the threshold; 0 .. threshold  default 0.5 */
+    float intensity;  /* the glow added is intensity / levels times the pyramid's sum; >= 0     default 0.2 */
+    int levels;       /* pyramid levels, 1..8: each doubles the glow's reach                    default 5   */
+} rt_bloom_params;
+void rt_bloom_default_params(rt_bloom_params* params);
+int rt_bloom(rt_context* ctx, int w, int h, const float* linear_rgba, const rt_bloom_params* params, float* rgba_out,
+             float* layer_out);
+int rt_bloom_device(rt_context* ctx, int w, int h, const void* d_linear, const rt_bloom_params* params, void* d_rgba_out,
+                    void* d_layer_out, void* stream);
 
 /* Counters of the last render when enabled (RT_STAT_* order, rt_device.h);
  * with n up to 2 * RT_STAT_COUNT the second block is the share of the

@@ -15,6 +15,7 @@
 //   rt_upscale.hip  guided upscale: a low-resolution frame taken to the output size along the full-size guides
 //   rt_meter.hip    exposure metering: the luminance histogram of a linear frame
 //   rt_gbuffer.hip  the first-hit G-buffer on the render's walks (quads in front, octets behind)
+//   rt_bloom.hip    bloom: the energy above a threshold spread by a Gaussian pyramid and added back
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -203,6 +204,7 @@ struct Backend {
     DevBuf firefly_io;   // rt_firefly: the frame and its sigma, then the three outputs
     DevBuf meter_io;     // rt_meter: the frame, then the histogram
     DevBuf upscale_io;   // rt_upscale: the low frame, its sigma and guides, the full-size guides, then the two outputs
+    DevBuf bloom;        // rt_bloom: the pyramid (levels 1.. back to back); host form: the frame and the two outputs, then the pyramid
     int cus = 0;         // the device's compute units, asked by the first rt_meter (rt_meter.hip; 0: not yet)
     DevBuf shard;     // multi-device renders: the root's N blocks of rows_max rows (scatter source /
                       // gather target); device d >= 1: its block
@@ -242,7 +244,7 @@ Backend* rt_backend_dev0(rt_context* c);  // rt_backend.hip: the root device's B
 // b's device is current until the StagedCall leaves scope, then the caller's again.
 // The host forms' streams are inherited from the stages as they were written, not chosen here:
 //   null stream   features, denoise and denoise_var (a Post::io each), temporal_accumulate
-//                 (temporal_io), firefly (firefly_io), meter (meter_io), upscale (upscale_io),
+//                 (temporal_io), firefly (firefly_io), meter (meter_io), upscale (upscale_io), bloom (bloom),
 //                 display (disp), queries (Query::io), rt_render (fb)
 //   Backend::own  noise and noise_sigma (pg_noise), progressive resolves (pg_out), pixel lists (fb)
 struct StagedCall {

@@ -1,6 +1,6 @@
 // rt_capi_stages.cpp — the frame stages of the C ABI (include/rt_hip.h), backend-independent like
 // rt_capi_host.cpp: camera rays and feature buffers, then denoise, denoise_var, temporal
-// accumulation, firefly rejection, guided upscale, metering and display. Each stage is its defaults,
+// accumulation, firefly rejection, guided upscale, bloom, metering and display. Each stage is its defaults,
 // a *_ready function that checks the call (the shared rules: rt_stage_args.h) and the two entry
 // points, host form and device form, over its rt_backend_* hook.
 #include <algorithm>
@@ -9,6 +9,7 @@
 #include <cstring>
 
 #include "rt_context.h"
+#include "rt_bloom.h"
 #include "rt_denoise.h"
 #include "rt_firefly.h"
 #include "rt_meter.h"
@@ -425,6 +426,56 @@ int rt_upscale_device(rt_context* c, int w_lo, int h_lo, int w, int h, const voi
                               albedo_hi, normal_depth_hi, params, rgba_out, sigma_out, true, A))
         return r;
     return rt_backend_upscale(c, A, rgba_out, sigma_out, true, stream);
+}
+
+// ---- bloom (rt_bloom.h)
+// The usual starting point, not a measured optimum: everything above display white glows, with a soft knee
+// half a unit wide, a fifth of the spread energy added back, five levels.
+void rt_bloom_default_params(rt_bloom_params* p)
+{
+    if (!p) return;
+    p->threshold = 1.0f;
+    p->knee = 0.5f;
+    p->intensity = 0.2f;
+    p->levels = 5;
+}
+
+static int bloom_ready(rt_context* c, const char* fn, int w, int h, const void* in, const rt_bloom_params* params,
+                       const void* out, const void* layer_out, bool device, rtk::BloomArgs& A)
+{
+    const size_t n = (size_t)w * h;
+    const StageArgs a{c, fn, device,
+                      {{in, 16 * n, SA_IN, SA_REQ, 16}, {out, 16 * n, SA_OUT, SA_REQ, 16}, {layer_out, 16 * n, SA_OUT, SA_OPT, 16}}};
+    if (!c) return a.fail(": ctx is NULL");
+    if (w <= 0 || h <= 0) return a.fail(": w and h must be at least 1");
+    if (a.missing()) return a.fail(": linear_rgba or rgba_out is NULL");
+    // (the composite tiles the frame 4 rows per block, as rt_denoise's kernels do)
+    if (int r = a.frame_limits(w, h, true)) return r;
+    const rt_bloom_params p = params_or_defaults(params, rt_bloom_default_params);
+    if (p.levels < 1 || p.levels > rtk::BL_MAX_LEVELS) return a.fail(": levels must be 1..8");
+    if (!std::isfinite(p.threshold) || !(p.threshold >= 0.0f)) return a.fail(": threshold is not finite and >= 0");
+    if (!std::isfinite(p.knee) || !(p.knee >= 0.0f)) return a.fail(": knee is not finite and >= 0");
+    if (!std::isfinite(p.intensity) || !(p.intensity >= 0.0f)) return a.fail(": intensity is not finite and >= 0");
+    if (p.knee > p.threshold) return a.fail(": knee is above threshold");
+    if (int r = a.overlap()) return r;
+    if (int r = a.aligned(": the buffers must be 16-byte aligned")) return r;
+    A = rtk::BloomArgs{w, h, p.levels, p.threshold, p.knee, p.intensity / (float)p.levels, (const float4_*)in};
+    return RT_OK;
+}
+
+int rt_bloom(rt_context* c, int w, int h, const float* linear, const rt_bloom_params* params, float* out, float* layer_out)
+{
+    rtk::BloomArgs A;
+    if (int r = bloom_ready(c, "rt_bloom", w, h, linear, params, out, layer_out, false, A)) return r;
+    return rt_backend_bloom(c, A, out, layer_out, false, nullptr);
+}
+
+int rt_bloom_device(rt_context* c, int w, int h, const void* d_linear, const rt_bloom_params* params, void* d_out,
+                    void* d_layer_out, void* stream)
+{
+    rtk::BloomArgs A;
+    if (int r = bloom_ready(c, "rt_bloom_device", w, h, d_linear, params, d_out, d_layer_out, true, A)) return r;
+    return rt_backend_bloom(c, A, d_out, d_layer_out, true, stream);
 }
 
 // ---- exposure metering (rt_meter.h)

@@ -23,6 +23,7 @@
 #include "rt_query.h"
 #include "rt_gbuffer.h"
 #include "rt_temporal.h"
+#include "rt_bloom.h"
 #include "rt_firefly.h"
 #include "rt_upscale.h"
 #include "rt_meter.h"
@@ -792,6 +793,56 @@ int rt_backend_firefly(rt_context* c, rtk::FireflyArgs A, void* rgba_out, void* 
     const double t0 = omp_get_wtime();
     if (A.radius == 1) firefly_rows<1>(A, (float4_*)rgba_out, (float*)sigma_out, (float*)scale_out);
     else firefly_rows<2>(A, (float4_*)rgba_out, (float*)sigma_out, (float*)scale_out);
+    c->last_kernel_ms = (omp_get_wtime() - t0) * 1e3;
+    return RT_OK;
+}
+
+// Bloom on the host: the loops around rt_bloom.h's texel functions that the kernels of rt_bloom.hip run one
+// thread per texel, every tap read straight from the level before (bl_reduce_texel over BlFrame / BlLevel).
+int rt_backend_bloom(rt_context* c, rtk::BloomArgs A, void* rgba_out, void* layer_out, bool, void*)
+{
+    const double t0 = omp_get_wtime();
+    std::vector<float4_> pyr(rtk::bl_pyramid_texels(A.w, A.h, A.levels));
+    struct Lv {
+        float4_* g;
+        int w, h;
+    } L[rtk::BL_MAX_LEVELS + 1];
+    L[0] = Lv{nullptr, A.w, A.h};
+    float4_* next = pyr.data();
+    for (int k = 1; k <= A.levels; k++) {
+        L[k] = Lv{next, rtk::bl_half(L[k - 1].w), rtk::bl_half(L[k - 1].h)};
+        next += (size_t)L[k].w * L[k].h;
+    }
+    for (int k = 1; k <= A.levels; k++) {
+        const Lv d = L[k];
+        const rtk::BlFrame F0{A};
+        const rtk::BlLevel Fk{L[k - 1].g, L[k - 1].w, L[k - 1].h};
+#pragma omp parallel for schedule(static)
+        for (int y = 0; y < d.h; y++)
+            for (int x = 0; x < d.w; x++)
+                d.g[(size_t)y * d.w + x] = k == 1 ? rtk::bl_reduce_texel(F0, x, y) : rtk::bl_reduce_texel(Fk, x, y);
+    }
+    for (int k = A.levels - 1; k >= 1; k--) {
+        const Lv d = L[k];
+        const rtk::BlLevel U{L[k + 1].g, L[k + 1].w, L[k + 1].h};
+#pragma omp parallel for schedule(static)
+        for (int y = 0; y < d.h; y++)
+            for (int x = 0; x < d.w; x++) {
+                const size_t p = (size_t)y * d.w + x;
+                d.g[p] = rtk::bl_accumulate(d.g[p], U, x, y);
+            }
+    }
+    const rtk::BlLevel U1{L[1].g, L[1].w, L[1].h};
+    float4_* out = (float4_*)rgba_out;
+    float4_* layer_o = (float4_*)layer_out;
+#pragma omp parallel for schedule(static)
+    for (int y = 0; y < A.h; y++)
+        for (int x = 0; x < A.w; x++) {
+            const size_t p = (size_t)y * A.w + x;
+            float4_ layer;
+            out[p] = rtk::bl_composite(A, A.in[p], U1, x, y, layer);
+            if (layer_o) layer_o[p] = layer;
+        }
     c->last_kernel_ms = (omp_get_wtime() - t0) * 1e3;
     return RT_OK;
 }

@@ -25,7 +25,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _capi
-from ._capi import (METER_STATS, METER_WORDS, DenoiseParams, DenoiseVarParams, DisplayParams, FireflyParams,  # noqa: F401
+from ._capi import (METER_STATS, METER_WORDS, BloomParams, DenoiseParams, DenoiseVarParams, DisplayParams, FireflyParams,  # noqa: F401
                     MeterParams, MeterResult, NoiseStats, TemporalParams, UpscaleParams)
 from ._capi import (RT_ERR_ARG, RT_ERR_HIP, RT_ERR_IO, RT_ERR_NODEV, RT_ERR_STATE, RT_OK,  # noqa: F401
                     RtError, check, lib, ptr)
@@ -35,7 +35,8 @@ __all__ = ["Camera", "Image", "ParsedOBJ", "parse_obj", "compute_env_map_cdf", "
            "image_to_rgba8", "DenoiseParams", "denoise_default_params", "DisplayParams", "write_image_hdr", "DenoiseVarParams",
            "denoise_var_default_params", "TemporalParams", "temporal_default_params", "TemporalHistory",
            "FireflyParams", "firefly_default_params", "MeterParams", "meter_default_params", "meter_stats", "meter_solve",
-           "ExposureAdapter", "METER_WORDS", "METER_STATS", "UpscaleParams", "upscale_default_params"]
+           "ExposureAdapter", "METER_WORDS", "METER_STATS", "UpscaleParams", "upscale_default_params",
+           "BloomParams", "bloom_default_params"]
 
 
 # ------------------------------------------------------------------ camera
@@ -183,6 +184,11 @@ def firefly_default_params(hostsim: bool = False) -> FireflyParams:
 def upscale_default_params(hostsim: bool = False) -> UpscaleParams:
     """rt_upscale_default_params: the guided upscale stage's defaults."""
     return _params(lib(hostsim), UpscaleParams, "upscale", None)
+
+
+def bloom_default_params(hostsim: bool = False) -> BloomParams:
+    """rt_bloom_default_params: the bloom stage's defaults."""
+    return _params(lib(hostsim), BloomParams, "bloom", None)
 
 
 def meter_default_params(hostsim: bool = False) -> MeterParams:
@@ -869,6 +875,35 @@ class RenderKernel:
                                                _vp(d_low_rgba), _vp(d_sigma), _vp(d_low_albedo), _vp(d_low_nd),
                                                _vp(d_hi_albedo), _vp(d_hi_nd), ctypes.byref(p), _vp(d_out), _vp(d_sigma_out),
                                                _vp(stream)), self.ctx, "rt_upscale_device")
+
+    # ---- bloom (rt_bloom; include/rt_hip.h)
+    def bloom(self, linear: Image, threshold=None, knee=None, intensity=None, levels=None, return_layer: bool = False,
+              params=None):
+        """rt_bloom: the energy of a linear frame above `threshold` (luminance, soft knee of half-width `knee`) spread by
+        a Gaussian pyramid of `levels` levels and added back, intensity / levels times the pyramid's sum. It goes between
+        render_linear() / the last filter and display(). A keyword left None keeps the stage's default (params: a
+        BloomParams or a dict of its fields instead). Returns the Image, or (Image, layer) with return_layer: layer
+        [h, w, 4] float32 = {what was added, 0}."""
+        src = np.ascontiguousarray(linear.pixels, dtype=np.float32)
+        h, w = src.shape[:2]
+        over = {k: v for k, v in dict(threshold=threshold, knee=knee, intensity=intensity, levels=levels).items() if v is not None}
+        p = _params(self.L, BloomParams, "bloom", params if params is not None else over)
+        if params is not None:
+            for k, v in over.items():
+                setattr(p, k, v)
+        out = Image(w, h)
+        layer = np.empty((h, w, 4), np.float32) if return_layer else None
+        check(self.L, self.L.rt_bloom(self.ctx, w, h, ptr(src), ctypes.byref(p), ptr(out.pixels), ptr(layer)), self.ctx,
+              "rt_bloom")
+        return (out, layer) if return_layer else out
+
+    def bloom_device(self, d_in: int, d_out: int, d_layer_out: int | None = None, params=None, stream: int | None = None,
+                     width=None, height=None):
+        """rt_bloom_device: device buffers of w*h*4 floats, no wait."""
+        p = _params(self.L, BloomParams, "bloom", params)
+        check(self.L, self.L.rt_bloom_device(self.ctx, int(width or self.width), int(height or self.height), _vp(d_in),
+                                             ctypes.byref(p), _vp(d_out), _vp(d_layer_out), _vp(stream)), self.ctx,
+              "rt_bloom_device")
 
     def render_variants(self, materials, frames=None, device_ptrs=None, row_offset: int = 0, row_stride: int = 1):
         """rt_render_variants: the material sweep as replicas. `materials` is

@@ -42,6 +42,7 @@ EXPORTS = [
     "rt_firefly_default_params", "rt_firefly", "rt_firefly_device",
     "rt_upscale_default_params", "rt_upscale", "rt_upscale_device",
     "rt_meter_default_params", "rt_meter", "rt_meter_device", "rt_meter_solve",
+    "rt_bloom_default_params", "rt_bloom", "rt_bloom_device",
 ]
 
 # return codes (include/rt_hip.h)
@@ -93,6 +94,11 @@ class MeterResult(ctypes.Structure):
 class UpscaleParams(ctypes.Structure):
     """struct rt_upscale_params (include/rt_hip.h)."""
     _fields_ = [("sigma_normal", F), ("sigma_albedo", F), ("sigma_depth", F), ("min_weight", F)]
+
+
+class BloomParams(ctypes.Structure):
+    """struct rt_bloom_params (include/rt_hip.h)."""
+    _fields_ = [("threshold", F), ("knee", F), ("intensity", F), ("levels", I)]
 
 
 class DisplayParams(ctypes.Structure):
@@ -200,7 +206,11 @@ _SIGS = {
     "rt_upscale_default_params": (None, [ctypes.POINTER(UpscaleParams)]),
     "rt_upscale": (I, [P, I, I, I, I, P, P, P, P, P, P, ctypes.POINTER(UpscaleParams), P, P]),
     "rt_upscale_device": (I, [P, I, I, I, I, P, P, P, P, P, P, ctypes.POINTER(UpscaleParams), P, P, P]),
+    "rt_bloom_default_params": (None, [ctypes.POINTER(BloomParams)]),
+    "rt_bloom": (I, [P, I, I, P, ctypes.POINTER(BloomParams), P, P]),
+    "rt_bloom_device": (I, [P, I, I, P, ctypes.POINTER(BloomParams), P, P, P]),
     # product-only extras
+    "rt_device_bloom_kernel_ms": (I, [P, I, I, P, ctypes.POINTER(BloomParams), P, P, I, I, P]),
     "rt_device_meter_kernel_ms": (I, [P, I, I, P, P, I, I, P]),
     "rt_device_upscale_kernel_ms": (I, [P, I, I, I, I, P, P, P, P, P, P, P, P, I, I, P]),
     "rt_device_libm": (I, [I, I, P, P, P, I]),

@@ -58,6 +58,12 @@ fixed-sigma filter and the four PNGs follow at w x h. The run goes through rende
 --gamma=. Previews, checkpoints and RT_samples.png have the low size. The line "upscale: WLxHL -> WxH" is printed.
 Without the flag a run writes the bytes it writes today.
 
+Bloom (RenderKernel.bloom): --bloom or --bloom=INTENSITY. The run goes through render_linear and display as with
+--gamma=. The frame that would be displayed (under --denoise=var the filtered one as well) is metered first, so that
+--auto-exposure does not chase the glow, then passes through rt_bloom (its defaults, or INTENSITY in the place of the
+default intensity), then is displayed; the line "bloom: N levels, M of P pixels above threshold" is printed. --hdr-out
+stays the frame before bloom, and previews are not bloomed. Without the flag a run writes the bytes it writes today.
+
 Guide source (RenderKernel.guide_source): --guides=walks|exact, default exact. exact takes the first-hit guides of the
 filters and of --upscale= from features(), as a run without the flag does, byte for byte; walks takes them from
 gbuffer(), the render's own search-BVH walks with the 8-lane exact walk behind them.
@@ -77,7 +83,7 @@ def parse(argv):
     a = dict(obj="data/OBJs/cornell_pbr.obj", sky="data/Skyspheres/evening_road_01_puresky_2k.hdr", w=512, h=512,
              samples=64, bounces=8, camera="dragon", out=".", hostsim=False, preview_every=0, checkpoint="",
              exposure=None, gamma=None, hdr_out="", noise_threshold=None, adaptive=False, denoise="atrous", firefly=None,
-             auto_exposure=None, upscale=None, guides="exact")
+             auto_exposure=None, upscale=None, guides="exact", bloom=None)
     for s in argv:
         if s == "--hostsim":
             a["hostsim"] = True
@@ -87,6 +93,10 @@ def parse(argv):
             a["firefly"] = {}
         elif s.startswith("--firefly="):
             a["firefly"] = {"gain": float(s.split("=", 1)[1])}
+        elif s == "--bloom":  # (the stage's default intensity)
+            a["bloom"] = {}
+        elif s.startswith("--bloom="):
+            a["bloom"] = {"intensity": float(s.split("=", 1)[1])}
         elif s == "--auto-exposure":  # (the solve's default key)
             a["auto_exposure"] = {}
         elif s.startswith("--auto-exposure="):
@@ -121,8 +131,8 @@ def display_stage(a: dict) -> bool:
 
 def linear_path(a: dict) -> bool:
     """The frame is rendered or resolved linear and displayed afterwards: the display stage's flags,
-    --denoise=var, which filters the linear frame, or --upscale=, which upscales it."""
-    return display_stage(a) or a["denoise"] == "var" or a["upscale"] is not None
+    --denoise=var, which filters the linear frame, --upscale=, which upscales it, or --bloom, which adds its glow."""
+    return display_stage(a) or a["denoise"] == "var" or a["upscale"] is not None or a["bloom"] is not None
 
 
 def low_size(a: dict):
@@ -144,6 +154,20 @@ def metered(rk: rt_amd.RenderKernel, linear: rt_amd.Image, a: dict, what: str = 
     e = rk.auto_exposure(linear, **a["auto_exposure"])
     print(f"auto-exposure{what}: {e:.9g}")
     return e
+
+
+def bloomed(rk: rt_amd.RenderKernel, linear: rt_amd.Image, a: dict, say: bool = True) -> rt_amd.Image:
+    """--bloom: the frame through RenderKernel.bloom, with its line printed (say); else the frame itself."""
+    if a["bloom"] is None:
+        return linear
+    p = rt_amd._params(rk.L, rt_amd.BloomParams, "bloom", a["bloom"])
+    c = linear.pixels
+    with np.errstate(all="ignore"):  # (rt_firefly's luminance in float32, as the stage computes it)
+        lum = (np.float32(0.2126) * c[..., 0] + np.float32(0.7152) * c[..., 1]) + np.float32(0.0722) * c[..., 2]
+        above = int((lum > np.float32(p.threshold)).sum())
+    if say:
+        print(f"bloom: {p.levels} levels, {above} of {lum.size} pixels above threshold")
+    return rk.bloom(linear, params=p)
 
 
 def render_progressive(rk: rt_amd.RenderKernel, fb: rt_amd.Image, a: dict):
@@ -252,6 +276,9 @@ def main(argv=None) -> int:
     if a["auto_exposure"] and not 0.0 < a["auto_exposure"]["key"] < 1.0:
         print("--auto-exposure=KEY takes a key inside (0, 1)", file=sys.stderr)
         return 2
+    if a["bloom"] and not (0.0 <= a["bloom"]["intensity"] < float("inf")):
+        print("--bloom=INTENSITY takes a finite intensity of at least 0", file=sys.stderr)
+        return 2
     if a["upscale"] is not None and not 1.0 < a["upscale"] <= 4.0:
         print("--upscale=F takes a factor with 1 < F <= 4", file=sys.stderr)
         return 2
@@ -294,9 +321,9 @@ def main(argv=None) -> int:
         if a["hdr_out"]:
             rt_amd.write_image_hdr(fb, a["hdr_out"])
         args = display_args(a, metered(rk, fb if filtered is None else filtered, a))
-        fb = rk.display(fb, **args)
+        fb = rk.display(bloomed(rk, fb, a), **args)
         if filtered is not None:
-            filtered = rk.display(filtered, **args)
+            filtered = rk.display(bloomed(rk, filtered, a, say=False), **args)
     print(f"{int((time.perf_counter() - t0) * 1e3)}ms")
     with np.errstate(all="ignore"):
         if filtered is None:
