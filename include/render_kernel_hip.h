@@ -398,6 +398,22 @@ public:
         return out;
     }
 
+    // Depth of field (rt_dof): a thin lens's blur built from `linear` and the first-hit distances of
+    // normal_depth (4 floats per pixel, .w = t: features() or gbuffer() at the frame's size); it goes behind
+    // the last filter or upscale and in front of bloom() and display(). params: null for the defaults.
+    // coc_out, when given, receives each pixel's radius in pixels. It needs no scene state and does not render.
+    Image dof(const Image& linear, const std::vector<float>& normal_depth, const rt_dof_params* params = nullptr,
+              std::vector<float>* coc_out = nullptr) const
+    {
+        std::lock_guard<std::mutex> lk(m_mu);
+        const int w = linear.width(), h = linear.height();
+        if (normal_depth.size() != (size_t)w * h * 4) throw std::runtime_error("librt_hip: dof: normal_depth is not width * height * 4 floats");
+        if (coc_out) coc_out->assign((size_t)w * h, 0.0f);
+        Image out(w, h);
+        check(rt_dof(m_ctx, w, h, linear.data(), normal_depth.data(), params, out.data(), coc_out ? coc_out->data() : nullptr));
+        return out;
+    }
+
     // INTERSECT_SCENE for a batch of rays through rt_query (the render's search-BVH walks, the
     // exact walk behind them): hits[i] as BVH::intersect + the sphere loop fill it (t = -1 and
     // primitive_index = -1 without a hit).

@@ -110,7 +110,8 @@ int rt_test_fail_device(rt_context* ctx, int device);
  * product's choice, 1 global atomics per pixel, 2 per-wave bins in LDS), "mt_blocks" (rt_meter's grid: 0 the
  * product's cap, n > 0 that many blocks, at most 65536), "up_variant" (rt_upscale's kernel: 0 the product's
  * choice, 1 direct loads, 2 the low-resolution footprint staged in LDS), "bloom_variant" (rt_bloom's reduce kernel:
- * 0 the product's choice, 1 direct loads, 2 the source footprint staged in LDS), "rq_variant" (rt_query's search-BVH kernel:
+ * 0 the product's choice, 1 direct loads, 2 the source footprint staged in LDS), "dof_variant" (rt_dof's kernel: 0 the
+ * product's choice, 1 the footprint staged in LDS, 2 direct loads), "rq_variant" (rt_query's search-BVH kernel:
  * 0 the product's choice, 1 plain rounds of one query per quad, 2 per-quad refill), "gb_variant" (the same three
  * for rt_render_gbuffer's search-BVH kernel), the stressor "gb_force_every" (N > 0: G-buffer pixels with
  * i mod N == 0 go to the exact walk's list instead of the search-BVH walk; 0: off),
@@ -898,6 +899,55 @@ int rt_bloom(rt_context* ctx, int w, int h, const float* linear_rgba, const rt_b
              float* layer_out);
 int rt_bloom_device(rt_context* ctx, int w, int h, const void* d_linear, const rt_bloom_params* params, void* d_rgba_out,
                     void* d_layer_out, void* stream);
+
+/* ---------------------------------------------- depth of field
+ * The render's camera is a pinhole: every frame is sharp from the near plane to the sky. This stage
+ * builds a thin lens's blur from the sharp linear frame and the first-hit distance the guides hold
+ * (normal_depth.w of rt_render_features or rt_render_gbuffer at the same size). It goes behind the
+ * last filter or upscale, which need pinhole guides, and in front of rt_bloom, rt_meter and
+ * rt_display, so that a highlight many times over white becomes a disc in linear radiance and then
+ * glows. Stateless, no scene or camera needed. Float32 throughout, no contraction, IEEE division; no
+ * expf, and no square root on the device.
+ *
+ * rt_dof / _device: linear_rgba (float4[h][w]) and normal_depth (float4[h][w]; only .w = t, the
+ *   distance along the camera ray, is read) in; rgba_out (float4[h][w], required) and coc_out
+ *   (float[h][w], NULL allowed) out. R = (float)max_radius. For pixel p, c = linear_rgba[p]:
+ *   1 Radius. far(p): t_p is not finite or not > 0 (a miss, a zero, a NaN). r_p = far ? min(coc_inf, R)
+ *     : min(coc_inf * (fabsf(t_p - focus) / t_p), R); coc_out[p] = r_p. For the ordering below a far
+ *     pixel's distance is +inf. The thin lens's circle of confusion with aperture and focal length
+ *     folded into its limit at infinity, coc_inf, in pixels. t runs along the ray, so the surface in
+ *     focus is a sphere about the eye; the planar form needs the camera and is not offered.
+ *   2 Gather. The taps q = p + (dx, dy), dy outer, dx inner, both -max_radius .. max_radius
+ *     ascending; a tap outside the image or whose rgb is not all finite is skipped. Else
+ *     re = (t_q > t_p) ? min(r_q, r_p) : r_q (a background tap spreads no further onto p than p's
+ *     own blur: a sharp foreground stays sharp); a = min((re + 0.5f) - D, 1.0f), D the float nearest
+ *     sqrt(dx^2 + dy^2) from a table built on the host; the tap is skipped unless a > 0;
+ *     k(r) = 1.0f / (max(r, 0.5f) * max(r, 0.5f)); wq = a * k(re); S += wq * c_q.rgb, W += wq, each
+ *     product formed and then added, in tap order.
+ *   3 rgba_out[p] = {S / W, c.a}. A centre whose rgb is not all finite is copied bit for bit; any
+ *     other centre's own tap has a > 0, so W > 0.
+ *   A skipped tap adds nothing. The gather is normalised, not energy-conserving: a pixel is a
+ *   weighted mean of what reaches it. coc_inf 0, or every t equal to focus, returns the input as
+ *   values (one tap of weight 2: 2c / 2). Nothing is clamped; a channel above half the largest
+ *   float sums to an infinity; a -0 channel comes back +0 (S starts at +0). With coc_inf 0 every
+ *   radius is 0, also where the ratio overflows. The input is not written.
+ *   RT_ERR_ARG for a NULL ctx, linear_rgba, normal_depth or rgba_out; w or h below 1; max_radius
+ *   outside 1..12; a focus that is not finite and > 0; a coc_inf that is negative, a NaN or an
+ *   infinity; an output whose bytes overlap an input's or the other output's; more than 262140 rows
+ *   or 2^27 - 1 pixels (rt_denoise's limits). The device form takes device pointers (the float4
+ *   buffers 16-byte aligned, coc_out 4-byte aligned: RT_ERR_ARG otherwise) and a stream (NULL:
+ *   default) and returns without waiting. params NULL: the defaults (rt_dof_default_params). Runs on
+ *   the root device of a multi-device context; rt_last_kernel_ms as for rt_denoise. */
+typedef struct rt_dof_params {
+    float focus;      /* ray distance in focus, > 0, finite                          default 1  */
+    float coc_inf;    /* radius in pixels of a point infinitely far away, >= 0       default 4  */
+    int   max_radius; /* radii are clamped to it; gather window, 1..12               default 8  */
+} rt_dof_params;
+void rt_dof_default_params(rt_dof_params* params);
+int rt_dof(rt_context* ctx, int w, int h, const float* linear_rgba, const float* normal_depth, const rt_dof_params* params,
+           float* rgba_out, float* coc_out);
+int rt_dof_device(rt_context* ctx, int w, int h, const void* d_linear, const void* d_normal_depth, const rt_dof_params* params,
+                  void* d_rgba_out, void* d_coc_out, void* stream);
 
 /* Counters of the last render when enabled (RT_STAT_* order, rt_device.h);
  * with n up to 2 * RT_STAT_COUNT the second block is the share of the

@@ -16,6 +16,7 @@
 //   rt_meter.hip    exposure metering: the luminance histogram of a linear frame
 //   rt_gbuffer.hip  the first-hit G-buffer on the render's walks (quads in front, octets behind)
 //   rt_bloom.hip    bloom: the energy above a threshold spread by a Gaussian pyramid and added back
+//   rt_dof.hip      depth of field: a gather over each pixel's circle of confusion, from the first-hit distance
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -205,6 +206,7 @@ struct Backend {
     DevBuf meter_io;     // rt_meter: the frame, then the histogram
     DevBuf upscale_io;   // rt_upscale: the low frame, its sigma and guides, the full-size guides, then the two outputs
     DevBuf bloom;        // rt_bloom: the pyramid (levels 1.. back to back); host form: the frame and the two outputs, then the pyramid
+    DevBuf dof_io;       // rt_dof: the frame and its guide record, then the two outputs
     int cus = 0;         // the device's compute units, asked by the first rt_meter (rt_meter.hip; 0: not yet)
     DevBuf shard;     // multi-device renders: the root's N blocks of rows_max rows (scatter source /
                       // gather target); device d >= 1: its block
@@ -244,7 +246,7 @@ Backend* rt_backend_dev0(rt_context* c);  // rt_backend.hip: the root device's B
 // b's device is current until the StagedCall leaves scope, then the caller's again.
 // The host forms' streams are inherited from the stages as they were written, not chosen here:
 //   null stream   features, denoise and denoise_var (a Post::io each), temporal_accumulate
-//                 (temporal_io), firefly (firefly_io), meter (meter_io), upscale (upscale_io), bloom (bloom),
+//                 (temporal_io), firefly (firefly_io), meter (meter_io), upscale (upscale_io), bloom (bloom), dof (dof_io),
 //                 display (disp), queries (Query::io), rt_render (fb)
 //   Backend::own  noise and noise_sigma (pg_noise), progressive resolves (pg_out), pixel lists (fb)
 struct StagedCall {

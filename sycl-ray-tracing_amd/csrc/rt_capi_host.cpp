@@ -154,7 +154,7 @@ bool rt_scene_has_emissive_prim(const rt_context* c) { return rt_table_has_emiss
 
 extern "C" {
 
-int rt_version(void) { return 10001; }
+int rt_version(void) { return 10002; }
 
 const char* rt_last_error(const rt_context* ctx)
 {
@@ -256,6 +256,7 @@ int rt_test_schedule(rt_context* c, const char* key, double value)
     else if (k == "mt_variant") s.mt_variant = std::max(0, std::min(2, v));
     else if (k == "up_variant") s.up_variant = std::max(0, std::min(2, v));
     else if (k == "bloom_variant") s.bloom_variant = std::max(0, std::min(2, v));
+    else if (k == "dof_variant") s.dof_variant = std::max(0, std::min(2, v));
     else if (k == "mt_blocks") s.mt_blocks = std::max(0, std::min(65536, v));
     else if (k == "rq_variant") s.rq_variant = std::max(0, std::min(2, v));
     else if (k == "gb_variant") s.gb_variant = std::max(0, std::min(2, v));

@@ -1,6 +1,6 @@
 // rt_capi_stages.cpp — the frame stages of the C ABI (include/rt_hip.h), backend-independent like
 // rt_capi_host.cpp: camera rays and feature buffers, then denoise, denoise_var, temporal
-// accumulation, firefly rejection, guided upscale, bloom, metering and display. Each stage is its defaults,
+// accumulation, firefly rejection, guided upscale, depth of field, bloom, metering and display. Each stage is its defaults,
 // a *_ready function that checks the call (the shared rules: rt_stage_args.h) and the two entry
 // points, host form and device form, over its rt_backend_* hook.
 #include <algorithm>
@@ -11,6 +11,7 @@
 #include "rt_context.h"
 #include "rt_bloom.h"
 #include "rt_denoise.h"
+#include "rt_dof.h"
 #include "rt_firefly.h"
 #include "rt_meter.h"
 #include "rt_stage_args.h"
@@ -476,6 +477,56 @@ int rt_bloom_device(rt_context* c, int w, int h, const void* d_linear, const rt_
     rtk::BloomArgs A;
     if (int r = bloom_ready(c, "rt_bloom_device", w, h, d_linear, params, d_out, d_layer_out, true, A)) return r;
     return rt_backend_bloom(c, A, d_out, d_layer_out, true, stream);
+}
+
+// ---- depth of field (rt_dof.h)
+// A starting point, not a measured optimum: the focus distance is the scene's to choose (rt_amd.focus_at), a point at
+// infinity blurs to a disc of 4 pixels' radius, and the window covers twice that.
+void rt_dof_default_params(rt_dof_params* p)
+{
+    if (!p) return;
+    p->focus = 1.0f;
+    p->coc_inf = 4.0f;
+    p->max_radius = 8;
+}
+
+static int dof_ready(rt_context* c, const char* fn, int w, int h, const void* in, const void* nd, const rt_dof_params* params,
+                     const void* out, const void* coc_out, bool device, rtk::DofArgs& A)
+{
+    const size_t n = (size_t)w * h;
+    const StageArgs a{c, fn, device,
+                      {{in, 16 * n, SA_IN, SA_REQ, 16}, {nd, 16 * n, SA_IN, SA_REQ, 16}, {out, 16 * n, SA_OUT, SA_REQ, 16},
+                       {coc_out, 4 * n, SA_OUT, SA_OPT, 4}}};
+    if (!c) return a.fail(": ctx is NULL");
+    if (w <= 0 || h <= 0) return a.fail(": w and h must be at least 1");
+    if (a.missing()) return a.fail(": linear_rgba, normal_depth or rgba_out is NULL");
+    // (k_dof_direct tiles the frame 4 rows per block, as rt_denoise's kernels do)
+    if (int r = a.frame_limits(w, h, true)) return r;
+    const rt_dof_params p = params_or_defaults(params, rt_dof_default_params);
+    if (p.max_radius < 1 || p.max_radius > rtk::DOF_MAX_RADIUS) return a.fail(": max_radius must be 1..12");
+    if (!std::isfinite(p.focus) || !(p.focus > 0.0f)) return a.fail(": focus is not finite and > 0");
+    if (!std::isfinite(p.coc_inf) || !(p.coc_inf >= 0.0f)) return a.fail(": coc_inf is not finite and >= 0");
+    if (int r = a.overlap()) return r;
+    if (int r = a.aligned()) return r;
+    A = rtk::DofArgs{w, h, p.max_radius, p.focus, p.coc_inf, (const float4_*)in, (const float4_*)nd, {}};
+    rtk::dof_build_table(A.D);
+    return RT_OK;
+}
+
+int rt_dof(rt_context* c, int w, int h, const float* linear, const float* normal_depth, const rt_dof_params* params, float* out,
+           float* coc_out)
+{
+    rtk::DofArgs A;
+    if (int r = dof_ready(c, "rt_dof", w, h, linear, normal_depth, params, out, coc_out, false, A)) return r;
+    return rt_backend_dof(c, A, out, coc_out, false, nullptr);
+}
+
+int rt_dof_device(rt_context* c, int w, int h, const void* d_linear, const void* d_normal_depth, const rt_dof_params* params,
+                  void* d_out, void* d_coc_out, void* stream)
+{
+    rtk::DofArgs A;
+    if (int r = dof_ready(c, "rt_dof_device", w, h, d_linear, d_normal_depth, params, d_out, d_coc_out, true, A)) return r;
+    return rt_backend_dof(c, A, d_out, d_coc_out, true, stream);
 }
 
 // ---- exposure metering (rt_meter.h)

@@ -39,6 +39,7 @@ struct RtSchedule {
     int mt_variant = 0;        // rt_meter's kernel: 0 as measured, 1 the direct kernel, 2 the LDS kernel
     int up_variant = 0;        // rt_upscale's kernel: 0 as measured, 1 direct loads, 2 the LDS footprint
     int bloom_variant = 0;     // rt_bloom's reduce kernel: 0 as measured, 1 direct loads, 2 the LDS tile
+    int dof_variant = 0;       // rt_dof's kernel: 0 as measured, 1 the LDS tile, 2 direct loads
     int mt_blocks = 0;         // rt_meter's grid: 0 the product's cap, n > 0 that many blocks (many grid-stride rounds)
     int rq_variant = 0;        // rt_query's fast kernel: 0 as measured, 1 plain grid-stride rounds, 2 per-quad refill
     int gb_variant = 0;        // rt_render_gbuffer's fast kernel: 0 as measured, 1 plain 16-pixel rounds, 2 per-quad refill
@@ -196,6 +197,13 @@ namespace rtk {
 struct BloomArgs;
 }
 int rt_backend_bloom(rt_context* ctx, rtk::BloomArgs A, void* rgba_out, void* layer_out, bool device, void* stream);
+// Depth of field (rt_dof.h), on the root device like the post stage: A holds the validated parameters, the table of
+// tap distances, the frame and its guide record (w*h float4 each); rgba_out (w*h float4) is required, coc_out (w*h
+// floats) may be null.
+namespace rtk {
+struct DofArgs;
+}
+int rt_backend_dof(rt_context* ctx, rtk::DofArgs A, void* rgba_out, void* coc_out, bool device, void* stream);
 // The display stage (rt_display.h), on the root device like the post stage: in (w*h float4) ->
 // out (w*h float4, may be `in`, or null) and out8 (w*h RGBA bytes, rows reversed when flip, or
 // null). The arguments are validated and inv_gamma = 1.0f / gamma (rt_capi_stages.cpp).

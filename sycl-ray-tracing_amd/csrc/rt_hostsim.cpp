@@ -24,6 +24,7 @@
 #include "rt_gbuffer.h"
 #include "rt_temporal.h"
 #include "rt_bloom.h"
+#include "rt_dof.h"
 #include "rt_firefly.h"
 #include "rt_upscale.h"
 #include "rt_meter.h"
@@ -842,6 +843,26 @@ int rt_backend_bloom(rt_context* c, rtk::BloomArgs A, void* rgba_out, void* laye
             float4_ layer;
             out[p] = rtk::bl_composite(A, A.in[p], U1, x, y, layer);
             if (layer_o) layer_o[p] = layer;
+        }
+    c->last_kernel_ms = (omp_get_wtime() - t0) * 1e3;
+    return RT_OK;
+}
+
+// Depth of field on the host: the loop around rt_dof.h's dof_pixel that k_dof_direct runs one thread per
+// pixel, every tap read straight from the frame and its guide record (DofDirect), over the rule's whole window.
+int rt_backend_dof(rt_context* c, rtk::DofArgs A, void* rgba_out, void* coc_out, bool, void*)
+{
+    const double t0 = omp_get_wtime();
+    const rtk::DofDirect F{A};
+    float4_* out = (float4_*)rgba_out;
+    float* coc = (float*)coc_out;
+#pragma omp parallel for schedule(static)
+    for (int y = 0; y < A.h; y++)
+        for (int x = 0; x < A.w; x++) {
+            const size_t p = (size_t)y * A.w + x;
+            float r;
+            out[p] = rtk::dof_pixel(A, x, y, A.in[p], A.nd[p].w, F, &r);
+            if (coc) coc[p] = r;
         }
     c->last_kernel_ms = (omp_get_wtime() - t0) * 1e3;
     return RT_OK;

@@ -25,7 +25,8 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _capi
-from ._capi import (METER_STATS, METER_WORDS, BloomParams, DenoiseParams, DenoiseVarParams, DisplayParams, FireflyParams,  # noqa: F401
+from ._capi import (METER_STATS, METER_WORDS, BloomParams, DenoiseParams, DenoiseVarParams, DisplayParams, DofParams,  # noqa: F401
+                    FireflyParams,
                     MeterParams, MeterResult, NoiseStats, TemporalParams, UpscaleParams)
 from ._capi import (RT_ERR_ARG, RT_ERR_HIP, RT_ERR_IO, RT_ERR_NODEV, RT_ERR_STATE, RT_OK,  # noqa: F401
                     RtError, check, lib, ptr)
@@ -36,7 +37,7 @@ __all__ = ["Camera", "Image", "ParsedOBJ", "parse_obj", "compute_env_map_cdf", "
            "denoise_var_default_params", "TemporalParams", "temporal_default_params", "TemporalHistory",
            "FireflyParams", "firefly_default_params", "MeterParams", "meter_default_params", "meter_stats", "meter_solve",
            "ExposureAdapter", "METER_WORDS", "METER_STATS", "UpscaleParams", "upscale_default_params",
-           "BloomParams", "bloom_default_params"]
+           "BloomParams", "bloom_default_params", "DofParams", "dof_default_params", "focus_at"]
 
 
 # ------------------------------------------------------------------ camera
@@ -189,6 +190,28 @@ def upscale_default_params(hostsim: bool = False) -> UpscaleParams:
 def bloom_default_params(hostsim: bool = False) -> BloomParams:
     """rt_bloom_default_params: the bloom stage's defaults."""
     return _params(lib(hostsim), BloomParams, "bloom", None)
+
+
+def dof_default_params(hostsim: bool = False) -> DofParams:
+    """rt_dof_default_params: the depth-of-field stage's defaults."""
+    return _params(lib(hostsim), DofParams, "dof", None)
+
+
+def focus_at(normal_depth, x: int, y: int) -> float:
+    """The focus distance for RenderKernel.dof that puts pixel (x, y) in focus: the t of normal_depth [h, w, 4]
+    (features() or gbuffer()) under it. A miss there (t not finite or not > 0): the nearest hit, the smallest t, of
+    the smallest square window about the pixel that holds one. ValueError for a frame without a hit."""
+    t = np.asarray(normal_depth)[..., 3]
+    h, w = t.shape
+    if not (0 <= x < w and 0 <= y < h):
+        raise ValueError(f"focus_at: pixel ({x}, {y}) is outside the {w} x {h} frame")
+    with np.errstate(all="ignore"):
+        hit = np.isfinite(t) & (t > 0)
+    for n in range(max(w, h)):
+        ys, xs = slice(max(y - n, 0), y + n + 1), slice(max(x - n, 0), x + n + 1)
+        if hit[ys, xs].any():
+            return float(t[ys, xs][hit[ys, xs]].min())
+    raise ValueError("focus_at: the frame has no hit")
 
 
 def meter_default_params(hostsim: bool = False) -> MeterParams:
@@ -904,6 +927,33 @@ class RenderKernel:
         check(self.L, self.L.rt_bloom_device(self.ctx, int(width or self.width), int(height or self.height), _vp(d_in),
                                              ctypes.byref(p), _vp(d_out), _vp(d_layer_out), _vp(stream)), self.ctx,
               "rt_bloom_device")
+
+    # ---- depth of field (rt_dof; include/rt_hip.h)
+    def dof(self, linear: Image, normal_depth, params=None, coc: bool = False):
+        """rt_dof: a thin lens's blur built from a linear frame and its first-hit distances, normal_depth [h, w, 4]
+        (features() or gbuffer() at the frame's size; only t is read). It goes behind the last filter or upscale and in
+        front of bloom(), auto_exposure() and display(). params: None (the defaults), a DofParams, or a dict of its
+        fields over the defaults; focus_at() gives the focus for a pixel. Returns the Image, or (Image, radius) with
+        coc: radius [h, w] float32, each pixel's circle of confusion in pixels."""
+        src = np.ascontiguousarray(linear.pixels, dtype=np.float32)
+        h, w = src.shape[:2]
+        nd = np.ascontiguousarray(normal_depth, dtype=np.float32)
+        if nd.shape != (h, w, 4):
+            raise ValueError(f"dof: normal_depth is {nd.shape}, the frame ({h}, {w}, 4)")
+        p = _params(self.L, DofParams, "dof", params)
+        out = Image(w, h)
+        radius = np.empty((h, w), np.float32) if coc else None
+        check(self.L, self.L.rt_dof(self.ctx, w, h, ptr(src), ptr(nd), ctypes.byref(p), ptr(out.pixels), ptr(radius)), self.ctx,
+              "rt_dof")
+        return (out, radius) if coc else out
+
+    def dof_device(self, d_in: int, d_normal_depth: int, d_out: int, d_coc_out: int | None = None, params=None,
+                   stream: int | None = None, width=None, height=None):
+        """rt_dof_device: device buffers of w*h*4 floats (d_coc_out: w*h floats or None), no wait."""
+        p = _params(self.L, DofParams, "dof", params)
+        check(self.L, self.L.rt_dof_device(self.ctx, int(width or self.width), int(height or self.height), _vp(d_in),
+                                           _vp(d_normal_depth), ctypes.byref(p), _vp(d_out), _vp(d_coc_out), _vp(stream)),
+              self.ctx, "rt_dof_device")
 
     def render_variants(self, materials, frames=None, device_ptrs=None, row_offset: int = 0, row_stride: int = 1):
         """rt_render_variants: the material sweep as replicas. `materials` is

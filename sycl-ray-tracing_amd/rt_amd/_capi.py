@@ -43,6 +43,7 @@ EXPORTS = [
     "rt_upscale_default_params", "rt_upscale", "rt_upscale_device",
     "rt_meter_default_params", "rt_meter", "rt_meter_device", "rt_meter_solve",
     "rt_bloom_default_params", "rt_bloom", "rt_bloom_device",
+    "rt_dof_default_params", "rt_dof", "rt_dof_device",
 ]
 
 # return codes (include/rt_hip.h)
@@ -99,6 +100,11 @@ class UpscaleParams(ctypes.Structure):
 class BloomParams(ctypes.Structure):
     """struct rt_bloom_params (include/rt_hip.h)."""
     _fields_ = [("threshold", F), ("knee", F), ("intensity", F), ("levels", I)]
+
+
+class DofParams(ctypes.Structure):
+    """struct rt_dof_params (include/rt_hip.h)."""
+    _fields_ = [("focus", F), ("coc_inf", F), ("max_radius", I)]
 
 
 class DisplayParams(ctypes.Structure):
@@ -209,7 +215,11 @@ _SIGS = {
     "rt_bloom_default_params": (None, [ctypes.POINTER(BloomParams)]),
     "rt_bloom": (I, [P, I, I, P, ctypes.POINTER(BloomParams), P, P]),
     "rt_bloom_device": (I, [P, I, I, P, ctypes.POINTER(BloomParams), P, P, P]),
+    "rt_dof_default_params": (None, [ctypes.POINTER(DofParams)]),
+    "rt_dof": (I, [P, I, I, P, P, ctypes.POINTER(DofParams), P, P]),
+    "rt_dof_device": (I, [P, I, I, P, P, ctypes.POINTER(DofParams), P, P, P]),
     # product-only extras
+    "rt_device_dof_kernel_ms": (I, [P, I, I, P, P, ctypes.POINTER(DofParams), P, P, I, I, P]),
     "rt_device_bloom_kernel_ms": (I, [P, I, I, P, ctypes.POINTER(BloomParams), P, P, I, I, P]),
     "rt_device_meter_kernel_ms": (I, [P, I, I, P, P, I, I, P]),
     "rt_device_upscale_kernel_ms": (I, [P, I, I, I, I, P, P, P, P, P, P, P, P, I, I, P]),

@@ -64,6 +64,18 @@ Bloom (RenderKernel.bloom): --bloom or --bloom=INTENSITY. The run goes through r
 default intensity), then is displayed; the line "bloom: N levels, M of P pixels above threshold" is printed. --hdr-out
 stays the frame before bloom, and previews are not bloomed. Without the flag a run writes the bytes it writes today.
 
+Depth of field (RenderKernel.dof): --dof or --dof=COC_INF, with --focus=T or --focus-at=X,Y (default: the centre
+pixel). The run goes through render_linear and display as with --gamma=. The linear frame (under --denoise=var the
+filtered one as well), after --upscale= if given, passes through rt_dof along the first-hit distances of the guides at
+its size (--guides=), before it is metered, bloomed and displayed: its defaults, or COC_INF in the place of the
+default coc_inf; the focus distance is T, or rt_amd.focus_at at pixel X,Y. The line "dof: focus T, coc_inf C,
+max_radius R, largest radius M" is printed. --hdr-out stays the frame before the blur, and previews are sharp.
+--dof=0 writes the bytes of a run without the flag. Under --denoise=var the variance-guided filter runs first, on
+the sharp frame with its pinhole guides, and the lens blurs its result. Under the default --denoise=atrous the three
+RT_output_denoised_* files are, as with --bloom, the a-trous filter applied to the displayed frame, here the blurred
+one, with the pinhole guides: the filter's edge-stops then follow the sharp geometry and not the blurred image, so
+those three files are not a filtered lens image in the sense above; RT_output.png is.
+
 Guide source (RenderKernel.guide_source): --guides=walks|exact, default exact. exact takes the first-hit guides of the
 filters and of --upscale= from features(), as a run without the flag does, byte for byte; walks takes them from
 gbuffer(), the render's own search-BVH walks with the 8-lane exact walk behind them.
@@ -83,7 +95,7 @@ def parse(argv):
     a = dict(obj="data/OBJs/cornell_pbr.obj", sky="data/Skyspheres/evening_road_01_puresky_2k.hdr", w=512, h=512,
              samples=64, bounces=8, camera="dragon", out=".", hostsim=False, preview_every=0, checkpoint="",
              exposure=None, gamma=None, hdr_out="", noise_threshold=None, adaptive=False, denoise="atrous", firefly=None,
-             auto_exposure=None, upscale=None, guides="exact", bloom=None)
+             auto_exposure=None, upscale=None, guides="exact", bloom=None, dof=None, focus=None, focus_at=None)
     for s in argv:
         if s == "--hostsim":
             a["hostsim"] = True
@@ -97,6 +109,15 @@ def parse(argv):
             a["bloom"] = {}
         elif s.startswith("--bloom="):
             a["bloom"] = {"intensity": float(s.split("=", 1)[1])}
+        elif s == "--dof":  # (the stage's default coc_inf)
+            a["dof"] = {}
+        elif s.startswith("--dof="):
+            a["dof"] = {"coc_inf": float(s.split("=", 1)[1])}
+        elif s.startswith("--focus-at="):
+            try:
+                a["focus_at"] = tuple(int(v) for v in s.split("=", 1)[1].split(","))
+            except ValueError:  # (not integers: main() refuses a tuple that is not a pixel)
+                a["focus_at"] = ()
         elif s == "--auto-exposure":  # (the solve's default key)
             a["auto_exposure"] = {}
         elif s.startswith("--auto-exposure="):
@@ -104,7 +125,7 @@ def parse(argv):
         elif s.startswith(("--sky=", "--camera=", "--out=", "--checkpoint=", "--hdr-out=", "--denoise=", "--guides=")):
             k, v = s[2:].split("=", 1)
             a[k.replace("-", "_")] = v
-        elif s.startswith(("--exposure=", "--gamma=", "--noise-threshold=", "--upscale=")):
+        elif s.startswith(("--exposure=", "--gamma=", "--noise-threshold=", "--upscale=", "--focus=")):
             k, v = s[2:].split("=", 1)
             a[k.replace("-", "_")] = float(v)
         elif s.startswith(("--w=", "--h=", "--samples=", "--bounces=", "--preview-every=")):
@@ -131,8 +152,9 @@ def display_stage(a: dict) -> bool:
 
 def linear_path(a: dict) -> bool:
     """The frame is rendered or resolved linear and displayed afterwards: the display stage's flags,
-    --denoise=var, which filters the linear frame, --upscale=, which upscales it, or --bloom, which adds its glow."""
-    return display_stage(a) or a["denoise"] == "var" or a["upscale"] is not None or a["bloom"] is not None
+    --denoise=var, which filters the linear frame, --upscale=, which upscales it, --dof, which blurs it, or --bloom, which adds its glow."""
+    return (display_stage(a) or a["denoise"] == "var" or a["upscale"] is not None or a["bloom"] is not None
+            or a["dof"] is not None)
 
 
 def low_size(a: dict):
@@ -168,6 +190,32 @@ def bloomed(rk: rt_amd.RenderKernel, linear: rt_amd.Image, a: dict, say: bool = 
     if say:
         print(f"bloom: {p.levels} levels, {above} of {lum.size} pixels above threshold")
     return rk.bloom(linear, params=p)
+
+
+def dof_setup(rk: rt_amd.RenderKernel, a: dict, size, guides):
+    """--dof: (normal_depth at `size`, the stage's parameters with the focus of --focus= or --focus-at=), with its
+    line printed; else None. guides: the (albedo, normal_depth) pair at `size` if the run has it already."""
+    if a["dof"] is None:
+        return None
+    nd = (guides if isinstance(guides, tuple) else rk.guides(size=size))[1]
+    p = rt_amd._params(rk.L, rt_amd.DofParams, "dof", a["dof"])
+    if a["focus"] is not None:
+        p.focus = a["focus"]
+    else:
+        x, y = a["focus_at"] if a["focus_at"] is not None else (size[0] // 2, size[1] // 2)
+        p.focus = rt_amd.focus_at(nd, x, y)
+    return nd, p
+
+
+def dof_blurred(rk: rt_amd.RenderKernel, linear: rt_amd.Image, setup, say: bool = True) -> rt_amd.Image:
+    """--dof: the frame through RenderKernel.dof, with its line printed (say); else the frame itself."""
+    if setup is None:
+        return linear
+    nd, p = setup
+    out, radius = rk.dof(linear, nd, p, coc=True)
+    if say:
+        print(f"dof: focus {p.focus:.9g}, coc_inf {p.coc_inf:.9g}, max_radius {p.max_radius}, largest radius {radius.max():.9g}")
+    return out
 
 
 def render_progressive(rk: rt_amd.RenderKernel, fb: rt_amd.Image, a: dict):
@@ -279,6 +327,21 @@ def main(argv=None) -> int:
     if a["bloom"] and not (0.0 <= a["bloom"]["intensity"] < float("inf")):
         print("--bloom=INTENSITY takes a finite intensity of at least 0", file=sys.stderr)
         return 2
+    if a["dof"] and not (0.0 <= a["dof"]["coc_inf"] < float("inf")):
+        print("--dof=COC_INF takes a finite radius in pixels of at least 0", file=sys.stderr)
+        return 2
+    if (a["focus"] is not None or a["focus_at"] is not None) and a["dof"] is None:
+        print("--focus= and --focus-at= need --dof", file=sys.stderr)
+        return 2
+    if a["focus"] is not None and a["focus_at"] is not None:
+        print("--focus=T and --focus-at=X,Y do not go together", file=sys.stderr)
+        return 2
+    if a["focus"] is not None and not (0.0 < a["focus"] < float("inf")):
+        print("--focus=T takes a finite distance above 0", file=sys.stderr)
+        return 2
+    if a["focus_at"] is not None and (len(a["focus_at"]) != 2 or not (0 <= a["focus_at"][0] < a["w"] and 0 <= a["focus_at"][1] < a["h"])):
+        print("--focus-at=X,Y takes a pixel of the frame", file=sys.stderr)
+        return 2
     if a["upscale"] is not None and not 1.0 < a["upscale"] <= 4.0:
         print("--upscale=F takes a factor with 1 < F <= 4", file=sys.stderr)
         return 2
@@ -320,6 +383,14 @@ def main(argv=None) -> int:
     if linear_path(a):  # fb holds the linear radiance: the .hdr file, then the displayed frame
         if a["hdr_out"]:
             rt_amd.write_image_hdr(fb, a["hdr_out"])
+        try:
+            lens = dof_setup(rk, a, full, guides)
+        except ValueError as e:  # (focus_at on a frame without a hit)
+            print(f"--dof: {e}", file=sys.stderr)
+            return 2
+        fb = dof_blurred(rk, fb, lens)
+        if filtered is not None:
+            filtered = dof_blurred(rk, filtered, lens, say=False)
         args = display_args(a, metered(rk, fb if filtered is None else filtered, a))
         fb = rk.display(bloomed(rk, fb, a), **args)
         if filtered is not None:
