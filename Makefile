@@ -55,12 +55,13 @@ $(OBJ)/rt_hostsim.o: $(SRC)/rt_hostsim.cpp $(HDRS) $(ALL_SRC)
 #   rt_gbuffer   the first-hit G-buffer on the render's walks: quads over the search BVH, octets over the octree behind them
 #   rt_bloom     bloom: the energy above a threshold spread by a Gaussian pyramid (reduce, expand, composite) and added back
 #   rt_dof       depth of field: a gather over each pixel's circle of confusion, from the first-hit distance of the guides
-# (the host forms of the last six stage through a DevBuf of Backend each, rt_backend_hip.h, as rt_display does)
+#   rt_motion    motion vectors from the guides and the previous camera, and motion blur: a gather along each 16 x 16 tile's line
+# (the host forms of the last seven stage through a DevBuf of Backend each, rt_backend_hip.h, as rt_display does)
 # the backend-independent C ABI, in both libraries: contexts, scene, renders, queries, progressions
 # (rt_capi_host) and the frame stages with their shared argument rules (rt_capi_stages, rt_stage_args.h)
 CAPI_OBJS := $(OBJ)/rt_capi_host.host.o $(OBJ)/rt_capi_stages.host.o
 HIP_UNITS := rt_render rt_wave_run rt_probe rt_denoise rt_query rt_display rt_noise rt_adapt rt_dnv rt_temporal rt_firefly \
-             rt_meter rt_upscale rt_gbuffer rt_bloom rt_dof
+             rt_meter rt_upscale rt_gbuffer rt_bloom rt_dof rt_motion
 $(HIP_UNITS:%=$(OBJ)/%.o): $(OBJ)/%.o: $(SRC)/%.hip $(HDRS)
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
@@ -161,7 +162,7 @@ hostsim-variant: $(OBJ)/rt_imageio.host.o
 # linked to the hostsim build of the C ABI (build/<p>) and to the product library (build/<p>_hip: built here by
 # `make shims-hip`, run on the GPU box, which has no reference tree; the binary carries what it needs).
 # tests/test_shims.py holds the invocations and runs both forms; each program's head says what it checks.
-SHIM_PROGS := shim_test $(addsuffix _shim_test,denoise query progress display noise adaptive dnv temporal firefly meter upscale gbuffer bloom dof)
+SHIM_PROGS := shim_test $(addsuffix _shim_test,denoise query progress display noise adaptive dnv temporal firefly meter upscale gbuffer bloom dof motion)
 shims: $(SHIM_PROGS:%=build/%)
 shims-hip: $(SHIM_PROGS:%=build/%_hip)
 .PHONY: shims shims-hip

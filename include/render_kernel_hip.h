@@ -414,6 +414,37 @@ public:
         return out;
     }
 
+    // Motion vectors (rt_motion_vectors): for every pixel, where its first hit stood in the frame of prev_camera minus
+    // where it stands now, in pixels (2 floats per pixel). normal_depth: features() or gbuffer() under the kernel's
+    // current camera at width x height.
+    std::vector<float> motion_vectors(const std::vector<float>& normal_depth, int width, int height, Camera prev_camera) const
+    {
+        std::lock_guard<std::mutex> lk(m_mu);
+        if (normal_depth.size() != (size_t)width * height * 4)
+            throw std::runtime_error("librt_hip: motion_vectors: normal_depth is not width * height * 4 floats");
+        std::vector<float> motion((size_t)width * height * 2);
+        check(rt_motion_vectors(m_ctx, width, height, normal_depth.data(), &prev_camera.view_matrix.m[0][0], prev_camera.fov_dist,
+                                motion.data()));
+        return motion;
+    }
+
+    // Motion blur (rt_motion_blur): a shutter's blur built from `linear`, the first-hit distances of normal_depth and
+    // `motion` (motion_vectors(), or the caller's own: 2 floats per pixel); it goes behind dof() and in front of bloom()
+    // and display(). params: null for the defaults. reach_out, when given, receives each pixel's half streak in pixels.
+    Image motion_blur(const Image& linear, const std::vector<float>& normal_depth, const std::vector<float>& motion,
+                      const rt_motion_params* params = nullptr, std::vector<float>* reach_out = nullptr) const
+    {
+        std::lock_guard<std::mutex> lk(m_mu);
+        const int w = linear.width(), h = linear.height();
+        if (normal_depth.size() != (size_t)w * h * 4) throw std::runtime_error("librt_hip: motion_blur: normal_depth is not width * height * 4 floats");
+        if (motion.size() != (size_t)w * h * 2) throw std::runtime_error("librt_hip: motion_blur: motion is not width * height * 2 floats");
+        if (reach_out) reach_out->assign((size_t)w * h, 0.0f);
+        Image out(w, h);
+        check(rt_motion_blur(m_ctx, w, h, linear.data(), normal_depth.data(), motion.data(), params, out.data(),
+                             reach_out ? reach_out->data() : nullptr));
+        return out;
+    }
+
     // INTERSECT_SCENE for a batch of rays through rt_query (the render's search-BVH walks, the
     // exact walk behind them): hits[i] as BVH::intersect + the sphere loop fill it (t = -1 and
     // primitive_index = -1 without a hit).

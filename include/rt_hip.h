@@ -111,7 +111,8 @@ int rt_test_fail_device(rt_context* ctx, int device);
  * product's cap, n > 0 that many blocks, at most 65536), "up_variant" (rt_upscale's kernel: 0 the product's
  * choice, 1 direct loads, 2 the low-resolution footprint staged in LDS), "bloom_variant" (rt_bloom's reduce kernel:
  * 0 the product's choice, 1 direct loads, 2 the source footprint staged in LDS), "dof_variant" (rt_dof's kernel: 0 the
- * product's choice, 1 the footprint staged in LDS, 2 direct loads), "rq_variant" (rt_query's search-BVH kernel:
+ * product's choice, 1 the footprint staged in LDS, 2 direct loads), "motion_variant" (rt_motion_blur's gather kernel, the
+ * same three), "rq_variant" (rt_query's search-BVH kernel:
  * 0 the product's choice, 1 plain rounds of one query per quad, 2 per-quad refill), "gb_variant" (the same three
  * for rt_render_gbuffer's search-BVH kernel), the stressor "gb_force_every" (N > 0: G-buffer pixels with
  * i mod N == 0 go to the exact walk's list instead of the search-BVH walk; 0: off),
@@ -948,6 +949,80 @@ int rt_dof(rt_context* ctx, int w, int h, const float* linear_rgba, const float*
            float* rgba_out, float* coc_out);
 int rt_dof_device(rt_context* ctx, int w, int h, const void* d_linear, const void* d_normal_depth, const rt_dof_params* params,
                   void* d_rgba_out, void* d_coc_out, void* stream);
+
+/* ---------------------------------------------- motion vectors and motion blur
+ * The render has no shutter: every frame is an instantaneous exposure, and a camera flown through a
+ * scene gives sharp, strobing frames. These two stages build a shutter's blur from the sharp linear
+ * frame, the guides and the previous camera. rt_motion_blur goes behind rt_dof and in front of
+ * rt_bloom, rt_meter and rt_display. Both are stateless. Float32 throughout, no contraction, IEEE
+ * division, a correctly rounded square root, floorf; no expf.
+ *
+ * rt_motion_vectors / _device: normal_depth (float4[h][w], the guides under the context's current
+ *   camera: rt_render_features or rt_render_gbuffer), prev_view[16] (row-major) and prev_fov_dist in;
+ *   motion_out (float2[h][w]) out. For pixel p = (x, y): (fx, fy) are rt_temporal_accumulate's steps
+ *   3 and 4, the same expressions in the same order (feature_ray; P = o + t d for a hit, o_prev + d
+ *   for a miss; q = the point in the previous camera's frame; ratio = q.z / prev_fov_dist;
+ *   fx = (((q.x / ratio) / aspect + 1) * 0.5) * (float)w, fy = ((q.y / ratio + 1) * 0.5) * (float)h);
+ *   m_p = {fx - (float)x, fy - (float)y}: where the point was, minus where it is now. m_p = {0, 0}
+ *   when one of the guide's four floats is a NaN, when ratio is not > 0, or when fx or fy is not
+ *   finite. Temporal's range test is not applied: a point that came from off-screen still moved.
+ *   A miss moves by the rotation only. RT_ERR_STATE without a camera; RT_ERR_ARG as
+ *   rt_temporal_accumulate for prev_view (singular, not finite), prev_fov_dist (zero, not finite),
+ *   NULL buffers, sizes and overlap; the device form takes device pointers (normal_depth 16-byte
+ *   aligned, motion_out 8-byte aligned) and a stream (NULL: default) and returns without waiting.
+ *
+ * rt_motion_blur / _device: linear_rgba (float4[h][w]), normal_depth (float4[h][w]; only .w = t is
+ *   read), motion (float2[h][w]: rt_motion_vectors' output or the caller's own, for example object
+ *   motion from elsewhere) in; rgba_out (float4[h][w], required) and reach_out (float[h][w], NULL
+ *   allowed) out. No scene or camera is needed. R = (float)max_radius. After McGuire et al. 2012, "A
+ *   Reconstruction Filter for Plausible Motion Blur", with nearest taps and a hard cylinder.
+ *   1 Reach per pixel. a = 0.5f * shutter, hx = a * m.x, hy = a * m.y, l2 = hx*hx + hy*hy. l2 not
+ *     finite: h = 0, l = 0. Else l = sqrt(l2); when l > R: s = R / l, hx *= s, hy *= s, l = R.
+ *     reach_out[p] = l. k_p = 1.0f / max(l, 0.5f). t'_p = (t finite and > 0) ? min(t, 1e30f) : 1e30f.
+ *     iz_p = 1.0f / (depth_soft * t'_p).
+ *   2 Tile max. Motion tiles are 16 x 16 pixels, partial at the right and bottom edges. A tile's
+ *     record {hx, hy, l} is that of its pixel of largest l, the first in raster order among equals.
+ *   3 Neighbour max. The tile and its up to eight neighbours inside the tile grid, dy outer, dx
+ *     inner; the first one's record, then a strictly larger l replaces it: {Nx, Ny, L}.
+ *   4 Gather. Unless L >= 0.5f every pixel of the tile is copied bit for bit. Else n = ceil(L) (as
+ *     (int)floorf(L), plus one when (float)n < L), dx = Nx / (float)n, dy = Ny / (float)n,
+ *     ds = L / (float)n. Taps j = -n .. n ascending; j = 0 is the centre with weight k_p; the others
+ *     lie at q = p + (ox_j, oy_j), ox_j = (int)floorf((float)j * dx + 0.5f), oy_j likewise. A tap
+ *     outside the image or whose rgb is not all finite is skipped. Else d = (float)|j| * ds,
+ *     fore = clamp01(1 - (t'_q - t'_p) * iz_p), back = clamp01(1 - (t'_p - t'_q) * iz_p),
+ *     cone(d, k) = max(1 - d * k, 0), cyl(d, l) = d <= l ? 1 : 0,
+ *     alpha = fore * cone(d, k_q) + back * cone(d, k_p) + 2 * (cyl(d, l_q) * cyl(d, l_p)), products
+ *     formed, then added left to right; S += alpha * c_q.rgb, W += alpha, in tap order.
+ *   5 rgba_out[p] = {S / W, c.a}. A centre whose rgb is not all finite is copied bit for bit; any
+ *     other centre has W >= k_p > 0.
+ *   A skipped tap adds nothing. Nothing is clamped. clamp01 of a NaN is 0. The inputs are not
+ *   written. A still pixel takes nothing from still neighbours at any depth, and nothing from moving
+ *   taps more than depth_soft behind it: it then comes back exactly. A moving nearer tap bleeds
+ *   over a still pixel up to its own reach and no further. shutter 0, or a motion of zeroes, returns
+ *   the input's bits. A gathered channel of -0 comes back +0.
+ *   RT_ERR_ARG for a NULL ctx, linear_rgba, normal_depth, motion or rgba_out; w or h below 1;
+ *   max_radius outside 1..16; a shutter outside [0, 1] or a NaN; a depth_soft that is not finite and
+ *   > 0; an output whose bytes overlap an input's or the other output's; more than 262140 rows or
+ *   2^27 - 1 pixels (rt_denoise's limits). The device form takes device pointers (the float4 buffers
+ *   16-byte aligned, motion 8-byte, reach_out 4-byte: RT_ERR_ARG otherwise) and a stream (NULL:
+ *   default) and returns without waiting; the tile records live in a buffer of the context, so two
+ *   device-form calls on different streams must not overlap in time. params NULL: the defaults
+ *   (rt_motion_default_params). Both run on the root device of a multi-device context;
+ *   rt_last_kernel_ms as for rt_denoise. */
+typedef struct rt_motion_params {
+    float shutter;     /* share of the frame interval the shutter is open, 0..1   default 0.5  */
+    float depth_soft;  /* relative depth over which fore/back fade, > 0, finite   default 0.05 */
+    int   max_radius;  /* half-length of the longest streak in pixels, 1..16      default 8    */
+} rt_motion_params;
+void rt_motion_default_params(rt_motion_params* params);
+int rt_motion_vectors(rt_context* ctx, int w, int h, const float* normal_depth, const float prev_view[16], float prev_fov_dist,
+                      float* motion_out);
+int rt_motion_vectors_device(rt_context* ctx, int w, int h, const void* d_normal_depth, const float prev_view[16],
+                             float prev_fov_dist, void* d_motion_out, void* stream);
+int rt_motion_blur(rt_context* ctx, int w, int h, const float* linear_rgba, const float* normal_depth, const float* motion,
+                   const rt_motion_params* params, float* rgba_out, float* reach_out);
+int rt_motion_blur_device(rt_context* ctx, int w, int h, const void* d_linear, const void* d_normal_depth, const void* d_motion,
+                          const rt_motion_params* params, void* d_rgba_out, void* d_reach_out, void* stream);
 
 /* Counters of the last render when enabled (RT_STAT_* order, rt_device.h);
  * with n up to 2 * RT_STAT_COUNT the second block is the share of the

@@ -17,6 +17,7 @@
 //   rt_gbuffer.hip  the first-hit G-buffer on the render's walks (quads in front, octets behind)
 //   rt_bloom.hip    bloom: the energy above a threshold spread by a Gaussian pyramid and added back
 //   rt_dof.hip      depth of field: a gather over each pixel's circle of confusion, from the first-hit distance
+//   rt_motion.hip   motion vectors from the guides and the previous camera; motion blur: a gather along each tile's line
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -207,6 +208,8 @@ struct Backend {
     DevBuf upscale_io;   // rt_upscale: the low frame, its sigma and guides, the full-size guides, then the two outputs
     DevBuf bloom;        // rt_bloom: the pyramid (levels 1.. back to back); host form: the frame and the two outputs, then the pyramid
     DevBuf dof_io;       // rt_dof: the frame and its guide record, then the two outputs
+    DevBuf motion_io;    // rt_motion_vectors: the guides, then the vectors; rt_motion_blur: the frame, its guide record and motion, then the two outputs
+    DevBuf motion_tiles; // rt_motion_blur: one record {hx, hy, l, 0} per 16 x 16 motion tile, host and device form
     int cus = 0;         // the device's compute units, asked by the first rt_meter (rt_meter.hip; 0: not yet)
     DevBuf shard;     // multi-device renders: the root's N blocks of rows_max rows (scatter source /
                       // gather target); device d >= 1: its block
@@ -247,6 +250,7 @@ Backend* rt_backend_dev0(rt_context* c);  // rt_backend.hip: the root device's B
 // The host forms' streams are inherited from the stages as they were written, not chosen here:
 //   null stream   features, denoise and denoise_var (a Post::io each), temporal_accumulate
 //                 (temporal_io), firefly (firefly_io), meter (meter_io), upscale (upscale_io), bloom (bloom), dof (dof_io),
+//                 motion_vectors and motion_blur (motion_io),
 //                 display (disp), queries (Query::io), rt_render (fb)
 //   Backend::own  noise and noise_sigma (pg_noise), progressive resolves (pg_out), pixel lists (fb)
 struct StagedCall {

@@ -257,6 +257,7 @@ int rt_test_schedule(rt_context* c, const char* key, double value)
     else if (k == "up_variant") s.up_variant = std::max(0, std::min(2, v));
     else if (k == "bloom_variant") s.bloom_variant = std::max(0, std::min(2, v));
     else if (k == "dof_variant") s.dof_variant = std::max(0, std::min(2, v));
+    else if (k == "motion_variant") s.motion_variant = std::max(0, std::min(2, v));
     else if (k == "mt_blocks") s.mt_blocks = std::max(0, std::min(65536, v));
     else if (k == "rq_variant") s.rq_variant = std::max(0, std::min(2, v));
     else if (k == "gb_variant") s.gb_variant = std::max(0, std::min(2, v));

@@ -1,6 +1,6 @@
 // rt_capi_stages.cpp — the frame stages of the C ABI (include/rt_hip.h), backend-independent like
 // rt_capi_host.cpp: camera rays and feature buffers, then denoise, denoise_var, temporal
-// accumulation, firefly rejection, guided upscale, depth of field, bloom, metering and display. Each stage is its defaults,
+// accumulation, firefly rejection, guided upscale, depth of field, motion vectors and motion blur, bloom, metering and display. Each stage is its defaults,
 // a *_ready function that checks the call (the shared rules: rt_stage_args.h) and the two entry
 // points, host form and device form, over its rt_backend_* hook.
 #include <algorithm>
@@ -14,6 +14,7 @@
 #include "rt_dof.h"
 #include "rt_firefly.h"
 #include "rt_meter.h"
+#include "rt_motion.h"
 #include "rt_stage_args.h"
 #include "rt_temporal.h"
 #include "rt_upscale.h"
@@ -527,6 +528,113 @@ int rt_dof_device(rt_context* c, int w, int h, const void* d_linear, const void*
     rtk::DofArgs A;
     if (int r = dof_ready(c, "rt_dof_device", w, h, d_linear, d_normal_depth, params, d_out, d_coc_out, true, A)) return r;
     return rt_backend_dof(c, A, d_out, d_coc_out, true, stream);
+}
+
+// ---- motion vectors and motion blur (rt_motion.h)
+// A starting point, not a measured optimum: a 180-degree shutter, SVGF's relative depth width (rt_temporal's
+// depth_tol) for the fade between fore and back, and streaks of at most 8 pixels either way.
+void rt_motion_default_params(rt_motion_params* p)
+{
+    if (!p) return;
+    p->shutter = 0.5f;
+    p->depth_soft = 0.05f;
+    p->max_radius = 8;
+}
+
+// The camera part of a vectors call, rt_temporal_accumulate's: the current view, the previous camera's inverse and origin.
+static int motion_camera(const StageArgs& a, rt_context* c, int w, int h, const float* prev_view, float prev_fov, rtk::MotionVecArgs& A)
+{
+    if (!std::isfinite(prev_fov) || prev_fov == 0.0f) return a.fail(": prev_fov_dist is zero or not finite");
+    A.cur = rtk::cam_view(c->cam, w, h);
+    if (!invert_view(prev_view, A.prev_inv.m)) return a.fail(": prev_view is singular or not finite");
+    A.prev_inv.fov_dist = prev_fov;
+    RtCamera prev;
+    std::memcpy(prev.m, prev_view, 64);
+    prev.fov_dist = prev_fov;
+    const rtk::V3 op = rtk::xform_point(prev, rtk::v3(0.0f, 0.0f, 0.0f));
+    A.o_prev[0] = op.x, A.o_prev[1] = op.y, A.o_prev[2] = op.z;
+    return RT_OK;
+}
+
+static int motion_vectors_ready(rt_context* c, const char* fn, int w, int h, const void* nd, const float* prev_view, float prev_fov,
+                                const void* out, bool device, rtk::MotionVecArgs& A)
+{
+    const size_t n = (size_t)w * h;
+    const StageArgs a{c, fn, device, {{nd, 16 * n, SA_IN, SA_REQ, 16}, {out, 8 * n, SA_OUT, SA_REQ, 8}}};
+    if (!c) return a.fail(": ctx is NULL");
+    if (!c->have_cam) return a.fail(": camera not set", RT_ERR_STATE);
+    if (w <= 0 || h <= 0 || a.missing() || !prev_view) return a.fail(": bad buffers");
+    if (int r = a.frame_limits(w, h, true)) return r;
+    if (!std::isfinite(prev_fov) || prev_fov == 0.0f) return a.fail(": prev_fov_dist is zero or not finite");
+    if (int r = a.overlap()) return r;
+    if (int r = a.aligned(": normal_depth must be 16-byte aligned, motion_out 8-byte aligned")) return r;
+    if (int r = motion_camera(a, c, w, h, prev_view, prev_fov, A)) return r;
+    A.nd = (const float4_*)nd;
+    return RT_OK;
+}
+
+int rt_motion_vec_args(rt_context* c, int w, int h, const void* nd, const float* prev_view, float prev_fov, rtk::MotionVecArgs& A)
+{
+    const StageArgs a{c, "rt_motion_vec_args", true, {}};
+    if (int r = motion_camera(a, c, w, h, prev_view, prev_fov, A)) return r;
+    A.nd = (const float4_*)nd;
+    return RT_OK;
+}
+
+int rt_motion_vectors(rt_context* c, int w, int h, const float* normal_depth, const float prev_view[16], float prev_fov_dist,
+                      float* motion_out)
+{
+    rtk::MotionVecArgs A;
+    if (int r = motion_vectors_ready(c, "rt_motion_vectors", w, h, normal_depth, prev_view, prev_fov_dist, motion_out, false, A)) return r;
+    return rt_backend_motion_vectors(c, A, motion_out, false, nullptr);
+}
+
+int rt_motion_vectors_device(rt_context* c, int w, int h, const void* d_normal_depth, const float prev_view[16], float prev_fov_dist,
+                             void* d_motion_out, void* stream)
+{
+    rtk::MotionVecArgs A;
+    if (int r = motion_vectors_ready(c, "rt_motion_vectors_device", w, h, d_normal_depth, prev_view, prev_fov_dist, d_motion_out, true, A))
+        return r;
+    return rt_backend_motion_vectors(c, A, d_motion_out, true, stream);
+}
+
+static int motion_ready(rt_context* c, const char* fn, int w, int h, const void* in, const void* nd, const void* motion,
+                        const rt_motion_params* params, const void* out, const void* reach_out, bool device, rtk::MotionArgs& A)
+{
+    const size_t n = (size_t)w * h;
+    const StageArgs a{c, fn, device,
+                      {{in, 16 * n, SA_IN, SA_REQ, 16}, {nd, 16 * n, SA_IN, SA_REQ, 16}, {motion, 8 * n, SA_IN, SA_REQ, 8},
+                       {out, 16 * n, SA_OUT, SA_REQ, 16}, {reach_out, 4 * n, SA_OUT, SA_OPT, 4}}};
+    if (!c) return a.fail(": ctx is NULL");
+    if (w <= 0 || h <= 0) return a.fail(": w and h must be at least 1");
+    if (a.missing()) return a.fail(": linear_rgba, normal_depth, motion or rgba_out is NULL");
+    if (int r = a.frame_limits(w, h, true)) return r;
+    const rt_motion_params p = params_or_defaults(params, rt_motion_default_params);
+    if (p.max_radius < 1 || p.max_radius > rtk::MB_MAX_RADIUS) return a.fail(": max_radius must be 1..16");
+    if (!(p.shutter >= 0.0f && p.shutter <= 1.0f)) return a.fail(": shutter is outside [0, 1]");
+    if (!std::isfinite(p.depth_soft) || !(p.depth_soft > 0.0f)) return a.fail(": depth_soft is not finite and > 0");
+    if (int r = a.overlap()) return r;
+    if (int r = a.aligned(": the float4 buffers must be 16-byte aligned, motion 8-byte aligned, reach_out 4-byte aligned")) return r;
+    A = rtk::MotionArgs{w, h, p.max_radius, 0.5f * p.shutter, p.depth_soft, (const float4_*)in, (const float4_*)nd,
+                        (const rtk::MbVec*)motion};
+    return RT_OK;
+}
+
+int rt_motion_blur(rt_context* c, int w, int h, const float* linear, const float* normal_depth, const float* motion,
+                   const rt_motion_params* params, float* out, float* reach_out)
+{
+    rtk::MotionArgs A;
+    if (int r = motion_ready(c, "rt_motion_blur", w, h, linear, normal_depth, motion, params, out, reach_out, false, A)) return r;
+    return rt_backend_motion_blur(c, A, out, reach_out, false, nullptr);
+}
+
+int rt_motion_blur_device(rt_context* c, int w, int h, const void* d_linear, const void* d_normal_depth, const void* d_motion,
+                          const rt_motion_params* params, void* d_out, void* d_reach_out, void* stream)
+{
+    rtk::MotionArgs A;
+    if (int r = motion_ready(c, "rt_motion_blur_device", w, h, d_linear, d_normal_depth, d_motion, params, d_out, d_reach_out, true, A))
+        return r;
+    return rt_backend_motion_blur(c, A, d_out, d_reach_out, true, stream);
 }
 
 // ---- exposure metering (rt_meter.h)

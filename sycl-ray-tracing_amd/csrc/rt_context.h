@@ -40,6 +40,7 @@ struct RtSchedule {
     int up_variant = 0;        // rt_upscale's kernel: 0 as measured, 1 direct loads, 2 the LDS footprint
     int bloom_variant = 0;     // rt_bloom's reduce kernel: 0 as measured, 1 direct loads, 2 the LDS tile
     int dof_variant = 0;       // rt_dof's kernel: 0 as measured, 1 the LDS tile, 2 direct loads
+    int motion_variant = 0;    // rt_motion_blur's kernel: 0 as measured, 1 the LDS tile, 2 direct loads
     int mt_blocks = 0;         // rt_meter's grid: 0 the product's cap, n > 0 that many blocks (many grid-stride rounds)
     int rq_variant = 0;        // rt_query's fast kernel: 0 as measured, 1 plain grid-stride rounds, 2 per-quad refill
     int gb_variant = 0;        // rt_render_gbuffer's fast kernel: 0 as measured, 1 plain 16-pixel rounds, 2 per-quad refill
@@ -204,6 +205,18 @@ namespace rtk {
 struct DofArgs;
 }
 int rt_backend_dof(rt_context* ctx, rtk::DofArgs A, void* rgba_out, void* coc_out, bool device, void* stream);
+// The motion stages (rt_motion.h), on the root device like the post stage. Vectors: A holds the current camera's view, the
+// previous camera's inverse and origin and the guides (w*h float4); motion_out is w*h float2. Blur: A holds the validated
+// parameters, the frame, its guide record (w*h float4 each) and the motion (w*h float2); rgba_out (w*h float4) is
+// required, reach_out (w*h floats) may be null. rt_motion_vec_args (rt_capi_stages.cpp) fills a MotionVecArgs from an
+// already validated call (the measurement hook of rt_motion.hip).
+namespace rtk {
+struct MotionVecArgs;
+struct MotionArgs;
+}
+int rt_backend_motion_vectors(rt_context* ctx, rtk::MotionVecArgs A, void* motion_out, bool device, void* stream);
+int rt_backend_motion_blur(rt_context* ctx, rtk::MotionArgs A, void* rgba_out, void* reach_out, bool device, void* stream);
+int rt_motion_vec_args(rt_context* ctx, int w, int h, const void* nd, const float* prev_view, float prev_fov_dist, rtk::MotionVecArgs& A);
 // The display stage (rt_display.h), on the root device like the post stage: in (w*h float4) ->
 // out (w*h float4, may be `in`, or null) and out8 (w*h RGBA bytes, rows reversed when flip, or
 // null). The arguments are validated and inv_gamma = 1.0f / gamma (rt_capi_stages.cpp).

@@ -25,6 +25,7 @@
 #include "rt_temporal.h"
 #include "rt_bloom.h"
 #include "rt_dof.h"
+#include "rt_motion.h"
 #include "rt_firefly.h"
 #include "rt_upscale.h"
 #include "rt_meter.h"
@@ -863,6 +864,54 @@ int rt_backend_dof(rt_context* c, rtk::DofArgs A, void* rgba_out, void* coc_out,
             float r;
             out[p] = rtk::dof_pixel(A, x, y, A.in[p], A.nd[p].w, F, &r);
             if (coc) coc[p] = r;
+        }
+    c->last_kernel_ms = (omp_get_wtime() - t0) * 1e3;
+    return RT_OK;
+}
+
+// The motion vectors on the host: the loop around rt_motion.h's mv_pixel that k_motion_vectors runs one thread per pixel.
+int rt_backend_motion_vectors(rt_context* c, rtk::MotionVecArgs A, void* motion_out, bool, void*)
+{
+    const double t0 = omp_get_wtime();
+    rtk::MbVec* out = (rtk::MbVec*)motion_out;
+    const int w = A.cur.W, h = A.cur.H;
+#pragma omp parallel for schedule(static)
+    for (int y = 0; y < h; y++)
+        for (int x = 0; x < w; x++) out[(size_t)y * w + x] = rtk::mv_pixel(A, x, y, A.nd[(size_t)y * w + x]);
+    c->last_kernel_ms = (omp_get_wtime() - t0) * 1e3;
+    return RT_OK;
+}
+
+// Motion blur on the host: rule 2 as a raster scan of each tile (a strictly larger l replaces the record, which is the
+// key's maximum that k_motion_tilemax reduces), then the loop around mb_neighbour_max and mb_pixel that k_mblur_direct
+// runs one thread per pixel, every tap read straight from the frame (MbDirect).
+int rt_backend_motion_blur(rt_context* c, rtk::MotionArgs A, void* rgba_out, void* reach_out, bool, void*)
+{
+    const double t0 = omp_get_wtime();
+    const int ntx = rtk::mb_tiles_x(A.w), nty = rtk::mb_tiles_y(A.h);
+    std::vector<float4_> tiles((size_t)ntx * nty);
+#pragma omp parallel for schedule(static)
+    for (int t = 0; t < ntx * nty; t++) {
+        const int X0 = (t % ntx) * rtk::MB_TILE, Y0 = (t / ntx) * rtk::MB_TILE;
+        float4_ best{0.0f, 0.0f, -1.0f, 0.0f};
+        for (int y = Y0; y < Y0 + rtk::MB_TILE && y < A.h; y++)
+            for (int x = X0; x < X0 + rtk::MB_TILE && x < A.w; x++) {
+                const float4_ r = rtk::mb_reach(A, A.motion[(size_t)y * A.w + x]);
+                if (r.z > best.z) best = r;
+            }
+        tiles[t] = best;
+    }
+    const rtk::MbDirect F{A};
+    float4_* out = (float4_*)rgba_out;
+    float* reach = (float*)reach_out;
+#pragma omp parallel for schedule(static)
+    for (int y = 0; y < A.h; y++)
+        for (int x = 0; x < A.w; x++) {
+            const size_t p = (size_t)y * A.w + x;
+            const float4_ N = rtk::mb_neighbour_max(tiles.data(), ntx, nty, x / rtk::MB_TILE, y / rtk::MB_TILE);
+            const float l = rtk::mb_reach(A, A.motion[p]).z;
+            out[p] = rtk::mb_pixel(A, x, y, A.in[p], A.nd[p].w, l, N, F);
+            if (reach) reach[p] = l;
         }
     c->last_kernel_ms = (omp_get_wtime() - t0) * 1e3;
     return RT_OK;

@@ -26,7 +26,7 @@ import numpy as np
 
 from . import _capi
 from ._capi import (METER_STATS, METER_WORDS, BloomParams, DenoiseParams, DenoiseVarParams, DisplayParams, DofParams,  # noqa: F401
-                    FireflyParams,
+                    FireflyParams, MotionParams,
                     MeterParams, MeterResult, NoiseStats, TemporalParams, UpscaleParams)
 from ._capi import (RT_ERR_ARG, RT_ERR_HIP, RT_ERR_IO, RT_ERR_NODEV, RT_ERR_STATE, RT_OK,  # noqa: F401
                     RtError, check, lib, ptr)
@@ -37,7 +37,8 @@ __all__ = ["Camera", "Image", "ParsedOBJ", "parse_obj", "compute_env_map_cdf", "
            "denoise_var_default_params", "TemporalParams", "temporal_default_params", "TemporalHistory",
            "FireflyParams", "firefly_default_params", "MeterParams", "meter_default_params", "meter_stats", "meter_solve",
            "ExposureAdapter", "METER_WORDS", "METER_STATS", "UpscaleParams", "upscale_default_params",
-           "BloomParams", "bloom_default_params", "DofParams", "dof_default_params", "focus_at"]
+           "BloomParams", "bloom_default_params", "DofParams", "dof_default_params", "focus_at",
+           "MotionParams", "motion_default_params"]
 
 
 # ------------------------------------------------------------------ camera
@@ -214,6 +215,11 @@ def focus_at(normal_depth, x: int, y: int) -> float:
     raise ValueError("focus_at: the frame has no hit")
 
 
+def motion_default_params(hostsim: bool = False) -> MotionParams:
+    """rt_motion_default_params: the motion-blur stage's defaults."""
+    return _params(lib(hostsim), MotionParams, "motion", None)
+
+
 def meter_default_params(hostsim: bool = False) -> MeterParams:
     """rt_meter_default_params: the defaults of rt_meter_solve."""
     return _params(lib(hostsim), MeterParams, "meter", None)
@@ -305,6 +311,11 @@ class TemporalHistory:
         self.rgba, self.sigma, self.length, self.normal_depth = out, s_out, l_out, nd
         self.camera = Camera(kernel.camera.view_matrix.copy(), kernel.camera.fov_dist)
         return out, s_out, l_out
+
+    def motion_vectors(self, kernel: "RenderKernel", normal_depth):
+        """RenderKernel.motion_vectors of normal_depth (guides under the kernel's current camera) against the camera of
+        the last push; before the first push the kernel's own camera, which gives zeroes but for rounding."""
+        return kernel.motion_vectors(normal_depth, kernel.camera if self.camera is None else self.camera)
 
 
 # --------------------------------------------------------------------- OBJ
@@ -954,6 +965,56 @@ class RenderKernel:
         check(self.L, self.L.rt_dof_device(self.ctx, int(width or self.width), int(height or self.height), _vp(d_in),
                                            _vp(d_normal_depth), ctypes.byref(p), _vp(d_out), _vp(d_coc_out), _vp(stream)),
               self.ctx, "rt_dof_device")
+
+    # ---- motion vectors and motion blur (rt_motion_vectors, rt_motion_blur; include/rt_hip.h)
+    def motion_vectors(self, normal_depth, prev_camera: Camera):
+        """rt_motion_vectors: [h, w, 2] float32, for every pixel where its first hit stood in prev_camera's frame minus
+        where it stands now, in pixels. normal_depth [h, w, 4]: features() or gbuffer() under the kernel's current
+        camera. prev_camera: a Camera, or (view_matrix, fov_dist)."""
+        nd = np.ascontiguousarray(normal_depth, dtype=np.float32)
+        if nd.ndim != 3 or nd.shape[2] != 4:
+            raise ValueError(f"motion_vectors: normal_depth is {nd.shape}, not (h, w, 4)")
+        h, w = nd.shape[:2]
+        view, fov = (prev_camera.view_matrix, prev_camera.fov_dist) if hasattr(prev_camera, "view_matrix") else prev_camera
+        view = np.ascontiguousarray(view, dtype=np.float32)
+        out = np.empty((h, w, 2), np.float32)
+        check(self.L, self.L.rt_motion_vectors(self.ctx, w, h, ptr(nd), ptr(view), float(fov), ptr(out)), self.ctx, "rt_motion_vectors")
+        return out
+
+    def motion_vectors_device(self, d_normal_depth: int, prev_camera: Camera, d_motion_out: int, stream: int | None = None,
+                              width=None, height=None):
+        """rt_motion_vectors_device: device buffers of w*h*4 and w*h*2 floats, no wait."""
+        check(self.L, self.L.rt_motion_vectors_device(self.ctx, int(width or self.width), int(height or self.height),
+                                                      _vp(d_normal_depth), ptr(prev_camera.view_matrix), prev_camera.fov_dist,
+                                                      _vp(d_motion_out), _vp(stream)), self.ctx, "rt_motion_vectors_device")
+
+    def motion_blur(self, linear: Image, normal_depth, motion, params=None, reach: bool = False):
+        """rt_motion_blur: a shutter's blur built from a linear frame, its first-hit distances normal_depth [h, w, 4]
+        (only t is read) and motion [h, w, 2] (motion_vectors(), or the caller's own). It goes behind dof() and in front
+        of bloom(), auto_exposure() and display(). params: None (the defaults), a MotionParams, or a dict of its fields
+        over the defaults. Returns the Image, or (Image, reach) with reach: [h, w] float32, each pixel's half streak."""
+        src = np.ascontiguousarray(linear.pixels, dtype=np.float32)
+        h, w = src.shape[:2]
+        nd = np.ascontiguousarray(normal_depth, dtype=np.float32)
+        mv = np.ascontiguousarray(motion, dtype=np.float32)
+        if nd.shape != (h, w, 4):
+            raise ValueError(f"motion_blur: normal_depth is {nd.shape}, the frame ({h}, {w}, 4)")
+        if mv.shape != (h, w, 2):
+            raise ValueError(f"motion_blur: motion is {mv.shape}, not ({h}, {w}, 2)")
+        p = _params(self.L, MotionParams, "motion", params)
+        out = Image(w, h)
+        r = np.empty((h, w), np.float32) if reach else None
+        check(self.L, self.L.rt_motion_blur(self.ctx, w, h, ptr(src), ptr(nd), ptr(mv), ctypes.byref(p), ptr(out.pixels), ptr(r)),
+              self.ctx, "rt_motion_blur")
+        return (out, r) if reach else out
+
+    def motion_blur_device(self, d_in: int, d_normal_depth: int, d_motion: int, d_out: int, d_reach_out: int | None = None,
+                           params=None, stream: int | None = None, width=None, height=None):
+        """rt_motion_blur_device: device buffers (w*h*4 floats, d_motion w*h*2, d_reach_out w*h or None), no wait."""
+        p = _params(self.L, MotionParams, "motion", params)
+        check(self.L, self.L.rt_motion_blur_device(self.ctx, int(width or self.width), int(height or self.height), _vp(d_in),
+                                                   _vp(d_normal_depth), _vp(d_motion), ctypes.byref(p), _vp(d_out),
+                                                   _vp(d_reach_out), _vp(stream)), self.ctx, "rt_motion_blur_device")
 
     def render_variants(self, materials, frames=None, device_ptrs=None, row_offset: int = 0, row_stride: int = 1):
         """rt_render_variants: the material sweep as replicas. `materials` is

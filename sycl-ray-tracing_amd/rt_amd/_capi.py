@@ -44,6 +44,7 @@ EXPORTS = [
     "rt_meter_default_params", "rt_meter", "rt_meter_device", "rt_meter_solve",
     "rt_bloom_default_params", "rt_bloom", "rt_bloom_device",
     "rt_dof_default_params", "rt_dof", "rt_dof_device",
+    "rt_motion_default_params", "rt_motion_vectors", "rt_motion_vectors_device", "rt_motion_blur", "rt_motion_blur_device",
 ]
 
 # return codes (include/rt_hip.h)
@@ -105,6 +106,11 @@ class BloomParams(ctypes.Structure):
 class DofParams(ctypes.Structure):
     """struct rt_dof_params (include/rt_hip.h)."""
     _fields_ = [("focus", F), ("coc_inf", F), ("max_radius", I)]
+
+
+class MotionParams(ctypes.Structure):
+    """struct rt_motion_params (include/rt_hip.h)."""
+    _fields_ = [("shutter", F), ("depth_soft", F), ("max_radius", I)]
 
 
 class DisplayParams(ctypes.Structure):
@@ -218,7 +224,13 @@ _SIGS = {
     "rt_dof_default_params": (None, [ctypes.POINTER(DofParams)]),
     "rt_dof": (I, [P, I, I, P, P, ctypes.POINTER(DofParams), P, P]),
     "rt_dof_device": (I, [P, I, I, P, P, ctypes.POINTER(DofParams), P, P, P]),
+    "rt_motion_default_params": (None, [ctypes.POINTER(MotionParams)]),
+    "rt_motion_vectors": (I, [P, I, I, P, P, F, P]),
+    "rt_motion_vectors_device": (I, [P, I, I, P, P, F, P, P]),
+    "rt_motion_blur": (I, [P, I, I, P, P, P, ctypes.POINTER(MotionParams), P, P]),
+    "rt_motion_blur_device": (I, [P, I, I, P, P, P, ctypes.POINTER(MotionParams), P, P, P]),
     # product-only extras
+    "rt_device_motion_kernel_ms": (I, [P, I, I, P, P, P, ctypes.POINTER(MotionParams), P, P, P, F, P, I, I, P]),
     "rt_device_dof_kernel_ms": (I, [P, I, I, P, P, ctypes.POINTER(DofParams), P, P, I, I, P]),
     "rt_device_bloom_kernel_ms": (I, [P, I, I, P, ctypes.POINTER(BloomParams), P, P, I, I, P]),
     "rt_device_meter_kernel_ms": (I, [P, I, I, P, P, I, I, P]),

@@ -76,6 +76,15 @@ RT_output_denoised_* files are, as with --bloom, the a-trous filter applied to t
 one, with the pinhole guides: the filter's edge-stops then follow the sharp geometry and not the blurred image, so
 those three files are not a filtered lens image in the sense above; RT_output.png is.
 
+Motion blur (RenderKernel.motion_vectors, RenderKernel.motion_blur): --motion-blur or --motion-blur=SHUTTER, with
+--prev-camera=PRESET, the camera of the frame before this one (the presets of --camera=). The run goes through
+render_linear and display as with --gamma=. The linear frame (under --denoise=var the filtered one as well), after
+--upscale= and --dof if given, passes through rt_motion_blur along the vectors rt_motion_vectors gives for the guides
+at its size and the previous camera, before it is metered, bloomed and displayed: its defaults, or SHUTTER in the place
+of the default shutter. The line "motion blur: shutter S, max_radius R, longest reach M" is printed. --hdr-out stays
+the sharp frame, previews are sharp, and --motion-blur=0 writes the bytes of a run without the flag. What --dof says
+about the three RT_output_denoised_* files under the default --denoise=atrous holds here too.
+
 Guide source (RenderKernel.guide_source): --guides=walks|exact, default exact. exact takes the first-hit guides of the
 filters and of --upscale= from features(), as a run without the flag does, byte for byte; walks takes them from
 gbuffer(), the render's own search-BVH walks with the 8-lane exact walk behind them.
@@ -95,7 +104,8 @@ def parse(argv):
     a = dict(obj="data/OBJs/cornell_pbr.obj", sky="data/Skyspheres/evening_road_01_puresky_2k.hdr", w=512, h=512,
              samples=64, bounces=8, camera="dragon", out=".", hostsim=False, preview_every=0, checkpoint="",
              exposure=None, gamma=None, hdr_out="", noise_threshold=None, adaptive=False, denoise="atrous", firefly=None,
-             auto_exposure=None, upscale=None, guides="exact", bloom=None, dof=None, focus=None, focus_at=None)
+             auto_exposure=None, upscale=None, guides="exact", bloom=None, dof=None, focus=None, focus_at=None,
+             motion_blur=None, prev_camera=None)
     for s in argv:
         if s == "--hostsim":
             a["hostsim"] = True
@@ -113,6 +123,10 @@ def parse(argv):
             a["dof"] = {}
         elif s.startswith("--dof="):
             a["dof"] = {"coc_inf": float(s.split("=", 1)[1])}
+        elif s == "--motion-blur":  # (the stage's default shutter)
+            a["motion_blur"] = {}
+        elif s.startswith("--motion-blur="):
+            a["motion_blur"] = {"shutter": float(s.split("=", 1)[1])}
         elif s.startswith("--focus-at="):
             try:
                 a["focus_at"] = tuple(int(v) for v in s.split("=", 1)[1].split(","))
@@ -122,7 +136,7 @@ def parse(argv):
             a["auto_exposure"] = {}
         elif s.startswith("--auto-exposure="):
             a["auto_exposure"] = {"key": float(s.split("=", 1)[1])}
-        elif s.startswith(("--sky=", "--camera=", "--out=", "--checkpoint=", "--hdr-out=", "--denoise=", "--guides=")):
+        elif s.startswith(("--sky=", "--camera=", "--out=", "--checkpoint=", "--hdr-out=", "--denoise=", "--guides=", "--prev-camera=")):
             k, v = s[2:].split("=", 1)
             a[k.replace("-", "_")] = v
         elif s.startswith(("--exposure=", "--gamma=", "--noise-threshold=", "--upscale=", "--focus=")):
@@ -152,9 +166,10 @@ def display_stage(a: dict) -> bool:
 
 def linear_path(a: dict) -> bool:
     """The frame is rendered or resolved linear and displayed afterwards: the display stage's flags,
-    --denoise=var, which filters the linear frame, --upscale=, which upscales it, --dof, which blurs it, or --bloom, which adds its glow."""
+    --denoise=var, which filters the linear frame, --upscale=, which upscales it, --dof or --motion-blur, which blur it, or
+    --bloom, which adds its glow."""
     return (display_stage(a) or a["denoise"] == "var" or a["upscale"] is not None or a["bloom"] is not None
-            or a["dof"] is not None)
+            or a["dof"] is not None or a["motion_blur"] is not None)
 
 
 def low_size(a: dict):
@@ -215,6 +230,27 @@ def dof_blurred(rk: rt_amd.RenderKernel, linear: rt_amd.Image, setup, say: bool 
     out, radius = rk.dof(linear, nd, p, coc=True)
     if say:
         print(f"dof: focus {p.focus:.9g}, coc_inf {p.coc_inf:.9g}, max_radius {p.max_radius}, largest radius {radius.max():.9g}")
+    return out
+
+
+def motion_setup(rk: rt_amd.RenderKernel, a: dict, size, guides):
+    """--motion-blur: (normal_depth at `size`, the vectors against --prev-camera=, the stage's parameters); else None.
+    guides: the (albedo, normal_depth) pair at `size` if the run has it already."""
+    if a["motion_blur"] is None:
+        return None
+    nd = (guides if isinstance(guides, tuple) else rk.guides(size=size))[1]
+    p = rt_amd._params(rk.L, rt_amd.MotionParams, "motion", a["motion_blur"])
+    return nd, rk.motion_vectors(nd, rt_amd.Camera.preset(a["prev_camera"])), p
+
+
+def motion_blurred(rk: rt_amd.RenderKernel, linear: rt_amd.Image, setup, say: bool = True) -> rt_amd.Image:
+    """--motion-blur: the frame through RenderKernel.motion_blur, with its line printed (say); else the frame itself."""
+    if setup is None:
+        return linear
+    nd, motion, p = setup
+    out, reach = rk.motion_blur(linear, nd, motion, p, reach=True)
+    if say:
+        print(f"motion blur: shutter {p.shutter:.9g}, max_radius {p.max_radius}, longest reach {reach.max():.9g}")
     return out
 
 
@@ -342,6 +378,18 @@ def main(argv=None) -> int:
     if a["focus_at"] is not None and (len(a["focus_at"]) != 2 or not (0 <= a["focus_at"][0] < a["w"] and 0 <= a["focus_at"][1] < a["h"])):
         print("--focus-at=X,Y takes a pixel of the frame", file=sys.stderr)
         return 2
+    if a["motion_blur"] and not (0.0 <= a["motion_blur"]["shutter"] <= 1.0):
+        print("--motion-blur=SHUTTER takes a share of the frame interval inside [0, 1]", file=sys.stderr)
+        return 2
+    if a["prev_camera"] is not None and a["motion_blur"] is None:
+        print("--prev-camera= needs --motion-blur", file=sys.stderr)
+        return 2
+    if a["motion_blur"] is not None:
+        try:
+            rt_amd.Camera.preset(a["prev_camera"])
+        except Exception:  # (no preset of that name, or none given)
+            print("--motion-blur needs --prev-camera=PRESET, a camera preset as --camera= takes", file=sys.stderr)
+            return 2
     if a["upscale"] is not None and not 1.0 < a["upscale"] <= 4.0:
         print("--upscale=F takes a factor with 1 < F <= 4", file=sys.stderr)
         return 2
@@ -391,6 +439,10 @@ def main(argv=None) -> int:
         fb = dof_blurred(rk, fb, lens)
         if filtered is not None:
             filtered = dof_blurred(rk, filtered, lens, say=False)
+        shutter = motion_setup(rk, a, full, guides)
+        fb = motion_blurred(rk, fb, shutter)
+        if filtered is not None:
+            filtered = motion_blurred(rk, filtered, shutter, say=False)
         args = display_args(a, metered(rk, fb if filtered is None else filtered, a))
         fb = rk.display(bloomed(rk, fb, a), **args)
         if filtered is not None:
