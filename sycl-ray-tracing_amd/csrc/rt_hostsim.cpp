@@ -114,6 +114,7 @@ static int run_wave_host(rt_context* c, int w, int h, int spp, int bounces, cons
     int32_t parkc[2] = {0, 0}, parka[2] = {0, 0};
     W.counters = counters;
     std::memset(W.r_park, 0, (size_t)n * 4);
+    std::memset(W.r_flags, 0, (size_t)n * 4);
     int32_t* lists[2] = {(int32_t*)W.act_in, W.act_out};
     std::vector<rtk::Stats> st(omp_get_max_threads());
     for (auto& s : st) std::memset(&s, 0, sizeof s);

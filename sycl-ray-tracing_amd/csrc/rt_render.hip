@@ -88,7 +88,7 @@ __device__ __forceinline__ void append_emit(const rtk::WaveView& W, int pout, in
     const int sh = min(RT_QSHARDS - 1, (base >> 6) / cps);
     const size_t seg = (size_t)sh * W.seg_cap;
     const unsigned long long lt = (lane_id() == 0) ? 0ull : (~0ull >> (64 - lane_id()));
-    if (W.r_heavy) {  // heavy class on: the rays of a path flagged heavy go to its kind's heavy shard
+    if (W.heavy_calls > 0) {  // heavy class on: the rays of a path flagged heavy go to its kind's heavy shard
         const int hs = sh % RT_HSHARDS;
         unsigned long long b[2 * rtk::RK_COUNT + 1];
 #pragma unroll
@@ -589,7 +589,7 @@ __device__ __forceinline__ void trace_stream(const rtk::WaveView& W, const RtSce
     auto finish = [&](int res, int gs) {
         // a long walk: the path's next rays go to the heavy class (head of the next streams)
         // (q.calls counts quad_visit calls; a row call covers two 4-wide levels and counts 2)
-        if (W.r_heavy && sub == 0 && q.calls >= W.heavy_calls) W.r_heavy[target >> 3] = 1;
+        if (W.heavy_calls > 0 && sub == 0 && q.calls >= W.heavy_calls) rtk::res_flag(W, (int)(target >> 3), rtk::RF_HEAVY) = 1;
         if (STATS && W.iterq && sub == 0 && W.iter < RT_MAX_TIMED_ITERS) {
             // (RT_ITER_LOG: the launch's longest walk in quad_visit calls per role, and
             // how many walks took more than 8)

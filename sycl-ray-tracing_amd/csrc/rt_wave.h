@@ -17,7 +17,10 @@
 // rule, emission at bounce 0, `break` on a dead BRDF sample).
 //
 // Buffers (device memory, one entry per path slot; slot = pixel index of
-// the launch's pixel source): 16-B records so a wave's loads coalesce.
+// the launch's pixel source): 16-B records so a wave's loads coalesce, and what
+// a step reads together packed together: the two closest-hit answers it opens
+// with are one record (HitRec), the byte-sized answers one word (ResFlag), the
+// pending bounce's three candidates one 48-B record (PendRec).
 #pragma once
 
 #include "rt_fast.h"
@@ -39,6 +42,23 @@ enum PathFlag : uint32_t {
     PF_CAM = 256u,       // the next sample's camera ray is in flight (next_camera)
 };
 #define RT_FLAG_BITS 12  // p_rd.w = flags | bounce << RT_FLAG_BITS
+
+// Closest-hit answer of one query: t, and k = leaf-order triangle, -2 - sphere index, or -1 for none.
+struct alignas(8) HitTK {
+    float t;
+    int32_t k;
+};
+// A slot's two answers that open a step: its continuation's and the next sample's camera ray's
+// (RK_CAM, traced ahead). finish_closest writes its kind's half with one 8-B store, path_step
+// reads both with one 16-B load.
+struct alignas(16) HitRec {
+    HitTK cont, cam;
+};
+// Bytes of a slot's flags word (r_flags): every writer stores its own byte, no two writers of a
+// launch share one, so nothing is read-modify-written; path_step reads the word once.
+enum ResFlag { RF_ESH = 0, RF_BENV = 1, RF_HEAVY = 2 };
+// Records of a slot's pending bounce (q_pend[3 slot + i], 48 B side by side).
+enum PendRec { QP_THR = 0, QP_ENV = 1, QP_BENV = 2 };
 
 struct RayRec {  // 32 B queue entry
     float4_ o;  // xyz origin, w = target (slot) bits
@@ -88,22 +108,16 @@ struct WaveView {
     float4_* q_bl;          // BRDF->light sample brdf * cos(n, dir) rgb, pdf
     float4_* q_sdir;        // BRDF->light dir xyz
     float4_* q_blo;         // BRDF->light origin xyz (sphere hit normals)
-    float4_* q_env;         // env candidate rgb
-    float4_* q_benv;        // BRDF->env candidate rgb
-    float4_* q_thr;         // thr at the shaded bounce
+    float4_* q_pend;        // [3 n_slots] PendRec: thr at the shaded bounce, env candidate rgb, BRDF->env candidate rgb
     // query results
-    float* r_cont_t;
-    int32_t* r_cont_k;
-    float* r_cam_t;         // the next sample's camera ray (RK_CAM), traced ahead
-    int32_t* r_cam_k;
-    float* r_lsh_t;
+    HitRec* r_hit;          // the continuation's and the camera ray's closest hits
+    float* r_lsh_t;         // (the light kinds' answers: only scenes with emitters write or read them)
     float* r_bl_t;
     int32_t* r_bl_k;
-    uint8_t* r_esh;
-    uint8_t* r_benv;
+    uint32_t* r_flags;      // ResFlag bytes: env shadow ray occluded, BRDF->env ray occluded, and (heavy class on)
+                            // a query of the slot took >= heavy_calls quad trips; zeroed with r_park
     // queues
     RayRec* q[RK_COUNT];    // [shards * seg_cap] each, then (heavy class on) as many of its heavy class
-    uint8_t* r_heavy;       // [n_slots] (heavy class on) a query of the slot took >= heavy_calls quad trips
     int heavy_calls;        // k_trace's heavy threshold (0: heavy class off; set before wave_carve)
     int spec_cam;           // 1: trace the next sample's camera ray ahead (next_camera); 0: at the sample's start
     int32_t* counters;      // queue sizes, tickets, live counts (rt_wave_layout.h C_*)
@@ -169,21 +183,14 @@ inline size_t wave_carve(char* base, size_t n, WaveView& W)  // uses W.park_cap,
     W.q_bl = (float4_*)take(n * 16);
     W.q_sdir = (float4_*)take(n * 16);
     W.q_blo = (float4_*)take(n * 16);
-    W.q_env = (float4_*)take(n * 16);
-    W.q_benv = (float4_*)take(n * 16);
-    W.q_thr = (float4_*)take(n * 16);
-    W.r_cont_t = (float*)take(n * 4);
-    W.r_cont_k = (int32_t*)take(n * 4);
-    W.r_cam_t = (float*)take(n * 4);
-    W.r_cam_k = (int32_t*)take(n * 4);
+    W.q_pend = (float4_*)take(3 * n * 16);
+    W.r_hit = (HitRec*)take(n * sizeof(HitRec));
     W.r_lsh_t = (float*)take(n * 4);
     W.r_bl_t = (float*)take(n * 4);
     W.r_bl_k = (int32_t*)take(n * 4);
-    W.r_esh = (uint8_t*)take(n);
-    W.r_benv = (uint8_t*)take(n);
+    W.r_flags = (uint32_t*)take(n * 4);
     const size_t qn = (size_t)W.shards * W.seg_cap;  // >= n
     for (int k = 0; k < RK_COUNT; k++) W.q[k] = (RayRec*)take((W.heavy_calls > 0 ? 2 : 1) * qn * sizeof(RayRec));
-    W.r_heavy = W.heavy_calls > 0 ? (uint8_t*)take(n) : nullptr;
     W.act_in = (const int32_t*)take(qn * 4);
     W.act_out = (int32_t*)take(qn * 4);
     W.r_park = (int32_t*)take(n * 4);
@@ -207,6 +214,8 @@ RT_HD bool forced_fallback(int k, const float4_& o, const float4_& d)
 {
     return k > 0 && ((rt_asuint(o.x) ^ rt_asuint(d.y) ^ (rt_asuint(d.z) >> 7)) % (uint32_t)k) == 0u;
 }
+RT_HD float4_& pend(const WaveView& W, int slot, int rec) { return W.q_pend[3 * (size_t)slot + rec]; }
+RT_HD uint8_t& res_flag(const WaveView& W, int slot, int byte) { return reinterpret_cast<uint8_t*>(W.r_flags + slot)[byte]; }
 RT_HD float4_ f4(V3 v, float w) { return float4_{v.x, v.y, v.z, w}; }
 RT_HD float4_ f4(Col c, float w) { return float4_{c.r, c.g, c.b, w}; }
 RT_HD V3 v3of(const float4_& f) { return v3(f.x, f.y, f.z); }
@@ -699,7 +708,7 @@ RT_HD void shade(const WaveView& W, int p, PathReg& P, const Hit& h, E& e, Stats
             Col brdf = ct_brdf(m, dir, neg(rd), h.n);
             float bp = ct_pdf(m, neg(rd), dir, h.n);
             float mis = power_heuristic(pdf, bp);
-            W.q_env[p] = f4(cdiv(cmul(cscale(cscale(brdf, cosine), mis), rad), pdf), 0.0f);
+            pend(W, p, QP_ENV) = f4(cdiv(cmul(cscale(cscale(brdf, cosine), mis), rad), pdf), 0.0f);
             fl |= PF_ESH;
             emit(e, RK_ESH, p, add(h.p, mul(1.0e-4f, h.n)), dir);
         }
@@ -715,7 +724,7 @@ RT_HD void shade(const WaveView& W, int p, PathReg& P, const Hit& h, E& e, Stats
             epdf *= (float)(S.ew * S.eh);
             epdf = (float)((double)epdf / (2.0 * 3.14159265358979323846 * 3.14159265358979323846 * (double)sth));
             float mis = power_heuristic(bsp, epdf);
-            W.q_benv[p] = f4(cdiv(cmul(cscale(cscale(sky, mis), cosine), bis), bsp), 0.0f);
+            pend(W, p, QP_BENV) = f4(cdiv(cmul(cscale(cscale(sky, mis), cosine), bis), bsp), 0.0f);
             fl |= PF_BENV;
             emit(e, RK_BENV, p, add(h.p, mul(1.0e-5f, h.n)), bdir);
         }
@@ -727,7 +736,7 @@ RT_HD void shade(const WaveView& W, int p, PathReg& P, const Hit& h, E& e, Stats
     // bounce 0: sample_color += material.emission (:126) — sc is still the sample start's 0 and
     // nothing else adds to it before this bounce's resolve, so the same addition happens here
     if (P.bounce == 0) P.sc = cadd(P.sc, m.emission);
-    W.q_thr[p] = f4(P.thr, 0.0f);
+    pend(W, p, QP_THR) = f4(P.thr, 0.0f);
     if ((brdf.r == 0.0f && brdf.g == 0.0f && brdf.b == 0.0f) || bpdf < 1.0e-8f || rt_isinf(bpdf)) {
         fl |= PF_END;  // `break` after this bounce's light is added
     } else {
@@ -751,20 +760,21 @@ RT_HD void shade(const WaveView& W, int p, PathReg& P, const Hit& h, E& e, Stats
 // reference's association: lr = light + bmis, er = brdf_sample + env_sample,
 // sc = sc + (lr + er) * thr (render_kernel.cpp:113-128).
 // The records a resolve reads first, loaded by path_step together with the hit's
-// triangle (one memory round trip): the pending bounce's candidates and their query results.
+// triangle (one memory round trip): the pending bounce's candidates and their query results
+// (the two occlusion answers came with the slot's flags word, a round trip earlier: rf).
 struct ResolveRec {
     float4_ thr, env, benv, light;
     float lsh_t, bl_t;
     uint8_t esh, benv_r;
 };
-RT_HD void resolve_load(const WaveView& W, int p, uint32_t fl, ResolveRec& R)
+RT_HD void resolve_load(const WaveView& W, int p, uint32_t fl, uint32_t rf, ResolveRec& R)
 {
     const float4_ z = float4_{0.0f, 0.0f, 0.0f, 0.0f};
-    R.thr = W.q_thr[p];
-    R.env = (fl & PF_ESH) ? W.q_env[p] : z;
-    R.benv = (fl & PF_BENV) ? W.q_benv[p] : z;
-    R.esh = (fl & PF_ESH) ? W.r_esh[p] : 1;
-    R.benv_r = (fl & PF_BENV) ? W.r_benv[p] : 1;
+    R.thr = pend(W, p, QP_THR);
+    R.env = (fl & PF_ESH) ? pend(W, p, QP_ENV) : z;
+    R.benv = (fl & PF_BENV) ? pend(W, p, QP_BENV) : z;
+    R.esh = (fl & PF_ESH) ? (uint8_t)(rf >> (8 * RF_ESH)) : 1;
+    R.benv_r = (fl & PF_BENV) ? (uint8_t)(rf >> (8 * RF_BENV)) : 1;
     R.light = (fl & PF_LSH) ? W.q_light[p] : z;
     R.lsh_t = (fl & PF_LSH) ? W.r_lsh_t[p] : 0.0f;
     R.bl_t = (fl & PF_BL) ? W.r_bl_t[p] : 0.0f;
@@ -830,28 +840,31 @@ RT_HD void path_step(const WaveView& W, int p, E& e, Stats* st)
     e.mask = 0;
     e.active = true;
     e.heavy = false;
-    // the slot's state, wait count and continuation result in one round trip
+    // the slot's state, wait count, flags word and both closest-hit results in one round trip
+    // (the record's cam half counts only with PF_CAM and fin only when a sample ends, but the flags and
+    // the answers that say so arrive with this round trip: loading either later would add a dependent one)
     const int park = W.r_park[p];
-    const int heavy = W.r_heavy ? W.r_heavy[p] : 0;
+    const uint32_t rf = W.r_flags[p];
     PathReg P;
     load_path(W, p, P);
-    const float cont_t = W.r_cont_t[p];
-    const int cont_k = W.r_cont_k[p];
-    const float cam_t = W.r_cam_t[p];  // (read only with PF_CAM)
-    const int cam_k = W.r_cam_k[p];
+    const HitRec hr = W.r_hit[p];
+    const float cont_t = hr.cont.t;
+    const int cont_k = hr.cont.k;
+    const float cam_t = hr.cam.t;
+    const int cam_k = hr.cam.k;
     if (park != 0) {  // a query of this path is parked: wait (-1: handed to the fast lane, leaves the list)
         e.active = park > 0;
         return;
     }
     if (st) st->c[RT_STAT_STEPS]++;
-    if (heavy) {  // its last walk was long: this step's rays head the next streams
+    if ((rf >> (8 * RF_HEAVY)) & 0xffu) {  // its last walk was long: this step's rays head the next streams
         e.heavy = true;
-        W.r_heavy[p] = 0;
+        res_flag(W, p, RF_HEAVY) = 0;
     }
     // what depends only on the state, loaded together: the bounce to resolve and the hit's triangle
     const uint32_t fl0 = P.flags;
     ResolveRec R;
-    if (fl0 & PF_AUX) resolve_load(W, p, fl0, R);
+    if (fl0 & PF_AUX) resolve_load(W, p, fl0, rf, R);
     // (the triangle the step shades: the continuation's hit, else the next sample's camera hit)
     float4_ tr0 = float4_{0.0f, 0.0f, 0.0f, 0.0f}, tr1 = tr0, tr2 = tr0;
     const bool cont_hit = (fl0 & PF_CONT) && cont_t > 0.0f && cont_k >= 0;
@@ -937,25 +950,23 @@ RT_HD void finish_closest(const WaveView& W, uint32_t target, V3 o, V3 d, float 
     spheres_closest(W.S, o, d, t, k);
     const int slot = (int)(target >> 3), kind = (int)(target & 7u);
     if (kind == RK_CONT) {
-        W.r_cont_t[slot] = t;
-        W.r_cont_k[slot] = k;
+        W.r_hit[slot].cont = HitTK{t, k};
     } else if (kind == RK_CAM) {
-        W.r_cam_t[slot] = t;
-        W.r_cam_k[slot] = k;
+        W.r_hit[slot].cam = HitTK{t, k};
     } else if (kind == RK_LSH) {
         W.r_lsh_t[slot] = t;
     } else if (kind == RK_BL) {
         W.r_bl_t[slot] = t;
         W.r_bl_k[slot] = k;
     } else {
-        (kind == RK_ESH ? W.r_esh : W.r_benv)[slot] = t > 0.0f ? 1 : 0;
+        res_flag(W, slot, kind == RK_ESH ? RF_ESH : RF_BENV) = t > 0.0f ? 1 : 0;
     }
 }
 
 RT_HD void finish_any(const WaveView& W, uint32_t target, bool hit)
 {
     const int slot = (int)(target >> 3), kind = (int)(target & 7u);
-    (kind == RK_ESH ? W.r_esh : W.r_benv)[slot] = hit ? 1 : 0;
+    res_flag(W, slot, kind == RK_ESH ? RF_ESH : RF_BENV) = hit ? 1 : 0;
 }
 
 // The queue item behind a trace work index: closest-hit kernels see

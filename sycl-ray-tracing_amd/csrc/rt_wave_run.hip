@@ -238,6 +238,7 @@ int WaveRun::init_lane(int l)
     La.lists[1] = W.act_out;
     HIPCHK(c, hipMemsetAsync(La.cnt, 0, C_COUNT * sizeof(int32_t), La.s));
     HIPCHK(c, hipMemsetAsync(W.r_park, 0, (size_t)La.n * 4, La.s));
+    HIPCHK(c, hipMemsetAsync(W.r_flags, 0, (size_t)La.n * 4, La.s));
     W.act_in = La.lists[1];
     W.act_out = La.lists[0];
     if (W.first > 0)
