@@ -111,8 +111,8 @@ int rt_test_fail_device(rt_context* ctx, int device);
  * product's cap, n > 0 that many blocks, at most 65536), "up_variant" (rt_upscale's kernel: 0 the product's
  * choice, 1 direct loads, 2 the low-resolution footprint staged in LDS), "bloom_variant" (rt_bloom's reduce kernel:
  * 0 the product's choice, 1 direct loads, 2 the source footprint staged in LDS), "dof_variant" (rt_dof's kernel: 0 the
- * product's choice, 1 the footprint staged in LDS, 2 direct loads), "motion_variant" (rt_motion_blur's gather kernel, the
- * same three), "rq_variant" (rt_query's search-BVH kernel:
+ * product's choice, 1 direct loads, 2 the footprint staged in LDS), "motion_variant" (rt_motion_blur's gather kernel, the
+ * same three: in every two-kernel stage 1 is direct loads and 2 the LDS kernel), "rq_variant" (rt_query's search-BVH kernel:
  * 0 the product's choice, 1 plain rounds of one query per quad, 2 per-quad refill), "gb_variant" (the same three
  * for rt_render_gbuffer's search-BVH kernel), the stressor "gb_force_every" (N > 0: G-buffer pixels with
  * i mod N == 0 go to the exact walk's list instead of the search-BVH walk; 0: off),

@@ -384,11 +384,11 @@ int rt_backend_progress_adapt_noise(rt_context* c, const rtk::NoiseArgs& A, int3
 // 3 k_adapt_scatter. out_active[2]: the list's tiles and pixels.
 extern "C" int rt_device_adapt_kernel_ms(rt_context* c, float threshold, int reps, double* out_ms, int* out_active)
 {
-    if (!c || !c->backend || !c->prog.active || !c->prog.adaptive || reps <= 0 || !out_ms || !out_active)
+    if (!c || !c->prog.active || !c->prog.adaptive || !out_active)
         return rt_fail(c, RT_ERR_ARG, "rt_device_adapt_kernel_ms: bad arguments or no adaptive progression");
+    TimedRounds T;
+    if (int r = T.enter(c, "rt_device_adapt_kernel_ms", reps, out_ms)) return r;
     Backend* b = rt_backend_dev0(c);
-    DeviceScope sc;
-    if (int r = sc.enter(c, b->device)) return r;
     HIPCHK(c, hipDeviceSynchronize());
     Adapt& ad = *b->adapt;
     int32_t hdr[rtk::AD_WORDS];
@@ -398,21 +398,12 @@ extern "C" int rt_device_adapt_kernel_ms(rt_context* c, float threshold, int rep
     if (int r = ensure(c, ad.xy, 8 * (size_t)std::max(n_px, 1))) return r;
     if (int r = ensure(c, ad.idx, 4 * (size_t)std::max(n_px, 1))) return r;
     if (int r = ensure(c, ad.cstate, 16 * (size_t)std::max(n_px, 1))) return r;
-    Event e0, e1;
-    HIPCHK(c, hipEventCreate(&e0.h));
-    HIPCHK(c, hipEventCreate(&e1.h));
     rtk::NoiseArgs F{};
     F.threshold = threshold;
-    for (int r = 0; r < reps; r++)
-        for (int k = 0; k < 4; k++) {
-            auto launch = [&]() -> int {
-                if (k == 0) return launch_tiles(c, b, F, nullptr, (float*)ad.err.p, nullptr, nullptr);
-                if (k == 1) return launch_select(c, b, 0, threshold, true, false, nullptr);
-                if (n_act == 0) return RT_OK;
-                if (k == 2) return rt_adapt_gather(c, b, n_act, false, nullptr);
-                return rt_adapt_scatter(c, b, n_px, false, nullptr);
-            };
-            if (int e = rt_time_alone(c, e0, e1, launch, &out_ms[(size_t)k * reps + r])) return e;
-        }
-    return RT_OK;
+    // (no active tile: the gather and the scatter are timed as an empty interval, not as absent kernels)
+    using K = TimedKernel;
+    return T.run(0, {K::fixed(0, [&] { return launch_tiles(c, b, F, nullptr, (float*)ad.err.p, nullptr, nullptr); }),
+                     K::fixed(1, [&] { return launch_select(c, b, 0, threshold, true, false, nullptr); }),
+                     K::fixed(2, [&] { return n_act ? rt_adapt_gather(c, b, n_act, false, nullptr) : RT_OK; }),
+                     K::fixed(3, [&] { return n_act ? rt_adapt_scatter(c, b, n_px, false, nullptr) : RT_OK; })});
 }

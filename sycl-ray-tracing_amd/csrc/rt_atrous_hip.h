@@ -103,10 +103,7 @@ __device__ __forceinline__ bool dn_lds_body(const rtk::DnPass& P, float4_& f, si
 // 0.02 ms at 1080p and leave the order standing: the tile up to step 2, direct loads from step 4.
 inline bool dn_use_lds(int variant, int step)
 {
-    if (step > 4) return false;
-    if (variant == 1) return false;
-    if (variant == 2) return true;
-    return step <= 2;
+    return step <= 4 && rt_use_lds(variant, step <= 2);
 }
 
 // A stage's entry points, in dn_launch_pass's order; A: what they take after the pass.

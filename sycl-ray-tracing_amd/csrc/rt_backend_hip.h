@@ -22,6 +22,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <functional>
 #include <memory>
 #include <string>
 #include <vector>
@@ -342,7 +343,7 @@ struct StagedCall {
     }
 };
 
-// The measurement hooks' loop body (rt_device_display_kernel_ms, rt_device_noise_kernel_ms): one
+// The measurement hooks' loop body (TimedRounds below): one
 // launch alone on the default stream between e0 and e1, waited for; its GPU time into *ms.
 template <class F>
 int rt_time_alone(rt_context* c, hipEvent_t e0, hipEvent_t e1, F launch, double* ms)
@@ -357,6 +358,62 @@ int rt_time_alone(rt_context* c, hipEvent_t e0, hipEvent_t e1, F launch, double*
     *ms = f;
     return RT_OK;
 }
+
+// The rounds of a measurement hook (rt_device_*_kernel_ms): reps rounds in which each kernel of a list runs alone
+// (rt_time_alone), its time stored at out_ms[slot * reps + r].
+//   enter  the reps / out_ms check, the root device made current, the two events
+//   run    the default stream synchronised (the hook's validating product call has ended), then the rounds
+// The kernels run in the list's order, but for the rotated ones: round r starts them at the (r + first)-th of them, so
+// that none always runs behind another; the others keep their place around them.
+struct TimedKernel {
+    int slot;
+    std::function<int()> launch;  // none: the kernel is absent and its slots hold 0
+    bool rotated;
+    std::function<int()> before;  // optional: runs in front of the first event (not timed)
+    static TimedKernel fixed(int slot, std::function<int()> launch, std::function<int()> before = nullptr)
+    {
+        return {slot, std::move(launch), false, std::move(before)};
+    }
+    static TimedKernel turns(int slot, std::function<int()> launch) { return {slot, std::move(launch), true, nullptr}; }
+    static TimedKernel absent(int slot) { return {slot, nullptr, false, nullptr}; }
+};
+struct TimedRounds {
+    rt_context* c = nullptr;
+    int reps = 0;
+    double* out_ms = nullptr;
+    DeviceScope sc;
+    Event e0, e1;
+    int enter(rt_context* ctx, const char* hook, int n_reps, double* out)
+    {
+        if (!ctx || !ctx->backend || n_reps <= 0 || !out) return rt_fail(ctx, RT_ERR_ARG, std::string(hook) + ": bad arguments");
+        c = ctx, reps = n_reps, out_ms = out;
+        if (int r = sc.enter(c, rt_backend_dev0(c)->device)) return r;
+        HIPCHK(c, hipEventCreate(&e0.h));
+        HIPCHK(c, hipEventCreate(&e1.h));
+        return RT_OK;
+    }
+    int run(int first, const std::vector<TimedKernel>& kernels)
+    {
+        HIPCHK(c, hipStreamSynchronize(nullptr));
+        std::vector<int> rot;  // the rotated kernels' places in the list
+        for (size_t i = 0; i < kernels.size(); i++)
+            if (kernels[i].rotated) rot.push_back((int)i);
+        const int n_rot = (int)rot.size();
+        for (int r = 0; r < reps; r++) {
+            int turn = n_rot ? ((r + first) % n_rot + n_rot) % n_rot : 0;
+            for (const TimedKernel& at : kernels) {
+                const TimedKernel& k = at.rotated ? kernels[rot[turn++ % n_rot]] : at;
+                double& ms = out_ms[(size_t)k.slot * reps + r];
+                ms = 0.0;
+                if (!k.launch) continue;
+                if (k.before)
+                    if (int e = k.before()) return e;
+                if (int e = rt_time_alone(c, e0, e1, k.launch, &ms)) return e;
+            }
+        }
+        return RT_OK;
+    }
+};
 
 // rt_wave_run.hip: the wavefront loop for n slots of `src` into fb (device, n float4) on b's
 // device (current), and the sizes of a lane's counters and of its pinned readback block.

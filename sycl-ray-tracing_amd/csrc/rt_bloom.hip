@@ -30,7 +30,7 @@
 //                        and in L2 from the launch before.
 //   k_bloom_composite    the frame's pixel, four taps of u_1, the output pixel and, when given, the layer.
 // The last two take k_firefly_direct's shape: 64 x 4 texels per block, a wave per row.
-// Which reduce kernel a call takes: bl_use_lds.
+// Which reduce kernel a call takes: rt_backend_bloom.
 #include <hip/hip_runtime.h>
 
 #include <string>
@@ -130,13 +130,6 @@ __global__ __launch_bounds__(256) void k_bloom_composite(rtk::BloomArgs A, const
     if (layer_out) layer_out[p] = layer;
 }
 
-// Which reduce kernel a call takes. bloom_variant (rt_test_schedule): 1 direct loads, 2 the LDS tile, 0
-// the faster of the two as measured on the MI355X (profiles/bloom_bench.json), LDS / direct ms:
-// the first reduce (PRE, the frame to level 1) 0.015 / 0.032 at 1920x1080 and 0.047 / 0.104 at 3840x2160, the second
-// 0.007 / 0.008 and 0.013 / 0.015; from the third level on both sit on the floor of a launch between two events,
-// 0.0064. The whole call at 5 levels: 0.067 / 0.080 and 0.178 / 0.235. The tile wins wherever the two differ.
-bool bl_use_lds(int variant) { return variant != 1; }
-
 template <bool PRE>
 void bl_reduce(const rtk::BloomArgs& A, bool lds, const float4_* src, int sw, int sh, const BlDev& d, hipStream_t s)
 {
@@ -194,7 +187,13 @@ int rt_backend_bloom(rt_context* c, rtk::BloomArgs A, void* rgba_out, void* laye
     float4_* d_layer = (float4_*)st.out(layer_out, bytes);  // (may be null)
     float4_* pyr = (float4_*)(device ? b->bloom.p : st.base + 3 * bytes);
     if (int r = st.begin()) return r;
-    if (int r = bl_run(c, A, bl_use_lds(c->sched.bloom_variant), d_out, d_layer, pyr, st.s, nullptr)) return r;
+    // Which reduce kernel the call takes (bloom_variant, rt_use_lds): the faster of the two as measured on the MI355X
+    // (profiles/bloom_bench.json), LDS / direct ms: the first reduce (PRE, the frame to level 1) 0.015 /
+    // 0.032 at 1920x1080 and 0.047 / 0.104 at 3840x2160, the second 0.007 / 0.008 and 0.013 / 0.015; from the third
+    // level on both sit on the floor of a launch between two events, 0.0064. The whole call at 5 levels: 0.067 / 0.080
+    // and 0.178 / 0.235. The tile wins wherever the two differ.
+    const bool lds = rt_use_lds(c->sched.variant[RT_VAR_BLOOM], true);
+    if (int r = bl_run(c, A, lds, d_out, d_layer, pyr, st.s, nullptr)) return r;
     return st.end();
 }
 
@@ -208,6 +207,7 @@ int rt_backend_bloom(rt_context* c, rtk::BloomArgs A, void* rgba_out, void* laye
 extern "C" int rt_device_bloom_kernel_ms(rt_context* c, int w, int h, const void* d_in, const rt_bloom_params* params,
                                          void* d_out, void* d_layer, int lds, int reps, double* out_ms)
 {
+    // (not TimedRounds: the launches are timed in sequence, not alone, and laid out by round)
     if (!c || !c->backend || reps <= 0 || !out_ms) return rt_fail(c, RT_ERR_ARG, "rt_device_bloom_kernel_ms: bad arguments");
     if (int r = rt_bloom_device(c, w, h, d_in, params, d_out, d_layer, nullptr)) return r;
     rt_bloom_params p;

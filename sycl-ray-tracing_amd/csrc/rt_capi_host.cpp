@@ -238,6 +238,11 @@ int rt_test_schedule(rt_context* c, const char* key, double value)
     if (!std::isfinite(value) || (!real_key && (value < -2147483648.0 || value > 2147483647.0)))
         return rt_fail(c, RT_ERR_ARG, "rt_test_schedule: value of " + k + " is out of range");
     const int v = real_key ? 0 : (int)value;
+    for (const auto& e : rt_variant_keys)
+        if (k == e.key) {
+            s.variant[e.slot] = std::max(0, std::min(2, v));
+            return RT_OK;
+        }
     if (k == "lanes") s.lanes = std::max(0, v);
     else if (k == "tail_paths") s.tail_paths = v;
     else if (k == "tail_enter") s.tail_enter = value;
@@ -251,16 +256,7 @@ int rt_test_schedule(rt_context* c, const char* key, double value)
     else if (k == "fast_k") s.fast_k = v;
     else if (k == "fast_spp") s.fast_spp = value;
     else if (k == "near_scale") s.near_scale = value;
-    else if (k == "dn_variant") s.dn_variant = std::max(0, std::min(2, v));
-    else if (k == "ff_variant") s.ff_variant = std::max(0, std::min(2, v));
-    else if (k == "mt_variant") s.mt_variant = std::max(0, std::min(2, v));
-    else if (k == "up_variant") s.up_variant = std::max(0, std::min(2, v));
-    else if (k == "bloom_variant") s.bloom_variant = std::max(0, std::min(2, v));
-    else if (k == "dof_variant") s.dof_variant = std::max(0, std::min(2, v));
-    else if (k == "motion_variant") s.motion_variant = std::max(0, std::min(2, v));
     else if (k == "mt_blocks") s.mt_blocks = std::max(0, std::min(65536, v));
-    else if (k == "rq_variant") s.rq_variant = std::max(0, std::min(2, v));
-    else if (k == "gb_variant") s.gb_variant = std::max(0, std::min(2, v));
     else if (k == "gb_force_every") s.gb_force_every = std::max(0, v);
     else if (k == "chain_full") {
         // the devices' views carry the flag: the next call uploads them again

@@ -14,6 +14,26 @@
 #include "rt_device.h"
 #include "rt_scene.h"
 
+// The stages that have two kernels for one result, and the rt_test_schedule key that forces one: a value is
+// clamped to 0..2 and 0 is the product's choice, the faster kernel as measured on the MI355X.
+//   the first seven (a kernel of direct global loads and one that stages its footprint in LDS; for rt_denoise
+//   and rt_denoise_var the à-trous filter of each step, for rt_bloom the reduce, for rt_motion_blur the gather):
+//   RT_KERNEL_DIRECT or RT_KERNEL_LDS, resolved by rt_use_lds
+//   rq, gb (the search-BVH kernel of rt_query and of rt_render_gbuffer): 1 plain rounds, 2 per-quad refill
+enum RtVariant { RT_VAR_DN, RT_VAR_FF, RT_VAR_MT, RT_VAR_UP, RT_VAR_BLOOM, RT_VAR_DOF, RT_VAR_MOTION, RT_VAR_RQ, RT_VAR_GB, RT_VAR_COUNT };
+constexpr struct {
+    const char* key;
+    RtVariant slot;
+} rt_variant_keys[] = {{"dn_variant", RT_VAR_DN},       {"ff_variant", RT_VAR_FF},   {"mt_variant", RT_VAR_MT},
+                       {"up_variant", RT_VAR_UP},       {"bloom_variant", RT_VAR_BLOOM}, {"dof_variant", RT_VAR_DOF},
+                       {"motion_variant", RT_VAR_MOTION}, {"rq_variant", RT_VAR_RQ},   {"gb_variant", RT_VAR_GB}};
+enum { RT_KERNEL_MEASURED = 0, RT_KERNEL_DIRECT = 1, RT_KERNEL_LDS = 2 };
+// measured_choice: whether the LDS kernel is the faster one for this call (the caller quotes the figures)
+inline bool rt_use_lds(int variant, bool measured_choice)
+{
+    return variant == RT_KERNEL_MEASURED ? measured_choice : variant == RT_KERNEL_LDS;
+}
+
 // Schedule of the wavefront loop (rt_wave_run.hip run_wave). The product runs the defaults
 // (-1: the backend's own choice); rt_test_schedule (tests and measurement tools only,
 // include/rt_hip.h) overrides them per context. No parameter changes a pixel: the GPU
@@ -34,16 +54,8 @@ struct RtSchedule {
     double fast_spp = -1.0;    // ... at the lanes' first readback from iteration fast_spp x spp on
     double near_scale = -1.0;  // near box: the scene's box widened by this x its largest extent (rt_view_near;
                                // study probes only: answers never depend on it, only which walk gives them)
-    int dn_variant = 0;        // rt_denoise's filter kernel: 0 per step as measured, 1 direct, 2 LDS tile where built
-    int ff_variant = 0;        // rt_firefly's kernel: 0 as measured, 1 direct loads, 2 the LDS tile of luminances
-    int mt_variant = 0;        // rt_meter's kernel: 0 as measured, 1 the direct kernel, 2 the LDS kernel
-    int up_variant = 0;        // rt_upscale's kernel: 0 as measured, 1 direct loads, 2 the LDS footprint
-    int bloom_variant = 0;     // rt_bloom's reduce kernel: 0 as measured, 1 direct loads, 2 the LDS tile
-    int dof_variant = 0;       // rt_dof's kernel: 0 as measured, 1 the LDS tile, 2 direct loads
-    int motion_variant = 0;    // rt_motion_blur's kernel: 0 as measured, 1 the LDS tile, 2 direct loads
+    int variant[RT_VAR_COUNT] = {};  // the forced kernel of each stage that has two (RtVariant), 0: as measured
     int mt_blocks = 0;         // rt_meter's grid: 0 the product's cap, n > 0 that many blocks (many grid-stride rounds)
-    int rq_variant = 0;        // rt_query's fast kernel: 0 as measured, 1 plain grid-stride rounds, 2 per-quad refill
-    int gb_variant = 0;        // rt_render_gbuffer's fast kernel: 0 as measured, 1 plain 16-pixel rounds, 2 per-quad refill
     int gb_force_every = 0;    // stressor: G-buffer pixels with i % N == 0 skip to the exact walk's list (0: off)
     bool chain_full = false;   // the scene view reports chain_monotone = 0: chain_ok / quad_chain_ok run their full
                                // ancestor-chain loop (rt_fast.h), which no tree the host builds reaches otherwise

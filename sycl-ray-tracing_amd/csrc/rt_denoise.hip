@@ -83,7 +83,7 @@ int rt_backend_denoise(rt_context* c, int w, int h, const void* in, const void* 
     if (int r = st.begin()) return r;
     if (int r = dn_run_timed(c, post, 0, st.s, w, h, p, d_in, 0, d_out, d_nd, d_alb,
                              [&](const rtk::DnPass& P, float4_* dst, bool last) {
-                                 return dn_launch_pass(c, dn_kernels, P, dn_use_lds(c->sched.dn_variant, P.step), st.s, dst,
+                                 return dn_launch_pass(c, dn_kernels, P, dn_use_lds(c->sched.variant[RT_VAR_DN], P.step), st.s, dst,
                                                        last ? d_in : nullptr, blend);
                              }))
         return r;

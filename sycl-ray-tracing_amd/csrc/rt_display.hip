@@ -106,32 +106,20 @@ int rt_display_resolve_linear(rt_context* c, const float4_* base, const float4_*
 extern "C" int rt_device_display_kernel_ms(rt_context* c, int w, int h, const void* d_in, const void* d_state,
                                            void* d_out, void* d_out8, int reps, double* out_ms)
 {
-    if (!c || !c->backend || w <= 0 || h <= 0 || (double)w * (double)h > 134217727.0 || !d_in || !d_state || !d_out ||
-        !d_out8 || reps <= 0 || !out_ms)
+    if (w <= 0 || h <= 0 || (double)w * (double)h > 134217727.0 || !d_in || !d_state || !d_out || !d_out8)
         return rt_fail(c, RT_ERR_ARG, "rt_device_display_kernel_ms: bad arguments");
-    DeviceScope sc;
-    if (int r = sc.enter(c, rt_backend_dev0(c)->device)) return r;
-    Event e0, e1;
-    HIPCHK(c, hipEventCreate(&e0.h));
-    HIPCHK(c, hipEventCreate(&e1.h));
+    TimedRounds T;
+    if (int r = T.enter(c, "rt_device_display_kernel_ms", reps, out_ms)) return r;
     const int n = w * h;
     const float4_ *in = (const float4_*)d_in, *state = (const float4_*)d_state;
     float4_* out = (float4_*)d_out;
     uint32_t* out8 = (uint32_t*)d_out8;
     const float ex = 1.5f, ig = 1.0f / 2.2f;
-    for (int r = 0; r < reps; r++)
-        for (int k = 0; k < 6; k++) {
-            auto launch = [&]() -> int {
-                switch (k) {
-                case 0: return rt_wave_resolve(c, in, state, out, n, 1, nullptr);
-                case 1: return rt_display_resolve_linear(c, in, state, out, n, 1, nullptr);
-                case 2: return launch_display(c, in, out, nullptr, w, h, false, ex, ig, nullptr);
-                case 3: return launch_display(c, in, nullptr, out8, w, h, false, ex, ig, nullptr);
-                case 4: return launch_display(c, in, nullptr, out8, w, h, true, ex, ig, nullptr);
-                default: return launch_display(c, in, out, out8, w, h, false, ex, ig, nullptr);
-                }
-            };
-            if (int e = rt_time_alone(c, e0, e1, launch, &out_ms[(size_t)k * reps + r])) return e;
-        }
-    return RT_OK;
+    using K = TimedKernel;
+    return T.run(0, {K::fixed(0, [&] { return rt_wave_resolve(c, in, state, out, n, 1, nullptr); }),
+                     K::fixed(1, [&] { return rt_display_resolve_linear(c, in, state, out, n, 1, nullptr); }),
+                     K::fixed(2, [&] { return launch_display(c, in, out, nullptr, w, h, false, ex, ig, nullptr); }),
+                     K::fixed(3, [&] { return launch_display(c, in, nullptr, out8, w, h, false, ex, ig, nullptr); }),
+                     K::fixed(4, [&] { return launch_display(c, in, nullptr, out8, w, h, true, ex, ig, nullptr); }),
+                     K::fixed(5, [&] { return launch_display(c, in, out, out8, w, h, false, ex, ig, nullptr); })});
 }

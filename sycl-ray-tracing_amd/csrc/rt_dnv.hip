@@ -94,7 +94,7 @@ int rt_backend_denoise_var(rt_context* c, int w, int h, const void* in, const vo
     // (the prep took the first of the two buffers: pass i writes the other one of pass i - 1's)
     if (int r = dn_run_timed(c, post, 1, s, w, h, p, rec0, 1, d_out, d_nd, d_alb,
                              [&](const rtk::DnPass& P, float4_* dst, bool last) {
-                                 return dn_launch_pass(c, dnv_kernels, P, dn_use_lds(c->sched.dn_variant, P.step), s, dst,
+                                 return dn_launch_pass(c, dnv_kernels, P, dn_use_lds(c->sched.variant[RT_VAR_DN], P.step), s, dst,
                                                        last ? d_in : nullptr, blend, last ? d_sout : nullptr);
                              }))
         return r;

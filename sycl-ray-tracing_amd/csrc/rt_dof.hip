@@ -40,7 +40,7 @@
 //                 whether the tap is inside or not, and the radius and k(r) computed again, two
 //                 divisions per tap; a tap outside the frame is then skipped. The yardstick for the
 //                 tile; 64 x 4 pixels per block, a wave per row, as k_firefly_direct.
-// Which kernel a call takes: dof_use_lds.
+// Which kernel a call takes: rt_backend_dof.
 #include <hip/hip_runtime.h>
 
 #include <string>
@@ -187,13 +187,6 @@ __global__ __launch_bounds__(DOF_TW* DOF_TH) void k_dof_lds(rtk::DofArgs A, floa
 
 size_t dof_lds_bytes(int R) { return (size_t)(DOF_TW + 2 * R) * (DOF_TH + 2 * R) * (sizeof(float4_) + sizeof(DofTK)); }
 
-// Which kernel a call takes. dof_variant (rt_test_schedule): 1 the LDS tile, 2 direct loads, 0 the
-// faster of the two as measured on the MI355X (profiles/dof_bench.json), LDS / direct ms at
-// 1920x1080 on a frame defocused everywhere: 0.10 / 0.30 at radius 4, 0.25 / 0.99 at 8, 0.55 / 2.1 at 12; in focus
-// everywhere 0.04 / 0.32, 0.05 / 1.0, 0.07 / 2.1; the same ratios at 3840x2160. The tile wins at every radius, so
-// the dispatch does not look at it.
-bool dof_use_lds(int variant) { return variant != 2; }
-
 int dof_launch(rt_context* c, const rtk::DofArgs& A, bool lds, float4_* d_out, float* d_coc, hipStream_t s)
 {
     if (lds) {
@@ -221,7 +214,12 @@ int rt_backend_dof(rt_context* c, rtk::DofArgs A, void* rgba_out, void* coc_out,
     float4_* d_out = (float4_*)st.out(rgba_out, bytes);
     float* d_coc = (float*)st.out(coc_out, n * sizeof(float));  // (may be null)
     if (int r = st.begin()) return r;
-    if (int r = dof_launch(c, A, dof_use_lds(c->sched.dof_variant), d_out, d_coc, st.s)) return r;
+    // Which kernel the call takes (dof_variant, rt_use_lds): the faster of the two as measured on the MI355X
+    // (profiles/dof_bench.json), LDS / direct ms at 1920x1080 on a frame defocused everywhere: 0.10 /
+    // 0.30 at radius 4, 0.25 / 0.99 at 8, 0.55 / 2.1 at 12; in focus everywhere 0.04 / 0.32, 0.05 / 1.0, 0.07 / 2.1;
+    // the same ratios at 3840x2160. The tile wins at every radius, so the dispatch does not look at it.
+    const bool lds = rt_use_lds(c->sched.variant[RT_VAR_DOF], true);
+    if (int r = dof_launch(c, A, lds, d_out, d_coc, st.s)) return r;
     return st.end();
 }
 
@@ -234,25 +232,14 @@ int rt_backend_dof(rt_context* c, rtk::DofArgs A, void* rgba_out, void* coc_out,
 extern "C" int rt_device_dof_kernel_ms(rt_context* c, int w, int h, const void* d_in, const void* d_nd, const rt_dof_params* params,
                                        void* d_out, void* d_coc, int reps, int first, double* out_ms)
 {
-    if (!c || !c->backend || reps <= 0 || !out_ms) return rt_fail(c, RT_ERR_ARG, "rt_device_dof_kernel_ms: bad arguments");
+    TimedRounds T;
+    if (int r = T.enter(c, "rt_device_dof_kernel_ms", reps, out_ms)) return r;
     if (int r = rt_dof_device(c, w, h, d_in, d_nd, params, d_out, d_coc, nullptr)) return r;
     rt_dof_params p;
     if (params) p = *params;
     else rt_dof_default_params(&p);
-    Backend* b = rt_backend_dev0(c);
-    DeviceScope sc;
-    if (int r = sc.enter(c, b->device)) return r;
-    HIPCHK(c, hipStreamSynchronize(nullptr));
     rtk::DofArgs A{w, h, p.max_radius, p.focus, p.coc_inf, (const float4_*)d_in, (const float4_*)d_nd, {}};
     rtk::dof_build_table(A.D);
-    Event e0, e1;
-    HIPCHK(c, hipEventCreate(&e0.h));
-    HIPCHK(c, hipEventCreate(&e1.h));
-    for (int r = 0; r < reps; r++)
-        for (int i = 0; i < 2; i++) {
-            const int k = (r + first + i) & 1;
-            auto launch = [&]() -> int { return dof_launch(c, A, k == 1, (float4_*)d_out, (float*)d_coc, nullptr); };
-            if (int e = rt_time_alone(c, e0, e1, launch, &out_ms[(size_t)k * reps + r])) return e;
-        }
-    return RT_OK;
+    auto kernel = [&](bool lds) { return [&, lds] { return dof_launch(c, A, lds, (float4_*)d_out, (float*)d_coc, nullptr); }; };
+    return T.run(first, {TimedKernel::turns(0, kernel(false)), TimedKernel::turns(1, kernel(true))});
 }

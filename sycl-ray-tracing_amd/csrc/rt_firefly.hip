@@ -16,7 +16,7 @@
 //   k_firefly_direct<R>  no LDS: each tap is a bounds test, a 16-B global load and the luminance
 //                        recomputed. The yardstick that shows whether the tile pays.
 // firefly_pixel evaluates no expf, so rtlibm::lds_tables_init() is not called here.
-// Which kernel a call takes: ff_use_lds.
+// Which kernel a call takes: rt_backend_firefly.
 #include <hip/hip_runtime.h>
 
 #include <string>
@@ -101,12 +101,6 @@ __global__ __launch_bounds__(256) void k_firefly_lds(rtk::FireflyArgs A, float4_
     ff_store(rtk::firefly_pixel<R>(A, x, y, c, s, F), p, rgba_out, sigma_out, scale_out);
 }
 
-// Which kernel a call takes. ff_variant (rt_test_schedule): 1 direct loads, 2 the LDS tile, 0 the
-// faster of the two as measured on the MI355X (profiles/firefly_bench.json), LDS /
-// direct ms at rank 2, 1920x1080: radius 1 0.023 / 0.059, radius 2 0.032 / 0.143 (3840x2160:
-// 0.080 / 0.220, 0.109 / 0.555). The tile wins at both radii and both sizes, at rank 8 as well.
-bool ff_use_lds(int variant) { return variant != 1; }
-
 }  // namespace
 
 int rt_backend_firefly(rt_context* c, rtk::FireflyArgs A, void* rgba_out, void* sigma_out, void* scale_out, bool device,
@@ -124,7 +118,11 @@ int rt_backend_firefly(rt_context* c, rtk::FireflyArgs A, void* rgba_out, void* 
     float* d_fout = (float*)st.out(scale_out, n * sizeof(float));
     if (int r = st.begin()) return r;
     const dim3 grid((A.w + FF_TW - 1) / FF_TW, (A.h + FF_TH - 1) / FF_TH);
-    const bool lds = ff_use_lds(c->sched.ff_variant);
+    // Which kernel the call takes (ff_variant, rt_use_lds): the faster of the two as measured on the MI355X
+    // (profiles/firefly_bench.json), LDS / direct ms at rank 2, 1920x1080: radius 1 0.023 / 0.059,
+    // radius 2 0.032 / 0.143 (3840x2160: 0.080 / 0.220, 0.109 / 0.555). The tile wins at both radii and both sizes,
+    // at rank 8 as well.
+    const bool lds = rt_use_lds(c->sched.variant[RT_VAR_FF], true);
     if (lds && A.radius == 1) hipLaunchKernelGGL(k_firefly_lds<1>, grid, dim3(256), 0, st.s, A, d_out, d_sout, d_fout);
     else if (lds) hipLaunchKernelGGL(k_firefly_lds<2>, grid, dim3(256), 0, st.s, A, d_out, d_sout, d_fout);
     else if (A.radius == 1) hipLaunchKernelGGL(k_firefly_direct<1>, grid, dim3(256), 0, st.s, A, d_out, d_sout, d_fout);

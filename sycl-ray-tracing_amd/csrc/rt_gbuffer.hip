@@ -297,7 +297,7 @@ int rt_backend_gbuffer(rt_context* c, int w, int h, bool all_exact, void* albedo
     } else {
         HIPCHK(c, hipMemsetAsync(count, 0, 8, s));
         if (routed) {
-            const bool refill = use_refill(c->sched.gb_variant);
+            const bool refill = use_refill(c->sched.variant[RT_VAR_GB]);
             // whole waves of 16 pixels; at most what is resident at once (the rest by stride)
             const unsigned resident = (unsigned)(G->cus * G->blocks[refill ? 1 : 0]);
             const unsigned fast_blocks = std::min((unsigned)((n + 63) / 64), resident);

@@ -21,7 +21,7 @@
 //                   words; the compiler's per-wave coalescing of a uniform-address atomicAdd(p, 1) is
 //                   all the help it gets. 600 to 1700 times slower on a rendered or a constant frame.
 // meter_pixel evaluates no expf, so rtlibm::lds_tables_init() is not called here.
-// Which kernel a call takes: mt_use_lds; the grid: mt_grid.
+// Which kernel a call takes: rt_backend_meter; the grid: mt_grid.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -138,10 +138,6 @@ __global__ __launch_bounds__(256) void k_meter_lds(const float4_* __restrict__ i
     }
 }
 
-// Which kernel a call takes. mt_variant (rt_test_schedule): 1 the direct kernel, 2 the LDS kernel, 0 the
-// faster of the two as measured on the MI355X (profiles/meter_bench.json).
-bool mt_use_lds(int variant) { return variant != 1; }
-
 // The grid. A block costs its flush (up to 263 global atomics on words every block adds to) and a
 // round of 256 pixels costs a block its time, so with R rounds in the frame the time is about
 // a R / B + b B and smallest at B = sqrt(a R / b). Measured on the MI355X (profiles/meter_bench.json,
@@ -180,7 +176,9 @@ int rt_backend_meter(rt_context* c, int w, int h, const void* in, void* hist, bo
     HIPCHK(c, hipMemsetAsync(d_hist, 0, hbytes, st.s));
     HIPCHK(c, hipMemsetAsync(d_hist + rtk::MT_MIN_BITS, 0xff, sizeof(uint32_t), st.s));
     const dim3 grid(mt_grid(n, b->cus, c->sched.mt_blocks));
-    if (mt_use_lds(c->sched.mt_variant))
+    // Which kernel the call takes (mt_variant, rt_use_lds): the faster of the two as measured on the MI355X
+    // (profiles/meter_bench.json), the LDS kernel.
+    if (rt_use_lds(c->sched.variant[RT_VAR_MT], true))
         hipLaunchKernelGGL(k_meter_lds, grid, dim3(threads), 0, st.s, d_in, (unsigned)n, d_hist);
     else
         hipLaunchKernelGGL(k_meter_direct, grid, dim3(threads), 0, st.s, d_in, (unsigned)n, d_hist);
@@ -197,30 +195,27 @@ int rt_backend_meter(rt_context* c, int w, int h, const void* in, void* hist, bo
 extern "C" int rt_device_meter_kernel_ms(rt_context* c, int w, int h, const void* d_in, void* d_hist, int blocks, int reps,
                                          double* out_ms)
 {
-    if (!c || !c->backend || w <= 0 || h <= 0 || (double)w * (double)h > 134217727.0 || !d_in || !d_hist || blocks < 0 ||
-        reps <= 0 || !out_ms)
+    if (w <= 0 || h <= 0 || (double)w * (double)h > 134217727.0 || !d_in || !d_hist || blocks < 0)
         return rt_fail(c, RT_ERR_ARG, "rt_device_meter_kernel_ms: bad arguments");
+    TimedRounds T;
+    if (int r = T.enter(c, "rt_device_meter_kernel_ms", reps, out_ms)) return r;
     Backend* b = rt_backend_dev0(c);
-    DeviceScope sc;
-    if (int r = sc.enter(c, b->device)) return r;
     if (int r = meter_cus(c, b)) return r;
-    Event e0, e1;
-    HIPCHK(c, hipEventCreate(&e0.h));
-    HIPCHK(c, hipEventCreate(&e1.h));
     const size_t n = (size_t)w * h;
     const dim3 grid(mt_grid(n, b->cus, blocks));
     uint32_t* hist = (uint32_t*)d_hist;
-    for (int r = 0; r < reps; r++)
-        for (int k = 0; k < 2; k++) {
-            HIPCHK(c, hipMemsetAsync(hist, 0, rtk::MT_WORDS * sizeof(uint32_t), nullptr));
-            HIPCHK(c, hipMemsetAsync(hist + rtk::MT_MIN_BITS, 0xff, sizeof(uint32_t), nullptr));
-            auto launch = [&]() -> int {
-                if (k == 0) hipLaunchKernelGGL(k_meter_direct, grid, dim3(threads), 0, nullptr, (const float4_*)d_in, (unsigned)n, hist);
-                else hipLaunchKernelGGL(k_meter_lds, grid, dim3(threads), 0, nullptr, (const float4_*)d_in, (unsigned)n, hist);
-                HIPCHK(c, hipGetLastError());
-                return RT_OK;
-            };
-            if (int e = rt_time_alone(c, e0, e1, launch, &out_ms[(size_t)k * reps + r])) return e;
-        }
-    return RT_OK;
+    auto clear = [&]() -> int {
+        HIPCHK(c, hipMemsetAsync(hist, 0, rtk::MT_WORDS * sizeof(uint32_t), nullptr));
+        HIPCHK(c, hipMemsetAsync(hist + rtk::MT_MIN_BITS, 0xff, sizeof(uint32_t), nullptr));
+        return RT_OK;
+    };
+    auto kernel = [&](bool lds) {
+        return [&, lds]() -> int {
+            if (lds) hipLaunchKernelGGL(k_meter_lds, grid, dim3(threads), 0, nullptr, (const float4_*)d_in, (unsigned)n, hist);
+            else hipLaunchKernelGGL(k_meter_direct, grid, dim3(threads), 0, nullptr, (const float4_*)d_in, (unsigned)n, hist);
+            HIPCHK(c, hipGetLastError());
+            return RT_OK;
+        };
+    };
+    return T.run(0, {TimedKernel::fixed(0, kernel(false), clear), TimedKernel::fixed(1, kernel(true), clear)});
 }

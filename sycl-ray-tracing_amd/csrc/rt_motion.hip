@@ -30,7 +30,7 @@
 //                     leaves between the first barrier and the last.
 //   k_mblur_direct    the rule as written (mb_pixel, what the CPU build runs) with every tap from global
 //                     memory, the same block shape and the same folded rule 3. The yardstick for the tile.
-// Which kernel a call takes: mb_use_lds.
+// Which kernel a call takes: rt_backend_motion_blur.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -229,10 +229,6 @@ int mb_lds_entries(int R)
 }
 size_t mb_lds_bytes(int R) { return (size_t)mb_lds_entries(R) * (sizeof(float4_) + sizeof(MbTK)); }
 
-// Which kernel a call takes. motion_variant (rt_test_schedule): 1 the LDS tile, 2 direct loads, 0 the faster of the
-// two as measured on the MI355X (profiles/motion_bench.json).
-bool mb_use_lds(int variant) { return variant != 2; }
-
 size_t mb_tile_bytes(int w, int h) { return (size_t)rtk::mb_tiles_x(w) * rtk::mb_tiles_y(h) * sizeof(float4_); }
 
 int mb_launch_tilemax(rt_context* c, const rtk::MotionArgs& A, float4_* tiles, hipStream_t s)
@@ -296,7 +292,10 @@ int rt_backend_motion_blur(rt_context* c, rtk::MotionArgs A, void* rgba_out, voi
     float4_* tiles = (float4_*)b->motion_tiles.p;
     if (int r = st.begin()) return r;
     if (int r = mb_launch_tilemax(c, A, tiles, st.s)) return r;
-    if (int r = mb_launch_blur(c, A, mb_use_lds(c->sched.motion_variant), tiles, d_out, d_reach, st.s)) return r;
+    // Which gather kernel the call takes (motion_variant, rt_use_lds): the faster of the two as measured on the MI355X
+    // (profiles/motion_bench.json), the tile at every radius.
+    const bool lds = rt_use_lds(c->sched.variant[RT_VAR_MOTION], true);
+    if (int r = mb_launch_blur(c, A, lds, tiles, d_out, d_reach, st.s)) return r;
     return st.end();
 }
 
@@ -311,39 +310,26 @@ extern "C" int rt_device_motion_kernel_ms(rt_context* c, int w, int h, const voi
                                           const rt_motion_params* params, void* d_out, void* d_reach, const float* prev_view,
                                           float prev_fov_dist, void* d_vec_out, int reps, int first, double* out_ms)
 {
-    if (!c || !c->backend || reps <= 0 || !out_ms) return rt_fail(c, RT_ERR_ARG, "rt_device_motion_kernel_ms: bad arguments");
+    TimedRounds T;
+    if (int r = T.enter(c, "rt_device_motion_kernel_ms", reps, out_ms)) return r;
     if (int r = rt_motion_blur_device(c, w, h, d_in, d_nd, d_motion, params, d_out, d_reach, nullptr)) return r;
     if (d_vec_out)
         if (int r = rt_motion_vectors_device(c, w, h, d_nd, prev_view, prev_fov_dist, d_vec_out, nullptr)) return r;
     rt_motion_params p;
     if (params) p = *params;
     else rt_motion_default_params(&p);
-    Backend* b = rt_backend_dev0(c);
-    DeviceScope sc;
-    if (int r = sc.enter(c, b->device)) return r;
-    HIPCHK(c, hipStreamSynchronize(nullptr));
     const rtk::MotionArgs A{w, h, p.max_radius, 0.5f * p.shutter, p.depth_soft, (const float4_*)d_in, (const float4_*)d_nd,
                             (const rtk::MbVec*)d_motion};
     rtk::MotionVecArgs V;
     if (d_vec_out)
         if (int r = rt_motion_vec_args(c, w, h, d_nd, prev_view, prev_fov_dist, V)) return r;
-    float4_* tiles = (float4_*)b->motion_tiles.p;
-    Event e0, e1;
-    HIPCHK(c, hipEventCreate(&e0.h));
-    HIPCHK(c, hipEventCreate(&e1.h));
-    for (int r = 0; r < reps; r++) {
-        auto tm = [&]() -> int { return mb_launch_tilemax(c, A, tiles, nullptr); };
-        if (int e = rt_time_alone(c, e0, e1, tm, &out_ms[(size_t)2 * reps + r])) return e;
-        for (int i = 0; i < 2; i++) {
-            const int k = (r + first + i) & 1;
-            auto launch = [&]() -> int { return mb_launch_blur(c, A, k == 1, tiles, (float4_*)d_out, (float*)d_reach, nullptr); };
-            if (int e = rt_time_alone(c, e0, e1, launch, &out_ms[(size_t)k * reps + r])) return e;
-        }
-        out_ms[(size_t)3 * reps + r] = 0.0;
-        if (d_vec_out) {
-            auto mv = [&]() -> int { return mv_launch(c, V, (rtk::MbVec*)d_vec_out, nullptr); };
-            if (int e = rt_time_alone(c, e0, e1, mv, &out_ms[(size_t)3 * reps + r])) return e;
-        }
-    }
-    return RT_OK;
+    float4_* tiles = (float4_*)rt_backend_dev0(c)->motion_tiles.p;
+    auto blur = [&](bool lds) {
+        return [&, lds] { return mb_launch_blur(c, A, lds, tiles, (float4_*)d_out, (float*)d_reach, nullptr); };
+    };
+    return T.run(first, {TimedKernel::fixed(2, [&] { return mb_launch_tilemax(c, A, tiles, nullptr); }),
+                         TimedKernel::turns(0, blur(false)),
+                         TimedKernel::turns(1, blur(true)),
+                         d_vec_out ? TimedKernel::fixed(3, [&] { return mv_launch(c, V, (rtk::MbVec*)d_vec_out, nullptr); })
+                                   : TimedKernel::absent(3)});
 }

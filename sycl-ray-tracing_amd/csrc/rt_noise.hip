@@ -170,24 +170,18 @@ int rt_backend_progress_noise(rt_context* c, const rtk::NoiseArgs& A, int32_t* s
 extern "C" int rt_device_noise_kernel_ms(rt_context* c, int w, int h, const void* d_state, void* d_half, void* d_pixel,
                                          void* d_tile, void* d_stats, int reps, double* out_ms)
 {
-    if (!c || !c->backend || w <= 0 || h <= 0 || (double)w * (double)h > 134217727.0 || !d_state || !d_half || !d_pixel ||
-        !d_tile || !d_stats || reps <= 0 || !out_ms)
+    if (w <= 0 || h <= 0 || (double)w * (double)h > 134217727.0 || !d_state || !d_half || !d_pixel || !d_tile || !d_stats)
         return rt_fail(c, RT_ERR_ARG, "rt_device_noise_kernel_ms: bad arguments");
-    Backend* b = rt_backend_dev0(c);
-    DeviceScope sc;
-    if (int r = sc.enter(c, b->device)) return r;
-    Event e0, e1;
-    HIPCHK(c, hipEventCreate(&e0.h));
-    HIPCHK(c, hipEventCreate(&e1.h));
+    TimedRounds T;
+    if (int r = T.enter(c, "rt_device_noise_kernel_ms", reps, out_ms)) return r;
     const rtk::NoiseArgs A{4.0f, 2.0f, 1.0f, 0.05f, 2, 2, 2};
-    for (int r = 0; r < reps; r++)
-        for (int k = 0; k < 3; k++) {
-            auto launch = [&]() -> int {
-                if (k == 0) return launch_fold(c, (float4_*)d_half, (const float4_*)d_state, w * h, (r & 1) != 0, nullptr);
-                return launch_tiles(c, (const float4_*)d_state, (const float4_*)d_half, w, h, A,
-                                    k == 1 ? nullptr : (float*)d_pixel, (float*)d_tile, (uint32_t*)d_stats, nullptr);
-            };
-            if (int e = rt_time_alone(c, e0, e1, launch, &out_ms[(size_t)k * reps + r])) return e;
-        }
-    return RT_OK;
+    int folds = 0;  // (one a round: -state, then +state in the next)
+    auto tiles = [&](float* pixel) {
+        return [&, pixel] {
+            return launch_tiles(c, (const float4_*)d_state, (const float4_*)d_half, w, h, A, pixel, (float*)d_tile,
+                                (uint32_t*)d_stats, nullptr);
+        };
+    };
+    auto fold = [&] { return launch_fold(c, (float4_*)d_half, (const float4_*)d_state, w * h, (folds++ & 1) != 0, nullptr); };
+    return T.run(0, {TimedKernel::fixed(0, fold), TimedKernel::fixed(1, tiles(nullptr)), TimedKernel::fixed(2, tiles((float*)d_pixel))});
 }

@@ -229,7 +229,7 @@ int rt_backend_query(rt_context* c, bool any, bool all_exact, const void* rays, 
     } else {
         int32_t* count = (int32_t*)Q->list.p;
         int32_t* list = count + 16;
-        const bool refill = use_refill(c->sched.rq_variant);
+        const bool refill = use_refill(c->sched.variant[RT_VAR_RQ]);
         // whole waves of 16 queries; at most what is resident at once (the rest by stride)
         const unsigned resident = (unsigned)(Q->cus * Q->blocks[(any ? 2 : 0) + (refill ? 1 : 0)]);
         const unsigned fast_blocks = std::min((unsigned)((n + 63) / 64), resident);

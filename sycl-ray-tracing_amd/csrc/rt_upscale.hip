@@ -22,7 +22,7 @@
 //                     2^24 / 64 pixels, where fx is rounded) the first and the last pixel's x0 can lie
 //                     64 apart, so the block measures its footprint (up_footprint) and, when it does
 //                     not fit, reads from global memory like the direct kernel: a uniform branch.
-// Which kernel a call takes: up_use_lds.
+// Which kernel a call takes: rt_backend_upscale.
 #include <hip/hip_runtime.h>
 
 #include <string>
@@ -104,12 +104,6 @@ __global__ __launch_bounds__(256) void k_upscale_lds(rtk::UpArgs A, float4_* __r
     }
 }
 
-// Which kernel a call takes. up_variant (rt_test_schedule): 1 direct loads, 2 the LDS footprint, 0
-// the faster of the two as measured on the MI355X with a sigma map at 960x540 -> 1920x1080 and at
-// 1920x1080 -> 3840x2160 (the figures: profiles/upscale_bench.json): the footprint
-// wins at both sizes, by a tenth at the first and by a quarter at the second.
-bool up_use_lds(int variant) { return variant != 1; }
-
 void up_launch(const rtk::UpArgs& A, bool lds, float4_* d_out, float* d_sout, hipStream_t s)
 {
     const dim3 grid((A.w + UP_TW - 1) / UP_TW, (A.h + UP_TH - 1) / UP_TH);
@@ -136,7 +130,10 @@ int rt_backend_upscale(rt_context* c, rtk::UpArgs A, void* rgba_out, void* sigma
     float4_* d_out = (float4_*)st.out(rgba_out, b_hi);
     float* d_sout = (float*)st.out(sigma_out, n * sizeof(float));  // (null exactly when A.sigma_lo is)
     if (int r = st.begin()) return r;
-    up_launch(A, up_use_lds(c->sched.up_variant), d_out, d_sout, st.s);
+    // Which kernel the call takes (up_variant, rt_use_lds): the faster of the two as measured on the MI355X with a
+    // sigma map at 960x540 -> 1920x1080 and at 1920x1080 -> 3840x2160 (the figures: profiles/upscale_bench.json,
+    // DESIGN.md §18): the footprint wins at both sizes, by a tenth at the first and by a quarter at the second.
+    up_launch(A, rt_use_lds(c->sched.variant[RT_VAR_UP], true), d_out, d_sout, st.s);
     HIPCHK(c, hipGetLastError());
     return st.end();
 }
@@ -154,33 +151,25 @@ extern "C" int rt_device_upscale_kernel_ms(rt_context* c, int w_lo, int h_lo, in
                                            const void* d_alb_hi, const void* d_nd_hi, void* d_rgba_out, void* d_sigma_out,
                                            int reps, int first, double* out_ms)
 {
-    if (!c || !c->backend || reps <= 0 || !out_ms) return rt_fail(c, RT_ERR_ARG, "rt_device_upscale_kernel_ms: bad arguments");
+    TimedRounds T;
+    if (int r = T.enter(c, "rt_device_upscale_kernel_ms", reps, out_ms)) return r;
     // the product's validation and parameters: one product call, whose arguments the loop then reuses
     if (int r = rt_upscale_device(c, w_lo, h_lo, w, h, d_rgba_lo, d_sigma_lo, d_alb_lo, d_nd_lo, d_alb_hi, d_nd_hi, nullptr,
                                   d_rgba_out, d_sigma_out, nullptr))
         return r;
-    Backend* b = rt_backend_dev0(c);
-    DeviceScope sc;
-    if (int r = sc.enter(c, b->device)) return r;
-    HIPCHK(c, hipStreamSynchronize(nullptr));
     rt_upscale_params p;
     rt_upscale_default_params(&p);
     const rtk::UpArgs A{w_lo, h_lo, w, h, (float)w_lo / (float)w, (float)h_lo / (float)h, rtk::dn_inv_sigma2(p.sigma_normal),
                         rtk::dn_inv_sigma2(p.sigma_albedo), rtk::dn_inv_sigma2(p.sigma_depth), p.min_weight,
                         (const float4_*)d_rgba_lo, (const float*)d_sigma_lo, (const float4_*)d_alb_lo, (const float4_*)d_nd_lo,
                         (const float4_*)d_alb_hi, (const float4_*)d_nd_hi};
-    Event e0, e1;
-    HIPCHK(c, hipEventCreate(&e0.h));
-    HIPCHK(c, hipEventCreate(&e1.h));
-    for (int r = 0; r < reps; r++)
-        for (int i = 0; i < 2; i++) {
-            const int k = (r + first + i) & 1;  // (the order alternates round by round: neither kernel always runs second)
-            auto launch = [&]() -> int {
-                up_launch(A, k == 1, (float4_*)d_rgba_out, (float*)d_sigma_out, nullptr);
-                HIPCHK(c, hipGetLastError());
-                return RT_OK;
-            };
-            if (int e = rt_time_alone(c, e0, e1, launch, &out_ms[(size_t)k * reps + r])) return e;
-        }
-    return RT_OK;
+    auto kernel = [&](bool lds) {
+        return [&, lds]() -> int {
+            up_launch(A, lds, (float4_*)d_rgba_out, (float*)d_sigma_out, nullptr);
+            HIPCHK(c, hipGetLastError());
+            return RT_OK;
+        };
+    };
+    // (rotated: the order alternates round by round, neither kernel always runs second)
+    return T.run(first, {TimedKernel::turns(0, kernel(false)), TimedKernel::turns(1, kernel(true))});
 }

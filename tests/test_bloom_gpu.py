@@ -12,20 +12,14 @@ import pytest
 import bloom_cases as bc
 import meter_cases as mc
 import noise_cases as nc
-import progress_cases as pc
 import rt_amd
 from bloom_cases import bloom, inputs, params
-from test_dnv_gpu import _Stream
+from stage_gpu import Stream, both_chains, forced_variant, post_chain
 
 NAMES = ("rgba_out", "layer_out")
 # bc.SHAPES: (1, 1) every level one texel, one live thread; (5, 3) every tap clamped; (37, 29) odd at every level, a
 # partial reduce tile on both axes; (130, 67) partial 64 x 4 blocks at level 0 and partial 32 x 8 tiles at level 1
 # (65 x 34); (263, 41) five tiles across at level 1 (132 x 21). Levels 8 takes every shape down to 1 x 1.
-
-
-def _gpu_variant(v):
-    L, h = bc.ctx(False)
-    rt_amd.check(L, L.rt_test_schedule(h, b"bloom_variant", float(v)), h, "rt_test_schedule")
 
 
 @pytest.mark.gpu
@@ -34,11 +28,8 @@ def _gpu_variant(v):
 @pytest.mark.parametrize("w,h", bc.SHAPES)
 def test_gpu_kernels_equal_hostsim(w, h, levels, variant):
     want = bc.host_result(w, h, levels)
-    _gpu_variant(variant)
-    try:
+    with forced_variant(bc.ctx, "bloom_variant", variant):
         got = bloom(inputs(w, h), params(levels=levels), hostsim=False)
-    finally:
-        _gpu_variant(0)
     for g, x, name in zip(got, want, NAMES):
         nc.assert_bits(g, x, f"{w}x{h} levels {levels} variant {variant}: {name}")
 
@@ -46,7 +37,7 @@ def test_gpu_kernels_equal_hostsim(w, h, levels, variant):
 @pytest.mark.gpu
 def test_gpu_device_pointers_own_stream_and_scratch_reuse():
     L, ctx = bc.ctx(False)
-    st = _Stream()
+    st = Stream()
     try:
         for (w, h) in [(263, 41), (37, 29)]:  # larger, then smaller: the context's pyramid is reused
             rgba = inputs(w, h)
@@ -74,45 +65,23 @@ def _lum32(rgba):
         return (f(0.2126) * rgba[..., 0] + f(0.7152) * rgba[..., 1]) + f(0.0722) * rgba[..., 2]
 
 
+def _params(C, frame):
+    lum = _lum32(C.get(frame))
+    thr = C.values["threshold"] = float(np.float32(np.percentile(lum[np.isfinite(lum)], 90)))
+    return rt_amd.BloomParams(thr, 0.5 * thr, 0.2, 5)
+
+
 def _chain(hostsim: bool, stream):
     """Cornell 40x30: a tracked [2, 2] progression, the linear resolve, rt_bloom with the 90th percentile of the frame's
     own luminance as its threshold, the histogram of the bloomed frame, the solve at the defaults and rt_display with
     that exposure, device forms on one stream; (linear, threshold, bloomed, layer, histogram, exposure, 8-bit frame)."""
-    s = pc.session(hostsim, "cornell")
-    pc.begin(s, total=4)
-    nc.track(s)
-    pc.advance(s, 2)
-    pc.advance(s, 2)
-    W, H = pc.W, pc.H
-    vp = ctypes.c_void_p
-    q = vp(stream) if stream else None
-    lin, out, layer = (s.array(np.full((H, W, 4), -3.0, np.float32)) for _ in range(3))
-    hist = s.array(np.full(mc.WORDS, 0xDEADBEEF, np.uint32))
-    out8 = s.array(np.zeros((H, W, 4), np.uint8))
-    s.ok(s.L.rt_progress_resolve_linear_device(s.ctx, vp(lin.ptr), q), "rt_progress_resolve_linear_device")
-    frame = lin.get()  # (the download waits for the device)
-    lum = _lum32(frame)
-    thr = float(np.float32(np.percentile(lum[np.isfinite(lum)], 90)))
-    p = rt_amd.BloomParams(thr, 0.5 * thr, 0.2, 5)
-    s.ok(s.L.rt_bloom_device(s.ctx, W, H, vp(lin.ptr), ctypes.byref(p), vp(out.ptr), vp(layer.ptr), q), "rt_bloom_device")
-    s.ok(s.L.rt_meter_device(s.ctx, W, H, vp(out.ptr), vp(hist.ptr), q), "rt_meter_device")
-    words = hist.get()
-    r = rt_amd.meter_solve(words, hostsim=hostsim)
-    d = rt_amd.DisplayParams(r["exposure"], 2.2, 0)
-    s.ok(s.L.rt_display_device(s.ctx, W, H, vp(out.ptr), ctypes.byref(d), None, vp(out8.ptr), q), "rt_display_device")
-    got = (frame, thr, out.get(), layer.get(), words, r["exposure"], out8.get())
-    s.close()
-    return got
+    got = post_chain(hostsim, stream, bloom=_params)
+    return tuple(got[k] for k in ("linear", "threshold", "bloomed", "layer", "histogram", "exposure", "out8"))
 
 
 @pytest.mark.gpu
 def test_gpu_chain_with_the_bloom_stage_equals_hostsim():
-    want = _chain(True, None)
-    st = _Stream()
-    try:
-        got = _chain(False, st.ptr)
-    finally:
-        st.close()
+    want, got = both_chains(_chain)
     nc.assert_bits(got[0], want[0], "chain: linear frame")
     assert got[1] == want[1], "chain: the threshold"
     nc.assert_bits(got[2], want[2], "chain: bloomed frame")

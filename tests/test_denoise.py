@@ -18,6 +18,7 @@ import rt_amd
 import rt_cases
 import scenes
 from rt_amd import DenoiseParams, ptr
+from stage_gpu import forced_variant
 
 SIZES = [(1, 1), (5, 3), (37, 29), (130, 67)]
 HK = np.array([1 / 16, 1 / 4, 3 / 8, 1 / 4, 1 / 16])
@@ -306,19 +307,13 @@ def test_cli_writes_the_four_images(tmp_path, cameras):
 GPU_SIZES = SIZES + [(257, 9)]
 
 
-def _gpu_variant(v):
-    L, h = ctx(False)
-    rt_amd.check(L, L.rt_test_schedule(h, b"dn_variant", float(v)), h, "rt_test_schedule")
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("variant", [0, 1, 2])
 @pytest.mark.parametrize("guides", [True, False])
 @pytest.mark.parametrize("w,h", GPU_SIZES)
 def test_gpu_filter_equals_hostsim(w, h, guides, variant):
     rgba, alb, nd = synth(w, h)
-    _gpu_variant(variant)
-    try:
+    with forced_variant(ctx, "dn_variant", variant):
         for passes in (1, 2, 3, 4, 5):
             for blend in (0.0, 0.75, 1.0):
                 want = host_result(w, h, passes, guides, blend)
@@ -326,8 +321,6 @@ def test_gpu_filter_equals_hostsim(w, h, guides, variant):
                               hostsim=False)
                 np.testing.assert_array_equal(got.view(np.uint32), want.view(np.uint32),
                                               err_msg=f"passes {passes} blend {blend}")
-    finally:
-        _gpu_variant(0)
 
 
 @pytest.mark.gpu
@@ -336,11 +329,8 @@ def test_gpu_nan_guide_equals_hostsim(variant):
     rgba, alb, nd = synth(37, 29)
     nd[10, 12, 0] = np.nan
     want = denoise(rgba, alb, nd, params(3), 1.0)
-    _gpu_variant(variant)
-    try:
+    with forced_variant(ctx, "dn_variant", variant):
         got = denoise(rgba, alb, nd, params(3), 1.0, hostsim=False)
-    finally:
-        _gpu_variant(0)
     np.testing.assert_array_equal(got.view(np.uint32), want.view(np.uint32))
 
 

@@ -11,19 +11,14 @@ import pytest
 
 import dnv_cases as dv
 import noise_cases as nc
-import progress_cases as pc
 import rt_amd
 from dnv_cases import denoise_var, inputs, params
+from stage_gpu import Stream, both_chains, forced_variant, post_chain
 
 # (w, h, passes): one live thread; every tap row, column and the 3x3 clipped; partial tiles on both axes at steps
 # 1, 2 and 4 (every k_dnv_lds instantiation under dn_variant 2, the 32x8 one included); more than two tiles across
 # and steps 8 and 16 on the direct kernel. Every shape carries sigma_map()'s NaN and +inf entries.
 SHAPES = [(1, 1, 3), (5, 3, 3), (37, 29, 3), (130, 67, 5)]
-
-
-def _gpu_variant(v):
-    L, h = dv.ctx(False)
-    rt_amd.check(L, L.rt_test_schedule(h, b"dn_variant", float(v)), h, "rt_test_schedule")
 
 
 @pytest.mark.gpu
@@ -33,51 +28,16 @@ def _gpu_variant(v):
 def test_gpu_filter_equals_hostsim(w, h, passes, guides, variant):
     rgba, sigma, alb, nd = inputs(w, h)
     want = dv.host_result(w, h, passes, guides, 0.75)
-    _gpu_variant(variant)
-    try:
+    with forced_variant(dv.ctx, "dn_variant", variant):
         got = denoise_var(rgba, sigma, alb if guides else None, nd if guides else None, params(passes), 0.75, hostsim=False)
-    finally:
-        _gpu_variant(0)
     nc.assert_bits(got[0], want[0], f"{w}x{h} passes {passes} guides {guides} variant {variant}: colour")
     nc.assert_bits(got[1], want[1], f"{w}x{h} passes {passes} guides {guides} variant {variant}: sigma_out")
-
-
-class _Stream:
-    """A non-blocking HIP stream and buffers that wait for it alone."""
-
-    def __init__(self):
-        from hip_mem import hip
-        self.hip = hip()
-        self.hip.hipStreamCreateWithFlags.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint]
-        self.hip.hipStreamSynchronize.argtypes = [ctypes.c_void_p]
-        self.hip.hipStreamDestroy.argtypes = [ctypes.c_void_p]
-        s = ctypes.c_void_p()
-        assert self.hip.hipStreamCreateWithFlags(ctypes.byref(s), 1) == 0  # hipStreamNonBlocking
-        self.ptr = s.value
-
-    def upload(self, a):
-        from hip_mem import DeviceBuffer
-        a = np.ascontiguousarray(a)
-        b = DeviceBuffer(a.nbytes)
-        b.upload(a)  # (a blocking copy: done when it returns)
-        return b
-
-    def download(self, b, shape, dtype=np.float32):
-        out = np.empty(shape, dtype)
-        assert self.hip.hipStreamSynchronize(self.ptr) == 0
-        assert self.hip.hipMemcpy(out.ctypes.data, b.ptr, out.nbytes, 2) == 0
-        return out
-
-    def close(self):
-        if self.ptr:
-            self.hip.hipStreamDestroy(self.ptr)
-            self.ptr = None
 
 
 @pytest.mark.gpu
 def test_gpu_device_pointers_own_stream_and_scratch_reuse():
     L, h = dv.ctx(False)
-    st = _Stream()
+    st = Stream()
     try:
         for (w, hh) in [(130, 67), (37, 29)]:  # larger, then smaller: the context's scratch is reused
             rgba, sigma, alb, nd = inputs(w, hh)
@@ -95,37 +55,21 @@ def test_gpu_device_pointers_own_stream_and_scratch_reuse():
         st.close()
 
 
+def _filter(C, frame):
+    C.call("rt_denoise_var_device", C.w, C.h, C.p(frame), C.p("sigma"), C.p("albedo"), C.p("normal_depth"), None, ctypes.c_float(1.0),
+           C.f4("filtered"), C.f1("sigma_out"))
+
+
 def _chain(hostsim: bool, stream):
     """Cornell 40x30: a tracked [2, 2] progression, then the linear resolve, the noise figure, the feature pass
     and the filter, device forms on one stream; (linear, sigma, rgba_out, sigma_out)."""
-    s = pc.session(hostsim, "cornell")
-    pc.begin(s, total=4)
-    nc.track(s)
-    pc.advance(s, 2)
-    pc.advance(s, 2)
-    W, H = pc.W, pc.H
-    vp = ctypes.c_void_p
-    q = vp(stream) if stream else None
-    bufs = [s.array(np.full(shape, -3.0, np.float32)) for shape in ((H, W, 4), (H, W), (H, W, 4), (H, W, 4), (H, W, 4), (H, W))]
-    lin, sg, alb, nd, out, left = bufs
-    s.ok(s.L.rt_progress_resolve_linear_device(s.ctx, vp(lin.ptr), q), "rt_progress_resolve_linear_device")
-    s.ok(s.L.rt_progress_noise_sigma_device(s.ctx, vp(sg.ptr), q), "rt_progress_noise_sigma_device")
-    s.ok(s.L.rt_render_features_device(s.ctx, W, H, vp(alb.ptr), vp(nd.ptr), q), "rt_render_features_device")
-    s.ok(s.L.rt_denoise_var_device(s.ctx, W, H, vp(lin.ptr), vp(sg.ptr), vp(alb.ptr), vp(nd.ptr), None, ctypes.c_float(1.0),
-                                   vp(out.ptr), vp(left.ptr), q), "rt_denoise_var_device")
-    got = tuple(b.get() for b in (lin, sg, out, left))  # (the download waits for the device)
-    s.close()
-    return got
+    got = post_chain(hostsim, stream, [_filter], sigma=True, features=True, display=False)
+    return tuple(got[k] for k in ("linear", "sigma", "filtered", "sigma_out"))
 
 
 @pytest.mark.gpu
 def test_gpu_progression_sigma_features_filter_chain_equals_hostsim():
-    want = _chain(True, None)
-    st = _Stream()
-    try:
-        got = _chain(False, st.ptr)
-    finally:
-        st.close()
+    want, got = both_chains(_chain)
     assert np.isfinite(want[1]).all() and (want[1] > 0).any()
     for name, g, w in zip(("linear frame", "sigma", "filtered", "sigma_out"), got, want):
         nc.assert_bits(g, w, f"chain: {name}")

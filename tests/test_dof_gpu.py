@@ -12,20 +12,14 @@ import pytest
 import dof_cases as dc
 import meter_cases as mc
 import noise_cases as nc
-import progress_cases as pc
 import rt_amd
 from dof_cases import dof, inputs, params
-from test_dnv_gpu import _Stream
+from stage_gpu import Stream, both_chains, forced_variant, post_chain
 
 NAMES = ("rgba_out", "coc_out")
 # dc.SHAPES: (1, 1) one live thread, every other entry of the footprint outside the image; (5, 3) the window larger than
 # the image; (37, 29) two 32 x 16 tiles each way, partial on both axes; (130, 67) five tiles across, partial 64 x 4 blocks
 # of the direct kernel; (70, 45) three tiles each way. dc.RADII: the footprint is 34 x 18, 40 x 24 and 56 x 40 entries.
-
-
-def _gpu_variant(v):
-    L, h = dc.ctx(False)
-    rt_amd.check(L, L.rt_test_schedule(h, b"dof_variant", float(v)), h, "rt_test_schedule")
 
 
 @pytest.mark.gpu
@@ -34,11 +28,8 @@ def _gpu_variant(v):
 @pytest.mark.parametrize("w,h", dc.SHAPES)
 def test_gpu_kernels_equal_hostsim(w, h, max_radius, variant):
     want = dc.host_result(w, h, max_radius)
-    _gpu_variant(variant)
-    try:
+    with forced_variant(dc.ctx, "dof_variant", variant):
         got = dof(*inputs(w, h), params(max_radius=max_radius), hostsim=False)
-    finally:
-        _gpu_variant(0)
     for g, x, name in zip(got, want, NAMES):
         nc.assert_bits(g, x, f"{w}x{h} max_radius {max_radius} variant {variant}: {name}")
 
@@ -52,11 +43,8 @@ def test_gpu_blur_reaches_into_a_tile_that_is_in_focus(variant):
     assert np.all(want[1][16:32, 32:64] == 0.0) and np.all(want[1][:16] == 12.0)
     inner = want[0][16:32, 32:64, :3]
     assert not np.array_equal(inner, rgba[16:32, 32:64, :3]), "the blur reaches into the in-focus tile"
-    _gpu_variant(variant)
-    try:
+    with forced_variant(dc.ctx, "dof_variant", variant):
         got = dof(rgba, nd, p, hostsim=False)
-    finally:
-        _gpu_variant(0)
     for g, x, name in zip(got, want, NAMES):
         nc.assert_bits(g, x, f"in-focus tile, variant {variant}: {name}")
 
@@ -64,7 +52,7 @@ def test_gpu_blur_reaches_into_a_tile_that_is_in_focus(variant):
 @pytest.mark.gpu
 def test_gpu_device_pointers_own_stream():
     L, ctx = dc.ctx(False)
-    st = _Stream()
+    st = Stream()
     try:
         for (w, h) in [(130, 67), (37, 29)]:  # larger, then smaller
             rgba, nd = inputs(w, h)
@@ -87,47 +75,25 @@ def test_gpu_device_pointers_own_stream():
         st.close()
 
 
+def _lens(C, frame):
+    C.values["focus"] = rt_amd.focus_at(C.get("normal_depth"), C.w // 2, C.h // 2)
+    p = rt_amd.DofParams(C.values["focus"], 6.0, 8)
+    C.call("rt_dof_device", C.w, C.h, C.p(frame), C.p("normal_depth"), ctypes.byref(p), C.f4("blurred"), C.f1("coc"))
+    return "blurred"
+
+
 def _chain(hostsim: bool, stream):
     """Cornell 40x30: a tracked [2, 2] progression, the linear resolve, rt_render_features, rt_dof focused by
     rt_amd.focus_at at the centre pixel, rt_bloom, the histogram of the bloomed frame, the solve at the defaults and
     rt_display with that exposure, device forms on one stream; every buffer on the way."""
-    s = pc.session(hostsim, "cornell")
-    pc.begin(s, total=4)
-    nc.track(s)
-    pc.advance(s, 2)
-    pc.advance(s, 2)
-    W, H = pc.W, pc.H
-    vp = ctypes.c_void_p
-    q = vp(stream) if stream else None
-    lin, alb, nd, blur, out, layer = (s.array(np.full((H, W, 4), -3.0, np.float32)) for _ in range(6))
-    coc = s.array(np.full((H, W), -3.0, np.float32))
-    hist = s.array(np.full(mc.WORDS, 0xDEADBEEF, np.uint32))
-    out8 = s.array(np.zeros((H, W, 4), np.uint8))
-    s.ok(s.L.rt_progress_resolve_linear_device(s.ctx, vp(lin.ptr), q), "rt_progress_resolve_linear_device")
-    s.ok(s.L.rt_render_features_device(s.ctx, W, H, vp(alb.ptr), vp(nd.ptr), q), "rt_render_features_device")
-    guide = nd.get()  # (the download waits for the device)
-    focus = rt_amd.focus_at(guide, W // 2, H // 2)
-    p = rt_amd.DofParams(focus, 6.0, 8)
-    s.ok(s.L.rt_dof_device(s.ctx, W, H, vp(lin.ptr), vp(nd.ptr), ctypes.byref(p), vp(blur.ptr), vp(coc.ptr), q), "rt_dof_device")
-    s.ok(s.L.rt_bloom_device(s.ctx, W, H, vp(blur.ptr), None, vp(out.ptr), vp(layer.ptr), q), "rt_bloom_device")
-    s.ok(s.L.rt_meter_device(s.ctx, W, H, vp(out.ptr), vp(hist.ptr), q), "rt_meter_device")
-    words = hist.get()
-    r = rt_amd.meter_solve(words, hostsim=hostsim)
-    d = rt_amd.DisplayParams(r["exposure"], 2.2, 0)
-    s.ok(s.L.rt_display_device(s.ctx, W, H, vp(out.ptr), ctypes.byref(d), None, vp(out8.ptr), q), "rt_display_device")
-    got = (lin.get(), guide, focus, blur.get(), coc.get(), out.get(), layer.get(), words, r["exposure"], out8.get())
-    s.close()
-    return got
+    got = post_chain(hostsim, stream, [_lens], features=True, bloom=True)
+    return tuple(got[k] for k in ("linear", "normal_depth", "focus", "blurred", "coc", "bloomed", "layer", "histogram", "exposure",
+                                  "out8"))
 
 
 @pytest.mark.gpu
 def test_gpu_chain_with_the_dof_stage_equals_hostsim():
-    want = _chain(True, None)
-    st = _Stream()
-    try:
-        got = _chain(False, st.ptr)
-    finally:
-        st.close()
+    want, got = both_chains(_chain)
     nc.assert_bits(got[0], want[0], "chain: linear frame")
     nc.assert_bits(got[1], want[1], "chain: normal_depth")
     assert got[2] == want[2], "chain: the focus"
@@ -138,5 +104,5 @@ def test_gpu_chain_with_the_dof_stage_equals_hostsim():
     mc.assert_words(got[7], want[7], "chain: histogram")
     assert got[8] == want[8], "chain: exposure"
     assert np.array_equal(got[9], want[9]), "chain: the 8-bit frame"
-    assert want[4][pc.H // 2, pc.W // 2] == 0.0 and want[4].max() > 1.0, "the centre is in focus, something is not"
+    assert want[4][want[4].shape[0] // 2, want[4].shape[1] // 2] == 0.0 and want[4].max() > 1.0, "the centre is in focus, something is not"
     assert not np.array_equal(want[3], want[0]), "the lens changed the frame"

@@ -11,21 +11,15 @@ import pytest
 
 import firefly_cases as fc
 import noise_cases as nc
-import progress_cases as pc
 import rt_amd
 import session_cases as sc
 from firefly_cases import clamp, inputs, params
-from test_dnv_gpu import _Stream
+from stage_gpu import Stream, both_chains, forced_variant, post_chain
 
 NAMES = ("colour", "sigma_out", "scale_out")
 GAIN, FLOOR = 1.0, 0.01  # (gain 1 clamps a third of the noisy frame: the scaling path runs in every wave)
 # fc.SHAPES: (1, 1) one live thread, no neighbour; (5, 3) every neighbourhood clipped; (37, 29) partial blocks on both
 # axes; (130, 67) more than two blocks across. At radius 2 the 288 halo entries take the fill loop's second round.
-
-
-def _gpu_variant(v):
-    L, h = fc.ctx(False)
-    rt_amd.check(L, L.rt_test_schedule(h, b"ff_variant", float(v)), h, "rt_test_schedule")
 
 
 @pytest.mark.gpu
@@ -35,11 +29,8 @@ def _gpu_variant(v):
 @pytest.mark.parametrize("w,h", fc.SHAPES)
 def test_gpu_kernel_equals_hostsim(w, h, radius, rank, variant):
     want = fc.host_result(w, h, radius, rank, GAIN, FLOOR)
-    _gpu_variant(variant)
-    try:
+    with forced_variant(fc.ctx, "ff_variant", variant):
         got = clamp(*inputs(w, h), params(radius, rank, GAIN, FLOOR), hostsim=False)
-    finally:
-        _gpu_variant(0)
     for g, x, name in zip(got, want, NAMES):
         nc.assert_bits(g, x, f"{w}x{h} radius {radius} rank {rank} variant {variant}: {name}")
 
@@ -47,7 +38,7 @@ def test_gpu_kernel_equals_hostsim(w, h, radius, rank, variant):
 @pytest.mark.gpu
 def test_gpu_device_pointers_own_stream_and_scratch_reuse():
     L, ctx = fc.ctx(False)
-    st = _Stream()
+    st = Stream()
     try:
         for (w, h) in [(130, 67), (37, 29)]:  # larger, then smaller: the context's scratch is reused
             rgba, sigma = inputs(w, h)
@@ -67,46 +58,40 @@ def test_gpu_device_pointers_own_stream_and_scratch_reuse():
         st.close()
 
 
+def _clamp(C, frame):
+    C.call("rt_firefly_device", C.w, C.h, C.p(frame), C.p("sigma"), None, C.f4("clamped"), C.f1("clamped sigma"), C.f1("scale"))
+    return "clamped"
+
+
+def _features(C, frame):
+    C.call("rt_render_features_device", C.w, C.h, C.f4("albedo"), C.f4("normal_depth"))
+
+
+def _accumulate(C, frame):
+    cam = sc.camera_of("cornell")  # (the session's camera: with no history only its validity counts)
+    view = np.ascontiguousarray(cam[:16])
+    C.call("rt_temporal_accumulate_device", C.w, C.h, C.p(frame), C.p("clamped sigma"), C.p("normal_depth"), rt_amd.ptr(view),
+           ctypes.c_float(float(cam[16])), None, None, None, None, None, C.f4("accumulated"), C.f1("accumulated sigma"),
+           C.f1("length"))
+    return "accumulated"
+
+
+def _filter(C, frame):
+    C.call("rt_denoise_var_device", C.w, C.h, C.p(frame), C.p("accumulated sigma"), C.p("albedo"), C.p("normal_depth"), None,
+           ctypes.c_float(1.0), C.f4("filtered"), C.f1("sigma_out"))
+
+
 def _chain(hostsim: bool, stream):
     """Cornell 40x30: a tracked [2, 2] progression, then the linear resolve, the noise figure, the firefly stage at its
     defaults, the feature pass, temporal accumulation without a history and the variance-guided filter, device forms
     on one stream; (linear, sigma, clamped, clamped sigma, scale, accumulated, filtered)."""
-    s = pc.session(hostsim, "cornell")
-    pc.begin(s, total=4)
-    nc.track(s)
-    pc.advance(s, 2)
-    pc.advance(s, 2)
-    W, H = pc.W, pc.H
-    vp = ctypes.c_void_p
-    q = vp(stream) if stream else None
-    c4, c1 = (H, W, 4), (H, W)
-    bufs = [s.array(np.full(shape, -3.0, np.float32)) for shape in (c4, c1, c4, c1, c1, c4, c4, c4, c1, c1, c4, c1)]
-    lin, sg, ff, ff_s, ff_f, alb, nd, acc, acc_s, acc_l, out, left = bufs
-    s.ok(s.L.rt_progress_resolve_linear_device(s.ctx, vp(lin.ptr), q), "rt_progress_resolve_linear_device")
-    s.ok(s.L.rt_progress_noise_sigma_device(s.ctx, vp(sg.ptr), q), "rt_progress_noise_sigma_device")
-    s.ok(s.L.rt_firefly_device(s.ctx, W, H, vp(lin.ptr), vp(sg.ptr), None, vp(ff.ptr), vp(ff_s.ptr), vp(ff_f.ptr), q),
-         "rt_firefly_device")
-    s.ok(s.L.rt_render_features_device(s.ctx, W, H, vp(alb.ptr), vp(nd.ptr), q), "rt_render_features_device")
-    cam = sc.camera_of("cornell")  # (the session's camera: with no history only its validity counts)
-    view = np.ascontiguousarray(cam[:16])
-    s.ok(s.L.rt_temporal_accumulate_device(s.ctx, W, H, vp(ff.ptr), vp(ff_s.ptr), vp(nd.ptr), rt_amd.ptr(view),
-                                           ctypes.c_float(float(cam[16])), None, None, None, None, None, vp(acc.ptr),
-                                           vp(acc_s.ptr), vp(acc_l.ptr), q), "rt_temporal_accumulate_device")
-    s.ok(s.L.rt_denoise_var_device(s.ctx, W, H, vp(acc.ptr), vp(acc_s.ptr), vp(alb.ptr), vp(nd.ptr), None, ctypes.c_float(1.0),
-                                   vp(out.ptr), vp(left.ptr), q), "rt_denoise_var_device")
-    got = tuple(b.get() for b in (lin, sg, ff, ff_s, ff_f, acc, out))  # (the download waits for the device)
-    s.close()
-    return got
+    got = post_chain(hostsim, stream, [_clamp, _features, _accumulate, _filter], sigma=True, display=False)
+    return tuple(got[k] for k in ("linear", "sigma", "clamped", "clamped sigma", "scale", "accumulated", "filtered"))
 
 
 @pytest.mark.gpu
 def test_gpu_chain_with_the_firefly_stage_equals_hostsim():
-    want = _chain(True, None)
-    st = _Stream()
-    try:
-        got = _chain(False, st.ptr)
-    finally:
-        st.close()
+    want, got = both_chains(_chain)
     assert (want[4] < 1).any() and (want[4] == 1).any(), "the frame has clamped and untouched pixels"
     for name, g, w in zip(("linear frame", "sigma", "clamped", "clamped sigma", "scale", "accumulated", "filtered"), got, want):
         nc.assert_bits(g, w, f"chain: {name}")

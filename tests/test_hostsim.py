@@ -245,3 +245,22 @@ def test_fast_walk_settles_same_leaf_ties_like_the_octree_walk(fixture):
     hit = ok & (ex[:, 0] == 1)
     np.testing.assert_array_equal(k[hit], ex[hit, 1])
     assert ok.mean() > 0.95, f"{(~ok).sum()} of {n} left to the exact walk"
+
+
+def test_schedule_variant_keys_clamp_and_reset():
+    """Every forced-kernel key of rt_test_schedule (rt_context.h rt_variant_keys) takes a value inside and outside
+    0..2, clamped; reset follows; an unknown key is refused."""
+    import ctypes
+
+    import rt_amd
+    L = rt_amd.lib(True)
+    h = ctypes.c_void_p()
+    assert L.rt_create(0, ctypes.byref(h)) == 0
+    keys = ("dn", "ff", "mt", "up", "bloom", "dof", "motion", "rq", "gb")
+    for k in keys:
+        for v in (0.0, 1.0, 2.0, -5.0, 9.0):
+            assert L.rt_test_schedule(h, f"{k}_variant".encode(), v) == 0, (k, v, L.rt_last_error(h))
+        assert L.rt_test_schedule(h, b"reset", 0.0) == 0
+    assert L.rt_test_schedule(h, b"dofs_variant", 1.0) != 0 and b"unknown key" in L.rt_last_error(h)
+    assert L.rt_test_schedule(h, b"dof_variant", float("nan")) != 0
+    L.rt_destroy(h)

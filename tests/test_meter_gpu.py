@@ -4,27 +4,18 @@ product's dispatch, forced block counts, the device form on a stream of its own,
 progression up to the displayed 8-bit frame."""
 from __future__ import annotations
 
-import ctypes
-
 import numpy as np
 import pytest
 
 import meter_cases as mc
 import noise_cases as nc
-import progress_cases as pc
 import rt_amd
 from meter_cases import frame, meter
-from test_dnv_gpu import _Stream
+from stage_gpu import Stream, both_chains, forced_variant, post_chain
 
 u32 = np.uint32
 # mc.SHAPES: (1, 1) one live thread; (5, 3) part of a wave; (37, 29) and (130, 67) several blocks, the last one
 # partial, so its waves ballot with idle lanes; (64, 4) one block exactly; (257, 1) a block and one pixel.
-
-
-def _schedule(**kw):
-    L, h = mc.ctx(False)
-    for k, v in kw.items():
-        rt_amd.check(L, L.rt_test_schedule(h, k.encode(), float(v)), h, "rt_test_schedule")
 
 
 @pytest.mark.gpu
@@ -33,11 +24,8 @@ def _schedule(**kw):
 @pytest.mark.parametrize("w,h", mc.SHAPES)
 def test_gpu_kernel_equals_hostsim(w, h, kind, variant):
     want = mc.host_result(kind, w, h)
-    _schedule(mt_variant=variant)
-    try:
+    with forced_variant(mc.ctx, "mt_variant", variant):
         got = meter(frame(kind, w, h), hostsim=False)
-    finally:
-        _schedule(mt_variant=0)
     mc.assert_words(got, want, f"{kind} {w}x{h} variant {variant}")
 
 
@@ -50,11 +38,8 @@ def test_gpu_forced_block_counts(w, h, kind, blocks, variant):
     """One block walks the frame in 35 (5) grid-stride rounds; three blocks do not divide the 35 (5) rounds evenly,
     and the last round has idle threads."""
     want = mc.host_result(kind, w, h)
-    _schedule(mt_variant=variant, mt_blocks=blocks)
-    try:
+    with forced_variant(mc.ctx, "mt_variant", variant, mt_blocks=blocks):
         got = meter(frame(kind, w, h), hostsim=False)
-    finally:
-        _schedule(mt_variant=0, mt_blocks=0)
     mc.assert_words(got, want, f"{kind} {w}x{h} variant {variant} blocks {blocks}")
 
 
@@ -62,11 +47,8 @@ def test_gpu_forced_block_counts(w, h, kind, blocks, variant):
 @pytest.mark.parametrize("variant", [1, 2])
 def test_gpu_constant_frame_counts_every_lane(variant):
     """Every lane of every wave hits one bin: the count must be exactly 130 * 67 = 8710."""
-    _schedule(mt_variant=variant)
-    try:
+    with forced_variant(mc.ctx, "mt_variant", variant):
         got = meter(frame("constant", 130, 67), hostsim=False)
-    finally:
-        _schedule(mt_variant=0)
     assert int(got[:256].max()) == 8710 and int(got[:256].sum()) == 8710 and int(got[mc.COUNTED]) == 8710
     mc.assert_words(got, mc.host_result("constant", 130, 67), f"constant 130x67 variant {variant}")
 
@@ -74,7 +56,7 @@ def test_gpu_constant_frame_counts_every_lane(variant):
 @pytest.mark.gpu
 def test_gpu_device_pointers_own_stream_no_carry_over():
     L, ctx = mc.ctx(False)
-    st = _Stream()
+    st = Stream()
     try:
         d_hist = st.upload(np.full(mc.WORDS, 0xDEADBEEF, u32))  # (garbage: the call clears it)
         # larger, then smaller: the staging of the host form is reused; the same d_hist twice in a row
@@ -93,36 +75,13 @@ def test_gpu_device_pointers_own_stream_no_carry_over():
 def _chain(hostsim: bool, stream):
     """Cornell 40x30: a tracked [2, 2] progression, the linear resolve, the histogram, the solve at the defaults and
     rt_display with that exposure, device forms on one stream; (linear, histogram, exposure, 8-bit frame)."""
-    s = pc.session(hostsim, "cornell")
-    pc.begin(s, total=4)
-    nc.track(s)
-    pc.advance(s, 2)
-    pc.advance(s, 2)
-    W, H = pc.W, pc.H
-    vp = ctypes.c_void_p
-    q = vp(stream) if stream else None
-    lin = s.array(np.full((H, W, 4), -3.0, np.float32))
-    hist = s.array(np.full(mc.WORDS, 0xDEADBEEF, u32))
-    out8 = s.array(np.zeros((H, W, 4), np.uint8))
-    s.ok(s.L.rt_progress_resolve_linear_device(s.ctx, vp(lin.ptr), q), "rt_progress_resolve_linear_device")
-    s.ok(s.L.rt_meter_device(s.ctx, W, H, vp(lin.ptr), vp(hist.ptr), q), "rt_meter_device")
-    words = hist.get()  # (the download waits for the device)
-    r = rt_amd.meter_solve(words, hostsim=hostsim)
-    p = rt_amd.DisplayParams(r["exposure"], 2.2, 0)
-    s.ok(s.L.rt_display_device(s.ctx, W, H, vp(lin.ptr), ctypes.byref(p), None, vp(out8.ptr), q), "rt_display_device")
-    got =(lin.get(), words, r["exposure"], out8.get())
-    s.close()
-    return got
+    got = post_chain(hostsim, stream)
+    return tuple(got[k] for k in ("linear", "histogram", "exposure", "out8"))
 
 
 @pytest.mark.gpu
 def test_gpu_chain_to_the_displayed_frame_equals_hostsim():
-    want = _chain(True, None)
-    st = _Stream()
-    try:
-        got = _chain(False, st.ptr)
-    finally:
-        st.close()
+    want, got = both_chains(_chain)
     nc.assert_bits(got[0], want[0], "chain: linear frame")
     mc.assert_words(got[1], want[1], "chain: histogram")
     assert got[2] == want[2] and want[2] != 1.5, "chain: exposure"

@@ -13,11 +13,10 @@ import pytest
 import meter_cases as mc_meter
 import motion_cases as mc
 import noise_cases as nc
-import progress_cases as pc
 import rt_amd
 import temporal_cases as tc
 from motion_cases import blur, field, inputs, params
-from test_dnv_gpu import _Stream
+from stage_gpu import Stream, both_chains, forced_variant, post_chain
 
 NAMES = ("rgba_out", "reach_out")
 # mc.SHAPES: (1, 1) one live thread and an empty footprint; (5, 3) the streak longer than the image, negative offsets at
@@ -26,17 +25,9 @@ NAMES = ("rgba_out", "reach_out")
 # along an axis, 40 x 38 near the diagonal.
 
 
-def _gpu_variant(v):
-    L, h = mc.ctx(False)
-    rt_amd.check(L, L.rt_test_schedule(h, b"motion_variant", float(v)), h, "rt_test_schedule")
-
-
 def _gpu_blur(variant, *args):
-    _gpu_variant(variant)
-    try:
+    with forced_variant(mc.ctx, "motion_variant", variant):
         return blur(*args, hostsim=False)
-    finally:
-        _gpu_variant(0)
 
 
 @pytest.mark.gpu
@@ -79,7 +70,7 @@ def test_gpu_vectors_equal_hostsim(w, h, kind):
 def test_gpu_device_pointers_own_stream():
     cur, prev = tc.cameras("turn", 130, 67)
     L, ctx = tc.ctx(False, cur)
-    st = _Stream()
+    st = Stream()
     try:
         for (w, h) in [(130, 67), (37, 29)]:  # larger, then smaller
             rgba, nd = inputs(w, h)
@@ -115,54 +106,38 @@ def test_gpu_device_pointers_own_stream():
         st.close()
 
 
+def _vectors(C, frame):
+    prev = tc.moved_camera(3, step=0.15)
+    C.call("rt_motion_vectors_device", C.w, C.h, C.p("normal_depth"), rt_amd.ptr(prev.view_matrix), ctypes.c_float(prev.fov_dist),
+           C.new("motion", (C.h, C.w, 2)))
+
+
+def _lens(C, frame):
+    dp = rt_amd.DofParams(rt_amd.focus_at(C.get("normal_depth"), C.w // 2, C.h // 2), 6.0, 8)
+    C.call("rt_dof_device", C.w, C.h, C.p(frame), C.p("normal_depth"), ctypes.byref(dp), C.f4("lens"), None)
+    return "lens"
+
+
+def _shutter(C, frame):
+    mp = rt_amd.MotionParams(1.0, 0.05, 8)
+    C.call("rt_motion_blur_device", C.w, C.h, C.p(frame), C.p("normal_depth"), C.p("motion"), ctypes.byref(mp), C.f4("shutter"),
+           C.f1("reach"))
+    return "shutter"
+
+
 def _chain(hostsim: bool, stream):
     """Cornell 40x30 under the Cornell camera, the previous frame's camera that preset moved three steps
     (temporal_cases.moved_camera): a tracked [2, 2] progression, the linear resolve, rt_render_features, rt_motion_vectors,
     rt_dof focused by rt_amd.focus_at at the centre pixel, rt_motion_blur, rt_bloom, the histogram of the bloomed frame,
     the solve at the defaults and rt_display with that exposure, device forms on one stream; every buffer on the way."""
-    s = pc.session(hostsim, "cornell")
-    pc.begin(s, total=4)
-    nc.track(s)
-    pc.advance(s, 2)
-    pc.advance(s, 2)
-    W, H = pc.W, pc.H
-    vp = ctypes.c_void_p
-    q = vp(stream) if stream else None
-    prev = tc.moved_camera(3, step=0.15)
-    lin, alb, nd, lens, shut, out, layer = (s.array(np.full((H, W, 4), -3.0, np.float32)) for _ in range(7))
-    mv = s.array(np.full((H, W, 2), -3.0, np.float32))
-    reach = s.array(np.full((H, W), -3.0, np.float32))
-    hist = s.array(np.full(mc_meter.WORDS, 0xDEADBEEF, np.uint32))
-    out8 = s.array(np.zeros((H, W, 4), np.uint8))
-    s.ok(s.L.rt_progress_resolve_linear_device(s.ctx, vp(lin.ptr), q), "rt_progress_resolve_linear_device")
-    s.ok(s.L.rt_render_features_device(s.ctx, W, H, vp(alb.ptr), vp(nd.ptr), q), "rt_render_features_device")
-    s.ok(s.L.rt_motion_vectors_device(s.ctx, W, H, vp(nd.ptr), rt_amd.ptr(prev.view_matrix), ctypes.c_float(prev.fov_dist), vp(mv.ptr),
-                                      q), "rt_motion_vectors_device")
-    guide = nd.get()  # (the download waits for the device)
-    dp = rt_amd.DofParams(rt_amd.focus_at(guide, W // 2, H // 2), 6.0, 8)
-    s.ok(s.L.rt_dof_device(s.ctx, W, H, vp(lin.ptr), vp(nd.ptr), ctypes.byref(dp), vp(lens.ptr), None, q), "rt_dof_device")
-    mp = rt_amd.MotionParams(1.0, 0.05, 8)
-    s.ok(s.L.rt_motion_blur_device(s.ctx, W, H, vp(lens.ptr), vp(nd.ptr), vp(mv.ptr), ctypes.byref(mp), vp(shut.ptr), vp(reach.ptr), q),
-         "rt_motion_blur_device")
-    s.ok(s.L.rt_bloom_device(s.ctx, W, H, vp(shut.ptr), None, vp(out.ptr), vp(layer.ptr), q), "rt_bloom_device")
-    s.ok(s.L.rt_meter_device(s.ctx, W, H, vp(out.ptr), vp(hist.ptr), q), "rt_meter_device")
-    words = hist.get()
-    r = rt_amd.meter_solve(words, hostsim=hostsim)
-    d = rt_amd.DisplayParams(r["exposure"], 2.2, 0)
-    s.ok(s.L.rt_display_device(s.ctx, W, H, vp(out.ptr), ctypes.byref(d), None, vp(out8.ptr), q), "rt_display_device")
-    got = (lin.get(), guide, mv.get(), lens.get(), shut.get(), reach.get(), out.get(), words, r["exposure"], out8.get())
-    s.close()
-    return got
+    got = post_chain(hostsim, stream, [_vectors, _lens, _shutter], features=True, bloom=True)
+    return tuple(got[k] for k in ("linear", "normal_depth", "motion", "lens", "shutter", "reach", "bloomed", "histogram", "exposure",
+                                  "out8"))
 
 
 @pytest.mark.gpu
 def test_gpu_chain_with_the_motion_stages_equals_hostsim():
-    want = _chain(True, None)
-    st = _Stream()
-    try:
-        got = _chain(False, st.ptr)
-    finally:
-        st.close()
+    want, got = both_chains(_chain)
     for i, name in ((0, "linear frame"), (1, "normal_depth"), (2, "motion vectors"), (3, "lens frame"), (4, "shutter frame"),
                     (5, "reach"), (6, "bloomed frame")):
         nc.assert_bits(got[i], want[i], "chain: " + name)

@@ -14,8 +14,8 @@ import progress_cases as pc
 import rt_amd
 import session_cases as sc
 import temporal_cases as tc
+from stage_gpu import Stream
 from temporal_cases import accumulate, inputs, params
-from test_dnv_gpu import _Stream
 
 NAMES = ("colour", "sigma_out", "len_out")
 # tc.SHAPES: (1, 1) one live thread; (5, 3) every tap clipped somewhere; (37, 29) partial blocks on both axes;
@@ -35,7 +35,7 @@ def test_gpu_kernel_equals_hostsim(w, h, kind, history):
 
 @pytest.mark.gpu
 def test_gpu_device_pointers_own_stream_and_scratch_reuse():
-    st = _Stream()
+    st = Stream()
     try:
         for (w, h) in [(130, 67), (37, 29)]:  # larger, then smaller: the context's scratch is reused
             for kind in ("shift", "turn"):
@@ -98,7 +98,7 @@ def _chain(hostsim: bool, stream):
 @pytest.mark.gpu
 def test_gpu_two_frame_chain_equals_hostsim():
     want = _chain(True, None)
-    st = _Stream()
+    st = Stream()
     try:
         got = _chain(False, st.ptr)
     finally:

@@ -4,18 +4,15 @@ upscale_cases.py under both forced up_variant values and the product's dispatch,
 own, and the chain from a tracked progression at 32x32 to the displayed 64x64 frame."""
 from __future__ import annotations
 
-import ctypes
-
 import numpy as np
 import pytest
 
 import meter_cases as mc
 import noise_cases as nc
-import progress_cases as pc
 import rt_amd
 import upscale_cases as uc
-from test_dnv_gpu import _Stream
 from upscale_cases import inputs, upscale
+from stage_gpu import Stream, both_chains, forced_variant, post_chain
 
 f32 = np.float32
 # uc.PAIRS: (1,1)->(1,1) one live thread; (1,1)->(3,2) every tap but one outside the frame; (5,3)->(10,6) a ratio of 2
@@ -30,11 +27,8 @@ f32 = np.float32
 @pytest.mark.parametrize("pair", uc.PAIRS)
 def test_gpu_kernel_equals_hostsim(pair, sigma, variant):
     want = uc.host_result(pair, sigma)
-    uc.schedule(False, up_variant=variant)
-    try:
+    with forced_variant(uc.ctx, "up_variant", variant):
         got = upscale(inputs(*pair), None, sigma, hostsim=False)
-    finally:
-        uc.schedule(False, up_variant=0)
     nc.assert_bits(got[0], want[0], f"{pair} sigma {sigma} variant {variant}: colour")
     if sigma:
         nc.assert_bits(got[1], want[1], f"{pair} sigma {sigma} variant {variant}: sigma_out")
@@ -46,72 +40,49 @@ def test_gpu_kernel_equals_hostsim(pair, sigma, variant):
 @pytest.mark.parametrize("variant", [1, 2])
 def test_gpu_device_pointers_own_stream_into_garbage(variant):
     L, ctx = uc.ctx(False)
-    st = _Stream()
-    uc.schedule(False, up_variant=variant)
+    st = Stream()
     try:
-        for pair in [(37, 29, 130, 67), (5, 3, 10, 6)]:  # larger, then smaller: the context's scratch is reused
-            case = inputs(*pair)
-            w_lo, h_lo, w, h = pair
-            upscale(case, None, True, hostsim=False)  # (the host form: it sizes the staging buffer)
-            want = uc.host_result(pair)
-            d = {k: st.upload(v) for k, v in case.items()}
-            d_out, d_sout = st.upload(np.full((h, w, 4), np.nan, f32)), st.upload(np.full((h, w), -7.0, f32))
-            rt_amd.check(L, L.rt_upscale_device(ctx, w_lo, h_lo, w, h, d["rgba"].ptr, d["sigma"].ptr, d["alb_lo"].ptr,
-                                                d["nd_lo"].ptr, d["alb_hi"].ptr, d["nd_hi"].ptr, None, d_out.ptr, d_sout.ptr,
-                                                st.ptr), ctx, "rt_upscale_device")
-            nc.assert_bits(st.download(d_out, (h, w, 4)), want[0], f"{pair}: colour")
-            nc.assert_bits(st.download(d_sout, (h, w)), want[1], f"{pair}: sigma_out")
-            for k, v in case.items():
-                nc.assert_bits(st.download(d[k], v.shape), v, f"{pair}: {k} changed")
-        assert L.rt_last_kernel_ms(ctx) == -1.0, "the device form does not wait"
+        with forced_variant(uc.ctx, "up_variant", variant):
+            for pair in [(37, 29, 130, 67), (5, 3, 10, 6)]:  # larger, then smaller: the context's scratch is reused
+                case = inputs(*pair)
+                w_lo, h_lo, w, h = pair
+                upscale(case, None, True, hostsim=False)  # (the host form: it sizes the staging buffer)
+                want = uc.host_result(pair)
+                d = {k: st.upload(v) for k, v in case.items()}
+                d_out, d_sout = st.upload(np.full((h, w, 4), np.nan, f32)), st.upload(np.full((h, w), -7.0, f32))
+                rt_amd.check(L, L.rt_upscale_device(ctx, w_lo, h_lo, w, h, d["rgba"].ptr, d["sigma"].ptr, d["alb_lo"].ptr,
+                                                    d["nd_lo"].ptr, d["alb_hi"].ptr, d["nd_hi"].ptr, None, d_out.ptr, d_sout.ptr,
+                                                    st.ptr), ctx, "rt_upscale_device")
+                nc.assert_bits(st.download(d_out, (h, w, 4)), want[0], f"{pair}: colour")
+                nc.assert_bits(st.download(d_sout, (h, w)), want[1], f"{pair}: sigma_out")
+                for k, v in case.items():
+                    nc.assert_bits(st.download(d[k], v.shape), v, f"{pair}: {k} changed")
+            assert L.rt_last_kernel_ms(ctx) == -1.0, "the device form does not wait"
     finally:
-        uc.schedule(False, up_variant=0)
         st.close()
 
 
 LO, HI = 32, 64
 
 
+def _upscale(C, frame):
+    C.call("rt_render_features_device", HI, HI, C.f4("albedo_hi", HI, HI), C.f4("normal_depth_hi", HI, HI))
+    C.call("rt_upscale_device", LO, LO, HI, HI, C.p(frame), C.p("sigma"), C.p("albedo"), C.p("normal_depth"), C.p("albedo_hi"),
+           C.p("normal_depth_hi"), None, C.f4("upscaled", HI, HI), C.f1("upscaled sigma", HI, HI))
+    return "upscaled"
+
+
 def _chain(hostsim: bool, stream):
     """Cornell: a tracked [2, 2] progression at 32x32, the linear resolve, the noise figure, the guides at 32x32 and at
     64x64, the upscale, the histogram, the solve at the defaults and rt_display with that exposure, device forms on one
     stream; (linear, sigma, upscaled, upscaled sigma, histogram, 8-bit frame)."""
-    s = pc.session(hostsim, "cornell")
-    pc.begin(s, total=4, w=LO, h=LO)
-    nc.track(s)
-    pc.advance(s, 2)
-    pc.advance(s, 2)
-    vp = ctypes.c_void_p
-    q = vp(stream) if stream else None
-    lo4, lo1, hi4, hi1 = (LO, LO, 4), (LO, LO), (HI, HI, 4), (HI, HI)
-    bufs = [s.array(np.full(shape, -3.0, f32)) for shape in (lo4, lo1, lo4, lo4, hi4, hi4, hi4, hi1)]
-    lin, sg, alb_lo, nd_lo, alb_hi, nd_hi, up, up_s = bufs
-    hist = s.array(np.full(mc.WORDS, 0xDEADBEEF, np.uint32))
-    out8 = s.array(np.zeros((HI, HI, 4), np.uint8))
-    s.ok(s.L.rt_progress_resolve_linear_device(s.ctx, vp(lin.ptr), q), "rt_progress_resolve_linear_device")
-    s.ok(s.L.rt_progress_noise_sigma_device(s.ctx, vp(sg.ptr), q), "rt_progress_noise_sigma_device")
-    s.ok(s.L.rt_render_features_device(s.ctx, LO, LO, vp(alb_lo.ptr), vp(nd_lo.ptr), q), "rt_render_features_device (low)")
-    s.ok(s.L.rt_render_features_device(s.ctx, HI, HI, vp(alb_hi.ptr), vp(nd_hi.ptr), q), "rt_render_features_device (full)")
-    s.ok(s.L.rt_upscale_device(s.ctx, LO, LO, HI, HI, vp(lin.ptr), vp(sg.ptr), vp(alb_lo.ptr), vp(nd_lo.ptr), vp(alb_hi.ptr),
-                               vp(nd_hi.ptr), None, vp(up.ptr), vp(up_s.ptr), q), "rt_upscale_device")
-    s.ok(s.L.rt_meter_device(s.ctx, HI, HI, vp(up.ptr), vp(hist.ptr), q), "rt_meter_device")
-    words = hist.get()  # (the download waits for the device)
-    r = rt_amd.meter_solve(words, hostsim=hostsim)
-    p = rt_amd.DisplayParams(r["exposure"], 2.2, 0)
-    s.ok(s.L.rt_display_device(s.ctx, HI, HI, vp(up.ptr), ctypes.byref(p), None, vp(out8.ptr), q), "rt_display_device")
-    got = (lin.get(), sg.get(), up.get(), up_s.get(), words, out8.get())
-    s.close()
-    return got
+    got = post_chain(hostsim, stream, [_upscale], size=(LO, LO), sigma=True, features=True)
+    return tuple(got[k] for k in ("linear", "sigma", "upscaled", "upscaled sigma", "histogram", "out8"))
 
 
 @pytest.mark.gpu
 def test_gpu_chain_to_the_displayed_frame_equals_hostsim():
-    want = _chain(True, None)
-    st = _Stream()
-    try:
-        got = _chain(False, st.ptr)
-    finally:
-        st.close()
+    want, got = both_chains(_chain)
     for name, g, w in zip(("linear frame", "sigma", "upscaled", "upscaled sigma"), got, want):
         nc.assert_bits(g, w, f"chain: {name}")
     mc.assert_words(got[4], want[4], "chain: histogram")

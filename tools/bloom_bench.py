@@ -18,19 +18,12 @@ from __future__ import annotations
 
 import argparse
 import ctypes
-import json
 import os
 import sys
 
 import numpy as np
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (os.path.join(REPO, "sycl-ray-tracing_amd"), os.path.join(REPO, "tools")):
-    if p not in sys.path:
-        sys.path.insert(0, p)
-
-import rt_amd  # noqa: E402
-from denoise_var_bench import _hip, dev_alloc, sync  # noqa: E402
+from stage_bench import REPO, _hip, dev_alloc, rt_amd, sync, test_frame, write_json
 
 SMALL = 64 * 64
 
@@ -56,9 +49,7 @@ def main() -> int:
     res = {"build": L.rt_build_id().decode(), "reps": a.reps, "sizes": {}}
     for w, h in ((1920, 1080), (3840, 2160)):
         nb = w * h * 16
-        rng = np.random.default_rng(0)
-        frame = rng.random((h, w, 4), dtype=np.float32)
-        frame.reshape(-1, 4)[::97, :3] = 50.0
+        frame = test_frame(w, h)
         t_in, t_out, t_layer, t_out8 = dev_alloc(nb, frame), dev_alloc(nb), dev_alloc(nb), dev_alloc(nb // 4)
         entry = {"levels": {}}
         disp = np.zeros(6 * reps)
@@ -96,11 +87,7 @@ def main() -> int:
         for q in (t_in, t_out, t_layer, t_out8):
             _hip.hipFree(q)
     L.rt_destroy(ctx)
-    print(json.dumps(res))
-    os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    with open(a.out, "w") as f:
-        json.dump(res, f, indent=1)
-        f.write("\n")
+    write_json(res, a.out)
     return 0
 
 

@@ -13,39 +13,14 @@ sigma read, 16 B record written).
 from __future__ import annotations
 
 import argparse
-import ctypes
-import json
 import os
 import sys
 
 import numpy as np
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (os.path.join(REPO, "sycl-ray-tracing_amd"), os.path.join(REPO, "tools")):
-    if p not in sys.path:
-        sys.path.insert(0, p)
-
-import rt_amd  # noqa: E402
-import scenes  # noqa: E402
+from stage_bench import REPO, _hip, cornell_kernel, dev_alloc, rt_amd, sync, write_json
 
 PASSES = 5
-
-_hip = ctypes.CDLL("libamdhip64.so")
-_hip.hipMalloc.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t]
-_hip.hipFree.argtypes = [ctypes.c_void_p]
-_hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
-
-
-def dev_alloc(nbytes: int, src: np.ndarray | None = None) -> int:
-    p = ctypes.c_void_p()
-    assert _hip.hipMalloc(ctypes.byref(p), nbytes) == 0
-    if src is not None:
-        assert _hip.hipMemcpy(p, src.ctypes.data, src.nbytes, 1) == 0
-    return p.value
-
-
-def sync():
-    assert _hip.hipDeviceSynchronize() == 0
 
 
 def main() -> int:
@@ -53,14 +28,10 @@ def main() -> int:
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "denoise_var_bench.json"))
     a = ap.parse_args()
-    P = rt_amd.parse_obj(scenes.scene_path("cornell12"))
-    sky = rt_amd.Image.from_rgb(scenes.make_sky("S"))
     res = {"build": rt_amd.lib().rt_build_id().decode(), "reps": a.reps, "passes": PASSES, "bytes_per_pixel_pass": 64,
            "bytes_per_pixel_prep": 36, "sizes": {}}
     for w, h in ((1920, 1080), (3840, 2160)):
-        rk = rt_amd.RenderKernel(w, h, 1, 1, rt_amd.Image(1, 1), P.triangles, P.materials, P.emissive_triangle_indices,
-                                 P.material_indices, None, rt_amd.BVH(P.triangles), sky, None)
-        rk.set_camera(rt_amd.Camera.preset("cornell"))
+        rk = cornell_kernel(w, h, 1, 1)
         L, ctx = rk.L, rk.ctx
         nb = w * h * 16
         t_alb, t_nd = dev_alloc(nb), dev_alloc(nb)
@@ -108,11 +79,7 @@ def main() -> int:
         del rk
         for p in (t_alb, t_nd, t_in, t_out, t_sg, t_left):
             _hip.hipFree(p)
-    print(json.dumps(res))
-    os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    with open(a.out, "w") as f:
-        json.dump(res, f, indent=1)
-        f.write("\n")
+    write_json(res, a.out)
     return 0
 
 

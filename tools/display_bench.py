@@ -17,38 +17,18 @@ Then rt_render_linear_device beside rt_render_device on Cornell (the render minu
 from __future__ import annotations
 
 import argparse
-import ctypes
-import json
 import os
 import sys
 
 import numpy as np
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (os.path.join(REPO, "sycl-ray-tracing_amd"), os.path.join(REPO, "tools")):
-    if p not in sys.path:
-        sys.path.insert(0, p)
+from stage_bench import REPO, _hip, dev_alloc, rt_amd, scenes, write_json
 
-import rt_amd  # noqa: E402
-import scenes  # noqa: E402
-
-_hip = ctypes.CDLL("libamdhip64.so")
-_hip.hipMalloc.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t]
-_hip.hipFree.argtypes = [ctypes.c_void_p]
-_hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
 
 # the hook's kernel order, and the bytes each moves per pixel
 KERNELS = (("k_resolve", 48), ("k_resolve_linear", 48), ("k_display_float", 32), ("k_display_rgba8", 20),
            ("k_display_rgba8_flip", 20), ("k_display_both", 36))
 WARMUP = 2
-
-
-def dev_alloc(nbytes: int, src: np.ndarray | None = None) -> int:
-    p = ctypes.c_void_p()
-    assert _hip.hipMalloc(ctypes.byref(p), nbytes) == 0
-    if src is not None:
-        assert _hip.hipMemcpy(p, src.ctypes.data, src.nbytes, 1) == 0
-    return p.value
 
 
 def stats(ms, bytes_per_pixel: int, n_px: int) -> dict:
@@ -115,11 +95,7 @@ def main() -> int:
             "rt_render_device_ms": float(np.median(rt)), "rt_render_device_ms_all": rt,
             "rt_render_linear_device_ms": float(np.median(rl)), "rt_render_linear_device_ms_all": rl}
         _hip.hipFree(d_fb)
-    print(json.dumps(res))
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        json.dump(res, f, indent=1)
-        f.write("\n")
+    write_json(res, a.out)
     return 0
 
 

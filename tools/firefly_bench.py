@@ -16,20 +16,12 @@ The input is a noisy gradient with a bright pixel in every 97th place, the defau
 from __future__ import annotations
 
 import argparse
-import json
 import os
 import sys
 
 import numpy as np
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (os.path.join(REPO, "sycl-ray-tracing_amd"), os.path.join(REPO, "tools")):
-    if p not in sys.path:
-        sys.path.insert(0, p)
-
-import rt_amd  # noqa: E402
-import scenes  # noqa: E402
-from denoise_var_bench import _hip, dev_alloc, sync  # noqa: E402
+from stage_bench import REPO, _hip, cornell_kernel, dev_alloc, rt_amd, sync, test_frame, write_json
 
 BPP, BPP_TEMPORAL, BPP_PREP = 44.0, 100.0, 36.0
 
@@ -39,13 +31,10 @@ def main() -> int:
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "firefly_bench.json"))
     a = ap.parse_args()
-    P = rt_amd.parse_obj(scenes.scene_path("cornell12"))
-    sky = rt_amd.Image.from_rgb(scenes.make_sky("S"))
     res = {"build": rt_amd.lib().rt_build_id().decode(), "reps": a.reps, "bytes_per_pixel": BPP,
            "bytes_per_pixel_k_temporal": BPP_TEMPORAL, "bytes_per_pixel_k_dnv_prep": BPP_PREP, "sizes": {}}
     for w, h in ((1920, 1080), (3840, 2160)):
-        rk = rt_amd.RenderKernel(w, h, 1, 1, rt_amd.Image(1, 1), P.triangles, P.materials, P.emissive_triangle_indices,
-                                 P.material_indices, None, rt_amd.BVH(P.triangles), sky, None)
+        rk = cornell_kernel(w, h, 1, 1)
         cam = rt_amd.Camera.preset("cornell")
         rk.set_camera(cam)
         L, ctx = rk.L, rk.ctx
@@ -54,8 +43,7 @@ def main() -> int:
         rk.features_device(t_alb, t_nd)
         sync()
         rng = np.random.default_rng(0)
-        frame = rng.random((h, w, 4), dtype=np.float32)
-        frame.reshape(-1, 4)[::97, :3] = 50.0
+        frame = test_frame(w, h, rng)
         t_in, t_hin, t_out = dev_alloc(nb, frame), dev_alloc(nb, rng.random((h, w, 4), dtype=np.float32)), dev_alloc(nb)
         t_sg, t_hsg, t_sout = (dev_alloc(nb // 4, (0.05 + 0.45 * rng.random((h, w), dtype=np.float32))) for _ in range(3))
         t_hlen, t_fout = (dev_alloc(nb // 4, (1 + 7 * rng.random((h, w), dtype=np.float32))) for _ in range(2))
@@ -101,11 +89,7 @@ def main() -> int:
         del rk
         for q in (t_alb, t_nd, t_in, t_hin, t_out, t_sg, t_hsg, t_sout, t_hlen, t_fout):
             _hip.hipFree(q)
-    print(json.dumps(res))
-    os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    with open(a.out, "w") as f:
-        json.dump(res, f, indent=1)
-        f.write("\n")
+    write_json(res, a.out)
     return 0
 
 

@@ -25,22 +25,10 @@ import time
 
 import numpy as np
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (REPO, os.path.join(REPO, "sycl-ray-tracing_amd"), os.path.join(REPO, "tools")):
-    if p not in sys.path:
-        sys.path.insert(0, p)
-
-import rt_amd  # noqa: E402
-import scenes  # noqa: E402
-from denoise_var_bench import _hip, dev_alloc, sync  # noqa: E402
+from stage_bench import REPO, _hip, dev_alloc, rt_amd, scenes, stat, sync, write_json
 
 vp = ctypes.c_void_p
 W, H = 1920, 1080
-
-
-def stat(ms, warm=2):
-    ms = np.asarray(ms[warm:])
-    return {"ms": float(np.median(ms)), "min": float(ms.min()), "max": float(ms.max())}
 
 
 def features(rk, w, h, d_alb, d_nd):
@@ -161,11 +149,7 @@ def main() -> int:
         print(scene, json.dumps(res["scenes"][scene]), flush=True)
     if a.end_to_end:
         res["end_to_end"] = end_to_end(a)
-    print(json.dumps(res))
-    os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    with open(a.out, "w") as f:
-        json.dump(res, f, indent=1)
-        f.write("\n")
+    write_json(res, a.out)
     return 0
 
 

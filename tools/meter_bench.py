@@ -21,27 +21,14 @@ RT_HIP_LIB names another build of the library (make variant V=peel2 DEFS=-DMT_PE
 from __future__ import annotations
 
 import argparse
-import json
 import os
 import sys
 
 import numpy as np
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (REPO, os.path.join(REPO, "sycl-ray-tracing_amd"), os.path.join(REPO, "tools")):
-    if p not in sys.path:
-        sys.path.insert(0, p)
-
-import rt_amd  # noqa: E402
-import scenes  # noqa: E402
-from denoise_var_bench import _hip, dev_alloc, sync  # noqa: E402
+from stage_bench import REPO, _hip, cornell_kernel, dev_alloc, rt_amd, scenes, stat, sync, write_json
 
 SWEEP = (128, 256, 512, 1024, 2048, 4096)
-
-
-def stat(ms):
-    ms = np.asarray(ms[2:])
-    return {"ms": float(np.median(ms)), "min": float(ms.min()), "max": float(ms.max())}
 
 
 def benchmark_exposure(cfg: str, samples: int | None = None) -> dict:
@@ -76,9 +63,7 @@ def main() -> int:
     res = {"build": rt_amd.lib().rt_build_id().decode(), "reps": a.reps, "bytes_per_pixel": 16.0,
            "bytes_per_pixel_k_display": 32.0, "sizes": {}}
     for w, h in ((1920, 1080), (3840, 2160)):
-        rk = rt_amd.RenderKernel(w, h, 1, 3, rt_amd.Image(1, 1), P.triangles, P.materials, P.emissive_triangle_indices,
-                                 P.material_indices, None, rt_amd.BVH(P.triangles), sky, None)
-        rk.set_camera(rt_amd.Camera.preset("cornell"))
+        rk = cornell_kernel(w, h, 1, 3)
         L, ctx = rk.L, rk.ctx
         nb = w * h * 16
         rng = np.random.default_rng(0)
@@ -125,7 +110,7 @@ def main() -> int:
             e["largest_bin_share"] = float(s["bins"].max() / max(s["counted"], 1))
             entry["frames"][f] = e
         fr = entry["frames"]
-        prod = "k_meter_lds"  # (mt_variant 0; rt_meter.hip mt_use_lds)
+        prod = "k_meter_lds"  # (mt_variant 0; rt_meter.hip rt_backend_meter)
         disp = fr["rendered"]["k_display float out"]
         entry["product_kernel"] = prod
         entry["rendered_vs_k_display"] = {
@@ -140,11 +125,7 @@ def main() -> int:
     if not a.kernels_only:
         res["auto_exposure_at_defaults"] = {"cfg1": benchmark_exposure("cfg1"),
                                             "cfg2": benchmark_exposure("cfg2", a.dragon_samples)}
-    print(json.dumps(res))
-    os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    with open(a.out, "w") as f:
-        json.dump(res, f, indent=1)
-        f.write("\n")
+    write_json(res, a.out)
     return 0
 
 

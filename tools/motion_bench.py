@@ -18,27 +18,14 @@ from __future__ import annotations
 
 import argparse
 import ctypes
-import json
 import os
 import sys
 
 import numpy as np
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (REPO, os.path.join(REPO, "sycl-ray-tracing_amd"), os.path.join(REPO, "tools")):
-    if p not in sys.path:
-        sys.path.insert(0, p)
-
-import rt_amd  # noqa: E402
-import scenes  # noqa: E402
-from denoise_var_bench import _hip, dev_alloc, sync  # noqa: E402
+from stage_bench import REPO, _hip, cornell_kernel, dev_alloc, rt_amd, stat, sync, test_frame, write_json, yardsticks
 
 vp = ctypes.c_void_p
-
-
-def stat(ms):
-    ms = np.asarray(ms[2:])
-    return {"ms": float(np.median(ms)), "min": float(ms.min()), "max": float(ms.max())}
 
 
 def yawed(cam, deg):
@@ -54,24 +41,19 @@ def main() -> int:
     ap.add_argument("--sizes", default="1920x1080,3840x2160")
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "motion_bench.json"))
     a = ap.parse_args()
-    P = rt_amd.parse_obj(scenes.scene_path("cornell12"))
-    sky = rt_amd.Image.from_rgb(scenes.make_sky("S"))
     res = {"reps": a.reps, "sizes": {},
            "how": "rt_device_motion_kernel_ms (one launch of each kernel per round), rt_motion_blur_device + rt_device_last_kernel_ms, "
                   "rt_device_denoise_pass_ms (one pass, dn_variant 1) and rt_device_display_kernel_ms (8-bit out); median / min / "
                   "max of the rounds after two warm-ups; buffers re-read every round (in cache at 1080p)"}
     for w, h in (tuple(int(v) for v in s.split("x")) for s in a.sizes.split(",")):
-        rk = rt_amd.RenderKernel(w, h, 1, 3, rt_amd.Image(1, 1), P.triangles, P.materials, P.emissive_triangle_indices,
-                                 P.material_indices, None, rt_amd.BVH(P.triangles), sky, None)
+        rk = cornell_kernel(w, h, 1, 3)
         cam = rt_amd.Camera.preset("cornell")
         rk.set_camera(cam)
         prev = yawed(cam, 2.0)
         L, ctx = rk.L, rk.ctx
         res["build"] = L.rt_build_id().decode()
         n = w * h
-        rng = np.random.default_rng(0)
-        frame = rng.random((h, w, 4), dtype=np.float32)
-        frame.reshape(-1, 4)[::97, :3] = 50.0
+        frame = test_frame(w, h)
         d_in, d_out, d_tmp, d_alb, d_gnd = dev_alloc(16 * n, frame), *(dev_alloc(16 * n) for _ in range(4))
         d_m, d_vec, d_reach, d_out8 = dev_alloc(8 * n), dev_alloc(8 * n), dev_alloc(4 * n), dev_alloc(4 * n)
         rt_amd.check(L, L.rt_render_features_device(ctx, w, h, vp(d_alb), vp(d_gnd), None), ctx, "rt_render_features_device")
@@ -83,18 +65,11 @@ def main() -> int:
                                     "max": float(np.hypot(real[..., 0], real[..., 1]).max())}}
         # the yardsticks on the same frame
         t = {"k_dn_direct": [], "k_display": []}
-        rk.test_schedule(dn_variant=1)
-        assert L.rt_device_denoise_pass_ms(ctx, 1, None, 0) == 0
-        six, one = np.zeros(6), np.zeros(1)
-        for _ in range(a.reps + 2):
-            rk.denoise_device(d_in, d_tmp, d_alb, d_gnd, 1.0, {"passes": 1}, width=w, height=h)
-            sync()
-            assert L.rt_device_denoise_pass_ms(ctx, -1, rt_amd.ptr(one), 1) == 1
-            assert L.rt_device_display_kernel_ms(ctx, w, h, vp(d_in), vp(d_tmp), vp(d_tmp), vp(d_out8), 1, rt_amd.ptr(six)) == 0
-            t["k_dn_direct"].append(one[0])
-            t["k_display"].append(six[3])
-        assert L.rt_device_denoise_pass_ms(ctx, 0, None, 0) == 0
-        rk.test_schedule(dn_variant=0)
+        with yardsticks(rk, w, h) as yard:
+            for _ in range(a.reps + 2):
+                dn, disp = yard(d_in, d_tmp, d_alb, d_gnd, d_out8)
+                t["k_dn_direct"].append(dn)
+                t["k_display"].append(disp)
         entry.update({k: stat(v) for k, v in t.items()})
         m = np.zeros((h, w, 2), np.float32)
         for R in (4, 8, 16):
@@ -125,11 +100,7 @@ def main() -> int:
         for q in (d_in, d_out, d_tmp, d_alb, d_gnd, d_m, d_vec, d_reach, d_out8):
             _hip.hipFree(vp(q))
         del rk
-    print(json.dumps(res))
-    os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    with open(a.out, "w") as f:
-        json.dump(res, f, indent=1)
-        f.write("\n")
+    write_json(res, a.out)
     return 0
 
 

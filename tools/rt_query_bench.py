@@ -10,37 +10,13 @@ bounce rays from those rays' hit points, and the same bounce rays shuffled.
 from __future__ import annotations
 
 import argparse
-import ctypes
 import json
 import os
 import sys
 
 import numpy as np
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (os.path.join(REPO, "sycl-ray-tracing_amd"), os.path.join(REPO, "tools")):
-    if p not in sys.path:
-        sys.path.insert(0, p)
-
-import rt_amd  # noqa: E402
-import scenes  # noqa: E402
-
-_hip = ctypes.CDLL("libamdhip64.so")
-_hip.hipMalloc.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t]
-_hip.hipFree.argtypes = [ctypes.c_void_p]
-_hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
-
-
-def dev_alloc(nbytes: int, src: np.ndarray | None = None) -> int:
-    p = ctypes.c_void_p()
-    assert _hip.hipMalloc(ctypes.byref(p), nbytes) == 0
-    if src is not None:
-        assert _hip.hipMemcpy(p, src.ctypes.data, src.nbytes, 1) == 0
-    return p.value
-
-
-def sync():
-    assert _hip.hipDeviceSynchronize() == 0
+from stage_bench import REPO, _hip, dev_alloc, rt_amd, scenes, sync
 
 
 def bounce_rays(cam_rays: np.ndarray, hits: np.ndarray, seed: int = 3) -> np.ndarray:

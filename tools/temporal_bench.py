@@ -13,20 +13,12 @@ tools/denoise_var_bench.py counts it.
 from __future__ import annotations
 
 import argparse
-import json
 import os
 import sys
 
 import numpy as np
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (os.path.join(REPO, "sycl-ray-tracing_amd"), os.path.join(REPO, "tools")):
-    if p not in sys.path:
-        sys.path.insert(0, p)
-
-import rt_amd  # noqa: E402
-import scenes  # noqa: E402
-from denoise_var_bench import _hip, dev_alloc, sync  # noqa: E402
+from stage_bench import REPO, _hip, cornell_kernel, dev_alloc, rt_amd, sync, write_json
 
 SHIFT_PIXELS = 3.0  # the previous camera's offset along x, in pixels of the back wall at 1920 columns
 
@@ -36,13 +28,10 @@ def main() -> int:
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "temporal_bench.json"))
     a = ap.parse_args()
-    P = rt_amd.parse_obj(scenes.scene_path("cornell12"))
-    sky = rt_amd.Image.from_rgb(scenes.make_sky("S"))
     res = {"build": rt_amd.lib().rt_build_id().decode(), "reps": a.reps, "bytes_per_pixel": 100,
            "bytes_per_pixel_dn_direct_pass": 64, "sizes": {}}
     for w, h in ((1920, 1080), (3840, 2160)):
-        rk = rt_amd.RenderKernel(w, h, 1, 1, rt_amd.Image(1, 1), P.triangles, P.materials, P.emissive_triangle_indices,
-                                 P.material_indices, None, rt_amd.BVH(P.triangles), sky, None)
+        rk = cornell_kernel(w, h, 1, 1)
         cur = rt_amd.Camera.preset("cornell")
         m = cur.view_matrix.copy()
         # the back wall is 4.5 away and the frame 2 * 4.5 * aspect / fov_dist wide there
@@ -90,11 +79,7 @@ def main() -> int:
         del rk
         for p in (t_alb, t_nd, t_hnd, t_in, t_hin, t_out, t_sg, t_hsg, t_sout, t_hlen, t_lout):
             _hip.hipFree(p)
-    print(json.dumps(res))
-    os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    with open(a.out, "w") as f:
-        json.dump(res, f, indent=1)
-        f.write("\n")
+    write_json(res, a.out)
     return 0
 
 

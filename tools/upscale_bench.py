@@ -21,28 +21,15 @@ from __future__ import annotations
 
 import argparse
 import ctypes
-import json
 import os
 import sys
 import time
 
 import numpy as np
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (REPO, os.path.join(REPO, "sycl-ray-tracing_amd"), os.path.join(REPO, "tools")):
-    if p not in sys.path:
-        sys.path.insert(0, p)
-
-import rt_amd  # noqa: E402
-import scenes  # noqa: E402
-from denoise_var_bench import _hip, dev_alloc, sync  # noqa: E402
+from stage_bench import REPO, _hip, cornell_kernel, dev_alloc, rt_amd, scenes, stat, sync, write_json, yardsticks
 
 vp = ctypes.c_void_p
-
-
-def stat(ms):
-    ms = np.asarray(ms[2:])
-    return {"ms": float(np.median(ms)), "min": float(ms.min()), "max": float(ms.max())}
 
 
 def features(rk, w, h, d_alb, d_nd):
@@ -55,9 +42,7 @@ def kernels(a) -> dict:
     sky = rt_amd.Image.from_rgb(scenes.make_sky("S"))
     out = {}
     for (wl, hl), (w, h) in (((960, 540), (1920, 1080)), ((1920, 1080), (3840, 2160))):
-        rk = rt_amd.RenderKernel(wl, hl, 1, 3, rt_amd.Image(1, 1), P.triangles, P.materials, P.emissive_triangle_indices,
-                                 P.material_indices, None, rt_amd.BVH(P.triangles), sky, None)
-        rk.set_camera(rt_amd.Camera.preset("cornell"))
+        rk = cornell_kernel(wl, hl, 1, 3)
         L, ctx = rk.L, rk.ctx
         n_lo, n = wl * hl, w * h
         rng = np.random.default_rng(0)
@@ -70,23 +55,17 @@ def kernels(a) -> dict:
         features(rk, w, h, d_ahi, d_nhi)
         sync()
         t = {k: [] for k in ("k_upscale_direct", "k_upscale_lds", "k_dn_direct", "k_display")}
-        rk.test_schedule(dn_variant=1)
-        assert L.rt_device_denoise_pass_ms(ctx, 1, None, 0) == 0
-        two, six, one = np.zeros(2), np.zeros(6), np.zeros(1)
-        for rnd in range(a.reps + 2):
-            rt_amd.check(L, L.rt_device_upscale_kernel_ms(ctx, wl, hl, w, h, vp(d_lo), vp(d_sg), vp(d_alo), vp(d_nlo), vp(d_ahi),
-                                                          vp(d_nhi), vp(d_out), vp(d_sout), 1, rnd, rt_amd.ptr(two)), ctx,
-                         "rt_device_upscale_kernel_ms")
-            rk.denoise_device(d_out, d_tmp, d_ahi, d_nhi, 1.0, {"passes": 1}, width=w, height=h)
-            sync()
-            assert L.rt_device_denoise_pass_ms(ctx, -1, rt_amd.ptr(one), 1) == 1
-            assert L.rt_device_display_kernel_ms(ctx, w, h, vp(d_out), vp(d_tmp), vp(d_tmp), vp(d_out8), 1, rt_amd.ptr(six)) == 0
-            t["k_upscale_direct"].append(two[0])
-            t["k_upscale_lds"].append(two[1])
-            t["k_dn_direct"].append(one[0])
-            t["k_display"].append(six[3])
-        assert L.rt_device_denoise_pass_ms(ctx, 0, None, 0) == 0
-        rk.test_schedule(dn_variant=0)
+        two = np.zeros(2)
+        with yardsticks(rk, w, h) as yard:
+            for rnd in range(a.reps + 2):
+                rt_amd.check(L, L.rt_device_upscale_kernel_ms(ctx, wl, hl, w, h, vp(d_lo), vp(d_sg), vp(d_alo), vp(d_nlo), vp(d_ahi),
+                                                              vp(d_nhi), vp(d_out), vp(d_sout), 1, rnd, rt_amd.ptr(two)), ctx,
+                             "rt_device_upscale_kernel_ms")
+                dn, disp = yard(d_out, d_tmp, d_ahi, d_nhi, d_out8)
+                t["k_upscale_direct"].append(two[0])
+                t["k_upscale_lds"].append(two[1])
+                t["k_dn_direct"].append(dn)
+                t["k_display"].append(disp)
         entry = {k: stat(v) for k, v in t.items()}
         model = 52.0 * n_lo + 52.0 * n
         for k in ("k_upscale_direct", "k_upscale_lds"):
@@ -163,11 +142,7 @@ def main() -> int:
            "kernels": kernels(a)}
     if a.end_to_end:
         res["end_to_end"] = end_to_end(a)
-    print(json.dumps(res))
-    os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    with open(a.out, "w") as f:
-        json.dump(res, f, indent=1)
-        f.write("\n")
+    write_json(res, a.out)
     return 0
 
 
